@@ -18,17 +18,32 @@ variances are not part of the headline step; the reference-fidelity step
 separately and reported in `extra.reference_step_ms_q*`.  Inputs are resident
 in HBM before the timed region.
 
-Timing: W warm-up steps, then R *blocks* of exactly K steps, every block
-bracketed by a barrier + torch.cuda.synchronize() on both sides and reduced with
-MAX over ranks; `ms_per_step` / `value` = ALL timed steps / the summed time of ALL
-timed blocks -- no block is left out (what a mean without the blocks slower than
-1.5x the median would read is in `extra`, with those blocks listed).  R is chosen
-so that the timed region lasts >= ~0.3 s (a single 20-step block is 5 ms).  The
-blocks of a pass are NOT alike -- at 50^3 the first ~45 steps after the init data
-need 3 CG iterations, the later ones 2 -- so the block times are bimodal; their
-median is reported beside the mean in `extra`.  The stream of a pass never exceeds
-UCI 3droad's 434 874 points: when it is used up the model is rebuilt from the init
-data (un-timed) and the next pass streams fresh points.
+Timing: W warm-up steps, then the K = --steps timed steps as ONE block, bracketed
+by a barrier + torch.cuda.synchronize() on both sides and reduced with MAX over
+ranks; `ms_per_step` / `value` = ALL timed steps / the summed time of ALL timed
+blocks.  `--blocks R` times R blocks of exactly K steps instead (R = 0: as many as
+fill >= ~0.3 s, the earlier default); then no block is left out either (what a
+mean without the blocks slower than 1.5x the median would read is in `extra`, with
+those blocks listed).  The blocks of a pass are NOT alike -- at 50^3 the first ~45
+steps after the init data need 3 CG iterations, the later ones 2 -- so the block
+times are bimodal; their median is reported beside the mean in `extra`.  A pass
+streams at most UCI 3droad's 434 874 points when K fits into it: when it is used
+up the model is rebuilt from the init data (un-timed) and the next pass streams
+fresh points; a longer block streams on past it.  Inputs are seeded: the same
+arguments stream the same points in every run.
+
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) does only what the
+headline needs: set up, warm up, time the K steps, write the outputs of the last
+step when `--dump-outputs DIR` is given (DIR/batch_mean.npy: the predictive mean
+the step returned for its batch; DIR/inducing_mean.npy: the refreshed posterior
+mean on the inducing grid), print the line.  `--full` adds everything else: the
+roofline leg (after the headline, the same stream in blocks of min(K, 20) steps
+by the --blocks 0 rule, whose SpMV dispatches carry the in-kernel stamps and, in
+one extra block, the events behind `roofline`; the timed headline carries none),
+`roofline_secondary`, the extra legs (other stream, tolerances, variances,
+reference step, dense regime, exchanges at N > 1) and `cpu_baseline`
+(`--no-extras` / `--no-cpu-baseline` drop parts of it).  `--sample-every` /
+`--stamp-dump` run the roofline leg by themselves.
 
 N > 1: `python bench.py --gpus N` spawns its own N ranks (re-executes itself under
 torch.distributed.run on 127.0.0.1) when no launcher set WORLD_SIZE; under
@@ -38,10 +53,10 @@ WISKI_BENCH_BACKEND=gloo asks for the self-test arrangement (every rank on cuda:
 gloo; exercises the N > 1 code path, never a reported number).  The line names the
 exchange that ran (`config.parallelism`) and what carried it (`collective`).
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel = the half-stencil
-SpMV of the CG, HBM-bound; per-dispatch HIP events on its launch stream),
-`roofline_secondary` (statistics scatter, ELL gather) and `cpu_baseline` (the
-OpenMP port of the same step on all host cores, rank 0, N=1 only).
+Prints ONE JSON line (rank 0); with --full it also holds `roofline` (dominant
+kernel = the half-stencil SpMV of the CG, HBM-bound; per-dispatch HIP events on its
+launch stream), `roofline_secondary` (statistics scatter, ELL gather) and
+`cpu_baseline` (the OpenMP port of the same step on all host cores, rank 0, N=1 only).
 """
 import argparse
 import ctypes
@@ -63,25 +78,49 @@ import torch.distributed as dist
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 
 
-def synth_stream(n, d, seed, device, dtype, kind="uniform"):
+def synth_stream(n, d, seed, device, dtype, kind="uniform", on_device=False):
     """S3 of SURVEY.md 8d: X ~ U(-1,1)^3, y = sin(2 pi x0) cos(pi x1) + 0.5 x2 + 0.1 N(0,1), standardised.
     kind="clustered": the road-like variant of 8d -- points along 64 random poly-lines (8 segments each, the same
-    lines for every seed) with sigma = 0.02 jitter, so that many points of a batch share grid cells."""
-    g = torch.Generator(device="cpu").manual_seed(seed)
+    lines for every seed) with sigma = 0.02 jitter, so that many points of a batch share grid cells.
+    on_device: the points are drawn by a generator on `device` (same law, other numbers; the host generator is serial:
+    ~1 s per 5 M points, too slow for streams longer than 3droad)."""
+    gdev = device if on_device else "cpu"
+    g = torch.Generator(device=gdev).manual_seed(seed)
     if kind == "clustered":
         gl = torch.Generator(device="cpu").manual_seed(12345)
-        knots = torch.rand(64, 9, d, generator=gl, dtype=torch.float64) * 1.8 - 0.9        # 64 lines x 9 knots
-        line = torch.randint(0, 64, (n,), generator=g)
-        t = torch.rand(n, generator=g, dtype=torch.float64) * 8
+        knots = (torch.rand(64, 9, d, generator=gl, dtype=torch.float64) * 1.8 - 0.9).to(gdev)   # 64 lines x 9 knots
+        line = torch.randint(0, 64, (n,), generator=g, device=gdev)
+        t = torch.rand(n, generator=g, dtype=torch.float64, device=gdev) * 8
         seg = t.floor().clamp(max=7).long()
         fr = (t - seg)[:, None]
-        X = (1 - fr) * knots[line, seg] + fr * knots[line, seg + 1] + 0.02 * torch.randn(n, d, generator=g, dtype=torch.float64)
+        X = (1 - fr) * knots[line, seg] + fr * knots[line, seg + 1] + 0.02 * torch.randn(n, d, generator=g, dtype=torch.float64, device=gdev)
         X = X.clamp(-1.0, 1.0)
     else:
-        X = torch.rand(n, d, generator=g, dtype=torch.float64) * 2 - 1
-    y = torch.sin(2 * np.pi * X[:, 0]) * torch.cos(np.pi * X[:, 1 % d]) + 0.5 * X[:, (2 % d)] + 0.1 * torch.randn(n, generator=g, dtype=torch.float64)
+        X = torch.rand(n, d, generator=g, dtype=torch.float64, device=gdev) * 2 - 1
+    y = (torch.sin(2 * np.pi * X[:, 0]) * torch.cos(np.pi * X[:, 1 % d]) + 0.5 * X[:, (2 % d)]
+         + 0.1 * torch.randn(n, generator=g, dtype=torch.float64, device=gdev))
     y = (y - y.mean()) / y.std()
     return X.to(device, dtype), y.to(device, dtype)[:, None]
+
+
+PROF_BLOCK_STEPS = 20                # roofline leg: steps per stamped block (~50 SpMV dispatches; the arena holds ~500, the event pool 256)
+DUMP_BYTES_PER_ARRAY = 32 << 20      # --dump-outputs writes at most 64 MB: two arrays
+
+
+def dump_outputs(dirpath, arrays):
+    """--dump-outputs: every tensor of `arrays` as DIR/<name>.npy in its own precision (float32 / float64).  One larger than
+    DUMP_BYTES_PER_ARRAY is written as a fixed sample: the elements at the sorted indices DIR/<name>_index.npy, drawn with seed 0."""
+    os.makedirs(dirpath, exist_ok=True)
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        a = t.detach().reshape(-1).cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > DUMP_BYTES_PER_ARRAY:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_BYTES_PER_ARRAY // (a.itemsize + 8), replace=False))   # sample + index
+            np.save(os.path.join(dirpath, name + "_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(dirpath, name + ".npy"), a)
 
 
 def usable_cpus():
@@ -258,15 +297,21 @@ def main():
     ap.add_argument("--n-init", type=int, default=21743, help="5%% of 434874 (init_ratio of the reference config)")
     ap.add_argument("--tol", type=float, default=None, help="CG relative-residual tolerance")
     ap.add_argument("--stream", default="clustered", choices=["uniform", "clustered"],
-                    help="synthetic stream of SURVEY.md 8d; default: the road-like variant (BASELINE config 3 is 3droad), the uniform one goes to extra")
-    ap.add_argument("--blocks", type=int, default=0, help="number of timed K-step blocks (0 = enough for ~0.3 s)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the un-timed extras (profiling runs)")
-    ap.add_argument("--sample-every", type=int, default=0, help="n > 0: the SpMV dispatches of every n-th TIMED step carry start/stop events too "
+                    help="synthetic stream of SURVEY.md 8d; default: the road-like variant (BASELINE config 3 is 3droad), the uniform one goes to extra (--full)")
+    ap.add_argument("--blocks", type=int, default=1, help="number of timed K-step blocks (default 1: the --steps steps are the timed region; "
+                    "0 = enough for ~0.3 s)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: roofline (kernel stamps, events), "
+                    "roofline_secondary, the extra legs and cpu_baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the un-timed extras (profiling runs)")
+    ap.add_argument("--sample-every", type=int, default=0, help="n > 0: the SpMV dispatches of every n-th step of the roofline leg's blocks carry start/stop events too "
                     "(they cost ~0.8 us per dispatch and skew the waves' start by XCD: default 0 = events only in one extra un-timed block)")
     ap.add_argument("--stamp-dump", default=None, help="write the raw per-wave stamps of every sampled SpMV dispatch here (.npz; tools/stamp_report.py)")
     ap.add_argument("--check-every", type=int, default=None, help="CG iterations between host convergence checks")
     args = ap.parse_args()
+    # the SpMV's in-kernel stamps / dispatch events and the roofline they feed: --full, or asked for by the stamp options themselves
+    kernels = args.full or args.sample_every > 0 or args.stamp_dump is not None
 
     # The host interpreter's cyclic garbage collector pauses for ~80 ms when it runs a FULL collection over torch's and numpy's
     # object graph (seen as one 10 ms "launch" in an event bracket and as 9 ms blocks of ten 0.15 ms steps).  Switching it off is
@@ -335,19 +380,28 @@ def main():
         return float(np.sum(kept)) / len(kept), len(bs) - len(kept)
 
     N_STREAM = 434874            # UCI 3droad size: a pass never streams more points than the dataset holds
+    pass_points = (N_STREAM - args.n_init) // world      # per rank; a longer stream (one block longer than a pass) is drawn on the device
 
-    def run_stream(kind, exchange, blocks, seed0, profile):
-        """`blocks` timed blocks of K steps.  A *pass* = fresh model on the init data, cold solve, W un-timed warm-up steps,
-        then as many timed K-step blocks as fit into a 3droad-sized stream (N_STREAM points over all ranks); passes are
+    def auto_blocks(step_s, Kb):
+        """The --blocks 0 rule for blocks of Kb steps, from the fastest warm-up step: >= ~0.3 s of blocks, <= 2400 steps,
+        at least 3 blocks."""
+        R_ = int(max(5, math.ceil(0.3 / max(step_s * Kb, 1e-6))))
+        return max(3, min(R_, 2400 // max(Kb, 1)))
+
+    def run_stream(kind, exchange, blocks, seed0, profile, steps=None):
+        """`blocks` timed blocks of `steps` (default K) steps.  A *pass* = fresh model on the init data, cold solve, W un-timed warm-up steps,
+        then as many timed blocks as fit into a 3droad-sized stream (N_STREAM points over all ranks); passes are
         repeated on fresh points until `blocks` blocks have been timed (blocks <= 0: enough for ~0.3 s).
-        Returns (model, updater, per-block seconds [MAX over ranks], CG iterations per step, SpMV event ms, SpMV launches)."""
+        Returns (model, updater, per-block seconds [MAX over ranks], CG iterations per step, SpMV event ms, SpMV launches);
+        run_stream.step_est = the fastest warm-up step of the last pass [MAX over ranks] (what --blocks 0 sizes R by)."""
+        K = args.steps if steps is None else steps        # this leg's block length (the headline's K unless `steps` is given)
         per_pass = max(1, ((N_STREAM - args.n_init) // (q * world) - Wm) // K)
         X0, y0 = synth_stream(args.n_init, d, seed0, dev, dtype, kind)        # identical init on every rank
         block_s, iters = [], []
         ms_sum, n_launch = 0.0, 0
         st_sum, st_n, st_each = 0.0, 0, []
         R, p = blocks, 0
-        model = upd = None
+        model = upd = mean = None
         while R <= 0 or len(block_s) < R:
             model = upd = None
             gc_settle()                                    # the previous pass's model (reference cycles) goes before the new one allocates
@@ -373,20 +427,22 @@ def main():
             gc_settle()
             nb = per_pass if R <= 0 else min(per_pass, R - len(block_s))
             ev_block = profile and p == 0 and args.sample_every <= 0     # one extra, UN-TIMED block whose SpMV dispatches carry events
-            Xs, ys = synth_stream((Wm + per_pass * K) * q, d, seed0 + 1000 + 97 * p + rank, dev, dtype, kind)
-            lib.wiski_prof_start(ctypes.c_int32(256))      # creates the event pool outside the timed region
-            lib.wiski_prof_stop(None, None)
+            n_pass = (Wm + per_pass * K) * q
+            Xs, ys = synth_stream(n_pass, d, seed0 + 1000 + 97 * p + rank, dev, dtype, kind, on_device=n_pass > pass_points)
+            if profile:
+                lib.wiski_prof_start(ctypes.c_int32(256))  # creates the event pool outside the timed region
+                lib.wiski_prof_stop(None, None)
             tw = float("inf")
             for t in range(Wm):                            # un-timed warm-up; the fastest step sizes the number of blocks
                 torch.cuda.synchronize(); t0 = time.perf_counter()
                 step(Xs[t * q:(t + 1) * q], ys[t * q:(t + 1) * q])
                 torch.cuda.synchronize(); tw = min(tw, time.perf_counter() - t0)
+            est = torch.tensor([tw if Wm > 0 else 4e-4], dtype=torch.float64, device=dev)
+            if world > 1:
+                dist.all_reduce(est, op=dist.ReduceOp.MAX)
+            run_stream.step_est = float(est.item())
             if R <= 0:                                      # same R on every rank: >= ~0.3 s of timed blocks, <= 2400 steps
-                est = torch.tensor([tw if Wm > 0 else 4e-4], dtype=torch.float64, device=dev)
-                if world > 1:
-                    dist.all_reduce(est, op=dist.ReduceOp.MAX)
-                R = int(max(5, math.ceil(0.3 / max(float(est.item()) * K, 1e-6))))
-                R = max(3, min(R, 2400 // max(K, 1)))
+                R = auto_blocks(run_stream.step_est, K)
                 nb = min(per_pass, R)
             for r in range(nb):
                 barrier()
@@ -399,7 +455,7 @@ def main():
                     sampled = profile and args.sample_every > 0 and t % args.sample_every == 0   # (option) events inside the timed region
                     if sampled:
                         lib.wiski_prof_enable(ctypes.c_int32(1))
-                    _, it = step(Xs[t * q:(t + 1) * q], ys[t * q:(t + 1) * q])
+                    mean, it = step(Xs[t * q:(t + 1) * q], ys[t * q:(t + 1) * q])
                     iters.append(it)
                     if sampled:
                         lib.wiski_prof_enable(ctypes.c_int32(0))
@@ -432,7 +488,7 @@ def main():
                 # the second clock, outside the timed region: the next K steps of the same stream with start/stop events on every SpMV
                 # dispatch (in-kernel stamps show what the events do to the dispatch they ride on: +0.8 us, the waves of six XCDs start
                 # 1.2 us after the other two -- profiles/r06_spmv_tail.txt section 5)
-                Xe, ye = synth_stream(K * q, d, seed0 + 5000 + rank, dev, dtype, kind)
+                Xe, ye = synth_stream(K * q, d, seed0 + 5000 + rank, dev, dtype, kind, on_device=K * q > pass_points)
                 barrier()
                 lib.wiski_prof_start(ctypes.c_int32(256))
                 for k in range(K):
@@ -448,6 +504,7 @@ def main():
         if world > 1:
             dist.all_reduce(bt, op=dist.ReduceOp.MAX)
         run_stream.stamps = (st_sum, st_n, st_each)
+        run_stream.last_mean = mean                        # what the last timed step returned to its caller
         if args.stamp_dump and profile and rank == 0 and run_stream.raw:
             np.savez_compressed(args.stamp_dump, **{f"d{i:04d}": r for i, r in enumerate(run_stream.raw)})
         return model, upd, bt.tolist(), iters, ms_sum, n_launch
@@ -478,8 +535,7 @@ def main():
             if calib.get("stencil") is None:
                 os.environ["WISKI_BENCH_NO_STENCIL_SHARD"] = "1"       # (the fallback below and the extras must not try it again)
         try:
-            model, upd, block_s, iters, spmv_ms, spmv_n = run_stream(args.stream, headline_ex, args.blocks, 0, profile=os.environ.get("WISKI_BENCH_NOSAMPLE") != "1")
-            stamp_ms, stamp_n, stamp_each = run_stream.stamps
+            model, upd, block_s, iters, _, _ = run_stream(args.stream, headline_ex, args.blocks, 0, profile=False)
             headline_note = None
         except Exception as exc:  # noqa: BLE001
             if world == 1:
@@ -488,9 +544,17 @@ def main():
             # line falls back to the point / statistics exchange and says so (every rank takes this branch: the failure is collective)
             headline_note = ("stencil-sharded step failed, fell back: " + repr(exc))[:300]
             os.environ["WISKI_BENCH_NO_STENCIL_SHARD"] = "1"
-            model, upd, block_s, iters, spmv_ms, spmv_n = run_stream(args.stream, "auto", args.blocks, 0, profile=False)
-            stamp_ms, stamp_n, stamp_each = 0.0, 0, []
+            model, upd, block_s, iters, _, _ = run_stream(args.stream, "auto", args.blocks, 0, profile=False)
+        if args.dump_outputs and rank == 0:
+            # what a caller of the timed path received from its last step: the predictive mean of the batch (returned by the step) and the
+            # refreshed posterior mean on the inducing grid (the model's prediction_cache["pred_mean"], read without touching the model)
+            ms_ = model._mean_state
+            dump_outputs(args.dump_outputs, {"batch_mean": run_stream.last_mean,
+                                             "inducing_mean": ms_["U"][0] if ms_ is not None else model.prediction_cache["pred_mean"][0, :, 0]})
         R = len(block_s)
+        # the extra legs are sized as the headline was before --steps set the timed region: the --blocks 0 rule on the headline's
+        # fastest warm-up step
+        R_ext = R if args.blocks <= 0 else auto_blocks(run_stream.step_est, K)
         med = float(np.median(block_s))
         # the headline counts EVERY timed block (round 5; rounds 1-4 left blocks > 1.5x the median out as host hiccups and said so): what a
         # hiccup-free mean would read is in extra, with the blocks it would have left out
@@ -502,7 +566,7 @@ def main():
                  "blocks_over_1.5x_median_ms": [b * 1e3 for b in block_s if b > 1.5 * med],
                  "timed_region_s": float(np.sum(block_s)), "cg_iters_per_step_mean": float(np.mean(iters)),
                  "stream_points_per_pass": int(model.num_data), "note": "each pass re-starts from the init data and streams at most a 3droad-sized "
-                 "stream (434 874 points) of fresh synthetic points"}
+                 "stream (434 874 points) of fresh synthetic points, or one block of K steps where that is longer"}
         exchange_used = upd.last_exchange
         tr = model.__dict__.get("_two_level")
         extra["two_level_preconditioner"] = ({"rank": tr.block.r, "refreshes_in_last_pass": tr.block.refreshes, "growth": settings.two_level_growth.value(),
@@ -514,12 +578,28 @@ def main():
             extra["exchange_calibration_ms_per_step"] = calib
             extra["exchange_chosen"] = headline_ex
 
-        if world > 1 and not args.no_extras:
+        # the roofline leg (--full, or the stamp options): in-kernel stamps on EVERY SpMV dispatch of its blocks and start / stop events on
+        # every SpMV dispatch of one extra un-timed block, as the headline took them before --steps set the timed region -- blocks of
+        # min(K, PROF_BLOCK_STEPS) steps by the --blocks 0 rule, same stream and seeds -- but in a leg of its own: the timed headline
+        # carries no stamps, and a block's dispatches always fit the stamp arena and the event pool (both re-armed per block)
+        prof, spmv_ms, spmv_n, stamp_ms, stamp_n, stamp_each = None, 0.0, 0, 0.0, 0, []
+        if kernels:
+            try:
+                Kp = min(K, PROF_BLOCK_STEPS)
+                _, _, pb, pit, spmv_ms, spmv_n = run_stream(args.stream, "auto" if headline_note else headline_ex, 0, 0,
+                                                            profile=os.environ.get("WISKI_BENCH_NOSAMPLE") != "1", steps=Kp)
+                stamp_ms, stamp_n, stamp_each = run_stream.stamps
+                prof = {"blocks": len(pb), "steps_per_block": Kp, "ms_per_step": float(np.sum(pb)) / (len(pb) * Kp) * 1e3,
+                        "cg_iters_per_step_mean": float(np.mean(pit))}
+            except Exception as exc:  # noqa: BLE001
+                extra.setdefault("errors", []).append(("roofline leg: " + repr(exc))[:400])
+
+        if world > 1 and args.full and not args.no_extras:
             try:                                   # same on every rank (deterministic legs): a failure is recorded, the headline line survives
                 # both exchanges, timed the same way: the point exchange divides no work (every rank scatters
                 # all N q points and solves), the statistics all-reduce is the north-star form
                 for ex in ("stencil", "points", "stats"):
-                    _, _, bs, its, _, _ = run_stream(args.stream, ex, max(3, R // 4), 0, profile=False)
+                    _, _, bs, its, _, _ = run_stream(args.stream, ex, max(3, R_ext // 4), 0, profile=False)
                     extra[f"updates_per_s_exchange_{ex}"] = world * K * q / (float(np.sum(bs)) / len(bs))
                     extra[f"cg_iters_exchange_{ex}"] = float(np.mean(its))
                     extra[f"cg_iters_exchange_{ex}_last_block"] = float(np.mean(its[-K:]))
@@ -542,18 +622,18 @@ def main():
                 extra.setdefault("errors", []).append(("extras (N > 1 legs): " + repr(exc))[:400])
 
         roofline_secondary = None
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             try:                                   # an extra that fails must not cost the JSON line: the error is recorded instead
                 # second value: the road-like clustered stream of SURVEY 8d (3droad IS road-like)
                 other = "clustered" if args.stream == "uniform" else "uniform"
-                _, _, bs, its, _, _ = run_stream(other, "auto", R, 0, profile=False)          # as many blocks as the headline, same seeds
+                _, _, bs, its, _, _ = run_stream(other, "auto", R_ext, 0, profile=False)      # as many blocks as the headline's --blocks 0 rule, same seeds
                 extra[f"{other}_stream_updates_per_s"] = K * q / (float(np.sum(bs)) / len(bs))
                 extra[f"{other}_stream_cg_iters_per_step_mean"] = float(np.mean(its))
 
                 # the reference's own CG tolerance (config/regression.yaml:24-27: cg_tolerance 1e-2; the headline uses 1e-4), and what
                 # each tolerance costs in accuracy: predictive mean after the same 24 streamed steps against a 1e-7 solve
                 with settings.cg_tolerance(1e-2):
-                    _, _, bs, its, _, _ = run_stream(args.stream, "auto", max(3, R // 3), 0, profile=False)
+                    _, _, bs, its, _, _ = run_stream(args.stream, "auto", max(3, R_ext // 3), 0, profile=False)
                 extra["updates_per_s_at_reference_cg_tolerance_1e-2"] = K * q / (float(np.sum(bs)) / len(bs))
                 extra["cg_iters_per_step_mean_at_1e-2"] = float(np.mean(its))
                 Xa, ya = synth_stream(args.n_init, d, 0, dev, dtype, args.stream)
@@ -729,7 +809,7 @@ def main():
             except Exception as exc:  # noqa: BLE001
                 extra.setdefault("errors", []).append(("extras (stream / roofline legs): " + repr(exc))[:400])
 
-    if world == 1 and not args.no_extras:
+    if world == 1 and args.full and not args.no_extras:
         try:
             # predictive variances of 64 queries, two ways: the product's default path (on this grid and kernel the spectral
             # Woodbury factor, lazy/spectral_woodbury.py: one projection kernel + one fp64 GEMM against the cached factor) and
@@ -900,14 +980,14 @@ def main():
             g_lo, g_hi = shard_groups(d, 0, world)
             spmv_bytes = sum(b - a for a, b in half_stencil_group_slices(grid, g_lo, g_hi)) * es + 3 * grid.m * es
         # two clocks: (a) stamps taken inside the kernel -- earliest wave start to latest wave end of a dispatch (100 MHz wall clock,
-        # wiski_prof_stamps): the kernel alone, what rocprofv3's begin / end timestamps measure too.  They cost nothing measurable, so
-        # EVERY SpMV dispatch of the timed blocks carries them (a stride-4 sample of the steps, the round-6 first cut, read 0.55-0.60
-        # from one run to the next with ~115 dispatches: profiles/r06_spmv_tail.txt section 4);
+        # wiski_prof_stamps): the kernel alone, what rocprofv3's begin / end timestamps measure too.  EVERY SpMV dispatch of the roofline
+        # leg's blocks carries them (a stride-4 sample of the steps, the round-6 first cut, read 0.55-0.60 from one run to the next with
+        # ~115 dispatches: profiles/r06_spmv_tail.txt section 4);
         # (b) the start / stop HIP events attached to the dispatch packet, which bracket [predecessor complete -> this kernel complete]
         # and so contain the ~2.4 us of dispatch latency in front of the first wave.  The events are not free -- the stamps of the
         # dispatches they ride on read 0.8 us more, the waves of six XCDs start 1.2 us after those of the other two, the step is 5 %
-        # slower with all of them on (profiles/r06_spmv_tail.txt section 5) -- so they are taken in ONE extra block of K steps of the
-        # same stream, outside the timed region.  `achieved` / `frac` use (a) where the kernel is stamped (k_spmv_sym_dma); (b) is
+        # slower with all of them on (profiles/r06_spmv_tail.txt section 5) -- so they are taken in ONE extra block of the roofline leg,
+        # outside its stamped blocks.  `achieved` / `frac` use (a) where the kernel is stamped (k_spmv_sym_dma); (b) is
         # reported beside it (event_*).
         ev_ms = spmv_ms / max(spmv_n, 1)
         ev_achieved = spmv_bytes / (ev_ms * 1e-3) / 1e9 if spmv_n else 0.0
@@ -952,9 +1032,12 @@ def main():
                                     "stats": "all-reduce of the half-stencil statistics"}.get(exchange_used, str(exchange_used)) + ")"
         # what an empty dispatch costs by the clock of `roofline.avg_launch_us` (events attached to the dispatch packet)
         empty_us = ctypes.c_double(0)
-        if lib.wiski_prof_empty(ctypes.c_int32(64), ctypes.byref(empty_us), _hip.stream_ptr(dev)) != 0:
+        if kernels and lib.wiski_prof_empty(ctypes.c_int32(64), ctypes.byref(empty_us), _hip.stream_ptr(dev)) != 0:
             empty_us.value = float("nan")
         net_us = ev_ms * 1e3 - empty_us.value
+        # a block longer than a 3droad-sized pass streams on past 434 874 points (drawn on the device)
+        stream_desc = ("3droad-sized synthetic stream" if Wm + K <= (N_STREAM - args.n_init) // (q * world) else
+                       f"synthetic stream longer than 3droad (init {args.n_init} + {(Wm + K) * q * world} streamed points in one pass)")
         res = {
             "metric": "streaming updates/sec (WISKI, 50^3 inducing grid)",
             "timed_region_s": float(np.sum(block_s)),
@@ -971,52 +1054,53 @@ def main():
             "dtype": args.dtype,
             "data": "synthetic",
             "collective": collective,
-            "config": {"workload": ("road-like CLUSTERED (points along 64 poly-lines, sigma 0.02: SURVEY 8d's stand-in for UCI 3droad; the uniform variant: extra.uniform_stream_*) " if args.stream == "clustered" else "UNIFORM (the road-like clustered variant of SURVEY 8d: extra.clustered_stream_*) ") + f"3droad-sized synthetic stream d={d}, {args.grid}^{d} inducing grid (m={grid.m}), RBF-ARD fixed hypers, "
+            "config": {"workload": ("road-like CLUSTERED (points along 64 poly-lines, sigma 0.02: SURVEY 8d's stand-in for UCI 3droad; the uniform variant: extra.uniform_stream_*) " if args.stream == "clustered" else "UNIFORM (the road-like clustered variant of SURVEY 8d: extra.clustered_stream_*) ") + stream_desc + f" d={d}, {args.grid}^{d} inducing grid (m={grid.m}), RBF-ARD fixed hypers, "
                                    f"CG solve path, q={q} points/step/GPU, init {args.n_init} points, cg_tol={tol:g}; {R} timed blocks of {K} steps (all steps / summed block time)",
                        "batch_per_gpu": q, "global_batch": q * world, "parallelism": par},
-            "roofline": {"bound": "hbm", "kernel": kname + " (symmetric half-stencil A_h . p inside wiski_pcg)", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                         "launches": stamp_n if stamped else spmv_n, "avg_launch_us": avg_ms * 1e3, "algorithmic_bytes_per_launch": spmv_bytes,
-                         "clock": ("in-kernel stamps: earliest wave start -> latest wave end of EVERY dispatch of the timed blocks (s_memrealtime, 100 MHz), wiski_prof_stamps"
-                                   if stamped else "HIP events attached to each dispatch (this kernel carries no in-kernel stamps)"),
-                         "median_launch_us": float(np.median(stamp_each)) if (stamped and stamp_each) else None,
-                         "frac_at_median_launch": (spmv_bytes / (float(np.median(stamp_each)) * 1e-6) / 1e9 / HBM_PEAK_GBS) if (stamped and stamp_each) else None,
-                         "launches_over_1.25x_median": int(np.sum(np.asarray(stamp_each) > 1.25 * np.median(stamp_each))) if (stamped and stamp_each) else None,
-                         "launch_us_percentiles_10_25_50_75_90_95_99": [float(v) for v in np.percentile(stamp_each, [10, 25, 50, 75, 90, 95, 99])] if (stamped and stamp_each) else None,
-                         "event_launches": spmv_n, "event_avg_launch_us": ev_ms * 1e3, "event_achieved": ev_achieved, "event_frac": ev_achieved / HBM_PEAK_GBS,
-                         # everything in `committed_take` (and `traffic` above) was read back from files under profiles/: a separate run of
-                         # this command under rocprofv3, committed with the round -- evidence beside this run's own events, not part of them
-                         "committed_take": {"rocprofv3_avg_launch_us": rp_us, "rocprofv3_frac": (spmv_bytes / (rp_us * 1e-6) / 1e9 / HBM_PEAK_GBS) if rp_us else None,
-                                            "source": rp_src},
-                         # how to read `frac`: the 86 MB operand is re-read every launch and is served by the 256 MB Infinity
-                         # Cache, not by HBM (a bare LDS-DMA read of it runs at 7.2-8 TB/s, profiles/r02_stream_ubench.txt);
-                         # and every per-dispatch time contains what an empty dispatch costs by the same clock
-                         "infinity_cache_resident": bool(spmv_bytes < 200e6),
-                         "empty_dispatch_us": empty_us.value,
-                         "net_of_empty_dispatch_frac": (spmv_bytes / (net_us * 1e-6) / 1e9 / HBM_PEAK_GBS) if net_us > 0 else None,
-                         "timing": "avg_launch_us / achieved / frac: the kernel's own begin / end stamps (first wave started -> last wave finished) of every SpMV dispatch of the timed blocks, read once per block after it has drained; event_*: the start/stop HIP events attached to every SpMV dispatch of one extra, un-timed block of the same stream (hipExtLaunchKernel; inside the timed region they would perturb what they measure: +0.8 us per dispatch by the stamps), whose pair brackets [predecessor complete -> this kernel complete] and so contains the dispatch latency in front of the first wave (an empty kernel reads ~4 us by it)",
-                         # context only: SURVEY.md 8(d) prices this product at the FULL stencil (R m s + 2 m s); the kernel
-                         # computes the same A.p from the symmetric half, so `frac` above uses the bytes it really needs
-                         "survey_8d_full_stencil_bytes": grid.R * grid.m * es + 2 * grid.m * es},
             "extra": extra,
         }
+        if kernels:                             # per-kernel figures: --full (or the stamp options)
+            res["roofline"] = {"bound": "hbm", "kernel": kname + " (symmetric half-stencil A_h . p inside wiski_pcg)", "achieved": achieved, "peak": HBM_PEAK_GBS,
+                               "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
+                               "launches": stamp_n if stamped else spmv_n, "avg_launch_us": avg_ms * 1e3, "algorithmic_bytes_per_launch": spmv_bytes, "leg": prof,
+                               "clock": ("in-kernel stamps: earliest wave start -> latest wave end of EVERY dispatch of the roofline leg's blocks (s_memrealtime, 100 MHz), wiski_prof_stamps"
+                                         if stamped else "HIP events attached to each dispatch (this kernel carries no in-kernel stamps)"),
+                               "median_launch_us": float(np.median(stamp_each)) if (stamped and stamp_each) else None,
+                               "frac_at_median_launch": (spmv_bytes / (float(np.median(stamp_each)) * 1e-6) / 1e9 / HBM_PEAK_GBS) if (stamped and stamp_each) else None,
+                               "launches_over_1.25x_median": int(np.sum(np.asarray(stamp_each) > 1.25 * np.median(stamp_each))) if (stamped and stamp_each) else None,
+                               "launch_us_percentiles_10_25_50_75_90_95_99": [float(v) for v in np.percentile(stamp_each, [10, 25, 50, 75, 90, 95, 99])] if (stamped and stamp_each) else None,
+                               "event_launches": spmv_n, "event_avg_launch_us": ev_ms * 1e3, "event_achieved": ev_achieved, "event_frac": ev_achieved / HBM_PEAK_GBS,
+                               # everything in `committed_take` (and `traffic` above) was read back from files under profiles/: a separate run of
+                               # this command under rocprofv3, committed with the round -- evidence beside this run's own events, not part of them
+                               "committed_take": {"rocprofv3_avg_launch_us": rp_us, "rocprofv3_frac": (spmv_bytes / (rp_us * 1e-6) / 1e9 / HBM_PEAK_GBS) if rp_us else None,
+                                                  "source": rp_src},
+                               # how to read `frac`: the 86 MB operand is re-read every launch and is served by the 256 MB Infinity
+                               # Cache, not by HBM (a bare LDS-DMA read of it runs at 7.2-8 TB/s, profiles/r02_stream_ubench.txt);
+                               # and every per-dispatch time contains what an empty dispatch costs by the same clock
+                               "infinity_cache_resident": bool(spmv_bytes < 200e6),
+                               "empty_dispatch_us": empty_us.value,
+                               "net_of_empty_dispatch_frac": (spmv_bytes / (net_us * 1e-6) / 1e9 / HBM_PEAK_GBS) if net_us > 0 else None,
+                               "timing": "avg_launch_us / achieved / frac: the kernel's own begin / end stamps (first wave started -> last wave finished) of every SpMV dispatch of the roofline leg (`leg`: blocks of min(K, %d) steps by the --blocks 0 rule on the headline's stream and seeds, run after the headline, whose timed block carries no stamps), read once per block after it has drained; event_*: the start/stop HIP events attached to every SpMV dispatch of one extra, un-timed block of that leg (hipExtLaunchKernel; inside the timed region they would perturb what they measure: +0.8 us per dispatch by the stamps), whose pair brackets [predecessor complete -> this kernel complete] and so contains the dispatch latency in front of the first wave (an empty kernel reads ~4 us by it)" % PROF_BLOCK_STEPS,
+                               # context only: SURVEY.md 8(d) prices this product at the FULL stencil (R m s + 2 m s); the kernel
+                               # computes the same A.p from the symmetric half, so `frac` above uses the bytes it really needs
+                               "survey_8d_full_stencil_bytes": grid.R * grid.m * es + 2 * grid.m * es}
         if roofline_secondary:
             res["roofline_secondary"] = roofline_secondary
             # which kernel the timed step spends most of its time in, from this run's own measurements: the absorb (one launch per
             # step) against the SpMVs of the solve (iterations x per-dispatch time); the roofline kernel is the latter (the metric's MVM)
             sc = next((r_ for r_ in roofline_secondary if r_["kernel"].startswith("k_scatter_stats_sym")), None)
-            if sc is not None and spmv_n:
-                step_us = sec / K * 1e6
-                it_mean = float(np.mean(iters))
+            if sc is not None and spmv_n and prof is not None:
+                step_us = prof["ms_per_step"] * 1e3                       # the roofline leg's own step (its blocks are the old headline's)
+                it_mean = prof["cg_iters_per_step_mean"]
                 res["dominant_by_time"] = {"kernel": "k_scatter_stats_sym (absorb of q points)", "us_per_step": sc["avg_launch_us"],
                                            "share_of_step": sc["avg_launch_us"] / step_us,
                                            "roofline_kernel_us_per_step": it_mean * avg_ms * 1e3, "roofline_kernel_share_of_step": it_mean * avg_ms * 1e3 / step_us,
-                                           "note": "kernel-only times of this run (event brackets / per-dispatch events) over the measured ms_per_step"}
+                                           "note": "kernel-only times of this run (event brackets / per-dispatch stamps) over the roofline leg's ms_per_step"}
         # SURVEY 8(d)'s batch sizes for the plain step (evaluate mean -> absorb -> refresh, fixed hyper-parameters), beside the headline's q
         if all(k_ in extra for k_ in ("step_ms_q1", "step_ms_q64", "step_ms_q1024", "updates_per_s_q16384")):
             extra["plain_step_updates_per_s_by_q"] = {"1": 1e3 / extra["step_ms_q1"], "64": 64e3 / extra["step_ms_q64"], "1024": 1024e3 / extra["step_ms_q1024"],
                                                       str(q): world * K * q / sec, "16384": extra["updates_per_s_q16384"]}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline(args, tol)
             except Exception as exc:  # noqa: BLE001

@@ -64,9 +64,51 @@ def sources():
     return [os.path.join(_CSRC, s) for s in _SOURCES if os.path.exists(os.path.join(_CSRC, s))]
 
 
+_COMPILE_BYTES = 512 << 20     # memory budget of one hipcc -c (the largest source peaks at ~270 MB)
+
+
+def _build_jobs(n):
+    """Concurrent compiles: at most n, the CPUs this process may use (affinity, cgroup CPU quota), MAX_JOBS when set, and
+    what the memory limit leaves room for (cgroup memory.max less what is in use, MemAvailable) at _COMPILE_BYTES each.
+    os.cpu_count() alone over-subscribes a container that shows far more CPUs or memory than its limits allow."""
+    cpus = os.cpu_count() or 1
+    try:
+        cpus = min(cpus, len(os.sched_getaffinity(0)))
+    except (AttributeError, OSError):
+        pass
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+        if quota != "max":
+            cpus = min(cpus, max(1, -(-int(quota) // int(period))))
+    except (OSError, ValueError):
+        pass
+    free = []
+    try:
+        lim = open("/sys/fs/cgroup/memory.max").read().strip()
+        if lim != "max":
+            free.append(int(lim) - int(open("/sys/fs/cgroup/memory.current").read()))
+    except (OSError, ValueError):
+        pass
+    try:
+        for line in open("/proc/meminfo"):
+            if line.startswith("MemAvailable:"):
+                free.append(int(line.split()[1]) * 1024)
+    except (OSError, ValueError, IndexError):
+        pass
+    jobs = min(n, cpus)
+    if free:
+        jobs = min(jobs, min(free) // _COMPILE_BYTES)
+    try:
+        jobs = min(jobs, int(os.environ["MAX_JOBS"]))
+    except (KeyError, ValueError):
+        pass
+    return max(1, jobs)
+
+
 def build(force=False, verbose=False):
     """Compile every HIP source for gfx950 into csrc/libwiski_hip.so: one object per source (built concurrently, only when
-    the source or a header is newer than its object), then one link."""
+    the source or a header is newer than its object), then one link.  Every output is written under a temporary name and
+    renamed into place, so that a build cut short leaves no partial file that a later build would take for current."""
     from concurrent.futures import ThreadPoolExecutor
 
     srcs = sources()
@@ -82,22 +124,28 @@ def build(force=False, verbose=False):
     objdir = os.path.join(_HERE, "..", "build", "obj")
     os.makedirs(objdir, exist_ok=True)
     objs, todo = [], []
+    tmp = ".%d.tmp" % os.getpid()                    # per process: two builds at once never write the same file
     for src in srcs:
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         objs.append(obj)
         if force or not os.path.exists(obj) or os.path.getmtime(obj) < max(os.path.getmtime(src), hdr_time):
-            todo.append([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", src, "-o", obj])
+            todo.append(([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", src, "-o", obj + tmp], obj))
     if not todo and os.path.exists(_SO) and all(os.path.getmtime(o) <= os.path.getmtime(_SO) for o in objs):
         return _SO
 
-    def run(cmd):
+    def run(job):
+        cmd, out = job
         if verbose:
-            print(" ".join(cmd))
+            print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
+        os.replace(cmd[cmd.index("-o") + 1], out)
 
-    with ThreadPoolExecutor(max_workers=max(1, min(len(todo), os.cpu_count() or 1))) as ex:
+    jobs = _build_jobs(len(todo)) if todo else 1
+    if verbose:
+        print(f"{len(todo)} HIP sources to compile, {jobs} at a time", flush=True)
+    with ThreadPoolExecutor(max_workers=jobs) as ex:
         list(ex.map(run, todo))
-    run([hipcc, "--offload-arch=gfx950", "-fPIC", "-shared", "-o", _SO] + objs + ["-ldl"])
+    run(([hipcc, "--offload-arch=gfx950", "-fPIC", "-shared", "-o", _SO + tmp] + objs + ["-ldl"], _SO))
     return _SO
 
 

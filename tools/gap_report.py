@@ -1,5 +1,5 @@
 """GPU-busy fraction and the largest inter-kernel gaps of a streaming run, from a rocprofv3 kernel_trace.csv
-(`rocprofv3 --kernel-trace --output-format csv -- python bench.py --no-cpu-baseline --no-extras`)."""
+(`rocprofv3 --kernel-trace --output-format csv -- python bench.py --blocks 8`: a plain run, no extras, no cpu_baseline)."""
 import csv
 import sys
 
