@@ -82,6 +82,10 @@ int wiski_gather_grad_f64(const wiski_grid* grid, const double* d_x, int64_t n, 
  * used for W* M with the cached dense posterior M of small grids (BFN:222-225). */
 int wiski_gather_rows_f32(const wiski_grid* grid, const float* d_x, int64_t n, const float* d_Vr, int32_t ncols, float* d_out, int32_t* d_err, void* stream);
 int wiski_gather_rows_f64(const wiski_grid* grid, const double* d_x, int64_t n, const double* d_Vr, int32_t ncols, double* d_out, int32_t* d_err, void* stream);
+/* Input gradient (VJP) of wiski_gather_rows: d_gx[n][d] = sum_c d_G[p][c] * d/dx_p ( W(x_p) Vr )[c] for the upstream gradient d_G[n][ncols]
+ * (same row-major d_Vr[m][ncols]).  Zero derivative in the one-hot boundary cells (as wiski_gather_grad); n = 0 is a no-op. */
+int wiski_gather_rows_vjp_f32(const wiski_grid* grid, const float* d_x, int64_t n, const float* d_Vr, int32_t ncols, const float* d_G, float* d_gx, void* stream);
+int wiski_gather_rows_vjp_f64(const wiski_grid* grid, const double* d_x, int64_t n, const double* d_Vr, int32_t ncols, const double* d_G, double* d_gx, void* stream);
 
 /* a14, ELL form -- same product from materialised (idx, val) rows of width T
  * (the layout InterpolatedLazyTensor keeps; BFN:206-210). k == 1 only. */
@@ -443,6 +447,12 @@ int wiski_root_update_f64(int32_t m, int32_t r, int32_t q, double* d_L, int32_t 
  *                         sum_jj' Wt[j][j'] b_j^T (kron_q SymToeplitz(tcol_q)) b_j' w.r.t. tcol_q -- the MLL backward (BWM:19-51). */
 int wiski_basis_project_f32(const wiski_grid* grid, const float* d_x, int64_t n, const double* d_V, int32_t kmax, const int32_t* d_S, int32_t r, const float* d_scale, const double* d_colscale, const double* d_tcol, double* d_F, int64_t ldf, double* d_prior, int32_t* d_err, void* stream);
 int wiski_basis_project_f64(const wiski_grid* grid, const double* d_x, int64_t n, const double* d_V, int32_t kmax, const int32_t* d_S, int32_t r, const double* d_scale, const double* d_colscale, const double* d_tcol, double* d_F, int64_t ldf, double* d_prior, int32_t* d_err, void* stream);
+/* Input gradient (VJP) of wiski_basis_project through both outputs: d_gx[n][d] (the dtype of d_x) = d/dx_p of
+ * sum_j d_GF[p][j] F[p][j] + d_Gprior[p] prior[p] for the upstream gradients d_GF [n, r] (fp64, leading dimension ldg) and d_Gprior [n]
+ * (fp64, may be NULL; needs d_tcol).  Same d_V / kmax / d_S / d_scale / d_colscale as the forward (d_scale is a constant, not differentiated).
+ * Zero derivative in the one-hot boundary cells and at points outside the grid; fp64 accumulation; deterministic (no atomics). */
+int wiski_basis_project_vjp_f32(const wiski_grid* grid, const float* d_x, int64_t n, const double* d_V, int32_t kmax, const int32_t* d_S, int32_t r, const float* d_scale, const double* d_colscale, const double* d_tcol, const double* d_GF, int64_t ldg, const double* d_Gprior, float* d_gx, void* stream);
+int wiski_basis_project_vjp_f64(const wiski_grid* grid, const double* d_x, int64_t n, const double* d_V, int32_t kmax, const int32_t* d_S, int32_t r, const double* d_scale, const double* d_colscale, const double* d_tcol, const double* d_GF, int64_t ldg, const double* d_Gprior, double* d_gx, void* stream);
 /* h[j] += sum_p F[p][j] t_p with t_p = d_wby[p] (/ d_scale[p] when the rows of F carry that scale; NULL: none): W^T D^-1 y of a batch in the
  * basis of F (wiski_basis_project), the right-hand-side half of a streamed update of the spectral factor's statistics (BFN:160). */
 int wiski_basis_absorb_h_f32(int64_t n, int32_t r, const double* d_F, int64_t ldf, const float* d_wby, const float* d_scale, double* d_h, void* stream);

@@ -331,6 +331,95 @@ static int gather_rows_impl(const wiski_grid* grid, const real* d_x, int64_t n, 
   return WISKI_OK;
 }
 
+// ------------------------------------------------ row-major gather: VJP ---
+// gx[p][q] = sum_c G[p][c] * d/dx_pq ( sum_a val_a(x_p) * Vr[idx_a(x_p)][c] ): the input gradient of k_gather_rows (the dense
+// posterior's W* M and its root W* L_M).  One block per query, like the forward.  The taps' flat index and their D derivative
+// weights (the other dims' cubic weights times this dim's k'(s)/h; zero in the one-hot boundary cells, as k_gather_grad) go to
+// LDS; the 256 threads are (tap slice) x (column) with L = min(256, pow2 >= ncols) lanes on consecutive columns, so a tap still
+// reads a contiguous row segment of Vr while narrow operands (the root of a 16^2 grid has 256 columns, a q-batch's rows a few)
+// keep every thread busy on a slice of the taps.  Each thread keeps D fp64 accumulators, one block reduction at the end.
+template <typename real, int D>
+__global__ __launch_bounds__(256) void k_gather_rows_vjp(GridDev<real> G, const real* __restrict__ x, int64_t n, const real* __restrict__ Vr,
+                                                         int ncols, int L, const real* __restrict__ Gout, real* __restrict__ gx) {
+  constexpr int T = 1 << (2 * D);
+  __shared__ int s_idx[T];
+  __shared__ real s_dval[D][T];
+  __shared__ double s_red[4][D];
+  const int64_t p = blockIdx.x;
+  for (int a = threadIdx.x; a < T; a += blockDim.x) {
+    int flat = 0;
+    real wv[D], dv[D];
+#pragma unroll
+    for (int q = 0; q < D; ++q) {
+      real w[4];
+      const real xv = x[p * D + q];
+      int j0 = dim_stencil<real>(xv, G.g0[q], G.h[q], G.hi[q], G.g[q], w);
+      const int c = (a >> (2 * (D - 1 - q))) & 3;
+      const real u = (xv - G.g0[q]) / G.h[q];
+      const real fl = floor(u);
+      const int jj = (int)fl - 1;
+      const bool interior = !(jj < 0 || jj > G.g[q] - 4);
+      if (j0 < 0) { j0 = 0; w[c] = (real)0; }
+      flat += (j0 + c) * G.stride[q];
+      wv[q] = w[c];
+      dv[q] = interior ? keys_cubic_deriv<real>(u - fl + (real)1 - (real)c) / G.h[q] : (real)0;
+    }
+#pragma unroll
+    for (int q = 0; q < D; ++q) {
+      real t = dv[q];
+#pragma unroll
+      for (int o = 0; o < D; ++o)
+        if (o != q) t *= wv[o];
+      s_dval[q][a] = t;
+    }
+    s_idx[a] = flat;
+  }
+  __syncthreads();
+  const int c0 = threadIdx.x % L, a0 = threadIdx.x / L, astep = blockDim.x / L;
+  double acc[D];
+#pragma unroll
+  for (int q = 0; q < D; ++q) acc[q] = 0.0;
+  for (int c = c0; c < ncols; c += L) {
+    const double g = (double)Gout[p * ncols + c];
+    for (int a = a0; a < T; a += astep) {
+      const double v = g * (double)Vr[(int64_t)s_idx[a] * ncols + c];
+#pragma unroll
+      for (int q = 0; q < D; ++q) acc[q] += (double)s_dval[q][a] * v;
+    }
+  }
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+  for (int q = 0; q < D; ++q) {
+    const double s = wave_reduce_sum<double>(acc[q]);
+    if (lane == 0) s_red[wid][q] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < D) {
+    double s = 0.0;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += s_red[w][threadIdx.x];
+    gx[p * D + threadIdx.x] = (real)s;
+  }
+}
+
+template <typename real>
+static int gather_rows_vjp_impl(const wiski_grid* grid, const real* d_x, int64_t n, const real* d_Vr, int32_t ncols, const real* d_G, real* d_gx,
+                                void* stream) {
+  GridDev<real> G;
+  int rc = make_grid_dev<real>(grid, &G);
+  if (rc) return rc;
+  if (n < 0 || ncols < 1) return WISKI_E_BADARG;
+  if (n == 0) return WISKI_OK;
+  if (!d_x || !d_Vr || !d_G || !d_gx) return WISKI_E_BADARG;
+  int L = 1;
+  while (L < ncols && L < 256) L <<= 1;
+  dim3 grd((unsigned)n);
+#define CALL(DD) hipLaunchKernelGGL((k_gather_rows_vjp<real, DD>), grd, dim3(256), 0, (hipStream_t)stream, G, d_x, n, d_Vr, ncols, L, d_G, d_gx)
+  WISKI_DISPATCH_D(G.d, CALL)
+#undef CALL
+  WISKI_LAUNCH_CHECK();
+  return WISKI_OK;
+}
+
 // ------------------------------------------------------------- host side ---
 template <typename real>
 static int interp_impl(const wiski_grid* grid, const real* d_x, int64_t n, int32_t* d_idx, real* d_val, int32_t* d_err, void* stream) {
@@ -562,6 +651,8 @@ int wiski_gather_grad_f32(const wiski_grid* g, const float* x, int64_t n, const 
 int wiski_gather_grad_f64(const wiski_grid* g, const double* x, int64_t n, const double* V, int32_t diag, double* out, void* s) { return gather_grad_impl<double>(g, x, n, V, diag, out, s); }
 int wiski_gather_rows_f32(const wiski_grid* g, const float* x, int64_t n, const float* Vr, int32_t ncols, float* out, int32_t* err, void* s) { return gather_rows_impl<float>(g, x, n, Vr, ncols, out, err, s); }
 int wiski_gather_rows_f64(const wiski_grid* g, const double* x, int64_t n, const double* Vr, int32_t ncols, double* out, int32_t* err, void* s) { return gather_rows_impl<double>(g, x, n, Vr, ncols, out, err, s); }
+int wiski_gather_rows_vjp_f32(const wiski_grid* g, const float* x, int64_t n, const float* Vr, int32_t ncols, const float* G, float* gx, void* s) { return gather_rows_vjp_impl<float>(g, x, n, Vr, ncols, G, gx, s); }
+int wiski_gather_rows_vjp_f64(const wiski_grid* g, const double* x, int64_t n, const double* Vr, int32_t ncols, const double* G, double* gx, void* s) { return gather_rows_vjp_impl<double>(g, x, n, Vr, ncols, G, gx, s); }
 int wiski_gather_ell_f32(const int32_t* idx, const float* val, int64_t n, int32_t T, const float* v, float* out, void* s) { return gather_ell_impl<float>(idx, val, n, T, v, out, s); }
 int wiski_gather_ell_f64(const int32_t* idx, const double* val, int64_t n, int32_t T, const double* v, double* out, void* s) { return gather_ell_impl<double>(idx, val, n, T, v, out, s); }
 int wiski_gather_ell_grid_f32(const wiski_grid* g, const int32_t* idx, const float* val, int64_t n, const float* v, float* vpack, float* out, void* s) { return gather_ell_grid_impl<float>(g, idx, val, n, v, vpack, out, s); }

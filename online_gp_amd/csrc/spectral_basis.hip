@@ -82,6 +82,134 @@ __global__ __launch_bounds__(256) void k_basis_project(GridDev<double> G, const 
   }
 }
 
+// VJP of k_basis_project w.r.t. the points, for both outputs (G_F [n, r] fp64 with leading dimension ldg, G_prior [n] optional):
+//   gx[p, q] = sum_j G_F[p,j] scale_p colscale_j dP_q[S_qj] prod_{q' != q} P_q'[S_q'j]
+//            + G_prior[p] 2 (dw_q^T K_q w_q) prod_{q' != q} (w_q'^T K_q' w_q')
+// with P_q[a] = w_q . V_q[j0 .. j0+3, a] as in the forward and dP_q[a] = dw_q . V_q[j0 .. j0+3, a] (dw_q = d w_q / d x_pq: k'(s)/h,
+// zero in the one-hot boundary cells).  Both tables sit in LDS (d x kmax each), lanes run over the r columns with d fp64
+// accumulators, then one wave reduction per dim.  Few points, many columns (the forward's gridDim.y split): the WPP = 4 waves of a
+// block share one point and deal its columns among them, and the four partial sums meet in LDS in a fixed order -- deterministic, no
+// float atomics and no workspace.
+template <typename real, int D>
+__global__ __launch_bounds__(256) void k_basis_project_vjp(GridDev<double> G, const real* __restrict__ x, int64_t n, const double* __restrict__ V,
+                                                           int kmax, const int32_t* __restrict__ S, int r, const real* __restrict__ scale,
+                                                           const double* __restrict__ colscale, const double* __restrict__ tcol,
+                                                           const double* __restrict__ GF, int64_t ldg, const double* __restrict__ Gprior, int wpp,
+                                                           real* __restrict__ gx) {
+  __shared__ double s_P[4][WISKI_MAX_DIM][SPB_KMAX];
+  __shared__ double s_dP[4][WISKI_MAX_DIM][SPB_KMAX];
+  __shared__ double s_red[4][WISKI_MAX_DIM];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  constexpr int d = D;
+  const int ppb = 4 / wpp, slot = wave / wpp, sub = wave % wpp;
+  for (int64_t p0 = (int64_t)blockIdx.x * ppb; p0 < n; p0 += (int64_t)gridDim.x * ppb) {
+    const int64_t p = p0 + slot;
+    const bool live = p < n;
+    const int64_t pp = live ? p : p0;
+    double w[D][4], dw[D][4];
+    int j0[D];
+    bool ok = true;
+#pragma unroll
+    for (int q = 0; q < d; ++q) {
+      const double xq = (double)x[pp * d + q];
+      int j = dim_stencil<double>(xq, G.g0[q], G.h[q], G.hi[q], G.g[q], w[q]);
+      const double u = (xq - G.g0[q]) / G.h[q];
+      const double fl = floor(u);
+      const int jj = (int)fl - 1;
+      const bool interior = !(jj < 0 || jj > G.g[q] - 4);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) dw[q][c] = interior ? keys_cubic_deriv<double>(u - fl + 1.0 - (double)c) / G.h[q] : 0.0;
+      if (j < 0) {
+        ok = false;
+        j = 0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) w[q][c] = dw[q][c] = 0.0;
+      }
+      j0[q] = j;
+    }
+    int voff = 0;
+#pragma unroll
+    for (int q = 0; q < d; ++q) {
+      if (lane < kmax) {
+        const double* __restrict__ vq = V + (int64_t)voff + (int64_t)j0[q] * kmax + lane;
+        const double v0 = vq[0], v1 = vq[kmax], v2 = vq[2 * kmax], v3 = vq[3 * kmax];
+        s_P[wave][q][lane] = w[q][0] * v0 + w[q][1] * v1 + w[q][2] * v2 + w[q][3] * v3;
+        s_dP[wave][q][lane] = dw[q][0] * v0 + dw[q][1] * v1 + dw[q][2] * v2 + dw[q][3] * v3;
+      }
+      voff += G.g[q] * kmax;
+    }
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    double acc[D];
+#pragma unroll
+    for (int q = 0; q < D; ++q) acc[q] = 0.0;
+    if (live && ok) {
+      const double sc = scale ? (double)scale[p] : 1.0;
+      const double* __restrict__ gf = GF + p * ldg;
+      for (int j = sub * 64 + lane; j < r; j += 64 * wpp) {
+        double coef = sc * gf[j];
+        if (colscale) coef *= colscale[j];
+        double Pj[D], dPj[D];
+#pragma unroll
+        for (int q = 0; q < d; ++q) {
+          const int a = S[(int64_t)q * r + j];
+          Pj[q] = s_P[wave][q][a];
+          dPj[q] = s_dP[wave][q][a];
+        }
+#pragma unroll
+        for (int q = 0; q < d; ++q) {
+          double t = coef * dPj[q];
+#pragma unroll
+          for (int o = 0; o < d; ++o)
+            if (o != q) t *= Pj[o];
+          acc[q] += t;
+        }
+      }
+      if (Gprior && sub == 0 && lane == 0) {
+        // prior = prod_q w_q^T K_q w_q: d/dx_q = 2 (dw_q^T K_q w_q) prod_{q' != q} (w_q'^T K_q' w_q')
+        double qf[D], dqf[D];
+        int toff = 0;
+#pragma unroll
+        for (int q = 0; q < d; ++q) {
+          double f = 0, df = 0;
+#pragma unroll
+          for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+              const double k = tcol[toff + (a > b ? a - b : b - a)];
+              f += w[q][a] * w[q][b] * k;
+              df += dw[q][a] * w[q][b] * k;
+            }
+          qf[q] = f;
+          dqf[q] = 2.0 * df;
+          toff += G.g[q];
+        }
+        const double gp = Gprior[p];
+#pragma unroll
+        for (int q = 0; q < d; ++q) {
+          double t = gp * dqf[q];
+#pragma unroll
+          for (int o = 0; o < d; ++o)
+            if (o != q) t *= qf[o];
+          acc[q] += t;
+        }
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < d; ++q) {
+      const double s = wave_reduce_sum<double>(acc[q]);
+      if (lane == 0) s_red[wave][q] = s;
+    }
+    __syncthreads();
+    if (sub == 0 && lane < d && live) {
+      double s = 0.0;
+      for (int w2 = 0; w2 < wpp; ++w2) s += s_red[wave + w2][lane];
+      gx[p * d + lane] = (real)s;
+    }
+    __syncthreads();
+  }
+}
+
 // D[q][a][a'] (kmax x kmax per dim, zeroed by the caller) from the r x r weight matrix Wt (row-major, ld = r).
 __global__ __launch_bounds__(256) void k_pair_reduce(int d, int r, int kmax, const double* __restrict__ Wt, const int32_t* __restrict__ S,
                                                      const double* __restrict__ ev, double* __restrict__ D) {
@@ -134,7 +262,38 @@ static int basis_project_impl(const wiski_grid* grid, const real* d_x, int64_t n
   return hipGetLastError() == hipSuccess ? WISKI_OK : WISKI_E_LAUNCH;
 }
 
+template <typename real>
+static int basis_project_vjp_impl(const wiski_grid* grid, const real* d_x, int64_t n, const double* d_V, int32_t kmax, const int32_t* d_S, int32_t r,
+                                  const real* d_scale, const double* d_colscale, const double* d_tcol, const double* d_GF, int64_t ldg,
+                                  const double* d_Gprior, real* d_gx, void* stream) {
+  GridDev<double> G;
+  int rc = make_grid_dev<double>(grid, &G);
+  if (rc) return rc;
+  if (n < 0 || r < 1 || kmax < 1 || kmax > SPB_KMAX || ldg < r) return WISKI_E_BADARG;
+  if (n == 0) return WISKI_OK;
+  if (!d_x || !d_V || !d_S || !d_GF || !d_gx || (d_Gprior && !d_tcol)) return WISKI_E_BADARG;
+  const int wpp = (n <= 64 && r > 128) ? 4 : 1;      // the forward's column split: few points, many columns
+  int64_t nb = (n * wpp + 3) / 4;
+  if (nb > 4096) nb = 4096;
+#define CALL(DD)                                                                                                                           \
+  hipLaunchKernelGGL((k_basis_project_vjp<real, DD>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, G, d_x, n, d_V, (int)kmax, d_S, \
+                     (int)r, d_scale, d_colscale, d_tcol, d_GF, ldg, d_Gprior, wpp, d_gx)
+  WISKI_DISPATCH_D(G.d, CALL)
+#undef CALL
+  return hipGetLastError() == hipSuccess ? WISKI_OK : WISKI_E_LAUNCH;
+}
+
 extern "C" {
+int wiski_basis_project_vjp_f32(const wiski_grid* grid, const float* d_x, int64_t n, const double* d_V, int32_t kmax, const int32_t* d_S, int32_t r,
+                                const float* d_scale, const double* d_colscale, const double* d_tcol, const double* d_GF, int64_t ldg,
+                                const double* d_Gprior, float* d_gx, void* stream) {
+  return basis_project_vjp_impl<float>(grid, d_x, n, d_V, kmax, d_S, r, d_scale, d_colscale, d_tcol, d_GF, ldg, d_Gprior, d_gx, stream);
+}
+int wiski_basis_project_vjp_f64(const wiski_grid* grid, const double* d_x, int64_t n, const double* d_V, int32_t kmax, const int32_t* d_S, int32_t r,
+                                const double* d_scale, const double* d_colscale, const double* d_tcol, const double* d_GF, int64_t ldg,
+                                const double* d_Gprior, double* d_gx, void* stream) {
+  return basis_project_vjp_impl<double>(grid, d_x, n, d_V, kmax, d_S, r, d_scale, d_colscale, d_tcol, d_GF, ldg, d_Gprior, d_gx, stream);
+}
 int wiski_basis_project_f32(const wiski_grid* grid, const float* d_x, int64_t n, const double* d_V, int32_t kmax, const int32_t* d_S, int32_t r,
                             const float* d_scale, const double* d_colscale, const double* d_tcol, double* d_F, int64_t ldf, double* d_prior,
                             int32_t* d_err, void* stream) {

@@ -122,10 +122,15 @@ class MultivariateNormal:
         s = self.stddev * 2
         return self.mean - s, self.mean + s
 
-    def rsample(self, sample_shape=torch.Size()):
+    def rsample(self, sample_shape=torch.Size(), base_samples=None):
+        """Draws loc + L z.  ``base_samples`` (optional, shape sample_shape + loc.shape): the standard normal z to use -- a draw is
+        then a deterministic (and differentiable) function of the distribution's parameters, which fixed-sample MC acquisition
+        functions need; they go through the Cholesky factor of the covariance."""
+        if base_samples is not None:
+            sample_shape = base_samples.shape[:base_samples.dim() - self.loc.dim()]
         # a covariance that knows a root of itself (RootLazyTensor; PredictiveCovariance from the spectral or the dense factor) is
         # sampled through it: loc + R z (+ sqrt(extra) z'), exact for R R^T + diag(extra), no n x n factorisation and no jitter
-        rd = getattr(self._covar, "root_decomposition", None)
+        rd = getattr(self._covar, "root_decomposition", None) if base_samples is None else None
         rt = rd() if rd is not None else None
         if rt is not None and rt.root.dim() == 2 and self.loc.dim() == 1:
             z = torch.randn(*sample_shape, rt.root.shape[-1], dtype=rt.root.dtype, device=rt.root.device)
@@ -142,7 +147,10 @@ class MultivariateNormal:
             L, info = torch.linalg.cholesky_ex(cov + (jitter * 10 ** i) * cov.diagonal(dim1=-2, dim2=-1).mean().clamp_min(1e-30) * eye)
             if int(info.max()) == 0:
                 break
-        z = torch.randn(*sample_shape, *self.loc.shape, dtype=cov.dtype, device=cov.device)
+        if base_samples is None:
+            z = torch.randn(*sample_shape, *self.loc.shape, dtype=cov.dtype, device=cov.device)
+        else:
+            z = base_samples.to(device=cov.device, dtype=cov.dtype)
         return self.loc + (L @ z.unsqueeze(-1)).squeeze(-1)
 
     sample = rsample

@@ -160,6 +160,72 @@ def gather_rows(grid, x, Vr, err):
     return out
 
 
+def gather_rows_vjp(grid, x, Vr, G):
+    """Input gradient of :func:`gather_rows`: gx[p] = sum_c G[p, c] d/dx_p (W(x_p) Vr)[c], [n, d] (``wiski_gather_rows_vjp``)."""
+    x = _x2d(x, grid)
+    Vr, G = Vr.contiguous(), G.contiguous().to(x.dtype)
+    assert Vr.shape[0] == grid.m and Vr.dtype == x.dtype and G.shape == (x.shape[0], Vr.shape[1])
+    gx = torch.empty((x.shape[0], grid.d), dtype=x.dtype, device=x.device)
+    rc = _hip.fn("wiski_gather_rows_vjp", x.dtype)(grid.ref, _hip.dptr(x), ctypes.c_int64(x.shape[0]), _hip.dptr(Vr), ctypes.c_int32(Vr.shape[1]),
+                                                   _hip.dptr(G), _hip.dptr(gx), _hip.stream_ptr(x.device))
+    _hip.check(rc, "wiski_gather_rows_vjp")
+    return gx
+
+
+class Gather(torch.autograd.Function):
+    """:func:`gather` (k columns, or ``diag``) differentiable w.r.t. the inputs x and the dense operand V [k, m] (or [n, m] with
+    ``diag``).  x: a few columns take wiski_gather_grad per column (``InterpDot``'s kernel), many take wiski_gather_rows_vjp on V^T;
+    V: the sparse scatter of g_p w_p (``scatter_stats`` per column, ``wt_columns`` rows for ``diag``) -- W itself is never formed."""
+
+    @staticmethod
+    def forward(ctx, grid, x, V, err, diag=False):
+        xd, Vd = x.detach().contiguous(), V.detach().contiguous()
+        ctx.grid, ctx.diag, ctx.err = grid, diag, err
+        ctx.save_for_backward(xd, Vd)
+        return gather(grid, xd, Vd, err, diag=diag)
+
+    @staticmethod
+    def backward(ctx, g):
+        xd, Vd = ctx.saved_tensors
+        grid, V2 = ctx.grid, Vd.reshape(-1, ctx.grid.m)
+        g = g.contiguous()
+        gx = gV = None
+        if ctx.needs_input_grad[1]:
+            if ctx.diag:
+                gx = gather_grad(grid, xd, V2, diag=True) * g[:, None]
+            elif V2.shape[0] <= 4:
+                gx = sum(gather_grad(grid, xd, V2[c]) * g[:, c, None] for c in range(V2.shape[0]))
+            else:
+                gx = gather_rows_vjp(grid, xd, V2.t(), g)
+        if ctx.needs_input_grad[2]:
+            if ctx.diag:
+                gV = wt_columns(grid, xd, ctx.err) * g[:, None]
+            else:
+                gV = torch.zeros_like(V2)
+                ones = torch.ones(xd.shape[0], dtype=xd.dtype, device=xd.device)
+                stats = torch.zeros(2, dtype=torch.float64, device=xd.device)
+                for c in range(V2.shape[0]):
+                    scatter_stats(grid, xd, g[:, c].contiguous(), ones, ones, ones, gV[c], None, stats, ctx.err)
+            gV = gV.reshape(Vd.shape)
+        return None, gx, gV, None, None
+
+
+class GatherRows(torch.autograd.Function):
+    """:func:`gather_rows` differentiable w.r.t. the inputs x (wiski_gather_rows_vjp); Vr is a constant."""
+
+    @staticmethod
+    def forward(ctx, grid, x, Vr, err):
+        xd, Vd = x.detach().contiguous(), Vr.detach().contiguous()
+        ctx.grid = grid
+        ctx.save_for_backward(xd, Vd)
+        return gather_rows(grid, xd, Vd, err)
+
+    @staticmethod
+    def backward(ctx, g):
+        xd, Vd = ctx.saved_tensors
+        return None, gather_rows_vjp(ctx.grid, xd, Vd, g), None, None
+
+
 _ELL_PACK = {}
 
 
@@ -744,6 +810,44 @@ def basis_project(grid, x, V, kmax, S, scale=None, colscale=None, tcol=None, wan
                                                   ctypes.c_int64(r), _hip.dptr(prior), _hip.dptr(err), _hip.stream_ptr(x2.device))
     _hip.check(rc, "wiski_basis_project")
     return (F, prior) if want_prior else F
+
+
+def basis_project_vjp(grid, x, V, kmax, S, GF, Gprior=None, scale=None, colscale=None, tcol=None):
+    """Input gradient of :func:`basis_project` through F (upstream GF [n, r] fp64) and, with `Gprior` [n] (fp64; needs `tcol`), the
+    prior variances: [n, d] in x's dtype (``wiski_basis_project_vjp``; `scale` is a constant)."""
+    x2 = _x2d(x, grid)
+    n, r = x2.shape[0], S.shape[1]
+    GF = GF.to(torch.float64).contiguous()
+    assert GF.shape == (n, r)
+    Gprior = None if Gprior is None else Gprior.to(torch.float64).contiguous()
+    gx = torch.empty((n, grid.d), dtype=x2.dtype, device=x2.device)
+    rc = _hip.fn("wiski_basis_project_vjp", x2.dtype)(grid.ref, _hip.dptr(x2), ctypes.c_int64(n), _hip.dptr(V), ctypes.c_int32(kmax), _hip.dptr(S),
+                                                      ctypes.c_int32(r), _hip.dptr(scale), _hip.dptr(colscale), _hip.dptr(tcol), _hip.dptr(GF),
+                                                      ctypes.c_int64(r), _hip.dptr(Gprior), _hip.dptr(gx), _hip.stream_ptr(x2.device))
+    _hip.check(rc, "wiski_basis_project_vjp")
+    return gx
+
+
+class BasisProject(torch.autograd.Function):
+    """(F, prior) of :func:`basis_project` with ``want_prior``, differentiable w.r.t. the inputs x (wiski_basis_project_vjp, both
+    outputs in one launch); the tables, index set and scales are constants."""
+
+    @staticmethod
+    def forward(ctx, grid, x, V, kmax, S, colscale, tcol, err):
+        xd = x.detach().contiguous()
+        ctx.args = (grid, V, kmax, S, colscale, tcol)
+        ctx.save_for_backward(xd)
+        F, prior = basis_project(grid, xd, V, kmax, S, colscale=colscale, tcol=tcol, want_prior=True, err=err)
+        return F, prior
+
+    @staticmethod
+    def backward(ctx, gF, gprior):
+        (xd,) = ctx.saved_tensors
+        grid, V, kmax, S, colscale, tcol = ctx.args
+        if gF is None:
+            gF = torch.zeros((xd.shape[0], S.shape[1]), dtype=torch.float64, device=xd.device)
+        gx = basis_project_vjp(grid, xd, V, kmax, S, gF, gprior, colscale=colscale, tcol=tcol)
+        return None, gx, None, None, None, None, None, None
 
 
 def stationary_columns(grid, kind, ell, scale):

@@ -9,8 +9,9 @@ library:
                                                             batched fantasies
 
 Hydra, datasets, loggers and BoTorch's optimisers are out of scope: callers pass tensors and get rows
-back; ``write_csv`` stores them.  The acquisition optimiser is a random search over candidate sets (BoTorch's
-``optimize_acqf`` is not in this image).
+back; ``write_csv`` stores them.  Two acquisition optimisers: a random search over candidate sets, and ``optimize_acqf`` --
+the gradient optimiser of the reference's loop (BoTorch's ``optimize_acqf``: raw samples, restarts, L-BFGS), driven by the
+posterior's gradients w.r.t. its query points.
 """
 import csv
 import math
@@ -119,8 +120,78 @@ def ucb_random_search(model, q, d, num_candidates=512, beta=2.0, generator=None,
     return cand[int(score.argmax())]
 
 
+def acqf_values(model, X, acqf, beta=2.0, best_f=None, base_samples=None):
+    """Acquisition value of every q-batch X [b, q, d] ([b]) from ONE batched posterior call, differentiable w.r.t. X:
+    ``"ucb"`` mu + sqrt(beta) sigma for q = 1, BoTorch's qUCB (mean_s max_q mu + sqrt(beta pi / 2) |s - mu|) otherwise;
+    ``"ei"`` analytic expected improvement over `best_f` for q = 1, qEI otherwise; ``"qei"`` qEI (mean_s max_q (s - best_f)^+).
+    The MC forms draw through the fixed standard normals `base_samples` [S, q] (a sample-average approximation: the value is a
+    deterministic function of X)."""
+    if acqf not in ("ucb", "ei", "qei"):
+        raise ValueError(f"unknown acquisition function {acqf!r} (ucb, ei, qei)")
+    if acqf in ("ei", "qei") and best_f is None:
+        raise ValueError("expected improvement needs best_f")
+    lead = X.shape[:-1]
+    post = model.posterior(X)
+    mu = post.mean[..., 0].reshape(lead)
+    if lead[-1] == 1 and acqf in ("ucb", "ei"):
+        mu, sd = mu[..., 0], post.variance[..., 0].reshape(lead)[..., 0].clamp_min(1e-18).sqrt()
+        if acqf == "ucb":
+            return mu + math.sqrt(beta) * sd
+        u = (mu - float(best_f)) / sd
+        return sd * (u * torch.special.ndtr(u) + torch.exp(-0.5 * u * u) / math.sqrt(2 * math.pi))
+    S = base_samples.shape[0]
+    z = base_samples.to(mu)[:, None, :].expand(S, *lead)
+    samples = post.rsample(torch.Size([S]), base_samples=z)[..., 0].reshape(S, *lead)
+    if acqf == "ucb":
+        return (mu + math.sqrt(beta * math.pi / 2) * (samples - mu).abs()).max(-1).values.mean(0)
+    return (samples - float(best_f)).clamp_min(0).max(-1).values.mean(0)
+
+
+def optimize_acqf(model, acqf, bounds, q, num_restarts=10, raw_samples=512, maxiter=200, seed=0, beta=2.0, best_f=None, num_mc_samples=256):
+    """The reference's ``optimize_acqf`` (experiments/bayesopt/utils.py:149-161, same defaults): score `raw_samples` random q-batches
+    in the box `bounds` [2, d], start from the `num_restarts` best and optimise all restarts at once -- one batched posterior call
+    (and its backward) per evaluation -- with ``torch.optim.LBFGS`` (strong-Wolfe line search, at most `maxiter` iterations) on a
+    sigmoid reparameterisation X = lo + (hi - lo) sigmoid(Z).  The sigmoid keeps every iterate strictly inside the box, hence
+    inside the model's grid (queries outside it raise), without a projection step that an unmodified L-BFGS would not expect; a
+    maximiser on the boundary is approached to within the sigmoid's saturation.  A restart that ends below its start keeps its
+    start.  `acqf` / `beta` / `best_f` as in :func:`acqf_values`; MC forms use `num_mc_samples` fixed normals drawn from `seed`.
+    Returns (best q-batch [q, d], its value)."""
+    bounds = torch.as_tensor(bounds)
+    device = getattr(model, "_device", bounds.device)
+    dtype = getattr(model, "_dtype", bounds.dtype if bounds.is_floating_point() else torch.float64)
+    lo, hi = bounds[0].to(device, dtype), bounds[1].to(device, dtype)
+    span = hi - lo
+    d = lo.numel()
+    g = torch.Generator(device="cpu").manual_seed(int(seed))
+    raw = lo + span * torch.rand((raw_samples, q, d), generator=g, dtype=torch.float64).to(device, dtype)
+    base = torch.randn((num_mc_samples, q), generator=g, dtype=torch.float64).to(device, dtype)
+    f = lambda X: acqf_values(model, X, acqf, beta=beta, best_f=best_f, base_samples=base)
+    with torch.no_grad():
+        vals = f(raw)
+    top = vals.topk(min(num_restarts, raw_samples)).indices
+    X0, v0 = raw[top], vals[top]
+    Z = torch.logit(((X0 - lo) / span).clamp(1e-6, 1 - 1e-6)).detach().requires_grad_(True)
+    opt = torch.optim.LBFGS([Z], lr=1.0, max_iter=maxiter, line_search_fn="strong_wolfe", tolerance_grad=1e-9, tolerance_change=1e-12)
+
+    def closure():
+        opt.zero_grad()
+        loss = -f(lo + span * torch.sigmoid(Z)).sum()
+        loss.backward()
+        return loss
+
+    opt.step(closure)
+    with torch.no_grad():
+        X1 = lo + span * torch.sigmoid(Z)
+        v1 = f(X1)
+        better = v1 > v0
+        X = torch.where(better[:, None, None], X1, X0)
+        v = torch.where(better, v1, v0)
+        best = int(v.argmax())
+    return X[best].detach(), v[best].detach()
+
+
 def bayesopt(test_function, bounds, make_model, init_x, init_y, num_steps, batch_size=3, noise=None, fit_iters=30,
-             num_candidates=512, beta=2.0, seed=0, on_step=None):
+             num_candidates=512, beta=2.0, seed=0, on_step=None, acqf_optimizer="random", acqf="ucb", num_restarts=10, maxiter=200):
     """The reference's BO loop with its three timers.  Per step:
         t0  re-initialise the model from the previous model's kernel cache (``make_model(train_x, train_y, old_model)``,
             bayesopt.py:86-96) and refit the hyper-parameters on the MLL,
@@ -128,7 +199,11 @@ def bayesopt(test_function, bounds, make_model, init_x, init_y, num_steps, batch
         t2  ``condition_on_observations`` (functional: returns the model of the next step).
     `bounds` [d, 2] are the test function's bounds; inputs handed to the model live in the unit cube (and the grid covers
     the raw bounds: the reference's quirk).  Targets are standardised with the initial statistics.  Returns
-    (rows, train_x, train_y) with rows = dict(fit_time, acqf_time, condition_time, total, max_achieved)."""
+    (rows, train_x, train_y) with rows = dict(fit_time, acqf_time, condition_time, total, max_achieved).
+    `acqf_optimizer`: ``"random"`` -- :func:`ucb_random_search` over `num_candidates` sets; ``"gradient"`` -- :func:`optimize_acqf`
+    of `acqf` with `num_candidates` raw samples, `num_restarts` restarts and `maxiter` L-BFGS iterations (the reference's loop)."""
+    if acqf_optimizer not in ("random", "gradient"):
+        raise ValueError(f"acqf_optimizer must be 'random' or 'gradient', got {acqf_optimizer!r}")
     g = torch.Generator(device="cpu").manual_seed(seed)
     d = bounds.shape[0]
     lo, hi = bounds[:, 0], bounds[:, 1]
@@ -142,7 +217,13 @@ def bayesopt(test_function, bounds, make_model, init_x, init_y, num_steps, batch
         fit_mll(model, fit_iters)
         _sync(train_x); t0 = time.perf_counter() - t
         t = time.perf_counter()
-        new_x = ucb_random_search(model, batch_size, d, num_candidates, beta, g)
+        if acqf_optimizer == "random":
+            new_x = ucb_random_search(model, batch_size, d, num_candidates, beta, g)
+        else:
+            unit = torch.stack([torch.zeros(d, dtype=torch.float64), torch.ones(d, dtype=torch.float64)])
+            new_x, _ = optimize_acqf(model, acqf, unit, batch_size, num_restarts=num_restarts, raw_samples=num_candidates, maxiter=maxiter,
+                                     seed=int(torch.randint(2 ** 31 - 1, (1,), generator=g)), beta=beta, best_f=float(train_y.max()))
+            new_x = new_x.to(train_x)
         raw = test_function(lo.to(new_x) + (hi - lo).to(new_x) * new_x)
         new_y = ((raw.reshape(-1, 1) - mean) / std).to(train_y)
         train_x, train_y = torch.cat([train_x, new_x]), torch.cat([train_y, new_y])

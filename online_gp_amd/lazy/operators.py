@@ -251,15 +251,39 @@ class InterpolatedKernel(_Operator):
         return grid_ops.gather(self.grid, self.x, KW, self.err, diag=True)
 
 
+class WithInputGrad(torch.autograd.Function):
+    """``val`` -- computed by the kernels, outside autograd -- as a function of the query points ``x`` whose vector-Jacobian
+    product is ``vjp(g) -> [n, d]``.  The values (and the launches that made them) are exactly those of a call without gradients;
+    only the backward is added."""
+
+    @staticmethod
+    def forward(ctx, x, val, vjp):
+        ctx.vjp = vjp
+        return val.view_as(val)
+
+    @staticmethod
+    def backward(ctx, g):
+        return ctx.vjp(g.contiguous()), None, None
+
+
+def with_input_grad(x, val, vjp):
+    return val if x is None else WithInputGrad.apply(x, val, vjp)
+
+
 class PredictiveCovariance(LazyCovariance):
     """sigma2 * W* M W*^T for a query batch (batched_fixed_noise_online_gp.py:222-228),
     evaluated lazily: the k = n* solves U = M W*^T run once, on first use, in
     column chunks; ``diag`` needs only the per-query quadratic forms."""
 
-    def __init__(self, post, x, sigma2, err, chunk=64, block=None, spectral=None):
+    # the PCG path keeps its solves U = M W*^T for the backward up to this many bytes (else the backward solves again)
+    grad_keep_bytes = 1 << 30
+
+    def __init__(self, post, x, sigma2, err, chunk=64, block=None, spectral=None, xg=None):
         self.post = post
         self.spectral = spectral  # callable -> SpectralQuery for x (or None): lazy/spectral_woodbury.py
-        self.x = x.contiguous()
+        self.x = x.detach().contiguous()
+        # the same points as an autograd input (None: no gradient wanted); the covariance is then differentiable w.r.t. them
+        self.xg = xg
         self.sigma2 = float(sigma2)
         self.err = err
         self.chunk = chunk
@@ -277,8 +301,11 @@ class PredictiveCovariance(LazyCovariance):
         if getattr(self, "_Mg", None) is None:
             self._Mg = grid_ops.gather_rows(grid, self.x, self.post.dense, self.err)    # [n, m]: row p = w_p^T M (coalesced row reads)
         Mg = self._Mg
+        s2, x = self.sigma2, self.x
         if self._diag is None:
             self._diag = grid_ops.gather(grid, self.x, Mg, self.err, diag=True) * self.sigma2
+            # d/dx_p (s2 w_p^T M w_p) = 2 s2 dw_p . Mg_p
+            self._diag = with_input_grad(self.xg, self._diag, lambda g: grid_ops.gather_grad(grid, x, Mg, diag=True) * (2.0 * s2) * g[:, None])
         if want_full:
             n = self.x.shape[0]
             if self.block is None:
@@ -291,14 +318,37 @@ class PredictiveCovariance(LazyCovariance):
                 cols = (base[:, None] + torch.arange(q, device=self.device)[None, :]).reshape(-1)
                 full = grid_ops.gather(grid, self.x[cols].contiguous(), Mg[rows].contiguous(), self.err, diag=True)
                 full = full.reshape(n // q, q, q) * self.sigma2
-            self._full = 0.5 * (full + full.transpose(-1, -2))
+            self._full = with_input_grad(self.xg, 0.5 * (full + full.transpose(-1, -2)), lambda G: self._rows_grad(G, lambda s, e: Mg[s:e]))
+
+    def _rows_grad(self, G, rows):
+        """Input gradient of the covariance s2 w_i^T M w_j = s2 w_i . R_j (M symmetric, R_j = M w_j: ``rows(s, e)`` gives R for the
+        points s..e) with upstream G ([n, n], or [nb, q, q] blocks): s2 dw_i . sum_j Gs_ij R_j with Gs = G + G^T -- a matrix product
+        (per block: a bmm) and the diag-gather gradient, in chunks of the points where R comes in chunks."""
+        grid, x, n = self.post.grid, self.x, self.x.shape[0]
+        Gs = (G + G.transpose(-1, -2)).to(self.dtype)
+        step = self.chunk if self.block is None else max(self.block, (self.chunk // self.block) * self.block)
+        if self.block is None:
+            V = None
+            for s in range(0, n, step):
+                e = min(s + step, n)
+                part = Gs[:, s:e] @ rows(s, e)
+                V = part if V is None else V + part
+            return grid_ops.gather_grad(grid, x, V, diag=True) * self.sigma2
+        q = self.block
+        gx = torch.empty_like(x)
+        for s in range(0, n, step):
+            e = min(s + step, n)
+            V = torch.bmm(Gs[s // q:e // q], rows(s, e).reshape((e - s) // q, q, -1)).reshape(e - s, -1)
+            gx[s:e] = grid_ops.gather_grad(grid, x[s:e], V, diag=True) * self.sigma2
+        return gx
 
     def _spectral_path(self, sp, want_full):
         """Reduced-eigenbasis factor (smooth kernels on large grids): one projection, one triangular solve."""
+        s2 = self.sigma2
         if self._diag is None:
-            self._diag = (sp.diag() * self.sigma2).to(self.dtype)
+            self._diag = with_input_grad(self.xg, (sp.diag() * self.sigma2).to(self.dtype), lambda g: sp.diag_grad(g * s2))
         if want_full:
-            self._full = (sp.full(self.block) * self.sigma2).to(self.dtype)
+            self._full = with_input_grad(self.xg, (sp.full(self.block) * self.sigma2).to(self.dtype), lambda G: sp.full_grad(G * s2, self.block))
 
     def _solve_chunks(self, want_full):
         if hasattr(self.post, "dense"):
@@ -317,8 +367,11 @@ class PredictiveCovariance(LazyCovariance):
         vt = settings.variance_cg_tolerance.value()
         if vt is not None and not want_full and tol_keep is not None:
             self.post.tol = max(float(vt), float(tol_keep))          # quadratic forms: second order in the residual
+        keep = None
+        if self.xg is not None and n * grid.m * self.x.element_size() <= self.grad_keep_bytes:
+            keep = {}
         try:
-            self._solve_chunk_loop(n, step, grid, diag, full, want_full)
+            self._solve_chunk_loop(n, step, grid, diag, full, want_full, keep)
         finally:
             if tol_keep is not None:
                 self.post.tol = tol_keep
@@ -326,13 +379,34 @@ class PredictiveCovariance(LazyCovariance):
         if want_full:
             full = full * self.sigma2
             self._full = 0.5 * (full + full.transpose(-1, -2))
+        if self.xg is not None:
+            # U = M W*^T of the forward where it fits under grad_keep_bytes, else solved again (at the operator's own tolerance):
+            # the gradient is as accurate as those solves -- it inherits the CG tolerance
+            def rows(s, e):
+                if keep is not None and s in keep:
+                    return keep[s]
+                U, _ = self.post.solve_columns(grid_ops.wt_columns(grid, self.x[s:e], self.err))
+                return U
 
-    def _solve_chunk_loop(self, n, step, grid, diag, full, want_full):
+            def diag_grad(g):
+                gx = torch.empty_like(self.x)
+                for s in range(0, n, step):
+                    e = min(s + step, n)
+                    gx[s:e] = grid_ops.gather_grad(grid, self.x[s:e], rows(s, e), diag=True) * (2.0 * self.sigma2) * g[s:e, None]
+                return gx
+
+            self._diag = with_input_grad(self.xg, self._diag, diag_grad)
+            if want_full:
+                self._full = with_input_grad(self.xg, self._full, lambda G: self._rows_grad(G, rows))
+
+    def _solve_chunk_loop(self, n, step, grid, diag, full, want_full, keep=None):
         for s in range(0, n, step):
             e = min(s + step, n)
             xs = self.x[s:e]
             RHS = grid_ops.wt_columns(grid, xs, self.err)
             U, _ = self.post.solve_columns(RHS)
+            if keep is not None:
+                keep[s] = U
             diag[s:e] = grid_ops.gather(grid, xs, U, self.err, diag=True)
             if want_full:
                 if self.block is None:
@@ -363,13 +437,17 @@ class PredictiveCovariance(LazyCovariance):
             if LM is None:
                 LM = self.post._chol_M = grid_ops.psd_safe_cholesky(self.post.dense.contiguous())
             R = grid_ops.gather(self.post.grid, self.x, LM.t().contiguous(), self.err) * s        # W* L_M  [n*, m]
+            # (its input gradient reads L_M row-major: the VJP of the row gather)
+            R = with_input_grad(self.xg, R, lambda G: grid_ops.gather_rows_vjp(self.post.grid, self.x, LM, G) * s)
             self._root = RootLazyTensor(R)
             return self._root
         sp = self.spectral() if self.spectral is not None else None
         if sp is None:
             return None
         Y = sp._solve()                                                                           # chol^-1 F*^T  [r, n*]
-        self._root = RootLazyTensor((Y.t() * s).to(self.dtype).contiguous(), (sp._tail * self.sigma2).to(self.dtype))
+        R = with_input_grad(self.xg, (Y.t() * s).to(self.dtype).contiguous(), lambda G: sp.root_grad(G * s))
+        extra = with_input_grad(self.xg, (sp._tail * self.sigma2).to(self.dtype), lambda g: sp.root_grad(gextra=g * self.sigma2))
+        self._root = RootLazyTensor(R, extra)
         return self._root
 
     def diag(self):

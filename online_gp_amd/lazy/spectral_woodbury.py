@@ -605,6 +605,7 @@ class SpectralQuery:
         self.Fs, prior = grid_ops.basis_project(fac.grid, X, basis.Vtab, basis.kmax, basis.S, colscale=st["sq"], tcol=tcol64_dev, want_prior=True,
                                                 err=fac.err)
         self.prior = prior
+        self.X, self.tcol = X, tcol64_dev
         self._Y = self._diag = self._tail = None
 
     def mean(self):
@@ -639,3 +640,50 @@ class SpectralQuery:
         full = torch.bmm(Yb.transpose(1, 2), Yb)
         full.diagonal(dim1=-2, dim2=-1).add_(self._tail.reshape(-1, block))
         return full
+
+    # ---- input gradients (the posterior w.r.t. its query points; DESIGN.md "Posterior gradients"): every moment is a function of F
+    # (and of the prior variances through the tail), so each backward below reduces the upstream gradient to (G_F, G_prior) in fp64
+    # and ends in ONE wiski_basis_project_vjp launch for the whole batch
+    def grad_x(self, GF, Gprior=None):
+        """d/dX of sum(GF * F) + sum(Gprior * prior): [n, d] in X's dtype."""
+        basis = self.st["basis"]
+        return grid_ops.basis_project_vjp(self.fac.grid, self.X, basis.Vtab, basis.kmax, basis.S, GF, Gprior, colscale=self.st["sq"], tcol=self.tcol)
+
+    def mean_grad(self, g):
+        """mean = F t."""
+        self.mean()
+        return self.grad_x(g.double()[:, None] * self.st["t"][None, :])
+
+    def _tail_grad(self, g, GF):
+        """tail = max(kscale prior - |F_p|^2, 0) with upstream g [n]: subtracts its F part from GF, returns G_prior."""
+        on = (self._tail > 0).double() * g
+        GF.sub_(2.0 * on[:, None] * self.Fs)
+        return on * self.st["kscale"]
+
+    def diag_grad(self, g):
+        """diag() = |Y_p|^2 + tail, Y = chol^-1 F^T: G_F[p] = 2 g_p (chol^-T Y_p)."""
+        g = g.double()
+        Y = self._solve()
+        GF = 2.0 * g[:, None] * (Y.t() @ self.st["Linv"])
+        return self.grad_x(GF, self._tail_grad(g, GF))
+
+    def full_grad(self, G, block=None):
+        """full(block) = Y^T Y + diag(tail) (per block of q): G_Y = Y (G + G^T), G_F = G_Y^T chol^-1."""
+        G = G.double()
+        Gs = G + G.transpose(-1, -2)
+        Y = self._solve()
+        r, n = Y.shape
+        if block is None:
+            GY, gd = Y @ Gs, G.diagonal()
+        else:
+            Yb = Y.reshape(r, -1, block).permute(1, 0, 2)
+            GY, gd = torch.bmm(Yb, Gs).permute(1, 0, 2).reshape(r, n), G.diagonal(dim1=-2, dim2=-1).reshape(-1)
+        GF = GY.t() @ self.st["Linv"]
+        return self.grad_x(GF, self._tail_grad(gd, GF))
+
+    def root_grad(self, GR=None, gextra=None):
+        """The root Y^T [n, r] and the diagonal term tail of ``root_decomposition``."""
+        self._solve()
+        n, r = self.Fs.shape
+        GF = torch.zeros((n, r), dtype=torch.float64, device=self.Fs.device) if GR is None else GR.double() @ self.st["Linv"]
+        return self.grad_x(GF, None if gextra is None else self._tail_grad(gextra.double(), GF))

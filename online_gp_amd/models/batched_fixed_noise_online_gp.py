@@ -23,7 +23,7 @@ import torch
 from .. import grid_ops, settings
 from ..distributions import MultivariateNormal, ZeroLazyTensor, DenseLazyTensor, LazyCovariance
 from ..kernels import GridInterpolationKernel, RBFKernel, ScaleKernel
-from ..lazy.operators import (InducingPosterior, InterpolatedKernel, KroneckerToeplitz, PredictiveCovariance, StencilWtW)
+from ..lazy.operators import (InducingPosterior, InterpolatedKernel, KroneckerToeplitz, PredictiveCovariance, StencilWtW, with_input_grad)
 from ..lazy.dense_woodbury import DenseInducingPosterior
 from ..likelihoods import FNMGLikelihood
 
@@ -860,6 +860,12 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         if X.dim() > 2:
             block = X.shape[-2]
         Xf = X.reshape(-1, grid.d).contiguous()
+        # gradients w.r.t. the query points (acquisition optimisers): the values below are computed exactly as without them, the
+        # backward of each moment is attached to the grad-tracking points Xg (DESIGN.md "Posterior gradients").  detach_interp_coeff
+        # detaches the covariance's W* only, as BFN:22-28 does
+        Xg = Xf if torch.is_grad_enabled() and Xf.requires_grad else None
+        Xf = Xf.detach()
+        Xg_cov = None if settings.detach_interp_coeff.on() else Xg
         n = Xf.shape[0]
         # smooth kernel on a large grid, variances wanted: the variance of the batch comes from the spectral factor (no solve at
         # all, with a per-query truncation bound).  The MEAN comes from the warm-started PCG state whenever that is current
@@ -902,9 +908,14 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
                 sp[0].mean_monitor(sp[1], sq[o], self._kernel_cache["interpolation_cache"][o, :, 0], sp[2], scale[o])
             factor_mean = all(sp[0].mean_ok for sp in sps)                         # (a verdict read just now may have turned it off)
             mean = mean.to(self._dtype)
+            if factor_mean:
+                mean = with_input_grad(Xg, mean, lambda G: sum(q_.mean_grad(G[:, o]) for o, q_ in enumerate(sq)))
         if not factor_mean:
             pc = self.prediction_cache
-            mean = grid_ops.gather(grid, Xf, pc["pred_mean"][..., 0], self._err)  # [n, out]   left_interp, :206-210
+            if Xg is None:
+                mean = grid_ops.gather(grid, Xf, pc["pred_mean"][..., 0], self._err)  # [n, out]   left_interp, :206-210
+            else:
+                mean = grid_ops.Gather.apply(grid, Xg, pc["pred_mean"][..., 0], self._err)    # (the same launch, differentiable)
         if settings.deferred_bounds_check.off():
             flag = grid_ops.read_flag(self._err)       # gpytorch raises inside this call for queries outside the grid
             if flag:
@@ -918,7 +929,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             else:
                 posts = pc["pred_cov"].ops if out > 1 else [pc["pred_cov"]]
             covs = [PredictiveCovariance(_wtw_post, Xf, self._hyper()[o][1] if self.has_learnable_noise else 1.0, self._err, chunk=chunk,
-                                         block=block if X.dim() > 2 else None, spectral=None if sq is None else (lambda o=o: sq[o]))
+                                         block=block if X.dim() > 2 else None, spectral=None if sq is None else (lambda o=o: sq[o]), xg=Xg_cov)
                     for o, _wtw_post in enumerate(posts)]
         if covs is not None and settings.fast_pred_samples.on():
             # BFN:229-243: hand out a root form of the covariance where a factor provides one (else the exact covariance, as always)

@@ -34,7 +34,11 @@ class WiskiPosterior:
         return self.mvn.mean.dtype
 
     def rsample(self, sample_shape=torch.Size(), base_samples=None):
-        return self.mvn.rsample(sample_shape).unsqueeze(-1)
+        """``base_samples`` as BoTorch passes them (sample_shape + event shape, the trailing output dimension of 1 optional): the
+        draws are then a deterministic, differentiable function of the query points (sample-average MC acquisitions)."""
+        if base_samples is not None and tuple(base_samples.shape[len(sample_shape):]) == tuple(self.mvn.mean.shape) + (1,):
+            base_samples = base_samples[..., 0]
+        return self.mvn.rsample(sample_shape, base_samples=base_samples).unsqueeze(-1)
 
 
 class OnlineSKIBotorchModel(FixedNoiseOnlineSKIGP):
