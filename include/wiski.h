@@ -86,6 +86,18 @@ int wiski_gather_rows_f64(const wiski_grid* grid, const double* d_x, int64_t n, 
  * (same row-major d_Vr[m][ncols]).  Zero derivative in the one-hot boundary cells (as wiski_gather_grad); n = 0 is a no-op. */
 int wiski_gather_rows_vjp_f32(const wiski_grid* grid, const float* d_x, int64_t n, const float* d_Vr, int32_t ncols, const float* d_G, float* d_gx, void* stream);
 int wiski_gather_rows_vjp_f64(const wiski_grid* grid, const double* d_x, int64_t n, const double* d_Vr, int32_t ncols, const double* d_G, double* d_gx, void* stream);
+/* Interpolated bilinear forms of a dense symmetric table (look-ahead acquisitions, csrc/lookahead.hip):
+ * d_out[s][a][b] = w(xL[s][a])^T A w(xR[s][b]) for d_A [m][lda] (lda >= m), d_xL [nbatch][qL][d], d_xR [nbatch][qR][d], d_out [nbatch][qL][qR].
+ * Symmetric mode (xR = xL) exactly when d_xR is NULL (qR must equal qL): one triangle is computed and mirrored (exactly symmetric output);
+ * a non-NULL d_xR is always the general mode, also when it aliases d_xL (two independent inputs for the VJP).
+ * Points outside the grid set *d_err (as wiski_gather_rows) and contribute zero.  nbatch, qL or qR = 0 is a no-op. */
+int wiski_interp_bilinear_f32(const wiski_grid* grid, const float* d_A, int64_t lda, const float* d_xL, int32_t qL, const float* d_xR, int32_t qR, int64_t nbatch, float* d_out, int32_t* d_err, void* stream);
+int wiski_interp_bilinear_f64(const wiski_grid* grid, const double* d_A, int64_t lda, const double* d_xL, int32_t qL, const double* d_xR, int32_t qR, int64_t nbatch, double* d_out, int32_t* d_err, void* stream);
+/* Input gradient (VJP) of wiski_interp_bilinear for the upstream gradient d_G [nbatch][qL][qR] (A symmetric): d_gxL [nbatch][qL][d] and
+ * d_gxR [nbatch][qR][d] (either may be NULL to skip it).  Symmetric mode (d_xR NULL): the whole gradient goes to d_gxL and d_gxR must be NULL.
+ * Zero derivative in the one-hot boundary cells and outside the grid; fp64 accumulation in a fixed order (deterministic, no atomics). */
+int wiski_interp_bilinear_vjp_f32(const wiski_grid* grid, const float* d_A, int64_t lda, const float* d_xL, int32_t qL, const float* d_xR, int32_t qR, int64_t nbatch, const float* d_G, float* d_gxL, float* d_gxR, void* stream);
+int wiski_interp_bilinear_vjp_f64(const wiski_grid* grid, const double* d_A, int64_t lda, const double* d_xL, int32_t qL, const double* d_xR, int32_t qR, int64_t nbatch, const double* d_G, double* d_gxL, double* d_gxR, void* stream);
 
 /* a14, ELL form -- same product from materialised (idx, val) rows of width T
  * (the layout InterpolatedLazyTensor keeps; BFN:206-210). k == 1 only. */

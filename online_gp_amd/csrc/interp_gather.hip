@@ -37,59 +37,6 @@ __global__ __launch_bounds__(256) void k_interp(GridDev<real> G, const real* __r
 // 4^D loads per column are independent (deep memory-level parallelism) and hit
 // L2 / MALL: V (k*m reals) is small and read-mostly, x is the only HBM stream.
 template <typename real, int D>
-__device__ __forceinline__ real gather_one(const GridDev<real>& G, const int j0[D], const real w[D][4], const real* __restrict__ v) {
-  constexpr int off = 0;
-  real acc = (real)0;
-  if constexpr (D == 1) {
-#pragma unroll
-    for (int c0 = 0; c0 < 4; ++c0) acc += w[0][c0] * v[j0[0] + c0];
-  } else if constexpr (D == 2) {
-#pragma unroll
-    for (int c0 = 0; c0 < 4; ++c0) {
-      const real* r0 = v + (j0[0] + c0) * G.stride[off] + j0[1];
-      real s = (real)0;
-#pragma unroll
-      for (int c1 = 0; c1 < 4; ++c1) s += w[1][c1] * r0[c1];
-      acc += w[0][c0] * s;
-    }
-  } else if constexpr (D == 3) {
-#pragma unroll
-    for (int c0 = 0; c0 < 4; ++c0) {
-      real s0 = (real)0;
-#pragma unroll
-      for (int c1 = 0; c1 < 4; ++c1) {
-        const real* r = v + (j0[0] + c0) * G.stride[off] + (j0[1] + c1) * G.stride[off + 1] + j0[2];
-        real s1 = (real)0;
-#pragma unroll
-        for (int c2 = 0; c2 < 4; ++c2) s1 += w[2][c2] * r[c2];
-        s0 += w[1][c1] * s1;
-      }
-      acc += w[0][c0] * s0;
-    }
-  } else {
-#pragma unroll
-    for (int c0 = 0; c0 < 4; ++c0) {
-      real s0 = (real)0;
-#pragma unroll
-      for (int c1 = 0; c1 < 4; ++c1) {
-        real s1 = (real)0;
-#pragma unroll
-        for (int c2 = 0; c2 < 4; ++c2) {
-          const real* r = v + (j0[0] + c0) * G.stride[0] + (j0[1] + c1) * G.stride[1] + (j0[2] + c2) * G.stride[2] + j0[3];
-          real s2 = (real)0;
-#pragma unroll
-          for (int c3 = 0; c3 < 4; ++c3) s2 += w[3][c3] * r[c3];
-          s1 += w[2][c2] * s2;
-        }
-        s0 += w[1][c1] * s1;
-      }
-      acc += w[0][c0] * s0;
-    }
-  }
-  return acc;
-}
-
-template <typename real, int D>
 __global__ __launch_bounds__(256) void k_gather(GridDev<real> G, const real* __restrict__ x, int64_t n, const real* __restrict__ V,
                                                 int k, int diag, real* __restrict__ out, int32_t* __restrict__ err) {
   int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -83,6 +83,23 @@ class RootLazyTensor(LazyCovariance):
         return DenseLazyTensor(self.evaluate()[item])
 
 
+def sampling_cholesky(cov, diag_scale=None):
+    """The lower Cholesky factor ``rsample`` draws through: of cov + jitter * diag_scale * I with jitter 1e-8 (fp64) / 1e-6 (fp32), escalated
+    tenfold up to five times until every factor of the batch succeeds.  `diag_scale` defaults to the mean diagonal entry over the whole
+    batch (rsample); a tensor broadcasting against cov (e.g. [b, 1, 1]) gives each matrix its own scale."""
+    n = cov.shape[-1]
+    jitter = 1e-6 if cov.dtype == torch.float32 else 1e-8
+    eye = torch.eye(n, dtype=cov.dtype, device=cov.device)
+    if diag_scale is None:
+        diag_scale = cov.diagonal(dim1=-2, dim2=-1).mean().clamp_min(1e-30)
+    L = None
+    for i in range(6):
+        L, info = torch.linalg.cholesky_ex(cov + (jitter * 10 ** i) * diag_scale * eye)
+        if int(info.max()) == 0:
+            break
+    return L
+
+
 class MultivariateNormal:
     def __init__(self, mean, covariance):
         self.loc = mean
@@ -139,14 +156,7 @@ class MultivariateNormal:
                 out = out + rt.extra.clamp_min(0).sqrt() * torch.randn(*sample_shape, *self.loc.shape, dtype=rt.root.dtype, device=rt.root.device)
             return out
         cov = self.covariance_matrix
-        n = cov.shape[-1]
-        jitter = 1e-6 if cov.dtype == torch.float32 else 1e-8
-        eye = torch.eye(n, dtype=cov.dtype, device=cov.device)
-        L = None
-        for i in range(6):
-            L, info = torch.linalg.cholesky_ex(cov + (jitter * 10 ** i) * cov.diagonal(dim1=-2, dim2=-1).mean().clamp_min(1e-30) * eye)
-            if int(info.max()) == 0:
-                break
+        L = sampling_cholesky(cov)
         if base_samples is None:
             z = torch.randn(*sample_shape, *self.loc.shape, dtype=cov.dtype, device=cov.device)
         else:

@@ -226,6 +226,88 @@ class GatherRows(torch.autograd.Function):
         return None, gather_rows_vjp(ctx.grid, xd, Vd, g), None, None
 
 
+def _bilinear_args(grid, A, xL, xR):
+    """(A, lda, xL [nb, qL, d], xR [nb, qR, d] or None) checked for wiski_interp_bilinear(_vjp)."""
+    if A.dim() != 2 or A.shape[0] != grid.m or A.shape[1] < grid.m or A.stride(1) != 1:
+        raise ValueError(f"interp_bilinear needs a row-major table A [{grid.m}, >= {grid.m}], got {tuple(A.shape)}")
+    if xL.dim() != 3 or xL.shape[-1] != grid.d or A.dtype != xL.dtype:
+        raise ValueError(f"interp_bilinear needs xL [nbatch, q, {grid.d}] in A's dtype, got {tuple(xL.shape)} ({xL.dtype})")
+    if xR is not None and (xR.dim() != 3 or xR.shape[0] != xL.shape[0] or xR.shape[-1] != grid.d or xR.dtype != xL.dtype):
+        raise ValueError(f"interp_bilinear needs xR [{xL.shape[0]}, q', {grid.d}] in xL's dtype, got {tuple(xR.shape)} ({xR.dtype})")
+    return A, A.stride(0), xL.contiguous(), None if xR is None else xR.contiguous()
+
+
+def interp_bilinear_raw(grid, A, xL, xR, err):
+    """out[s, a, b] = w(xL[s, a])^T A w(xR[s, b]) for a dense symmetric A [m, m] (``wiski_interp_bilinear``); xR None: xL against
+    itself in the kernel's symmetric mode.  xL [nb, qL, d], xR [nb, qR, d] -> [nb, qL, qR]."""
+    A, lda, xL, xR = _bilinear_args(grid, A, xL, xR)
+    nb, qL = xL.shape[0], xL.shape[1]
+    qR = qL if xR is None else xR.shape[1]
+    out = torch.empty((nb, qL, qR), dtype=xL.dtype, device=xL.device)
+    if out.numel() == 0:
+        return out
+    rc = _hip.fn("wiski_interp_bilinear", xL.dtype)(grid.ref, _hip.dptr(A), ctypes.c_int64(lda), _hip.dptr(xL), ctypes.c_int32(qL), _hip.dptr(xR),
+                                                    ctypes.c_int32(qR), ctypes.c_int64(nb), _hip.dptr(out), _hip.dptr(err), _hip.stream_ptr(xL.device))
+    _hip.check(rc, "wiski_interp_bilinear")
+    return out
+
+
+def interp_bilinear_vjp(grid, A, xL, xR, G, want_left=True, want_right=True):
+    """Input gradients of :func:`interp_bilinear_raw` for the upstream gradient G [nb, qL, qR]: (gxL, gxR) -- gxR is None in the
+    symmetric mode (xR None), where gxL carries the whole gradient (``wiski_interp_bilinear_vjp``)."""
+    A, lda, xL, xR = _bilinear_args(grid, A, xL, xR)
+    nb, qL = xL.shape[0], xL.shape[1]
+    qR = qL if xR is None else xR.shape[1]
+    G = G.to(xL.dtype).contiguous()
+    assert G.shape == (nb, qL, qR)
+    gxL = torch.empty_like(xL) if (want_left or xR is None) else None
+    gxR = torch.empty_like(xR) if (want_right and xR is not None) else None
+    if nb * qL * qR == 0:                                     # no pairs: zero gradients
+        return (None if gxL is None else gxL.zero_()), (None if gxR is None else gxR.zero_())
+    rc = _hip.fn("wiski_interp_bilinear_vjp", xL.dtype)(grid.ref, _hip.dptr(A), ctypes.c_int64(lda), _hip.dptr(xL), ctypes.c_int32(qL), _hip.dptr(xR),
+                                                        ctypes.c_int32(qR), ctypes.c_int64(nb), _hip.dptr(G), _hip.dptr(gxL), _hip.dptr(gxR),
+                                                        _hip.stream_ptr(xL.device))
+    _hip.check(rc, "wiski_interp_bilinear_vjp")
+    return gxL, gxR
+
+
+class InterpBilinear(torch.autograd.Function):
+    """:func:`interp_bilinear_raw` differentiable w.r.t. the points xL and xR (wiski_interp_bilinear_vjp); the table A is a constant."""
+
+    @staticmethod
+    def forward(ctx, grid, A, xL, xR, err):
+        xLd = xL.detach().contiguous()
+        xRd = None if xR is None else xR.detach().contiguous()
+        Ad = A.detach()
+        ctx.grid, ctx.sym = grid, xR is None
+        ctx.save_for_backward(Ad, xLd, *(() if xRd is None else (xRd,)))
+        return interp_bilinear_raw(grid, Ad, xLd, xRd, err)
+
+    @staticmethod
+    def backward(ctx, g):
+        saved = ctx.saved_tensors
+        Ad, xLd = saved[0], saved[1]
+        xRd = None if ctx.sym else saved[2]
+        gxL, gxR = interp_bilinear_vjp(ctx.grid, Ad, xLd, xRd, g, want_left=ctx.needs_input_grad[2],
+                                       want_right=(not ctx.sym) and ctx.needs_input_grad[3])
+        return None, None, gxL, gxR, None
+
+
+def interp_bilinear(grid, A, xL, xR=None, err=None):
+    """w(xL)^T A w(xR) for a dense symmetric table A [m, m] (the posterior M of the dense regime, or qNIPV's H): xL [..., qL, d] and
+    xR [..., qR, d] with the same leading dimensions -> [..., qL, qR]; xR None: xL against itself (exactly symmetric output).
+    Differentiable w.r.t. xL and xR.  `err`: the out-of-grid flag to set (a fresh one when None)."""
+    lead = tuple(xL.shape[:-2])
+    if xR is not None and tuple(xR.shape[:-2]) != lead:
+        raise ValueError(f"interp_bilinear: leading dimensions of xL {tuple(xL.shape)} and xR {tuple(xR.shape)} differ")
+    err = new_err_flag(xL.device) if err is None else err
+    nb = math.prod(lead)
+    xL3 = xL.reshape((nb,) + tuple(xL.shape[-2:]))
+    xR3 = None if xR is None else xR.reshape((nb,) + tuple(xR.shape[-2:]))
+    out = InterpBilinear.apply(grid, A, xL3, xR3, err)
+    return out.reshape(lead + tuple(out.shape[-2:]))
+
+
 _ELL_PACK = {}
 
 

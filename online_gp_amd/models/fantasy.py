@@ -20,6 +20,11 @@ HEAD, so this is specified from the maths instead and never copies
 which is exactly ``condition_on_observations`` applied to every (f, j) copy (tests/test_fantasy_gpu.py checks it
 against a per-fantasy data-space oracle).  Everything that touches m goes through the HIP operators (wt_columns, the
 dense M gather / PCG solves); what remains are batched q x q and q' x q products.
+
+Gradients (dense regime only): when grad is enabled and the fantasy inputs X, the fantasy targets Y or the
+query points X* require grad, S_j, W* M W_j^T and W* M W*^T come from ``grid_ops.interp_bilinear`` on the cached M (no
+interpolation row is formed) and the Cholesky and solves run in differentiable torch; the mean gathers W mu go through
+``grid_ops.Gather``.  Otherwise the path above runs unchanged.
 """
 import torch
 
@@ -40,6 +45,14 @@ def _batched_cholesky(S):
         if j + 1 < q:
             L[..., j + 1:, j] = (S[..., j + 1:, j] - (L[..., j + 1:, :j] * L[..., j:j + 1, :j]).sum(-1)) / L[..., j:j + 1, j]
     return L
+
+
+_DENSE_ONLY = ("gradients of fantasy models are implemented in the dense regime only (a cached posterior M: m <= "
+               "settings.max_cholesky_size with settings.dense_small_grids on) and for a single output; values without grad work everywhere")
+
+
+def _wants_grad(*ts):
+    return torch.is_grad_enabled() and any(t is not None and torch.is_tensor(t) and t.requires_grad for t in ts)
 
 
 def _chol_solve(L, B):
@@ -123,6 +136,10 @@ class BatchedFantasyModel:
         self._post = pc["pred_cov"].ops[o] if base.num_outputs > 1 else pc["pred_cov"]
         self._mu = pc["pred_mean"][o, :, 0].contiguous()                                   # [m]
         self._sigma2 = base._sigma2(o)
+        self._grad = _wants_grad(X, Y)
+        if self._grad:
+            self._init_grad(X, Y, Nj, q)
+            return
         Xf = X.reshape(-1, grid.d).contiguous()
         W = grid_ops.wt_columns(grid, Xf, base._err)                                       # [Bq, m] dense rows (small grids) ...
         P = self._apply_M(W)                                                               # ... and W M, row by row
@@ -140,6 +157,56 @@ class BatchedFantasyModel:
         self.train_inputs = [X]
         self.train_targets = Y
 
+    def _dense_M(self):
+        M = getattr(self._post, "dense", None)
+        if M is None or self.base.num_outputs > 1:
+            raise NotImplementedError(_DENSE_ONLY)
+        return M
+
+    def _init_grad(self, X, Y, Nj, q):
+        """The differentiable build (dense regime): S_j = W_j M W_j^T + diag(noise) from interp_bilinear, torch Cholesky / solves,
+        the residuals y_fj - W_j mu through Gather -- differentiable w.r.t. X and Y."""
+        base, grid = self.base, self.base._grid
+        M = self._dense_M()
+        Bn = X.reshape(-1, grid.d).shape[0] // q
+        Xj = X.reshape(Bn, q, grid.d)
+        S = grid_ops.interp_bilinear(grid, M, Xj, None, base._err)                         # W_j M W_j^T, exactly symmetric
+        flag = grid_ops.read_flag(base._err)
+        if flag:
+            base._raise_out_of_bounds(flag)
+        S = S + torch.diag_embed(Nj.reshape(Bn, q).clamp_min(1e-7))
+        L, info = torch.linalg.cholesky_ex(S)
+        if bool((info != 0).any()):
+            raise RuntimeError("fantasy covariance block is not positive definite")
+        ib = tuple(self.input_batch_shape)
+        mean_j = grid_ops.Gather.apply(grid, Xj.reshape(-1, grid.d), self._mu[None], base._err)[:, 0]       # W_j mu
+        resid = Y - mean_j.reshape(ib + (q,))
+        R = resid.reshape((-1, Bn, q)).permute(1, 2, 0)                                    # [Bn, q, F]
+        self._Xj, self._L = Xj, L
+        self._alpha = _chol_solve(L, R)
+        self._F = R.shape[-1]
+        self._W = self._P = None
+        self.train_inputs = [X]
+        self.train_targets = Y
+
+    def _posterior_blocks_grad(self, X, qq):
+        """(W* mu [Bq, q'], W* M W*^T [Bq, q', q'], W* M W_j^T [Bn, q', q]) through interp_bilinear / Gather: differentiable w.r.t. the
+        queries X and the fantasy inputs."""
+        base, grid = self.base, self.base._grid
+        M = self._dense_M()
+        Xj = self._Xj if self._grad else self.train_inputs[0].reshape(-1, self.q, grid.d)
+        Xf = X.reshape(-1, grid.d)
+        Bq = Xf.shape[0] // qq
+        Xq = Xf.reshape(Bq, qq, grid.d)
+        mean0 = grid_ops.Gather.apply(grid, Xf, self._mu[None], base._err)[:, 0].reshape(Bq, qq)
+        prior = grid_ops.interp_bilinear(grid, M, Xq, None, base._err)
+        Xqn = Xq if Bq == Xj.shape[0] else Xq.expand(Xj.shape[0], qq, grid.d)
+        K = grid_ops.interp_bilinear(grid, M, Xqn, Xj, base._err)
+        flag = grid_ops.read_flag(base._err)
+        if flag:
+            base._raise_out_of_bounds(flag)
+        return mean0, prior, K
+
     def _apply_M(self, rows):
         """rows [k, m] -> rows M (M symmetric): the dense factor's M when it exists, chunked PCG solves otherwise."""
         out = []
@@ -150,7 +217,7 @@ class BatchedFantasyModel:
 
     def _lead(self):
         """(has a fantasy dimension, F, Bn)"""
-        return len(self.batch_shape) == len(self.input_batch_shape) + 1, self._F, self._W.shape[0]
+        return len(self.batch_shape) == len(self.input_batch_shape) + 1, self._F, self._L.shape[0]
 
     def posterior(self, X, observation_noise=False, **kwargs):
         """X: [q', d] or [1.., q', d] shared by the whole batch, or [*input_batch_shape, q', d] per candidate set.  Returns a
@@ -168,18 +235,21 @@ class BatchedFantasyModel:
             lead_eff = lead[1:] if (has_f and len(lead) == len(self.batch_shape) and lead[0] == 1) else lead
             if tuple(lead_eff) != tuple(self.input_batch_shape):
                 raise RuntimeError(f"query batch shape {lead} does not broadcast against the fantasy batch shape {tuple(self.batch_shape)}")
-        Xf = X.reshape(-1, grid.d).contiguous()
-        Wq = grid_ops.wt_columns(grid, Xf, base._err)                                      # [Bq * q', m]
-        flag = grid_ops.read_flag(base._err)
-        if flag:
-            base._raise_out_of_bounds(flag)
-        MWq = self._apply_M(Wq)                                                            # rows W* M
-        Bq = Xf.shape[0] // qq
-        Wq = Wq.reshape(Bq, qq, grid.m)
-        MWq = MWq.reshape(Bq, qq, grid.m)
-        mean0 = torch.matmul(Wq, self._mu)                                                 # [Bq, q']
-        prior = torch.matmul(MWq, Wq.transpose(-1, -2))                                    # W* M W*^T      [Bq, q', q']
-        K = torch.matmul(MWq, self._W.transpose(-1, -2)) if Bq == Bn else torch.matmul(MWq[0], self._W.transpose(-1, -2))   # W* M W_j^T [Bn, q', q]
+        if self._grad or _wants_grad(X):
+            mean0, prior, K = self._posterior_blocks_grad(X, qq)
+        else:
+            Xf = X.reshape(-1, grid.d).contiguous()
+            Wq = grid_ops.wt_columns(grid, Xf, base._err)                                  # [Bq * q', m]
+            flag = grid_ops.read_flag(base._err)
+            if flag:
+                base._raise_out_of_bounds(flag)
+            MWq = self._apply_M(Wq)                                                        # rows W* M
+            Bq = Xf.shape[0] // qq
+            Wq = Wq.reshape(Bq, qq, grid.m)
+            MWq = MWq.reshape(Bq, qq, grid.m)
+            mean0 = torch.matmul(Wq, self._mu)                                             # [Bq, q']
+            prior = torch.matmul(MWq, Wq.transpose(-1, -2))                                # W* M W*^T      [Bq, q', q']
+            K = torch.matmul(MWq, self._W.transpose(-1, -2)) if Bq == Bn else torch.matmul(MWq[0], self._W.transpose(-1, -2))   # W* M W_j^T [Bn, q', q]
         mean = mean0.unsqueeze(-1) + torch.matmul(K, self._alpha)                          # [Bn, q', F]
         KS = _chol_solve(self._L, K.transpose(-1, -2))                                     # S^-1 K^T       [Bn, q, q']
         cov = self._sigma2 * (prior - torch.matmul(K, KS))                                 # [Bn, q', q']
@@ -207,6 +277,8 @@ class _MultiOutputFantasyModel(BatchedFantasyModel):
     """num_outputs > 1: one single-output core per output (see BatchedFantasyModel)."""
 
     def __init__(self, base, inputs, targets, noise, _output=None):
+        if _wants_grad(inputs, targets):
+            raise NotImplementedError(_DENSE_ONLY)
         out = base.num_outputs
         Y = targets
         if Y.shape[-1] != out:
@@ -222,6 +294,8 @@ class _MultiOutputFantasyModel(BatchedFantasyModel):
         self.train_targets = torch.stack([c.train_targets for c in self.cores], dim=-1)
 
     def posterior(self, X, observation_noise=False, **kwargs):
+        if _wants_grad(X):
+            raise NotImplementedError(_DENSE_ONLY)
         return MultiOutputFantasyPosterior([c.posterior(X, observation_noise=observation_noise, **kwargs).mvn for c in self.cores])
 
     def __call__(self, X):
