@@ -637,6 +637,33 @@ int wiski_mll_s2_grad_f64(const double* d_g, const double* d_coef, const double*
 int wiski_gaussian_metrics_f32(int64_t n, const float* d_mu, const float* d_var, const float* d_y, const float* d_add_var, float* d_out, void* stream);
 int wiski_gaussian_metrics_f64(int64_t n, const double* d_mu, const double* d_var, const double* d_y, const double* d_add_var, double* d_out, void* stream);
 
+/* ---- probe vectors of posterior sample paths (sample_paths.hip) ----
+ * d_P [m][S] (probe-minor: the S probes of a grid node are contiguous) += sum_i sqrt(wa_i) eps(first_index + i, s) w(x_i) over the q points
+ * d_x [q][d]; d_wa [q] is the weight point i enters W^T D^-1 W with, NULL = unit weights.  Then cov(P_s) = W^T diag(wa) W exactly, whatever
+ * the hyper-parameters, and P is additive over batches and shards as long as every point has its own global index.  S even, 2..1024.
+ * Points outside the grid set bit 0 of *d_err and contribute nothing; one-hot boundary cells as wiski_interp.  q = 0 is a no-op.
+ * Precondition: every wa > 0 and finite (not checked: a negative or NaN weight gives NaN increments at the point's taps, without a flag).
+ * Inside / outside is decided as wiski_scatter_stats decides it -- in the working precision, against g0 and the last grid point rounded to
+ * it -- so that a point enters P exactly when it enters W^T D^-1 W; an fp32 point accepted within an ulp outside the fp64 grid is moved
+ * onto the edge node before its weights are taken.  WHICH cell of a dim is a one-hot boundary cell is decided in fp64: a point within an
+ * fp32 ulp of node 1 or node g - 2 may get the cubic's weights here and the one-hot weights in the fp32 absorb; the two agree at the node,
+ * so the difference is of the order of that ulp.
+ *
+ * The standard normals are part of the ABI: eps(index, s) is a function of (seed, index, s) alone, so that the probes of a model can be
+ * reproduced (and continued) from its seed and point count.  For probe pair j = s / 2:
+ *   (w0, w1, w2, w3) = Philox4x32-10(counter = (index & 0xffffffff, index >> 32, j, 0), key = (seed & 0xffffffff, seed >> 32))
+ *                      [multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85; counter 0, key 0 gives
+ *                       6627e8d5 e169c58d bc57ac4c 9b00dbd8];
+ *   u0 = ((w0 >> 5) * 2^26 + (w1 >> 6) + 1) * 2^-53,  u1 = ((w2 >> 5) * 2^26 + (w3 >> 6) + 1) * 2^-53      (both in (0, 1], exact in fp64);
+ *   r = sqrt(-2 log u0), theta = 6.283185307179586 * u1;   eps(index, 2 j) = r cos(theta),  eps(index, 2 j + 1) = r sin(theta).
+ * All of this, the interpolation weights and the product are evaluated in IEEE fp64 for both entry points, one rounding per operation (no
+ * fused multiply-adds) in the order written here and in wiski_interp's rule: u = (x - g0) / h, t = u - floor(u), the Keys polynomials in
+ * Horner form ((1.5 a - 2.5) a) a + 1 and ((-0.5 a + 2.5) a - 4) a + 2, w = ((w_0 w_1) w_2) w_3 over the dims, increment =
+ * w * (sqrt(wa) * eps).  Each increment is rounded once to the working precision before its atomic add (the order of the adds, hence the
+ * last bits of P, is not fixed).  A host implementation therefore reproduces every increment up to the last bits of log / cos / sin. */
+int wiski_scatter_probes_f32(const wiski_grid* grid, const float* d_x, const float* d_wa, int64_t q, int64_t first_index, uint64_t seed, int32_t S, float* d_P, int32_t* d_err, void* stream);
+int wiski_scatter_probes_f64(const wiski_grid* grid, const double* d_x, const double* d_wa, int64_t q, int64_t first_index, uint64_t seed, int32_t S, double* d_P, int32_t* d_err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

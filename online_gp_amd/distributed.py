@@ -183,6 +183,9 @@ class ShardedStatsUpdater:
         compared first (one tiny all-reduce + host read) and unequal shards fall back to the statistics exchange."""
         if exchange not in ("auto", "stats", "points", "stencil"):
             raise ValueError("exchange must be 'auto', 'stats', 'points' or 'stencil'")
+        if getattr(model, "_kernel_cache", None) is not None and "path_probes" in model._kernel_cache:
+            # the probes are additive over shards and would all-reduce like b (every point has its own global index), but no exchange here carries them
+            raise NotImplementedError("ShardedStatsUpdater does not carry path probes yet: build the model with num_path_probes=0")
         self.model = model
         self.group = group
         self.exchange = exchange

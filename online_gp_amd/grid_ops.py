@@ -379,6 +379,22 @@ def scatter_stats_multi(grid, x, Yt, wa, wb, noise, b, A_pack, cnt, stats, err, 
     _hip.check(rc, "wiski_scatter_stats_multi")
 
 
+def scatter_probes(grid, x, wa, first_index, seed, P, err):
+    """P [m, S] += the probe increments sum_i sqrt(wa_i) eps(first_index + i, s) w(x_i) of the points x [q, d]
+    (``wiski_scatter_probes``; wa [q] or None = unit weights; the normals are a function of (seed, global point index, s):
+    include/wiski.h).  One launch; a no-op for q = 0."""
+    x = _x2d(x, grid)
+    if P.dim() != 2 or P.shape[0] != grid.m or P.dtype != x.dtype or not P.is_contiguous():
+        raise ValueError(f"scatter_probes needs contiguous probes [m = {grid.m}, S] in the points' dtype, got {tuple(P.shape)} ({P.dtype})")
+    if wa is not None:
+        wa = wa.contiguous()
+        assert wa.shape == (x.shape[0],) and wa.dtype == x.dtype
+    rc = _hip.fn("wiski_scatter_probes", x.dtype)(grid.ref, _hip.dptr(x), _hip.dptr(wa), ctypes.c_int64(x.shape[0]), ctypes.c_int64(int(first_index)),
+                                                  ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), ctypes.c_int32(P.shape[1]), _hip.dptr(P), _hip.dptr(err),
+                                                  _hip.stream_ptr(x.device))
+    _hip.check(rc, "wiski_scatter_probes")
+
+
 def stencil_expand_add(grid, A_half, A_st):
     """A_st += expand(A_half) (delta and its mirror image); A_half is zeroed."""
     rc = _hip.fn("wiski_stencil_expand_add", A_st.dtype)(grid.ref, _hip.dptr(A_half), _hip.dptr(A_st), _hip.stream_ptr(A_st.device))

@@ -216,10 +216,46 @@ def kg_values(model, X, Xp, base_samples, current_value):
     return (mp + (C * alpha).sum(-2)).mean(-1) - float(current_value)
 
 
-_ACQFS = ("ucb", "ei", "qei", "qnipv", "kg")
+# ------------------------------------------------------------------------------------- pathwise acquisitions (every regime)
+def _paths_for(model, want):
+    """How many of `want` sample paths the model can draw: any number in the dense regime, its probe count beyond it."""
+    if not hasattr(model, "sample_paths"):
+        raise ValueError("pathwise acquisitions (ts, nei) need an online SKI model")
+    P = model._kernel_cache.get("path_probes")
+    if model._use_dense() or P is None:
+        return want                       # (beyond the dense regime without probes sample_paths raises and says how to get them)
+    return min(want, P.shape[1])
 
 
-def acqf_values(model, X, acqf, beta=2.0, best_f=None, base_samples=None, mc_points=None, current_value=None):
+def ts_values(paths, X):
+    """q-batch Thompson sampling: point j of every q-batch X [b, q, d] is scored by path j; value = sum_j f_j(x_j) ([b])."""
+    q = X.shape[-2]
+    if paths.num_paths != q:
+        raise ValueError(f"ts needs one path per point of the batch: {paths.num_paths} paths for q = {q}")
+    F = paths(X)                                                       # [q, b, q]
+    return F.diagonal(dim1=0, dim2=-1).sum(-1)
+
+
+def nei_values(paths, X, baseline_max):
+    """Pathwise qNoisyExpectedImprovement of every q-batch X [b, q, d]: mean_s (max_j f_s(x_j) - max_i f_s(X_baseline_i))^+ ([b]); the
+    candidates and the baseline are scored by the SAME draws (`baseline_max` [num_paths] = ``paths.max_values(X_baseline)``)."""
+    F = paths(X)                                                       # [S, b, q]
+    return (F.max(-1).values - baseline_max[:, None]).clamp_min(0).mean(0)
+
+
+def thompson_sample(model, candidates, q, seed=0):
+    """Discrete Thompson sampling (BoTorch's ``MaxPosteriorSampling``): draw q posterior sample paths and return, for each, the
+    candidate [N, d] that maximises it: [q, d]."""
+    paths = model.sample_paths(q, seed=seed)
+    cand = candidates.reshape(-1, candidates.shape[-1])
+    return cand[paths.argmax(cand).to(cand.device)]
+
+
+_ACQFS = ("ucb", "ei", "qei", "qnipv", "kg", "ts", "nei")
+
+
+def acqf_values(model, X, acqf, beta=2.0, best_f=None, base_samples=None, mc_points=None, current_value=None, X_baseline=None, paths=None,
+                baseline_max=None, seed=0, num_mc_samples=256):
     """Acquisition value of every q-batch X [b, q, d] ([b]) from ONE batched posterior call, differentiable w.r.t. X:
     ``"ucb"`` mu + sqrt(beta) sigma for q = 1, BoTorch's qUCB (mean_s max_q mu + sqrt(beta pi / 2) |s - mu|) otherwise;
     ``"ei"`` analytic expected improvement over `best_f` for q = 1, qEI otherwise; ``"qei"`` qEI (mean_s max_q (s - best_f)^+).
@@ -227,7 +263,11 @@ def acqf_values(model, X, acqf, beta=2.0, best_f=None, base_samples=None, mc_poi
     deterministic function of X).
     Look-ahead forms (dense regime): ``"qnipv"`` qNegIntegratedPosteriorVariance over `mc_points` [N, d] in its
     collapsed form (:class:`QNIPVCache`); ``"kg"`` one-shot qKG (:func:`kg_values`): X is [b, q + J, d], the q-batch followed by
-    one point per fantasy, `base_samples` [J, q] are the fantasies' normals and `current_value` (default `best_f`) is subtracted."""
+    one point per fantasy, `base_samples` [J, q] are the fantasies' normals and `current_value` (default `best_f`) is subtracted.
+    Pathwise forms (every regime), on posterior sample paths (`paths`, or drawn from `seed` by ``model.sample_paths``):
+    ``"ts"`` q-batch Thompson sampling, sum_j f_j(x_j) with one path per point of the batch; ``"nei"`` qNoisyExpectedImprovement,
+    mean_s (max_j f_s(x_j) - max_i f_s(`X_baseline`_i))^+ over `num_mc_samples` paths (at most the model's probe count beyond the dense
+    regime); `baseline_max` may carry ``paths.max_values(X_baseline)`` computed once."""
     if acqf not in _ACQFS:
         raise ValueError(f"unknown acquisition function {acqf!r} ({', '.join(_ACQFS)})")
     if acqf in ("ei", "qei") and best_f is None:
@@ -236,6 +276,16 @@ def acqf_values(model, X, acqf, beta=2.0, best_f=None, base_samples=None, mc_poi
         if mc_points is None:
             raise ValueError("qnipv needs mc_points")
         return qnipv_cache(model, mc_points).values(X)
+    if acqf == "ts":
+        return ts_values(paths if paths is not None else model.sample_paths(X.shape[-2], seed=seed), X)
+    if acqf == "nei":
+        if X_baseline is None and baseline_max is None:
+            raise ValueError("nei needs X_baseline")
+        if paths is None:
+            paths = model.sample_paths(_paths_for(model, num_mc_samples), seed=seed)
+        if baseline_max is None:
+            baseline_max = paths.max_values(X_baseline.to(paths.values))
+        return nei_values(paths, X, baseline_max)
     if acqf == "kg":
         if base_samples is None or base_samples.dim() != 2:
             raise ValueError("kg needs base_samples [num_fantasies, q]")
@@ -264,7 +314,7 @@ def acqf_values(model, X, acqf, beta=2.0, best_f=None, base_samples=None, mc_poi
 
 
 def optimize_acqf(model, acqf, bounds, q, num_restarts=10, raw_samples=512, maxiter=200, seed=0, beta=2.0, best_f=None, num_mc_samples=256,
-                  mc_points=None, num_fantasies=64, current_value=None):
+                  mc_points=None, num_fantasies=64, current_value=None, X_baseline=None):
     """The reference's ``optimize_acqf`` (experiments/bayesopt/utils.py:149-161, same defaults): score `raw_samples` random q-batches
     in the box `bounds` [2, d], start from the `num_restarts` best and optimise all restarts at once -- one batched posterior call
     (and its backward) per evaluation -- with ``torch.optim.LBFGS`` (strong-Wolfe line search, at most `maxiter` iterations) on a
@@ -274,13 +324,17 @@ def optimize_acqf(model, acqf, bounds, q, num_restarts=10, raw_samples=512, maxi
     start.  `acqf` / `beta` / `best_f` as in :func:`acqf_values`; MC forms use `num_mc_samples` fixed normals drawn from `seed`.
     ``"qnipv"`` needs `mc_points`.  ``"kg"`` is one-shot: the variables are [b, q + num_fantasies, d] (the q-batch and one look-ahead
     point per fantasy) under the same reparameterisation, the fantasies' normals [num_fantasies, q] are drawn from `seed`, and
-    `current_value` defaults to `best_f`.  Returns (best q-batch [q, d], its value)."""
+    `current_value` defaults to `best_f`.  ``"ts"`` draws q sample paths and ``"nei"`` `num_mc_samples` of them (at most the model's
+    probe count beyond the dense regime) ONCE per call, from `seed`; ``"nei"`` needs `X_baseline`, whose per-path maxima are computed
+    once.  Returns (best q-batch [q, d], its value)."""
     if acqf not in _ACQFS:
         raise ValueError(f"unknown acquisition function {acqf!r} ({', '.join(_ACQFS)})")
     if acqf == "qnipv" and mc_points is None:
         raise ValueError("qnipv needs mc_points")
     if acqf == "kg" and current_value is None and best_f is None:
         raise ValueError("kg needs current_value (or best_f)")
+    if acqf == "nei" and X_baseline is None:
+        raise ValueError("nei needs X_baseline")
     bounds = torch.as_tensor(bounds)
     device = getattr(model, "_device", bounds.device)
     dtype = getattr(model, "_dtype", bounds.dtype if bounds.is_floating_point() else torch.float64)
@@ -291,7 +345,13 @@ def optimize_acqf(model, acqf, bounds, q, num_restarts=10, raw_samples=512, maxi
     nv = q + num_fantasies if acqf == "kg" else q
     raw = lo + span * torch.rand((raw_samples, nv, d), generator=g, dtype=torch.float64).to(device, dtype)
     base = torch.randn((num_fantasies if acqf == "kg" else num_mc_samples, q), generator=g, dtype=torch.float64).to(device, dtype)
-    f = lambda X: acqf_values(model, X, acqf, beta=beta, best_f=best_f, base_samples=base, mc_points=mc_points, current_value=current_value)
+    paths = baseline_max = None
+    if acqf in ("ts", "nei"):
+        paths = model.sample_paths(q if acqf == "ts" else _paths_for(model, num_mc_samples), seed=int(seed))
+        if acqf == "nei":
+            baseline_max = paths.max_values(X_baseline.to(device, dtype))
+    f = lambda X: acqf_values(model, X, acqf, beta=beta, best_f=best_f, base_samples=base, mc_points=mc_points, current_value=current_value,
+                              paths=paths, baseline_max=baseline_max)
     with torch.no_grad():
         vals = f(raw)
     top = vals.topk(min(num_restarts, raw_samples)).indices
@@ -329,7 +389,9 @@ def bayesopt(test_function, bounds, make_model, init_x, init_y, num_steps, batch
     (rows, train_x, train_y) with rows = dict(fit_time, acqf_time, condition_time, total, max_achieved).
     `acqf_optimizer`: ``"random"`` -- :func:`ucb_random_search` over `num_candidates` sets; ``"gradient"`` -- :func:`optimize_acqf`
     of `acqf` with `num_candidates` raw samples, `num_restarts` restarts and `maxiter` L-BFGS iterations (the reference's loop);
-    ``acqf="kg"`` is the reference's ``--acqf kg``: one-shot qKG with `num_fantasies` fantasies and current_value = max train_y."""
+    ``acqf="kg"`` is the reference's ``--acqf kg``: one-shot qKG with `num_fantasies` fantasies and current_value = max train_y;
+    ``acqf="ts"`` q-batch Thompson sampling and ``acqf="nei"`` the reference's ``--acqf nei`` (pathwise, X_baseline = train_x), both on
+    posterior sample paths: beyond the dense regime `make_model` must build its models with ``num_path_probes``."""
     if acqf_optimizer not in ("random", "gradient"):
         raise ValueError(f"acqf_optimizer must be 'random' or 'gradient', got {acqf_optimizer!r}")
     g = torch.Generator(device="cpu").manual_seed(seed)
@@ -351,7 +413,7 @@ def bayesopt(test_function, bounds, make_model, init_x, init_y, num_steps, batch
             unit = torch.stack([torch.zeros(d, dtype=torch.float64), torch.ones(d, dtype=torch.float64)])
             new_x, _ = optimize_acqf(model, acqf, unit, batch_size, num_restarts=num_restarts, raw_samples=num_candidates, maxiter=maxiter,
                                      seed=int(torch.randint(2 ** 31 - 1, (1,), generator=g)), beta=beta, best_f=float(train_y.max()),
-                                     num_fantasies=num_fantasies)
+                                     num_fantasies=num_fantasies, X_baseline=train_x if acqf == "nei" else None)
             new_x = new_x.to(train_x)
         raw = test_function(lo.to(new_x) + (hi - lo).to(new_x) * new_x)
         new_y = ((raw.reshape(-1, 1) - mean) / std).to(train_y)

@@ -87,6 +87,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         likelihood=None,
         learn_additional_noise=False,
         num_data=None,
+        num_path_probes=0,
+        path_seed=0,
     ):
         super().__init__()
         assert train_inputs is not None or kernel_cache is not None
@@ -106,6 +108,18 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             num_dims = None
         self.num_outputs = num_outputs
         _batch_shape = torch.Size([num_outputs]) if num_outputs > 1 else torch.Size()
+        # probe vectors of the posterior sample paths (sample_paths): S of them, rounded up to even (the generator
+        # makes Box-Muller pairs); they live in the kernel cache beside b and follow it through every hand-over
+        num_path_probes = int(num_path_probes) + (int(num_path_probes) & 1)
+        if kernel_cache is not None and num_path_probes > 0 and "path_probes" not in kernel_cache:
+            raise ValueError("num_path_probes > 0, but the kernel cache handed over carries no path probes: they can only be accumulated "
+                             "while the points stream by (build the first model of the chain from data with num_path_probes)")
+        if kernel_cache is not None and num_path_probes > 0 and kernel_cache["path_probes"].shape[1] != num_path_probes:
+            raise ValueError(f"num_path_probes={num_path_probes}, but the kernel cache handed over carries {kernel_cache['path_probes'].shape[1]} "
+                             "probes (their number is fixed when the first model of the chain is built; num_path_probes=0 takes the cache's)")
+        if num_path_probes > 0 and num_outputs > 1:
+            raise NotImplementedError("path probes (num_path_probes > 0) are implemented for a single output")
+        self._path_probes_init = (num_path_probes, int(path_seed))
 
         if covar_module is None:
             if grid_bounds is None:
@@ -182,7 +196,12 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         pack = torch.zeros((out, (self._grid.R + 1) // 2, m), dtype=self._dtype, device=self._device)
         ops = [StencilWtW(self._grid, pack[o]) for o in range(out)]
         cnt = torch.zeros((out, m), dtype=self._dtype, device=self._device)
-        return self._pack_cache(b, stats, ops, cnt)
+        cache = self._pack_cache(b, stats, ops, cnt)
+        S, seed = self._path_probes_init
+        if S > 0:
+            # P [m, S], probe-minor; path_count: global index of the next point (the generator is keyed on (seed, index, s))
+            cache.update(path_probes=torch.zeros((m, S), dtype=self._dtype, device=self._device), path_seed=seed, path_count=0)
+        return cache
 
     def _pack_cache(self, b, stats, ops, cnt=None):
         out = b.shape[0]
@@ -209,6 +228,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         else:
             new_ops = [op.clone() for op in ops]
         new = self._pack_cache(cache["interpolation_cache"].clone(), stats, new_ops, cnt)
+        if "path_probes" in cache:                      # a child's increments never reach the parent's buffer
+            new.update(path_probes=cache["path_probes"].clone(), path_seed=cache["path_seed"], path_count=cache["path_count"])
         facs = cache.get("_spectral")
         if facs:
             new["_spectral"] = {o: fac.clone() for o, fac in facs.items() if fac.ref is not None and not fac.stale}
@@ -247,6 +268,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         per point).  With `half_delta` given (data-parallel path) the increments go to those
         buffers instead, for the caller to all-reduce and add; `res_delta` ([out, m], zeroed) then receives this shard's
         innovation W^T (wb y - wa (W U)) of the carried residual, to be all-reduced and added to R alongside."""
+        if "path_probes" in cache and half_delta is not None:
+            raise NotImplementedError("path probes do not follow the data-parallel statistics exchange")
         self._finish_pending()
         if cache is self._kernel_cache:
             self.leave_stencil_shard()               # the generic absorb writes every group
@@ -326,7 +349,21 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
                 else:
                     self._wsum_dev[o] += wa.sum(dtype=torch.float64)
                     self._wsum_dirty = True
+        if "path_probes" in cache:                   # (single output: `wa` is the weight the points just entered A with)
+            self._absorb_probes(cache, X, None if unit else wa, init)
         return carry_delta
+
+    def _absorb_probes(self, cache, X, wa, init=False):
+        """Every point that enters A enters the probes P with the same weight wa (None: unit) and its global index, so that
+        cov(P_s) = A whatever the hyper-parameters (one launch, wiski_scatter_probes).  init: the statistics restart at index 0."""
+        P = cache["path_probes"]
+        if init:
+            P.zero_()
+            cache["path_count"] = 0
+        n = X.shape[0]
+        if n:
+            grid_ops.scatter_probes(self._grid, X, wa, cache["path_count"], cache["path_seed"], P, self._err)
+            cache["path_count"] += n
 
     def _absorb_all_outputs(self, cache, X, Y, noise, unit, init, half_delta, ops, dst, carry, ms, mine, n):
         """Several outputs, native packed half stencils, no root pairs to carry: ONE scatter launch for all of them
@@ -1033,6 +1070,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             self._spectral_absorb(0, X, None, y1)
         if settings.deferred_refresh.on() or step.pending:
             prev, pending = step(X, y1, ones, ones, ones, mean, carry, fc, defer=settings.deferred_refresh.on())
+            if "path_probes" in self._kernel_cache and not (prev is not None and prev[2]):
+                self._absorb_probes(self._kernel_cache, X, None)
             self._pending_step = step if pending else None
             if prev is not None:
                 if prev[2]:                              # the PREVIOUS batch held out-of-grid points: this one was not queued at all
@@ -1044,7 +1083,10 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             if not pending:                              # deferral switched off meanwhile: this call ran to convergence
                 self._note_solve(ms, (step.it.value, step.rr.value, step.herr.value, True), fc, probe)
             return mean
-        self._note_solve(ms, step(X, y1, ones, ones, ones, mean, carry, fc), fc, probe)
+        res = step(X, y1, ones, ones, ones, mean, carry, fc)
+        if "path_probes" in self._kernel_cache:
+            self._absorb_probes(self._kernel_cache, X, None)       # one extra launch; none without probes
+        self._note_solve(ms, res, fc, probe)
         return mean
 
     # ------------------------------------------------- two-level preconditioner --
@@ -1321,6 +1363,98 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         self._memo["prediction_cache"] = {"pred_mean": U[..., None], "pred_cov": posts[0] if out == 1 else BatchOperator(posts),
                                           "cg_iters": [0] * out, "ver": ver}
 
+    # --------------------------------------------------------- sample paths --
+    def sample_paths(self, num_paths, seed=0, base_samples=None, tol=None):
+        """`num_paths` joint draws u_s ~ N(M b, sigma2 M) of the m inducing values, as a :class:`GridSamplePaths`: each is a posterior
+        FUNCTION sample f_s(x) = w(x)^T u_s (the SKI kernel is W Kuu W^T: no residual term), to be evaluated, differentiated and
+        maximised at any number of points.  z [num_paths, m] standard normals: `base_samples`, or drawn from `seed`
+        on the host generator.
+          dense regime (a cached dense M):  u = M b + sigma chol(M + jitter) z; any num_paths, no probes needed;
+          otherwise, Matheron's rule in statistics space:  u_s = eta_s + M (b - A eta_s - sigma P_s), eta_s = Kuu^(1/2) z_s, with the
+          probe vectors P_s accumulated beside b while the points streamed by (``num_path_probes``): path s uses probe s, so
+          num_paths <= num_path_probes.  The columns are solved by the system the mean solves, at `tol` (default: the mean's).
+        Nothing is cached: two calls with the same arguments on the same state compute the same paths again (the normals come from the
+        seeded host generator, the probes are fixed; beyond the dense regime the values agree to the solver's tolerance).  The paths of ONE call are independent draws; beyond
+        the dense regime, paths with the same index s from calls with different seeds share probe s (the data-noise half of their
+        randomness) and are therefore correlated: draw all the paths an acquisition needs in one call."""
+        from ..sample_paths import GridSamplePaths
+
+        if self.num_outputs != 1:
+            raise NotImplementedError("sample_paths is implemented for a single output")
+        num_paths = int(num_paths)
+        if num_paths < 1:
+            raise ValueError("num_paths must be positive")
+        grid, m = self._grid, self._grid.m
+        pc = self.prediction_cache                  # (finishes a deferred refresh, rejoins a sharded stencil)
+        post = pc["pred_cov"]
+        cache = self._kernel_cache
+        if base_samples is None:
+            gen = torch.Generator(device="cpu").manual_seed(int(seed))
+            z = torch.randn((num_paths, m), generator=gen, dtype=torch.float64)
+        else:
+            z = base_samples
+            if tuple(z.shape) != (num_paths, m):
+                raise ValueError(f"base_samples must be [num_paths = {num_paths}, m = {m}], got {tuple(z.shape)}")
+        z = z.to(self._device, self._dtype).contiguous()
+        sigma = math.sqrt(self._sigma2(0))
+        gb = self.covar_module.grid_bounds
+        if hasattr(post, "dense"):
+            fac = getattr(post, "_path_chol", None)
+            if fac is None:
+                # the sampling factor in fp64 whatever the model's precision (m <= max_cholesky_size), with rsample's jitter rule
+                # (distributions.sampling_cholesky): jitter * mean(diag) on the diagonal, escalated tenfold until the factor exists
+                M64 = post.dense.double()
+                M64 = 0.5 * (M64 + M64.t())
+                scale = float(M64.diagonal().mean().clamp_min(1e-30))
+                base = 1e-6 if self._dtype == torch.float32 else 1e-8
+                for i in range(6):
+                    jit = base * 10 ** i * scale
+                    L = M64.clone()
+                    L.diagonal().add_(jit)
+                    if int(grid_ops.potrf_(L).item()) == 0 and bool(torch.isfinite(L.diagonal()).all()):
+                        break
+                else:
+                    raise RuntimeError("the posterior covariance of the inducing values is not positive definite after jitter")
+                fac = post._path_chol = (L.tril().contiguous(), jit)
+            L, jit = fac
+            dev = grid_ops.gemm(z.double(), L, tb=True)                       # rows z_s^T L^T = (L z_s)^T
+            u = (pc["pred_mean"][0, :, 0].double()[None] + sigma * dev).to(self._dtype)
+            paths = GridSamplePaths(grid, u.contiguous(), gb, True, [0], jit)
+        else:
+            P = cache.get("path_probes")
+            if P is None:
+                raise RuntimeError("sample_paths beyond the dense regime needs the probe vectors that are accumulated while the data stream by: "
+                                   "build the model with num_path_probes=S (S >= the number of paths wanted)")
+            if num_paths > P.shape[1]:
+                raise ValueError(f"{num_paths} paths asked for, but the model keeps num_path_probes={P.shape[1]} probes (path s uses probe s): "
+                                 "build it with a larger num_path_probes")
+            tcol = self._hyper()[0][0]
+            ver = self._hyper_version()
+            pe = self._memo.get("path_eig")
+            if pe is None or pe[0] != ver:
+                pe = self._memo["path_eig"] = (ver, grid_ops.kron_eigen(grid, tcol))
+            eta = grid_ops.kron_spectral_mm(grid, pe[1], z, kscale=1.0, power=0.5)                    # Kuu^(1/2) z   [k, m]
+            rhs = cache["interpolation_cache"][0, :, 0][None] - grid_ops.stencil_spmv(grid, post.wtw.stencil, eta)
+            rhs -= sigma * P[:, :num_paths].t()
+            u = torch.empty_like(eta)
+            chunk = max(1, int(settings.variance_chunk.value()))
+            tol_keep, conv, iters = post.tol, True, []
+            if tol is not None:
+                post.tol = float(tol)
+            try:
+                for s in range(0, num_paths, chunk):
+                    e = min(s + chunk, num_paths)
+                    U, _ = post.solve_columns(rhs[s:e].contiguous())
+                    u[s:e] = eta[s:e] + U
+                    iters.append(post.last_iters)
+                    conv = conv and bool(getattr(post, "last_converged", True))
+                    if post.last_err:
+                        self._raise_out_of_bounds(post.last_err)
+            finally:
+                post.tol = tol_keep
+            paths = GridSamplePaths(grid, u, gb, conv, iters)
+        return paths
+
     def get_fantasy_model(self, inputs, targets, noise_term=None, **kwargs):
         """BFN:287-332.  inputs [*b, q, d], targets [*b, q] or [num_fantasies, *b, q]: a batch of conditioned copies
         (``models/fantasy.py``: specified from the maths, the reference's cache expansion is broken at HEAD, SURVEY 0);
@@ -1383,6 +1517,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             else:
                 new_ops = [op.to(device) for op in ops]
             self._kernel_cache = self._pack_cache(c["interpolation_cache"].to(device), stats, new_ops, c["_cnt"].to(device) if "_cnt" in c else None)
+            if "path_probes" in c:
+                self._kernel_cache.update(path_probes=c["path_probes"].to(device), path_seed=c["path_seed"], path_count=c["path_count"])
             self._device = torch.device(device)
             self._err = grid_ops.new_err_flag(device)
             self._mean_state = None

@@ -37,6 +37,7 @@ class OnlineSKIRegression(StreamingSKIWrapper):
             grid_bounds=torch.tensor([[-half_width, half_width]] * stem.output_dim),
             grid_size=[grid_size] * stem.output_dim,
             learn_additional_noise=True,
+            num_path_probes=kwargs.get("num_path_probes", 0), path_seed=kwargs.get("path_seed", 0),
         )
         self._setup(stem, gp, lr, init_x)
 
