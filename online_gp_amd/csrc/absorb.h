@@ -1,0 +1,61 @@
+// The absorb's contract: everything one statistics scatter
+//   b += W^T D^-1 y,  A += W^T D^-1 W,  cnt += W^T wa,  stats += (y^T D^-1 y, logdet D)
+// may be asked to do, as ONE named record.  Every member defaults to "off"; the extern "C" entry points of scatter_stats.hip
+// and the streaming step (stream_step.hip) fill the fields they expose and call absorb().  Which combinations are refused is
+// absorb_validate() in scatter_stats.hip; whoever writes another form of the absorb has to honour every group below.
+#pragma once
+#include "wiski_common.h"
+
+// strides (in elements) between the outputs of a batched launch; all zero for a single output
+struct ScatterBatch {
+  int64_t y_stride = 0;    // between the outputs' targets y
+  int64_t w_stride = 0;    // between their wa / wb / noise (0: one weight vector shared by all outputs)
+  int64_t vec_stride = 0;  // between their b / cnt / u / res: the grid's node count m, which absorb() fills in
+  int64_t A_stride = 0;    // between their half stencils
+};
+
+template <typename real>
+struct AbsorbArgs {
+  // points
+  const real* x = nullptr;      // [n, d] coordinates; a point outside the grid is flagged in err and contributes nothing at all
+  const real* y = nullptr;      // [n] targets
+  const real* wa = nullptr;     // [n] weight a point enters A, cnt and the carried residual with
+  const real* wb = nullptr;     // [n] weight it enters b and y^T D^-1 y with
+  const real* noise = nullptr;  // [n] its noise: stats[1] += log noise
+  int64_t n = 0;                // 0: nothing happens, whatever the other fields hold
+  // targets
+  real* b = nullptr;            // [m]
+  real* A = nullptr;            // half: row-interleaved symmetric half stencil [(7^d + 1) / 2 * m], else offset-major [7^d, m]; NULL: no A at all
+  bool half = false;            // every optional behaviour below except cnt needs the half-stencil form
+  real* cnt = nullptr;          // [m] row sums of the increment (preconditioner density model); optional
+  double* stats = nullptr;      // [2]: sum wb y^2 and sum log(noise) over the points inside the grid
+  int32_t* err = nullptr;       // bit 0: any point outside the grid; bits 1..: number of points dropped
+  // carry
+  const real* u = nullptr;      // [m] current posterior mean on the grid
+  real* res = nullptr;          // [m] res += W^T (wb y - wa (W u)): keeps res = b - z - A u exact under the increment
+  real* mean_out = nullptr;     // [n] w_p . u, the predictive mean of the batch BEFORE this update (saves the gather launch of a step)
+  // zero regions: two word arrays of the solve that follows in the same streaming step (its scalar block, its partial vector)
+  void* z1 = nullptr;
+  int64_t n1_bytes = 0;         // multiples of 4
+  void* z2 = nullptr;
+  int64_t n2_bytes = 0;
+  // guard: speculative launch behind a solve whose convergence poll the host has not read yet (wiski_pcg_async_guard)
+  const void* guard = nullptr;  // device int64 the poll's publishing block writes
+  int64_t guard_expect = 0;     // the absorb happens iff *guard == guard_expect, decided on the device
+  // owner workspace: selects the owner-computes form (scatter_owner.h) where it applies; the atomic form runs otherwise
+  void* bin = nullptr;          // wiski_scatter_bin_bytes bytes, zero-initialised once by the caller
+  int64_t bin_bytes = 0;
+  // shard: the stencil groups [g_lo, g_hi) this replica owns (wiski_shard).  A rank of a stencil-sharded step scatters the tap
+  // pairs of ITS groups only -- 1 / N of the atomics per point; b, cnt, res and the statistics stay replicated
+  int g_lo = 0, g_hi = 1 << 30;
+  // batch: several independent outputs in one launch -- same points, per-output y / weights / targets / statistics at `bt`
+  int nout = 1;
+  ScatterBatch bt;
+
+  bool sharded() const { return g_lo > 0 || g_hi < (1 << 30); }
+};
+
+// Validates, then queues the absorb on `stream`: WISKI_OK, WISKI_E_BADARG (nothing was launched) or WISKI_E_LAUNCH.
+// Instantiated for float and double in scatter_stats.hip.
+template <typename real>
+int absorb(const wiski_grid* grid, const AbsorbArgs<real>& args, void* stream);

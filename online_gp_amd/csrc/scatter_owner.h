@@ -12,7 +12,7 @@
 //                  walks those lists, accumulates every point's contribution to the line's rows -- 172 half-stencil slots,
 //                  b, cnt and res per row -- in LDS (LDS atomics), and adds the non-zero accumulators to global memory with
 //                  plain, row-contiguous read-modify-writes.
-// Measured at 50^3 fp32 (tools/owner_probe.py): 69 us per 4 096 uniform points (atomic form 79; clustered 80 / 80), 255 us per
+// Measured at 50^3 fp32: 69 us per 4 096 uniform points (atomic form 79; clustered 80 / 80), 255 us per
 // 32 768 (585) -- binning 8 us, then per line: heads + records fetched in two batched memory latencies, ~38 point visits of ~110
 // instructions each (33 us in all), and the write-back of the non-zero accumulators (17 us).  At 32 768 points: binning 27 us,
 // scan 13, visits 193 (20 per point, ~720 SIMD cycles each: the record broadcast and index set-up are paid again by each of the
@@ -37,9 +37,9 @@ __device__ __forceinline__ void lds_atomic_add(float* p, float v) { __hip_atomic
 __device__ __forceinline__ void lds_atomic_add(double* p, double v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
 // bytes of the binning workspace for n points on grid G (heads | next | records); must be zero-initialised once by the caller
-template <typename real>
-static inline int64_t owner_work_bytes(const wiski_grid* g, int64_t n) {
-  const int64_t ncell = (int64_t)(g->g[0] - 3) * (g->g[1] - 3) * (g->g[2] - 3);
+template <typename real, typename Grid>   // Grid: wiski_grid or GridDev<real>
+static inline int64_t owner_work_bytes(const Grid& g, int64_t n) {
+  const int64_t ncell = (int64_t)(g.g[0] - 3) * (g.g[1] - 3) * (g.g[2] - 3);
   const int64_t heads = (ncell * 8 + 255) / 256 * 256, next = (n * 4 + 255) / 256 * 256;
   return heads + next + n * OwnerRec<real>::N * (int64_t)sizeof(real);
 }
@@ -51,9 +51,7 @@ __global__ __launch_bounds__(256) void k_bin_points(GridDev<real> G, const real*
                                                     real* __restrict__ mean_out, unsigned long long* __restrict__ head, int32_t* __restrict__ next,
                                                     real* __restrict__ rec, unsigned epoch, uint32_t* __restrict__ z1, int64_t n1,
                                                     uint32_t* __restrict__ z2, int64_t n2, const long long* __restrict__ guard, long long guard_expect) {
-  if (guard && *guard != guard_expect) return;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n1; e += (int64_t)gridDim.x * blockDim.x) z1[e] = 0u;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n2; e += (int64_t)gridDim.x * blockDim.x) z2[e] = 0u;
+  if (!absorb_prologue(guard, guard_expect, z1, n1, z2, n2, blockDim.x, gridDim.x)) return;
   __shared__ double s_red[16];
   const int lane = threadIdx.x & 63, loc = threadIdx.x >> 6;
   const int nc1 = G.g[1] - 3, nc2 = G.g[2] - 3;
@@ -65,11 +63,9 @@ __global__ __launch_bounds__(256) void k_bin_points(GridDev<real> G, const real*
     int j0[3];
 #pragma unroll
     for (int q = 0; q < 3; ++q) xp[q] = x[p * 3 + q];
-    const bool inside = point_stencil<real, 3>(G, xp, j0, w);
-    if (!inside) {                               // flagged, contributes nothing (as k_scatter_stats_sym)
-      bad = true;
+    if (!point_stencil<real, 3>(G, xp, j0, w)) {
+      flag_outside(err, lane == 0, bad);
       if (lane == 0) {
-        atomicAdd(err, 2);
         next[p] = -2;
         if (mean_out) mean_out[p] = (real)0;
       }
@@ -115,11 +111,12 @@ __global__ __launch_bounds__(256) void k_bin_points(GridDev<real> G, const real*
 __device__ __forceinline__ int owner_slot(int g, int s) { return g == 0 ? s - 3 : 4 + 7 * (g - 1) + s; }
 
 // NT threads per block = NT / 64 waves, each owning 1 / (NT / 64) of the line's rows
+constexpr int OWNER_NT = 256;                    // what is launched (measured at 50^3, 4096 points: 69 us with 256, 88 us with 512)
 template <typename real, int NT>
 __global__ __launch_bounds__(NT) void k_owner_lines(GridDev<real> G, real* __restrict__ A, real* __restrict__ b, real* __restrict__ cnt,
                                                      real* __restrict__ res, const unsigned long long* __restrict__ head,
                                                      const int32_t* __restrict__ next, const real* __restrict__ rec, unsigned epoch,
-                                                     const long long* __restrict__ guard, long long guard_expect, int abl) {
+                                                     const long long* __restrict__ guard, long long guard_expect) {
   if (guard && *guard != guard_expect) return;
   extern __shared__ __attribute__((aligned(16))) char smem_owner[];
   constexpr int NS = 172;                        // half-stencil slots per row (d = 3)
@@ -251,7 +248,6 @@ __global__ __launch_bounds__(NT) void k_owner_lines(GridDev<real> G, real* __res
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) {
       unsigned long long live = __ballot(p0[rb] >= 0);
-      if (abl & 1) { found |= live != 0; live = 0; }        // timing ablation: scan only
       while (live) {
         const int src = __ffsll((long long)live) - 1;
         live &= live - 1;
@@ -270,7 +266,7 @@ __global__ __launch_bounds__(NT) void k_owner_lines(GridDev<real> G, real* __res
   }
   if (found && lane == 0) s_any = 1;
   __syncthreads();
-  if (!s_any || (abl & 2)) return;                          // block-uniform: nothing touches this line (abl 2: no write-back)
+  if (!s_any) return;                                       // block-uniform: nothing touches this line
   const int64_t m = G.m;
   const int64_t row0 = ((int64_t)i0 * g1 + i1) * g2;
   // write-back: the line's 172 g2 accumulators group by group (group 0: 4 g2 reals, then 24 x 7 g2), each group a contiguous
@@ -307,6 +303,8 @@ __global__ __launch_bounds__(NT) void k_owner_lines(GridDev<real> G, real* __res
       const real* __restrict__ Ag = A + (int64_t)(7 * (gq + k + 1) - 3) * m + row0 * 7;
       // untouched accumulators read a hot dummy word instead of their A_h entry (a select on the loaded VALUE would make the
       // load unconditional: the whole 86 MB read again per call)
+      // (non-temporal stores for the write-back below, to keep A_h Infinity-Cache resident for the SpMV that follows, had no
+      // effect: 21.4 us either way)
 #pragma unroll
       for (int j = 0; j < NE; ++j) o[k][j] = *(v[k][j] != (real)0 ? Ag + t + NT * j : A);
     }
@@ -315,13 +313,7 @@ __global__ __launch_bounds__(NT) void k_owner_lines(GridDev<real> G, real* __res
       real* __restrict__ Ag = A + (int64_t)(7 * (gq + k + 1) - 3) * m + row0 * 7;
 #pragma unroll
       for (int j = 0; j < NE; ++j)
-        if (v[k][j] != (real)0) {
-#ifdef WISKI_OWNER_NT_STORES   // tried in order to keep A_h Infinity-Cache resident for the SpMV that follows: no effect (21.4 us either way)
-          __builtin_nontemporal_store(o[k][j] + v[k][j], Ag + t + NT * j);
-#else
-          Ag[t + NT * j] = o[k][j] + v[k][j];
-#endif
-        }
+        if (v[k][j] != (real)0) Ag[t + NT * j] = o[k][j] + v[k][j];
     }
   }
   for (int e = t; e < g2; e += NT) {

@@ -4,43 +4,39 @@
 //   c  = y^T D^-1 y   (response_cache, BFN:45), ld = logdet D (BFN:55)
 // The reference densifies W^T (m x q) and adds a dense m x m outer product per
 // update; here each streamed point touches exactly its 4^d x 4^d stencil block.
-#include "wiski_common.h"
-
-// The half-stencil atomics of k_scatter_stats_sym.  WISKI_SCATTER_ATOMIC_MOD (timing builds; the round-4 job script is in the git history): cache-policy bits on the
-// atomic -- does any of them leave A_h better placed for the SpMV that follows?  0 = the default (what ships).  Measured (bench traces, SpMV
-// dispatches right after the absorb / absorb kernel): default 18.0-18.2 us / 66.6-67.4 us, sc1 18.1-18.4 / 67.7, nt 18.3-18.4 / 69.3, sc1 nt 18.2-18.3 / 68.7 -- no.
-#ifndef WISKI_SCATTER_ATOMIC_MOD
-#define WISKI_SCATTER_ATOMIC_MOD 0
-#endif
-__device__ __forceinline__ void stencil_atomic(float* p, float v) {
-#if WISKI_SCATTER_ATOMIC_MOD == 1
-  asm volatile("global_atomic_add_f32 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
-#elif WISKI_SCATTER_ATOMIC_MOD == 2
-  asm volatile("global_atomic_add_f32 %0, %1, off nt" ::"v"(p), "v"(v) : "memory");
-#elif WISKI_SCATTER_ATOMIC_MOD == 3
-  asm volatile("global_atomic_add_f32 %0, %1, off sc1 nt" ::"v"(p), "v"(v) : "memory");
-#else
-  unsafeAtomicAdd(p, v);
-#endif
-}
-__device__ __forceinline__ void stencil_atomic(double* p, double v) { unsafeAtomicAdd(p, v); }
+#include "absorb.h"
 #include <atomic>
 #include <cstdlib>
 
-// GRP = min(T, 64) lanes cooperate on one point (lane <-> tap a); each lane
-// walks all taps b and issues fire-and-forget L2 atomics on A_st[o(a,b)][idx_a].
-// Tap values are exchanged through LDS (broadcast reads, conflict-free).
-// This is the full offset-major form A_st[o][i] (all 7^d offsets, T^2 atomics per point); the model itself
-// keeps the symmetric half (k_scatter_stats_sym below: T(T+1)/2 atomics, ~5x faster).
+// The half-stencil atomics of k_scatter_stats_sym.  Cache-policy bits on the fp32 atomic (sc1, nt, sc1 nt) leave A_h no better
+// placed for the SpMV that follows -- SpMV dispatches right after the absorb / absorb kernel: default 18.0-18.2 us / 66.6-67.4 us,
+// sc1 18.1-18.4 / 67.7, nt 18.3-18.4 / 69.3, sc1 nt 18.2-18.3 / 68.7 -- so it is the plain fire-and-forget add.
+__device__ __forceinline__ void stencil_atomic(float* p, float v) { unsafeAtomicAdd(p, v); }
+__device__ __forceinline__ void stencil_atomic(double* p, double v) { unsafeAtomicAdd(p, v); }
+
+// What the point-sweeping kernels of an absorb (k_scatter_stats_sym, k_bin_points) do before their first point.  False: a guarded
+// launch (AbsorbArgs::guard) that is not to happen.  Otherwise the two zero regions are cleared on the way, grid-strided.
+// nt / nb = blockDim.x / gridDim.x: read in here they would lose what the kernel's launch bounds tell the compiler about them.
+__device__ __forceinline__ bool absorb_prologue(const long long* __restrict__ guard, long long guard_expect, uint32_t* __restrict__ z1, int64_t n1,
+                                                uint32_t* __restrict__ z2, int64_t n2, unsigned nt, unsigned nb) {
+  if (guard && *guard != guard_expect) return false;
+  for (int64_t e = (int64_t)blockIdx.x * nt + threadIdx.x; e < n1; e += (int64_t)nb * nt) z1[e] = 0u;
+  for (int64_t e = (int64_t)blockIdx.x * nt + threadIdx.x; e < n2; e += (int64_t)nb * nt) z2[e] = 0u;
+  return true;
+}
+
+// A point outside the grid raises the flag and contributes nothing at all (zero weights; no y^2 / log-noise term either, so a
+// caller that catches the error keeps statistics that agree with A and b).  `count`: the one lane that counts the point --
+// bits 1..: number of training points dropped; bit 0 (any point outside) is set from `bad` when the kernel ends.
+__device__ __forceinline__ void flag_outside(int32_t* __restrict__ err, bool count, bool& bad) {
+  bad = true;
+  if (count) atomicAdd(err, 2);
+}
+
 // stats[0] += sum wb y^2, stats[1] += sum log(noise) over the points inside the grid.  Atomics of many blocks on one address
 // serialise at the memory side (~12 ns each): with one pair per block the 1 024 blocks of a q = 4 096 absorb spent 25 us of
 // their 87 us queueing on these two doubles.  So a few designated blocks sweep the points once more (x, y, wb, noise: 24 B per
 // point) and issue one pair each.
-// strides (in elements) between the outputs of a batched launch; all zero for a single output
-struct ScatterBatch {
-  int64_t y_stride = 0, w_stride = 0, vec_stride = 0, A_stride = 0;
-};
-
 template <typename real, int D>
 __device__ __forceinline__ void scatter_stats_pass(const GridDev<real>& G, const real* __restrict__ x, const real* __restrict__ y,
                                                    const real* __restrict__ wb, const real* __restrict__ noise, int64_t n,
@@ -69,6 +65,11 @@ __device__ __forceinline__ void scatter_stats_pass(const GridDev<real>& G, const
   }
 }
 
+// GRP = min(T, 64) lanes cooperate on one point (lane <-> tap a); each lane
+// walks all taps b and issues fire-and-forget L2 atomics on A_st[o(a,b)][idx_a].
+// Tap values are exchanged through LDS (broadcast reads, conflict-free).
+// This is the full offset-major form A_st[o][i] (all 7^d offsets, T^2 atomics per point); the model itself
+// keeps the symmetric half (k_scatter_stats_sym below: T(T+1)/2 atomics, ~5x faster).
 template <typename real, int D>
 __global__ __launch_bounds__(256) void k_scatter_stats(GridDev<real> G, const real* __restrict__ x, const real* __restrict__ y,
                                                        const real* __restrict__ wa, const real* __restrict__ wb,
@@ -99,13 +100,7 @@ __global__ __launch_bounds__(256) void k_scatter_stats(GridDev<real> G, const re
       real xp[D];
 #pragma unroll
       for (int q = 0; q < D; ++q) xp[q] = x[p * D + q];
-      // a point outside the grid raises the flag and contributes nothing at all (zero weights; no y^2 / log-noise
-      // term either, so a caller that catches the error keeps statistics that agree with A and b)
-      const bool inside = point_stencil<real, D>(G, xp, j0, w);
-      if (!inside) {
-        bad = true;
-        if (sub == 0) atomicAdd(err, 2);      // bits 1..: number of training points dropped (bit 0: any point outside)
-      }
+      if (!point_stencil<real, D>(G, xp, j0, w)) flag_outside(err, sub == 0, bad);
       yp = y[p];
       wap = wa[p];
       wbp = wb[p];
@@ -187,12 +182,11 @@ __global__ __launch_bounds__(256) void k_scatter_stats_sym(GridDev<real> G, cons
                                                            const real* __restrict__ noise, int64_t n, real* __restrict__ b,
                                                            real* __restrict__ A, double* __restrict__ stats, int32_t* __restrict__ err,
                                                            real* __restrict__ cnt, const real* __restrict__ u, real* __restrict__ res,
-                                                           real* __restrict__ mean_out = nullptr, uint32_t* __restrict__ z1 = nullptr,
-                                                           int64_t n1 = 0, uint32_t* __restrict__ z2 = nullptr, int64_t n2 = 0,
-                                                           const long long* __restrict__ guard = nullptr, long long guard_expect = 0,
-                                                           int g_lo = 0, int g_hi = 1 << 30, ScatterBatch bt = ScatterBatch{}) {
-  // several independent outputs in ONE launch (BFN:37-55 carries num_outputs as a batch dimension): blockIdx.y = output;
-  // same points, per-output targets / weights / statistics at fixed strides (a weight stride of 0 shares one weight vector)
+                                                           real* __restrict__ mean_out, uint32_t* __restrict__ z1, int64_t n1,
+                                                           uint32_t* __restrict__ z2, int64_t n2, const long long* __restrict__ guard,
+                                                           long long guard_expect, int g_lo, int g_hi, ScatterBatch bt) {
+  // the parameters are the members of AbsorbArgs (absorb.h), which documents them
+  // several independent outputs in ONE launch (BFN:37-55 carries num_outputs as a batch dimension): blockIdx.y = output
   {
     const int64_t o = blockIdx.y;
     y += o * bt.y_stride; wa += o * bt.w_stride; wb += o * bt.w_stride; noise += o * bt.w_stride;
@@ -202,15 +196,7 @@ __global__ __launch_bounds__(256) void k_scatter_stats_sym(GridDev<real> G, cons
     if (u) u += o * bt.vec_stride;
     if (res) res += o * bt.vec_stride;
   }
-  // [g_lo, g_hi): the stencil groups this replica owns (wiski_shard: a rank of a stencil-sharded step scatters the tap pairs
-  // of ITS groups only -- 1 / N of the atomics per point; b, cnt, res and the statistics stay replicated)
-  // speculative launch behind a solve whose convergence poll the host has not read yet (wiski_pcg_async_guard): the poll's
-  // publishing block decides on the device whether this absorb happens
-  if (guard && *guard != guard_expect) return;
-  // optional (wiski_scatter_stats_step): zero two word arrays on the way -- the scalar block and the accumulated partial
-  // vector of the solve that follows in the same streaming step
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n1; e += (int64_t)gridDim.x * blockDim.x) z1[e] = 0u;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n2; e += (int64_t)gridDim.x * blockDim.x) z2[e] = 0u;
+  if (!absorb_prologue(guard, guard_expect, z1, n1, z2, n2, blockDim.x, gridDim.x)) return;
   constexpr int T = 1 << (2 * D);
   constexpr int TP = T / 4;                      // tap prefixes (leading d-1 digits)
   constexpr int NPAIR = TP * (TP + 1) / 2;       // prefix pairs with code(pb) >= code(pa)
@@ -257,13 +243,7 @@ __global__ __launch_bounds__(256) void k_scatter_stats_sym(GridDev<real> G, cons
       real xp[D];
 #pragma unroll
       for (int q = 0; q < D; ++q) xp[q] = x[p * D + q];
-      // a point outside the grid raises the flag and contributes nothing at all (zero weights; no y^2 / log-noise
-      // term either, so a caller that catches the error keeps statistics that agree with A and b)
-      const bool inside = point_stencil<real, D>(G, xp, j0, w);
-      if (!inside) {
-        bad = true;
-        if (lane == 0 && blockIdx.y == 0) atomicAdd(err, 2);      // bits 1..: number of training points dropped (bit 0: any point outside)
-      }
+      if (!point_stencil<real, D>(G, xp, j0, w)) flag_outside(err, lane == 0 && blockIdx.y == 0, bad);      // (a dropped point counts once, not once per output)
       yp = y[p];
       wap = wa[p];
       wbp = wb[p];
@@ -408,86 +388,88 @@ static int64_t owner_min_points() {
   return v;
 }
 
-static int owner_ablate() { return 0; }
+// Every combination of AbsorbArgs an absorb refuses, each with its reason.  Nothing has been launched when this returns.
+template <typename real>
+static int absorb_validate(const AbsorbArgs<real>& a) {
+  if (a.n == 0) return WISKI_OK;                       // nothing to absorb: not even the pointers are looked at
+  if (!a.x || !a.y || !a.wa || !a.wb || !a.noise || !a.b || !a.stats || !a.err) return WISKI_E_BADARG;   // what every form reads and writes
+  if (a.mean_out == nullptr && (a.u != nullptr) != (a.res != nullptr)) return WISKI_E_BADARG;            // a carry without the mean is the pair (u, res)
+  if ((a.res && !a.u) || (a.mean_out && !a.u) || (a.u && !a.half)) return WISKI_E_BADARG;                // residual carry-over / mean: need u, half-stencil form only
+  if (a.guard && !a.half) return WISKI_E_BADARG;                                                         // so is the guard
+  // zero regions: whole words, with somewhere to write them, half-stencil form only
+  if ((a.n1_bytes | a.n2_bytes) & 3 || (a.n1_bytes && !a.z1) || (a.n2_bytes && !a.z2) || ((a.n1_bytes || a.n2_bytes) && !a.half)) return WISKI_E_BADARG;
+  if (a.sharded() && !a.half) return WISKI_E_BADARG;                                                     // stencil groups are groups of the half stencil
+  // batched outputs: the plain half-stencil absorb (with cnt and the carry pair) only
+  if (a.nout < 1 || (a.nout > 1 && (!a.half || a.mean_out || a.n1_bytes || a.n2_bytes || a.guard))) return WISKI_E_BADARG;
+  return WISKI_OK;
+}
+
+// Large single-output batches on a d = 3 half stencil with a binning workspace take the owner-computes form (scatter_owner.h);
+// a stencil shard never does (the owner form walks whole lines).  Its LDS accumulators ((g2 * 175 + 512) reals per block:
+// 172 slots + b, cnt, res per row, one scratch word per thread) must fit the device limit and the opt-in must succeed HERE,
+// before the first kernel of the pair is queued -- k_bin_points already updates statistics; otherwise the atomic form runs.
+template <typename real>
+static size_t owner_lds_bytes(const GridDev<real>& G) { return ((size_t)G.g[2] * (172 + 3) + 512) * sizeof(real); }
 
 template <typename real>
-static int scatter_impl(const wiski_grid* grid, const real* d_x, const real* d_y, const real* d_wa, const real* d_wb, const real* d_noise,
-                        int64_t n, real* d_b, real* d_A_st, double* d_stats, int32_t* d_err, void* stream, bool half = false,
-                        real* d_cnt = nullptr, const real* d_u = nullptr, real* d_res = nullptr, real* d_mean_out = nullptr,
-                        void* z1 = nullptr, int64_t n1_bytes = 0, void* z2 = nullptr, int64_t n2_bytes = 0, const void* d_guard = nullptr,
-                        int64_t guard_expect = 0, void* d_bin = nullptr, int64_t bin_bytes = 0, int g_lo = 0, int g_hi = 1 << 30, int nout = 1,
-                        ScatterBatch bt = ScatterBatch{}) {
-  GridDev<real> G;
-  int rc = make_grid_dev<real>(grid, &G);
-  if (rc) return rc;
-  if (n == 0) return WISKI_OK;
-  // argument validation comes first: the owner-computes branch below must not start mutating statistics on arguments the
-  // atomic form would have refused
-  if (!d_x || !d_y || !d_wa || !d_wb || !d_noise || !d_b || !d_stats || !d_err) return WISKI_E_BADARG;
-  if (d_mean_out == nullptr && (d_u != nullptr) != (d_res != nullptr)) return WISKI_E_BADARG;
-  if ((d_res && !d_u) || (d_mean_out && !d_u) || (d_u && !half)) return WISKI_E_BADARG;  // residual carry-over / mean: half-stencil form only
-  if (d_guard && !half) return WISKI_E_BADARG;
-  if ((n1_bytes | n2_bytes) & 3 || (n1_bytes && !z1) || (n2_bytes && !z2) || ((n1_bytes || n2_bytes) && !half)) return WISKI_E_BADARG;
-  // large batches on a d = 3 half stencil with a binning workspace: the owner-computes form (scatter_owner.h).  Its LDS
-  // accumulators ((g2 * 175 + 512) reals per block) must fit the device limit and the opt-in must succeed BEFORE the first
-  // kernel of the pair is queued -- k_bin_points already updates statistics; otherwise the atomic form runs.
-  const bool ranged = g_lo > 0 || g_hi < (1 << 30);      // a stencil shard: atomic form only (the owner form walks whole lines)
-  if (ranged && !half) return WISKI_E_BADARG;
-  if (nout < 1 || (nout > 1 && (!half || d_mean_out || n1_bytes || n2_bytes || d_guard))) return WISKI_E_BADARG;   // batched outputs: plain absorb only
-  bool owner = !ranged && nout == 1 && half && G.d == 3 && d_bin && d_cnt && d_A_st && G.g[2] <= 64 && G.g[0] > 3 && G.g[1] > 3 && G.g[2] > 3 && n < (int64_t)1 << 31 &&
-               n >= owner_min_points() && bin_bytes >= owner_work_bytes<real>(grid, n);
-  const size_t owner_lds = ((size_t)G.g[2] * (172 + 3) + 512) * sizeof(real);      // accumulators + one scratch word per thread
-  if (owner) {
-    static int lds_max = -1;
-    static size_t lds_set = 0;
-    if (lds_max < 0) {
-      int dev = 0, v = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) v = 64 * 1024;
-      lds_max = v;
-    }
-    if (owner_lds > (size_t)lds_max) {
-      owner = false;
-    } else if (owner_lds > 48 * 1024 && owner_lds > lds_set) {
-      if (hipFuncSetAttribute((const void*)k_owner_lines<real, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)owner_lds) != hipSuccess ||
-          hipFuncSetAttribute((const void*)k_owner_lines<real, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)owner_lds) != hipSuccess ||
-          hipFuncSetAttribute((const void*)k_owner_lines<real, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)owner_lds) != hipSuccess) {
-        (void)hipGetLastError();
-        owner = false;                               // the atomic form needs no opt-in
-      } else {
-        lds_set = owner_lds;
-      }
-    }
+static bool owner_applies(const GridDev<real>& G, const AbsorbArgs<real>& a) {
+  if (a.sharded() || a.nout != 1 || !a.half || G.d != 3 || !a.bin || !a.cnt || !a.A) return false;
+  if (G.g[2] > 64 || G.g[0] <= 3 || G.g[1] <= 3 || G.g[2] <= 3 || a.n >= (int64_t)1 << 31) return false;
+  if (a.n < owner_min_points() || a.bin_bytes < owner_work_bytes<real>(G, a.n)) return false;
+  static int lds_max = -1;
+  static size_t lds_set = 0;
+  if (lds_max < 0) {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) v = 64 * 1024;
+    lds_max = v;
   }
-  if (owner) {
-    static std::atomic<unsigned> epoch_src{0};
-    unsigned epoch = ++epoch_src;                    // never 0 (a zero-initialised head is "empty")
-    if (!epoch) epoch = ++epoch_src;
-    const int64_t ncell = (int64_t)(G.g[0] - 3) * (G.g[1] - 3) * (G.g[2] - 3);
-    char* w = static_cast<char*>(d_bin);
-    unsigned long long* head = reinterpret_cast<unsigned long long*>(w);
-    int32_t* next = reinterpret_cast<int32_t*>(w + (ncell * 8 + 255) / 256 * 256);
-    real* rec = reinterpret_cast<real*>(w + (ncell * 8 + 255) / 256 * 256 + (n * 4 + 255) / 256 * 256);
-    int64_t nb = (n + 3) / 4;
-    if (nb > 2048) nb = 2048;
-    hipLaunchKernelGGL((k_bin_points<real>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, G, d_x, d_y, d_wa, d_wb, d_noise, n, d_stats, d_err,
-                       d_u, d_res != nullptr ? 1 : 0, d_mean_out, head, next, rec, epoch, (uint32_t*)z1, n1_bytes / 4, (uint32_t*)z2, n2_bytes / 4,
-                       (const long long*)d_guard, (long long)guard_expect);
-    constexpr int owner_nt = 256;                    // threads per owner block (measured at 50^3, 4096 points: 69 us with 256, 88 us with 512)
-    const size_t lds = owner_lds;
-    const int abl = owner_ablate();
-    hipLaunchKernelGGL((k_owner_lines<real, owner_nt>), dim3((unsigned)(G.g[0] * G.g[1])), dim3(owner_nt), lds, (hipStream_t)stream, G, d_A_st, d_b, d_cnt, d_res,
-                       (const unsigned long long*)head, (const int32_t*)next, (const real*)rec, epoch, (const long long*)d_guard, (long long)guard_expect, abl);
-    return hipGetLastError() == hipSuccess ? WISKI_OK : WISKI_E_LAUNCH;
+  const size_t lds = owner_lds_bytes(G);
+  if (lds > (size_t)lds_max) return false;
+  if (lds > 48 * 1024 && lds > lds_set) {
+    if (hipFuncSetAttribute((const void*)k_owner_lines<real, OWNER_NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+      (void)hipGetLastError();
+      return false;                                    // the atomic form needs no opt-in
+    }
+    lds_set = lds;
   }
-  const int grp = half ? 64 : (G.T < 64 ? G.T : 64);
+  return true;
+}
+
+template <typename real>
+static int launch_owner(const GridDev<real>& G, const AbsorbArgs<real>& a, hipStream_t stream) {
+  static std::atomic<unsigned> epoch_src{0};
+  unsigned epoch = ++epoch_src;                        // never 0 (a zero-initialised head is "empty")
+  if (!epoch) epoch = ++epoch_src;
+  const int64_t n = a.n, ncell = (int64_t)(G.g[0] - 3) * (G.g[1] - 3) * (G.g[2] - 3);
+  char* w = static_cast<char*>(a.bin);                 // heads | next | records (owner_work_bytes)
+  unsigned long long* head = reinterpret_cast<unsigned long long*>(w);
+  int32_t* next = reinterpret_cast<int32_t*>(w + (ncell * 8 + 255) / 256 * 256);
+  real* rec = reinterpret_cast<real*>(w + (ncell * 8 + 255) / 256 * 256 + (n * 4 + 255) / 256 * 256);
+  int64_t nb = (n + 3) / 4;
+  if (nb > 2048) nb = 2048;
+  hipLaunchKernelGGL((k_bin_points<real>), dim3((unsigned)nb), dim3(256), 0, stream, G, a.x, a.y, a.wa, a.wb, a.noise, n, a.stats, a.err, a.u,
+                     a.res != nullptr ? 1 : 0, a.mean_out, head, next, rec, epoch, (uint32_t*)a.z1, a.n1_bytes / 4, (uint32_t*)a.z2, a.n2_bytes / 4,
+                     (const long long*)a.guard, (long long)a.guard_expect);
+  hipLaunchKernelGGL((k_owner_lines<real, OWNER_NT>), dim3((unsigned)(G.g[0] * G.g[1])), dim3(OWNER_NT), owner_lds_bytes(G), stream, G, a.A, a.b, a.cnt, a.res,
+                     (const unsigned long long*)head, (const int32_t*)next, (const real*)rec, epoch, (const long long*)a.guard, (long long)a.guard_expect);
+  return hipGetLastError() == hipSuccess ? WISKI_OK : WISKI_E_LAUNCH;
+}
+
+template <typename real>
+static int launch_atomic(const GridDev<real>& G, const AbsorbArgs<real>& a, hipStream_t stream) {
+  const int grp = a.half ? 64 : (G.T < 64 ? G.T : 64);
   const int64_t ppb = 256 / grp;
-  int64_t blocks = (n + ppb - 1) / ppb;
+  int64_t blocks = (a.n + ppb - 1) / ppb;
   if (blocks > 256 * 8) blocks = 256 * 8;
-  dim3 grd((unsigned)blocks, (unsigned)nout);
-#define CALL(DD)                                                                                                                              \
-  do {                                                                                                                                        \
-    if (half) hipLaunchKernelGGL((k_scatter_stats_sym<real, DD>), grd, dim3(256), 0, (hipStream_t)stream, G, d_x, d_y, d_wa, d_wb, d_noise, n, d_b, d_A_st, d_stats, d_err, d_cnt, d_u, d_res, d_mean_out, (uint32_t*)z1, n1_bytes / 4, (uint32_t*)z2, n2_bytes / 4, (const long long*)d_guard, (long long)guard_expect, g_lo, g_hi, bt); \
-    else hipLaunchKernelGGL((k_scatter_stats<real, DD>), grd, dim3(256), 0, (hipStream_t)stream, G, d_x, d_y, d_wa, d_wb, d_noise, n, d_b, d_A_st, d_stats, d_err, d_cnt);   \
+  dim3 grd((unsigned)blocks, (unsigned)a.nout);
+  ScatterBatch bt = a.bt;
+  bt.vec_stride = G.m;                                 // b / cnt / u / res of consecutive outputs are one grid vector apart
+#define CALL(DD)                                                                                                                                             \
+  do {                                                                                                                                                       \
+    if (a.half) hipLaunchKernelGGL((k_scatter_stats_sym<real, DD>), grd, dim3(256), 0, stream, G, a.x, a.y, a.wa, a.wb, a.noise, a.n, a.b, a.A, a.stats, a.err, \
+                                   a.cnt, a.u, a.res, a.mean_out, (uint32_t*)a.z1, a.n1_bytes / 4, (uint32_t*)a.z2, a.n2_bytes / 4, (const long long*)a.guard,  \
+                                   (long long)a.guard_expect, a.g_lo, a.g_hi, bt);                                                                              \
+    else hipLaunchKernelGGL((k_scatter_stats<real, DD>), grd, dim3(256), 0, stream, G, a.x, a.y, a.wa, a.wb, a.noise, a.n, a.b, a.A, a.stats, a.err, a.cnt);     \
   } while (0)
   WISKI_DISPATCH_D(G.d, CALL)
 #undef CALL
@@ -495,48 +477,93 @@ static int scatter_impl(const wiski_grid* grid, const real* d_x, const real* d_y
   return WISKI_OK;
 }
 
+template <typename real>
+int absorb(const wiski_grid* grid, const AbsorbArgs<real>& a, void* stream) {
+  // validation comes first: no branch below may start mutating statistics on arguments another branch would have refused
+  GridDev<real> G;
+  int rc = make_grid_dev<real>(grid, &G);
+  if (rc == WISKI_OK) rc = absorb_validate(a);
+  if (rc != WISKI_OK || a.n == 0) return rc;
+  return owner_applies(G, a) ? launch_owner(G, a, (hipStream_t)stream) : launch_atomic(G, a, (hipStream_t)stream);
+}
+template int absorb<float>(const wiski_grid*, const AbsorbArgs<float>&, void*);
+template int absorb<double>(const wiski_grid*, const AbsorbArgs<double>&, void*);
+
+// the points and targets every entry point passes on, in the order of its own parameter list
+template <typename real>
+static AbsorbArgs<real> absorb_args(const real* x, const real* y, const real* wa, const real* wb, const real* noise, int64_t n, real* b, real* A, bool half,
+                                    double* stats, int32_t* err) {
+  AbsorbArgs<real> a;
+  a.x = x; a.y = y; a.wa = wa; a.wb = wb; a.noise = noise; a.n = n;
+  a.b = b; a.A = A; a.half = half; a.stats = stats; a.err = err;
+  return a;
+}
 extern "C" {
 int wiski_scatter_stats_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A, double* stats, int32_t* err, void* s) {
-  return scatter_impl<float>(g, x, y, wa, wb, noise, n, b, A, stats, err, s);
+  return absorb(g, absorb_args(x, y, wa, wb, noise, n, b, A, false, stats, err), s);
 }
 int wiski_scatter_stats_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A, double* stats, int32_t* err, void* s) {
-  return scatter_impl<double>(g, x, y, wa, wb, noise, n, b, A, stats, err, s);
+  return absorb(g, absorb_args(x, y, wa, wb, noise, n, b, A, false, stats, err), s);
 }
 int wiski_scatter_stats_sym_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, double* stats, int32_t* err, void* s) {
-  return scatter_impl<float>(g, x, y, wa, wb, noise, n, b, A_half, stats, err, s, true);
+  return absorb(g, absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err), s);
 }
 int wiski_scatter_stats_sym_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* stats, int32_t* err, void* s) {
-  return scatter_impl<double>(g, x, y, wa, wb, noise, n, b, A_half, stats, err, s, true);
+  return absorb(g, absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err), s);
 }
 int wiski_scatter_stats_cnt_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A, int32_t half, float* cnt, const float* u, float* res, double* stats, int32_t* err, void* s) {
-  return scatter_impl<float>(g, x, y, wa, wb, noise, n, b, A, stats, err, s, half != 0, cnt, u, res);
+  AbsorbArgs<float> a = absorb_args(x, y, wa, wb, noise, n, b, A, half != 0, stats, err);
+  a.cnt = cnt; a.u = u; a.res = res;
+  return absorb(g, a, s);
 }
 int wiski_scatter_stats_cnt_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A, int32_t half, double* cnt, const double* u, double* res, double* stats, int32_t* err, void* s) {
-  return scatter_impl<double>(g, x, y, wa, wb, noise, n, b, A, stats, err, s, half != 0, cnt, u, res);
+  AbsorbArgs<double> a = absorb_args(x, y, wa, wb, noise, n, b, A, half != 0, stats, err);
+  a.cnt = cnt; a.u = u; a.res = res;
+  return absorb(g, a, s);
 }
 int wiski_scatter_stats_step_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, void* z1, int64_t n1, void* z2, int64_t n2, const void* guard, int64_t guard_expect, void* bin, int64_t bin_bytes, void* s) {
-  return scatter_impl<float>(g, x, y, wa, wb, noise, n, b, A_half, stats, err, s, true, cnt, u, res, mean_out, z1, n1, z2, n2, guard, guard_expect, bin, bin_bytes);
+  AbsorbArgs<float> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
+  a.cnt = cnt; a.u = u; a.res = res; a.mean_out = mean_out;
+  a.z1 = z1; a.n1_bytes = n1; a.z2 = z2; a.n2_bytes = n2; a.guard = guard; a.guard_expect = guard_expect;
+  a.bin = bin; a.bin_bytes = bin_bytes;
+  return absorb(g, a, s);
 }
 int wiski_scatter_stats_step_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, void* z1, int64_t n1, void* z2, int64_t n2, const void* guard, int64_t guard_expect, void* bin, int64_t bin_bytes, void* s) {
-  return scatter_impl<double>(g, x, y, wa, wb, noise, n, b, A_half, stats, err, s, true, cnt, u, res, mean_out, z1, n1, z2, n2, guard, guard_expect, bin, bin_bytes);
+  AbsorbArgs<double> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
+  a.cnt = cnt; a.u = u; a.res = res; a.mean_out = mean_out;
+  a.z1 = z1; a.n1_bytes = n1; a.z2 = z2; a.n2_bytes = n2; a.guard = guard; a.guard_expect = guard_expect;
+  a.bin = bin; a.bin_bytes = bin_bytes;
+  return absorb(g, a, s);
 }
 int wiski_scatter_stats_step_sharded_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, void* z1, int64_t n1, void* z2, int64_t n2, const void* guard, int64_t guard_expect, int32_t g_lo, int32_t g_hi, void* s) {
-  return scatter_impl<float>(g, x, y, wa, wb, noise, n, b, A_half, stats, err, s, true, cnt, u, res, mean_out, z1, n1, z2, n2, guard, guard_expect, nullptr, 0, g_lo, g_hi);
+  AbsorbArgs<float> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
+  a.cnt = cnt; a.u = u; a.res = res; a.mean_out = mean_out;
+  a.z1 = z1; a.n1_bytes = n1; a.z2 = z2; a.n2_bytes = n2; a.guard = guard; a.guard_expect = guard_expect;
+  a.g_lo = g_lo; a.g_hi = g_hi;
+  return absorb(g, a, s);
 }
 int wiski_scatter_stats_step_sharded_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, void* z1, int64_t n1, void* z2, int64_t n2, const void* guard, int64_t guard_expect, int32_t g_lo, int32_t g_hi, void* s) {
-  return scatter_impl<double>(g, x, y, wa, wb, noise, n, b, A_half, stats, err, s, true, cnt, u, res, mean_out, z1, n1, z2, n2, guard, guard_expect, nullptr, 0, g_lo, g_hi);
+  AbsorbArgs<double> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
+  a.cnt = cnt; a.u = u; a.res = res; a.mean_out = mean_out;
+  a.z1 = z1; a.n1_bytes = n1; a.z2 = z2; a.n2_bytes = n2; a.guard = guard; a.guard_expect = guard_expect;
+  a.g_lo = g_lo; a.g_hi = g_hi;
+  return absorb(g, a, s);
 }
 int wiski_scatter_stats_multi_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, int32_t nout, int64_t y_stride, int64_t w_stride, float* b, float* A_half, int64_t A_stride, float* cnt, const float* u, float* res, double* stats, int32_t* err, void* s) {
-  ScatterBatch bt; bt.y_stride = y_stride; bt.w_stride = w_stride; bt.vec_stride = g ? (int64_t)g->g[0] * (g->d > 1 ? g->g[1] : 1) * (g->d > 2 ? g->g[2] : 1) * (g->d > 3 ? g->g[3] : 1) : 0; bt.A_stride = A_stride;
-  return scatter_impl<float>(g, x, y, wa, wb, noise, n, b, A_half, stats, err, s, true, cnt, u, res, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, 0, 1 << 30, nout, bt);
+  AbsorbArgs<float> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
+  a.cnt = cnt; a.u = u; a.res = res;
+  a.nout = nout; a.bt.y_stride = y_stride; a.bt.w_stride = w_stride; a.bt.A_stride = A_stride;
+  return absorb(g, a, s);
 }
 int wiski_scatter_stats_multi_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, int32_t nout, int64_t y_stride, int64_t w_stride, double* b, double* A_half, int64_t A_stride, double* cnt, const double* u, double* res, double* stats, int32_t* err, void* s) {
-  ScatterBatch bt; bt.y_stride = y_stride; bt.w_stride = w_stride; bt.vec_stride = g ? (int64_t)g->g[0] * (g->d > 1 ? g->g[1] : 1) * (g->d > 2 ? g->g[2] : 1) * (g->d > 3 ? g->g[3] : 1) : 0; bt.A_stride = A_stride;
-  return scatter_impl<double>(g, x, y, wa, wb, noise, n, b, A_half, stats, err, s, true, cnt, u, res, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, 0, 1 << 30, nout, bt);
+  AbsorbArgs<double> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
+  a.cnt = cnt; a.u = u; a.res = res;
+  a.nout = nout; a.bt.y_stride = y_stride; a.bt.w_stride = w_stride; a.bt.A_stride = A_stride;
+  return absorb(g, a, s);
 }
 int64_t wiski_scatter_bin_bytes(const wiski_grid* g, int64_t n, int32_t elem_size) {
   if (!g || g->d != 3 || n < 0 || (elem_size != 4 && elem_size != 8)) return -1;
-  return elem_size == 4 ? owner_work_bytes<float>(g, n) : owner_work_bytes<double>(g, n);
+  return elem_size == 4 ? owner_work_bytes<float>(*g, n) : owner_work_bytes<double>(*g, n);
 }
 int wiski_stencil_expand_add_f32(const wiski_grid* g, float* half, float* full, void* s) { return expand_impl<float>(g, half, full, s); }
 int wiski_stencil_expand_add_f64(const wiski_grid* g, double* half, double* full, void* s) { return expand_impl<double>(g, half, full, s); }

@@ -7,7 +7,7 @@
 // poll, guarded on the device by the poll's own verdict (wiski_pcg_async_guard): the GPU goes from the last iteration
 // straight into the absorb instead of idling through the host's poll round trip (~20 us of a 220 us step).
 // Pure host code: it only sequences the entry points above.
-#include "wiski_common.h"
+#include "absorb.h"
 
 template <typename real>
 struct StreamArgs;
@@ -16,36 +16,30 @@ struct StreamArgs<float> { using type = wiski_stream_args_f32; };
 template <>
 struct StreamArgs<double> { using type = wiski_stream_args_f64; };
 
-static int scatter1(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* nz, int64_t n, float* b, float* A, float* cnt, const float* u, float* res, double* st, int32_t* err, void* s) {
-  return wiski_scatter_stats_cnt_f32(g, x, y, wa, wb, nz, n, b, A, 1, cnt, u, res, st, err, s);
-}
-static int scatter1(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* nz, int64_t n, double* b, double* A, double* cnt, const double* u, double* res, double* st, int32_t* err, void* s) {
-  return wiski_scatter_stats_cnt_f64(g, x, y, wa, wb, nz, n, b, A, 1, cnt, u, res, st, err, s);
-}
-// absorb + predictive mean of the batch (+ the zeroing the following solve would do in a launch of its own) in ONE kernel
-static int scatter_step1(const wiski_grid* g, const wiski_stream_args_f32* a, const float* x, const float* y, const float* wa, const float* wb, const float* nz, int64_t n, int carry, float* mean_out, int zero, const void* guard, int64_t expect, void* s) {
-  void *p1 = nullptr, *p2 = nullptr;
-  int64_t n1 = 0, n2 = 0;
-  if (zero)
-    if (int rc = wiski_pcg_zero_regions_f32(g, 1, a->max_iter, a->d_work, 1, &p1, &n1, &p2, &n2)) return rc;
+// The absorb of one batch into the statistics `a` points at.  mean_out given: absorb + predictive mean of the batch in ONE
+// kernel -- it reads U whether or not it carries the residual, takes the owner-computes form or this rank's stencil groups
+// where they apply and, with `zero`, does the zeroing the following solve would do in a launch of its own; `guard`: see
+// wiski_pcg_async_guard.  Without mean_out: the plain absorb, U read for the residual carry only.
+template <typename real>
+static int absorb_batch(const wiski_grid* g, const typename StreamArgs<real>::type* a, AbsorbArgs<real> r, int carry, int zero, void* s) {
+  r.b = a->d_b; r.A = a->d_A_half; r.half = true; r.cnt = a->d_cnt; r.stats = a->d_stats; r.err = a->d_err;
+  r.u = carry || r.mean_out ? a->d_U : nullptr;
+  r.res = carry ? a->d_R : nullptr;
+  if (!r.mean_out) return absorb(g, r, s);
+  if (zero) {
+    int rc;
+    if constexpr (sizeof(real) == 4) rc = wiski_pcg_zero_regions_f32(g, 1, a->max_iter, a->d_work, 1, &r.z1, &r.n1_bytes, &r.z2, &r.n2_bytes);
+    else rc = wiski_pcg_zero_regions_f64(g, 1, a->max_iter, a->d_work, 1, &r.z1, &r.n1_bytes, &r.z2, &r.n2_bytes);
+    if (rc) return rc;
+  }
   if (wiski_shard_active(a->shard)) {
     int32_t glo = 0, ghi = 0;
     if (int rc = wiski_shard_groups(g->d, a->shard->rank, a->shard->nranks, &glo, &ghi)) return rc;
-    return wiski_scatter_stats_step_sharded_f32(g, x, y, wa, wb, nz, n, a->d_b, a->d_A_half, a->d_cnt, a->d_U, carry ? a->d_R : nullptr, mean_out, a->d_stats, a->d_err, p1, n1, p2, n2, guard, expect, glo, ghi, s);
+    r.g_lo = glo; r.g_hi = ghi;
+  } else {
+    r.bin = a->d_bin; r.bin_bytes = a->bin_bytes;
   }
-  return wiski_scatter_stats_step_f32(g, x, y, wa, wb, nz, n, a->d_b, a->d_A_half, a->d_cnt, a->d_U, carry ? a->d_R : nullptr, mean_out, a->d_stats, a->d_err, p1, n1, p2, n2, guard, expect, a->d_bin, a->bin_bytes, s);
-}
-static int scatter_step1(const wiski_grid* g, const wiski_stream_args_f64* a, const double* x, const double* y, const double* wa, const double* wb, const double* nz, int64_t n, int carry, double* mean_out, int zero, const void* guard, int64_t expect, void* s) {
-  void *p1 = nullptr, *p2 = nullptr;
-  int64_t n1 = 0, n2 = 0;
-  if (zero)
-    if (int rc = wiski_pcg_zero_regions_f64(g, 1, a->max_iter, a->d_work, 1, &p1, &n1, &p2, &n2)) return rc;
-  if (wiski_shard_active(a->shard)) {
-    int32_t glo = 0, ghi = 0;
-    if (int rc = wiski_shard_groups(g->d, a->shard->rank, a->shard->nranks, &glo, &ghi)) return rc;
-    return wiski_scatter_stats_step_sharded_f64(g, x, y, wa, wb, nz, n, a->d_b, a->d_A_half, a->d_cnt, a->d_U, carry ? a->d_R : nullptr, mean_out, a->d_stats, a->d_err, p1, n1, p2, n2, guard, expect, glo, ghi, s);
-  }
-  return wiski_scatter_stats_step_f64(g, x, y, wa, wb, nz, n, a->d_b, a->d_A_half, a->d_cnt, a->d_U, carry ? a->d_R : nullptr, mean_out, a->d_stats, a->d_err, p1, n1, p2, n2, guard, expect, a->d_bin, a->bin_bytes, s);
+  return absorb(g, r, s);
 }
 static int pcg1(const wiski_grid* g, const wiski_stream_args_f32* a, int warm, int first_check, int32_t* it, double* rr, int32_t* herr, void* s,
                 wiski_pcg_async* as, int mode) {
@@ -69,6 +63,8 @@ static int stream_step_impl(const wiski_grid* grid, const typename StreamArgs<re
   if (wiski_shard_active(a->shard) && q > 0 && !d_mean_out) return WISKI_E_BADARG;   // the sharded absorb is the mean-emitting kernel
   int rc = WISKI_OK;
   if (h_resumed) *h_resumed = 0;
+  AbsorbArgs<real> batch;                    // the points of this call; absorb_batch adds the targets
+  batch.x = d_x; batch.y = d_y; batch.wa = d_wa; batch.wb = d_wb; batch.noise = d_noise; batch.n = q; batch.mean_out = d_mean_out;
   bool absorbed = false;                     // the speculative absorb below has run
   if (as && as->state == 1) {
     // A solve the previous call started is pending.  It has to finish BEFORE anything reads U (the batch mean) or changes the
@@ -81,7 +77,9 @@ static int stream_step_impl(const wiski_grid* grid, const typename StreamArgs<re
       const void* guard = nullptr;
       int64_t expect = 0;
       if (wiski_pcg_async_guard(as, &guard, &expect) == WISKI_OK) {
-        rc = scatter_step1(grid, a, d_x, d_y, d_wa, d_wb, d_noise, q, carry, d_mean_out, 1, guard, expect, stream);
+        AbsorbArgs<real> spec_batch = batch;
+        spec_batch.guard = guard; spec_batch.guard_expect = expect;
+        rc = absorb_batch<real>(grid, a, spec_batch, carry, 1, stream);
         if (rc) return rc;
         spec = true;
       }
@@ -106,12 +104,11 @@ static int stream_step_impl(const wiski_grid* grid, const typename StreamArgs<re
     if (d_mean_out) {
       // the absorb kernel forms w_p . U for the residual carry anyway: it is the predictive mean of the batch, so there is no
       // gather launch; with a handle the same kernel also zeroes what the solve below would zero in a launch of its own
-      rc = scatter_step1(grid, a, d_x, d_y, d_wa, d_wb, d_noise, q, carry, d_mean_out, as ? 1 : 0, nullptr, 0, stream);
+      rc = absorb_batch<real>(grid, a, batch, carry, as ? 1 : 0, stream);
       if (rc) return rc;
       if (as) as->prezeroed = 1;           // nothing touches the solve's workspace between this kernel and the solve below
     } else {
-      rc = scatter1(grid, d_x, d_y, d_wa, d_wb, d_noise, q, a->d_b, a->d_A_half, a->d_cnt, carry ? a->d_U : nullptr, carry ? a->d_R : nullptr, a->d_stats,
-                    a->d_err, stream);
+      rc = absorb_batch<real>(grid, a, batch, carry, 0, stream);
       if (rc) return rc;
     }
   }

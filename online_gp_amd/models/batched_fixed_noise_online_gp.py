@@ -279,11 +279,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             Y = Y[:, None]
         n = X.shape[0]
         unit = noise is None            # unit noise (OnlineSKIRegression, OSR:25,122): no per-point weight tensors at all
-        if unit:
-            if getattr(self, "_ones_cache", None) is None or self._ones_cache.shape[0] < n:
-                self._ones_cache = torch.ones(max(n, 4096), dtype=self._dtype, device=self._device)
-            ones = self._ones_cache[:n]
-        else:
+        if not unit:
             noise = noise.to(self._device, self._dtype)
         b = cache["interpolation_cache"]
         stats = cache["_stats"]
@@ -305,7 +301,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
                 else:
                     self._two_level_lose()
             else:
-                self._two_level_note(X, None if unit else (1.0 / noise[:, 0] if init else 1.0 / noise[:, 0].clamp_min(1e-7)), init=init)
+                self._two_level_note(X, None if unit else self._weight_a(noise[:, 0], init), init=init)
         carry = (mine and half_delta is None and not init and ms is not None and ms.get("R_ok", False)
                  and settings.residual_carry_over.on())
         carry_delta = (half_delta is not None and res_delta is not None and not init and ms is not None and ms.get("R_ok", False)
@@ -314,16 +310,11 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             ms["R_ok"] = False
         if getattr(self, "_scratch_stats", None) is None:
             self._scratch_stats = torch.zeros(2, dtype=torch.float64, device=self._device)
-        if self._absorb_all_outputs(cache, X, Y, noise, unit, init, half_delta, ops, dst, carry, ms, mine, n):
+        if half_delta is None and self._absorb_all_outputs(cache, X, Y, noise, init, ops, ms if carry else None):
             return carry_delta
         for o in range(self.num_outputs):
             yo = Y[:, o].contiguous()
-            if unit:
-                no = wa = wb = ones
-            else:
-                no = noise[:, o].contiguous()
-                wb = 1.0 / no
-                wa = wb if init else 1.0 / no.clamp_min(1e-7)   # clamp_min(1e-7)**0.5 of :163, squared
+            no, wa, wb = self._batch_weights(None if unit else noise[:, o].contiguous(), init, n)
             cnt_o = cache["_cnt"][o] if "_cnt" in cache else None     # row sums W^T wa ride on the same launch
             half = grid_ops.is_half_stencil(self._grid, dst[o])      # a handed-over cache may carry a full stencil
             if carry and not half:
@@ -343,12 +334,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
                 ops[o].update_roots_((Wd * wa.sqrt()[:, None]).t().contiguous())   # V = W^T diag(wa)^(1/2), BFN:163-168
             if mine and n > 0:
                 self._spectral_absorb(o, X, None if unit else wa, yo if unit else yo * wb, init=init, bypass=half_delta is not None)
-            if cache is self._kernel_cache or init:
-                if unit:
-                    self._wsum_host[o] += float(n)
-                else:
-                    self._wsum_dev[o] += wa.sum(dtype=torch.float64)
-                    self._wsum_dirty = True
+            if mine or init:
+                self._wsum_add(o, n, None if unit else wa)
         if "path_probes" in cache:                   # (single output: `wa` is the weight the points just entered A with)
             self._absorb_probes(cache, X, None if unit else wa, init)
         return carry_delta
@@ -365,37 +352,57 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             grid_ops.scatter_probes(self._grid, X, wa, cache["path_count"], cache["path_seed"], P, self._err)
             cache["path_count"] += n
 
-    def _absorb_all_outputs(self, cache, X, Y, noise, unit, init, half_delta, ops, dst, carry, ms, mine, n):
+    def _absorb_all_outputs(self, cache, X, Y, noise, init, ops, ms):
         """Several outputs, native packed half stencils, no root pairs to carry: ONE scatter launch for all of them
-        (wiski_scatter_stats_multi) instead of one per output.  False: not applicable, the caller loops."""
-        out = self.num_outputs
-        if out == 1 or half_delta is not None or n == 0 or "_cnt" not in cache or any(getattr(op, "root", None) is not None for op in ops):
+        (wiski_scatter_stats_multi) instead of one per output.  The arguments are what _absorb has prepared (noise None: unit;
+        ms: the mean state whose residual is carried, or None).  False: not applicable, the caller loops."""
+        out, n = self.num_outputs, X.shape[0]
+        if out == 1 or n == 0 or "_cnt" not in cache or any(getattr(op, "root", None) is not None for op in ops):
             return False
         pack = self._stencil_pack(ops)
         if pack is None:
             return False
+        unit, mine = noise is None, cache is self._kernel_cache
         Yt = Y.t().contiguous()                                   # [out, n]
-        if unit:
-            wa = wb = no = self._ones_cache[:n]
-        else:
-            no = noise.t().contiguous()
-            wb = 1.0 / no
-            wa = wb if init else 1.0 / no.clamp_min(1e-7)        # clamp_min(1e-7)**0.5 of :163, squared
+        no, wa, wb = self._batch_weights(None if unit else noise.t().contiguous(), init, n)
         b = cache["interpolation_cache"][:, :, 0]
         if not b.is_contiguous():
             return False
         grid_ops.scatter_stats_multi(self._grid, X, Yt, wa, wb, no, b, pack, cache["_cnt"], cache["_stats"], self._err,
-                                     u=ms["U"] if carry else None, res=ms["R"] if carry else None)
+                                     u=ms["U"] if ms else None, res=ms["R"] if ms else None)
         for o in range(out):
             if mine:
                 self._spectral_absorb(o, X, None if unit else wa[o], Yt[o] if unit else Yt[o] * wb[o], init=init)
             if mine or init:
-                if unit:
-                    self._wsum_host[o] += float(n)
-                else:
-                    self._wsum_dev[o] += wa[o].sum(dtype=torch.float64)
-                    self._wsum_dirty = True
+                self._wsum_add(o, n, None if unit else wa[o])
         return True
+
+    def _ones(self, n):
+        """[n] ones, a view of one cached vector (unit noise: weights and noise of every point)."""
+        if getattr(self, "_ones_cache", None) is None or self._ones_cache.shape[0] < n:
+            self._ones_cache = torch.ones(max(n, 4096), dtype=self._dtype, device=self._device)
+        return self._ones_cache[:n]
+
+    @staticmethod
+    def _weight_a(noise, init):
+        """The weight a point enters A with: 1 / noise, the noise floored at 1e-7 in an update (clamp_min(1e-7)**0.5 of :163, squared)."""
+        return 1.0 / noise if init else 1.0 / noise.clamp_min(1e-7)
+
+    def _batch_weights(self, noise, init, n):
+        """(noise, wa, wb) of a batch of n points, as the absorb kernels take them; noise None: unit noise, three times _ones(n)."""
+        if noise is None:
+            ones = self._ones(n)
+            return ones, ones, ones
+        wb = 1.0 / noise
+        return noise, wb if init else self._weight_a(noise, init), wb
+
+    def _wsum_add(self, o, n, wa):
+        """Output o's noise-weight sum grows by the weights wa of n absorbed points: on the host for unit noise (wa None), else on the device."""
+        if wa is None:
+            self._wsum_host[o] += float(n)
+        else:
+            self._wsum_dev[o] += wa.sum(dtype=torch.float64)
+            self._wsum_dirty = True
 
     # (the return value of _absorb tells the data-parallel caller whether res_delta was filled)
     @property
@@ -1051,12 +1058,10 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             return mean
         step, ms, pst = st
         q = X.shape[0]
-        if getattr(self, "_ones_cache", None) is None or self._ones_cache.shape[0] < q:
-            self._ones_cache = torch.ones(max(q, 4096), dtype=self._dtype, device=self._device)
-        ones = self._ones_cache[:q]
+        ones = self._ones(q)
         mean = torch.empty(q, dtype=self._dtype, device=self._device) if want_mean else None
         # bookkeeping of _absorb / prediction_cache
-        self._wsum_host[0] += float(q)
+        self._wsum_add(0, q, None)
         self.num_data = self.num_data + q
         self._refresh_count = getattr(self, "_refresh_count", 0) + 1
         self._two_level_step(step, pst, X, q)            # (may set the poll hint: before _first_poll)
@@ -1340,7 +1345,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             if noise is None:
                 was.append(torch.ones(X.shape[0], dtype=target._dtype, device=target._device))
             else:
-                was.append(1.0 / noise.to(target._device, target._dtype)[:, o].clamp_min(1e-7))
+                was.append(target._weight_a(noise.to(target._device, target._dtype)[:, o], False))
         target._memo["pending_rank_update"] = (old_posts, X, was, target._hyper_version())
 
     def _apply_pending_rank_update(self):

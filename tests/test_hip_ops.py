@@ -251,6 +251,69 @@ def test_scatter_stats_step_emits_mean_and_zeroes(tdt, d, g, n):
 
 
 @pytest.mark.parametrize("tdt", [torch.float32, torch.float64])
+def test_absorb_refusal_table(tdt):
+    """Every argument combination the absorb refuses, through the C ABI (d = 3, g = 8, n = 5): WISKI_E_BADARG before any launch
+    -- b, A, cnt, res, stats still all-zero, mean_out still NaN, the zero region untouched -- and n = 0 is WISKI_OK whatever
+    the pointers are."""
+    import ctypes
+
+    from online_gp_amd import _hip, grid_ops
+
+    BADARG, d, g, n = -1, 3, 8, 5
+    rng = np.random.default_rng(9)
+    grid = grid_ops.GridSpec([[-1.1, 1.1]] * d, g)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    mk = lambda a: torch.as_tensor(a, device="cuda", dtype=tdt)
+    zeros = lambda *s: torch.zeros(s, device="cuda", dtype=tdt)
+    noise = mk(rng.uniform(0.5, 2.0, n))
+    H = (grid.R + 1) // 2
+    t = dict(x=mk(rng.uniform(-1, 1, (n, d))), y=mk(rng.standard_normal(n)), wa=1.0 / noise, wb=1.0 / noise, noise=noise, u=mk(rng.standard_normal(grid.m)),
+             b=zeros(grid.m), A=zeros(H, grid.m), cnt=zeros(grid.m), res=zeros(grid.m), stats=torch.zeros(2, device="cuda", dtype=torch.float64),
+             mean_out=torch.full((n,), float("nan"), device="cuda", dtype=tdt), err=grid_ops.new_err_flag("cuda"),
+             z1=torch.full((2,), 0x01010101, device="cuda", dtype=torch.int32))
+    full = zeros(grid.R, grid.m)                              # the full-stencil target of the half = 0 case
+    stream = _hip.stream_ptr(dev)
+    i64, i32 = ctypes.c_int64, ctypes.c_int32
+
+    def p(a, k):                                               # the pointer of argument k: a[k] = None passes NULL, a tensor replaces the default
+        v = a.get(k, t[k])
+        return None if v is None else _hip.dptr(v)
+
+    def points(a, n_):
+        return [grid.ref] + [p(a, k) for k in ("x", "y", "wa", "wb", "noise")] + [i64(n_)]
+
+    def step(n_=n, n1=0, **a):
+        return _hip.fn("wiski_scatter_stats_step", tdt)(*points(a, n_), p(a, "b"), p(a, "A"), p(a, "cnt"), p(a, "u"), p(a, "res"), p(a, "mean_out"), p(a, "stats"),
+                                                      p(a, "err"), p(a, "z1") if n1 or "z1" in a else None, i64(n1), None, i64(0), None, i64(0), None, i64(0), stream)
+
+    def cnt(half=1, n_=n, **a):
+        return _hip.fn("wiski_scatter_stats_cnt", tdt)(*points(a, n_), p(a, "b"), p(a, "A"), i32(half), p(a, "cnt"), p(a, "u"), p(a, "res"), p(a, "stats"), p(a, "err"),
+                                                     stream)
+
+    def multi(nout, n_=n, **a):
+        return _hip.fn("wiski_scatter_stats_multi", tdt)(*points(a, n_), i32(nout), i64(n), i64(0), p(a, "b"), p(a, "A"), i64(H * grid.m), p(a, "cnt"), p(a, "u"),
+                                                       p(a, "res"), p(a, "stats"), p(a, "err"), stream)
+
+    refused = []
+    for k in ("x", "y", "wa", "wb", "noise", "b", "stats", "err"):        # a required pointer is NULL
+        refused += [(f"step {k}", step(**{k: None})), (f"cnt {k}", cnt(**{k: None}))]
+    refused += [("cnt u, no res", cnt(res=None)), ("cnt res, no u", cnt(u=None)),
+                ("cnt full stencil with carry", cnt(half=0, A=full)),
+                ("step mean_out, no u", step(u=None, res=None)), ("step res, no u", step(u=None, mean_out=None)), ("step mean_out and res, no u", step(u=None)),
+                ("step n1_bytes = 6", step(n1=6)), ("step n1_bytes = 8, z1 NULL", step(n1=8, z1=None)),
+                ("multi nout = 0", multi(0))]
+    torch.cuda.synchronize()
+    assert [(what, rc) for what, rc in refused if rc != BADARG] == []
+    null = {k: None for k in ("x", "y", "wa", "wb", "noise", "b", "A", "cnt", "u", "res", "mean_out", "stats", "err")}
+    assert step(n_=0, **null) == 0 and cnt(n_=0, **null) == 0 and multi(1, n_=0, **null) == 0 and step(n_=0) == 0
+    torch.cuda.synchronize()
+    for k in ("b", "A", "cnt", "res", "stats"):
+        assert float(t[k].abs().max()) == 0.0, k
+    assert float(full.abs().max()) == 0.0 and int(t["err"].item()) == 0
+    assert bool(torch.isnan(t["mean_out"]).all()) and bool((t["z1"] == 0x01010101).all())
+
+
+@pytest.mark.parametrize("tdt", [torch.float32, torch.float64])
 @pytest.mark.parametrize("gs,n", [((12, 12, 12), 9000), ((20, 9, 33), 8192), ((50, 50, 50), 10000), ((8, 64, 8), 12000)])
 def test_owner_computes_absorb_equals_the_atomic_form(tdt, gs, n):
     """wiski_scatter_stats_step with a binning workspace (batches >= 8192 points, d = 3): points binned by cell, one block per
