@@ -664,6 +664,29 @@ int wiski_gaussian_metrics_f64(int64_t n, const double* d_mu, const double* d_va
 int wiski_scatter_probes_f32(const wiski_grid* grid, const float* d_x, const float* d_wa, int64_t q, int64_t first_index, uint64_t seed, int32_t S, float* d_P, int32_t* d_err, void* stream);
 int wiski_scatter_probes_f64(const wiski_grid* grid, const double* d_x, const double* d_wa, int64_t q, int64_t first_index, uint64_t seed, int32_t S, double* d_P, int32_t* d_err, void* stream);
 
+/* ---- exponential forgetting of the streamed statistics (decay_stats.hip) ----
+ * Scaling every statistic by gamma in (0, 1] is the same GP with the noise d_i of every absorbed point replaced by d_i / gamma.  ONE launch,
+ * in place, plain loads and stores (16-byte vectors on the aligned body of every region, element-wise head and tail), no workspace:
+ *   plan         up to WISKI_DECAY_MAX_REGIONS regions of `real`s, x <- factor x: the half-stencil pack, b, cnt with factor gamma, the probe
+ *                vectors P [m][S] with sqrt(gamma) (cov(P_s) = A stays exact).  Each factor (in (0, 1], a double) is rounded ONCE to the working
+ *                precision, so a scaled element is the correctly rounded product x * (real)factor.  Regions must not overlap; n = 0 is skipped.
+ *   d_R, d_Z     (both or neither; n_res reals) the carried residual of wiski_pcg: R <- gamma R - (1 - gamma) Z keeps R = b - Z - A U for the
+ *                decayed (b, A) -- Z = Kt^-1 U does not depend on the data -- so the next solve stays warm without an A U product.
+ *   d_stats      [nout][2] fp64 (may be NULL with nout = 0): slot 0 (y^T D^-1 y) *= gamma, slot 1 (log|D|) -= h_count[o] log gamma, with
+ *                h_count [nout] (HOST) the number of points output o has absorbed.  nout <= WISKI_DECAY_MAX_OUTPUTS per call.
+ *   d_side       nside <= WISKI_DECAY_MAX_OUTPUTS further fp64 device scalars *= gamma (the model's noise-weight sums), or NULL / 0.
+ * gamma = 1 returns without a launch; gamma outside (0, 1] or NaN (or such a factor): WISKI_E_BADARG. */
+#define WISKI_DECAY_MAX_REGIONS 8
+#define WISKI_DECAY_MAX_OUTPUTS 8
+typedef struct wiski_decay_plan {
+  void* ptr[WISKI_DECAY_MAX_REGIONS];      /* DEVICE pointers to `real`s */
+  int64_t n[WISKI_DECAY_MAX_REGIONS];      /* elements */
+  double factor[WISKI_DECAY_MAX_REGIONS];
+  int32_t count, reserved;
+} wiski_decay_plan;
+int wiski_decay_stats_f32(const wiski_decay_plan* plan, double gamma, float* d_R, const float* d_Z, int64_t n_res, double* d_stats, int32_t nout, const double* h_count, double* d_side, int32_t nside, void* stream);
+int wiski_decay_stats_f64(const wiski_decay_plan* plan, double gamma, double* d_R, const double* d_Z, int64_t n_res, double* d_stats, int32_t nout, const double* h_count, double* d_side, int32_t nside, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 _SO = os.path.join(_CSRC, "libwiski_hip.so")
-_SOURCES = ["interp_gather.hip", "scatter_stats.hip", "solve.hip", "spectral.hip", "dense.hip", "collective.hip", "stream_step.hip", "spectral_basis.hip", "hyper_columns.hip", "two_level.hip", "hyper_step.hip", "lookahead.hip", "sample_paths.hip"]
+_SOURCES = ["interp_gather.hip", "scatter_stats.hip", "solve.hip", "spectral.hip", "dense.hip", "collective.hip", "stream_step.hip", "spectral_basis.hip", "hyper_columns.hip", "two_level.hip", "hyper_step.hip", "lookahead.hip", "sample_paths.hip", "decay_stats.hip"]
 _HEADERS = ["wiski_common.h", "spmv_sym_dma.h", "spmv_sym_dma_mc.h", "spmm_sym_cols.h", "spmm_sym_bcast.h", "scatter_owner.h", "absorb.h", "dense_small.h", "dense_coop.h",
             os.path.join("..", "..", "include", "wiski.h")]
 MAX_DIM = 4
@@ -58,6 +58,15 @@ COPY_MAX_SEGMENTS = 12
 class wiski_copy_plan(ctypes.Structure):
     _fields_ = [("src", ctypes.c_void_p * COPY_MAX_SEGMENTS), ("dst", ctypes.c_void_p * COPY_MAX_SEGMENTS), ("n", ctypes.c_int64 * COPY_MAX_SEGMENTS),
                 ("count", ctypes.c_int32), ("reserved", ctypes.c_int32), ("scalar", ctypes.c_double), ("scalar_dst", ctypes.c_void_p)]
+
+
+DECAY_MAX_REGIONS = 8
+DECAY_MAX_OUTPUTS = 8
+
+
+class wiski_decay_plan(ctypes.Structure):
+    _fields_ = [("ptr", ctypes.c_void_p * DECAY_MAX_REGIONS), ("n", ctypes.c_int64 * DECAY_MAX_REGIONS), ("factor", ctypes.c_double * DECAY_MAX_REGIONS),
+                ("count", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 def sources():

@@ -186,6 +186,10 @@ class ShardedStatsUpdater:
         if getattr(model, "_kernel_cache", None) is not None and "path_probes" in model._kernel_cache:
             # the probes are additive over shards and would all-reduce like b (every point has its own global index), but no exchange here carries them
             raise NotImplementedError("ShardedStatsUpdater does not carry path probes yet: build the model with num_path_probes=0")
+        if getattr(model, "forgetting_factor", None) is not None:
+            # a decay is one local launch per replica and would commute with the all-reduce, but the deltas in flight and the stencil shards
+            # would have to decay with it: single-GPU for now
+            raise NotImplementedError("ShardedStatsUpdater does not decay the statistics: build the model with forgetting_factor=None")
         self.model = model
         self.group = group
         self.exchange = exchange

@@ -395,6 +395,52 @@ def scatter_probes(grid, x, wa, first_index, seed, P, err):
     _hip.check(rc, "wiski_scatter_probes")
 
 
+def decay_stats(gamma, regions, stats=None, counts=None, R=None, Z=None, side=None):
+    """Exponential forgetting in ONE launch (``wiski_decay_stats``): every ``(tensor, factor)`` of `regions` is scaled in
+    place, ``x <- x * factor`` with the factor rounded once to the tensors' dtype (the stencil pack, b, cnt: gamma; the path probes:
+    sqrt(gamma)); ``stats [out, 2]`` (fp64) gets slot 0 times gamma and slot 1 minus ``counts[o] * log(gamma)``; the carried residual
+    ``R <- gamma R - (1 - gamma) Z`` (both or neither); ``side`` (a flat fp64 tensor of a few scalars) is scaled by gamma.  All tensors contiguous, on one
+    device, the regions / R / Z of one dtype.  gamma = 1 launches nothing; gamma outside (0, 1] or NaN raises WiskiError.  More than 8
+    regions, outputs or side scalars take one launch per 8."""
+    gamma = float(gamma)
+    regions = [(t, float(f)) for t, f in regions if t is not None and t.numel() > 0]
+    reals = [t for t, _ in regions] + [t for t in (R, Z) if t is not None]
+    if (R is None) != (Z is None) or (R is not None and (R.shape != Z.shape)):
+        raise _hip.WiskiError("decay_stats: R and Z go together and have one shape")
+    dtype = reals[0].dtype if reals else torch.float64
+    if any(t.dtype != dtype for t in reals):
+        raise _hip.WiskiError("decay_stats: the regions, R and Z must have one dtype")
+    nout = 0 if stats is None else stats.shape[0]
+    if stats is not None and (stats.dtype != torch.float64 or stats.dim() != 2 or stats.shape[1] != 2 or counts is None or len(counts) != nout):
+        raise _hip.WiskiError("decay_stats: stats is fp64 [out, 2] with one point count per output")
+    if side is not None and (side.dtype != torch.float64 or side.dim() != 1):
+        raise _hip.WiskiError("decay_stats: side is a flat fp64 tensor")
+    nside = 0 if side is None else side.numel()
+    every = reals + [t for t in (stats, side) if t is not None]
+    if not every:
+        if not (0.0 < gamma <= 1.0):
+            raise _hip.WiskiError("wiski_decay_stats failed: WISKI_E_BADARG")
+        return
+    dev = every[0].device
+    f = _hip.fn("wiski_decay_stats", dtype)
+    R_MAX, O_MAX = _hip.DECAY_MAX_REGIONS, _hip.DECAY_MAX_OUTPUTS
+    calls = max(1, -(-len(regions) // R_MAX), -(-nout // O_MAX), -(-nside // O_MAX))
+    for c in range(calls):
+        plan = _hip.wiski_decay_plan()
+        part = regions[c * R_MAX:(c + 1) * R_MAX]
+        plan.count = len(part)
+        for i, (t, fac) in enumerate(part):
+            plan.ptr[i], plan.n[i], plan.factor[i] = _hip.dptr(t).value, t.numel(), fac
+        o0, o1 = min(c * O_MAX, nout), min((c + 1) * O_MAX, nout)
+        cnts = (ctypes.c_double * max(1, o1 - o0))(*[float(v) for v in counts[o0:o1]]) if o1 > o0 else None
+        s0, s1 = min(c * O_MAX, nside), min((c + 1) * O_MAX, nside)
+        first = c == 0
+        rc = f(ctypes.byref(plan), ctypes.c_double(gamma), _hip.dptr(R) if first else None, _hip.dptr(Z) if first else None,
+               ctypes.c_int64(R.numel() if (first and R is not None) else 0), _hip.dptr(stats[o0:o1]) if o1 > o0 else None, ctypes.c_int32(o1 - o0), cnts,
+               _hip.dptr(side[s0:s1]) if s1 > s0 else None, ctypes.c_int32(s1 - s0), _hip.stream_ptr(dev))
+        _hip.check(rc, "wiski_decay_stats")
+
+
 def stencil_expand_add(grid, A_half, A_st):
     """A_st += expand(A_half) (delta and its mirror image); A_half is zeroed."""
     rc = _hip.fn("wiski_stencil_expand_add", A_st.dtype)(grid.ref, _hip.dptr(A_half), _hip.dptr(A_st), _hip.stream_ptr(A_st.device))

@@ -89,9 +89,16 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         num_data=None,
         num_path_probes=0,
         path_seed=0,
+        forgetting_factor=None,
     ):
         super().__init__()
         assert train_inputs is not None or kernel_cache is not None
+        # exponential forgetting (forget_): every update scales the statistics by this factor before it absorbs its batch
+        if forgetting_factor is not None:
+            forgetting_factor = float(forgetting_factor)
+            if not (0.0 < forgetting_factor <= 1.0):
+                raise ValueError(f"forgetting_factor must lie in (0, 1], got {forgetting_factor}")
+        self.forgetting_factor = forgetting_factor
 
         if train_targets is not None:
             if train_targets.dim() == 1:
@@ -592,6 +599,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         op = _wtw_ops(self._kernel_cache["WtW"])[0]
         if (world <= 1 and not comm) or self.num_outputs != 1 or self._use_dense() or not op.is_half or self._grid.m % 4 or op.root is not None:
             return False
+        if self.forgetting_factor is not None:
+            return False                             # (a decay touches the whole stencil: forgetting replicas are not sharded)
         if self.__dict__.get("_stencil_shard") is not None:
             return True
         self._finish_pending()
@@ -994,10 +1003,12 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         return MultivariateNormal(mean_o, cov)
 
     # -------------------------------------------------------------- updates --
-    def condition_on_observations(self, X, Y, noise=None, inplace=False):
+    def condition_on_observations(self, X, Y, noise=None, inplace=False, _decay=True):
         """a7, :258-285.  inplace: the statistics buffers are updated where they
         live (O(4^{2d}) atomics per point); otherwise they are cloned first and a
-        sibling model sharing covar_module / likelihood is returned."""
+        sibling model sharing covar_module / likelihood is returned.  With a ``forgetting_factor`` the statistics -- of the clone,
+        in the functional form -- decay once before the batch is absorbed (not for fantasies: batched conditioning,
+        ``get_fantasy_model``)."""
         if X.dim() > 2 or Y.dim() > 2:
             # batch-expanded conditioning (what OSB.fantasize asks for, OSB:51-61): a batch of conditioned copies
             if inplace:
@@ -1010,7 +1021,12 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         if noise is not None:
             noise = self._canon_noise(noise, Y)
         q = X.reshape(-1, self._grid.d).shape[0]
-        old_pc = self._rank_update_source(q)
+        gamma = self.forgetting_factor if _decay else None
+        if gamma == 1.0:
+            gamma = None
+        if gamma is not None and inplace:
+            self.forget_(gamma)
+        old_pc = None if gamma is not None else self._rank_update_source(q)      # (a rank-q update starts from the factor of the undecayed A)
         if inplace:
             self._absorb(self._kernel_cache, X, Y, noise, init=False)
             self.num_data = self.num_data + q
@@ -1024,11 +1040,14 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             learn_additional_noise=self.has_learnable_noise,
             likelihood=self.likelihood,
             num_data=self.num_data + q,
+            forgetting_factor=self.forgetting_factor,
         )
         new_gp._wsum_dev = self._wsum_dev.clone()
         new_gp._wsum_host = list(self._wsum_host)
         new_gp._wsum_dev_host = list(self._wsum_dev_host)
         new_gp._wsum_dirty = self._wsum_dirty
+        if gamma is not None:
+            new_gp._decay(gamma, self.num_data)          # the clone's buffers: the parent keeps its statistics bit for bit
         new_gp._absorb(new_cache, X, Y, noise, init=False)
         if self._mean_state is not None:
             new_gp._mean_state = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in self._mean_state.items()}
@@ -1044,7 +1063,13 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         ``condition_on_observations(X, Y, inplace=True)``, then the posterior mean refreshed.  Equivalent to
         ``m = self(X).mean; self.condition_on_observations(X, Y, inplace=True); self.prediction_cache`` -- which is also the
         fallback -- but on large single-output grids the three launches go through ONE C-ABI call (``wiski_stream_step``) with
-        the per-step host work reduced to bookkeeping.  Unit noise.  Returns the mean [n] (or None)."""
+        the per-step host work reduced to bookkeeping.  Unit noise.  Returns the mean [n] (or None).  With a ``forgetting_factor``
+        the statistics decay between the evaluation and the absorb (one more launch, ``wiski_decay_stats``)."""
+        gamma = self.forgetting_factor
+        if gamma is not None and gamma != 1.0:
+            self._finish_pending()                   # the solve in flight belongs to the undecayed statistics
+        else:
+            gamma = None
         st = self._stream_fast_state(X, Y)
         if st is None:
             self._finish_pending()
@@ -1057,6 +1082,10 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             self.prediction_cache
             return mean
         step, ms, pst = st
+        if gamma is not None:
+            # the absorb below reads the mean of the batch from the solution U of the undecayed system, which the prediction cache keeps
+            # pointing at; the refresh that ends this call makes it the solution of the decayed one
+            self._decay(gamma, self.num_data, keep_mean_cache=True)
         q = X.shape[0]
         ones = self._ones(q)
         mean = torch.empty(q, dtype=self._dtype, device=self._device) if want_mean else None
@@ -1473,7 +1502,70 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             targets = targets[:, None]
         if noise_term is None:
             noise_term = torch.ones_like(targets)
-        return self.condition_on_observations(inputs, targets, noise_term, inplace=False)
+        return self.condition_on_observations(inputs, targets, noise_term, inplace=False, _decay=False)   # a what-if on the current state
+
+    # ------------------------------------------------------------ forgetting --
+    def forget_(self, gamma):
+        """Exponential forgetting, in place: every streamed statistic is scaled by gamma in (0, 1] -- A, b, c, cnt by
+        gamma, the path probes by sqrt(gamma), log|D| moved by -n log gamma -- in ONE launch (``wiski_decay_stats``).  The model is then
+        exactly the GP in which every point absorbed so far has its noise d_i replaced by d_i / gamma (k calls: d_i gamma^-k): posterior,
+        marginal likelihood and sample paths follow.  ``num_data`` counts points and stays.  The warm-start state of the mean solve is
+        kept (its carried residual follows in closed form in the same launch); everything else derived from A is rebuilt on next use.
+        gamma = 1 does nothing.  Returns the model.
+
+        log|D| moves by ``num_data`` log gamma.  Points outside the grid that an absorb dropped are still counted in ``num_data`` until
+        the next ``check_bounds()`` takes them out (it is the one host sync), though they never entered log|D|: a decay between the two
+        moves log|D| -- the marginal likelihood only, not the posterior -- by ``dropped`` log gamma too much.  A stream that may
+        leave the grid and reads the MLL calls ``check_bounds()`` before it forgets."""
+        gamma = float(gamma)
+        if not (0.0 < gamma <= 1.0):
+            raise ValueError(f"gamma must lie in (0, 1], got {gamma}")
+        if gamma != 1.0:
+            if self.num_data is None:
+                raise RuntimeError("forget_ needs the number of absorbed points (log|D| moves by -n log gamma): hand num_data over with the kernel cache")
+            self._decay(gamma, self.num_data)
+        return self
+
+    def _decay(self, gamma, count, keep_mean_cache=False):
+        """forget_ for statistics that hold `count` points per output.  keep_mean_cache (the one-call streaming step, whose refresh
+        follows in the same call): the prediction cache of the PCG regime -- the operator and a view of the mean state -- stays."""
+        self._finish_pending()
+        self.leave_stencil_shard()
+        cache = self._kernel_cache
+        ops = _wtw_ops(cache["WtW"])
+        pack = self._stencil_pack(ops)
+        regions = [(pack, gamma)] if pack is not None else [(op.stencil, gamma) for op in ops]
+        regions.append((cache["interpolation_cache"], gamma))
+        if "_cnt" in cache:
+            regions.append((cache["_cnt"], gamma))
+        if "path_probes" in cache:
+            regions.append((cache["path_probes"], math.sqrt(gamma)))          # cov(P_s) = A stays exact
+        # R = b - Z - A U of the mean state: Z = Kt^-1 U does not depend on the data, so gamma R - (1 - gamma) Z is the residual of the
+        # same (U, Z) in the decayed system -- the next refresh starts warm and without an A U product
+        ms = self._mean_state
+        carry = ms is not None and ms.get("R_ok", False) and settings.residual_carry_over.on()
+        if ms is not None and not carry:
+            ms["R_ok"] = False
+        # (one launch for up to 8 outputs; beyond, one per 8 -- of stats rows and of the device parts of the noise-weight sums alike)
+        grid_ops.decay_stats(gamma, regions, stats=cache["_stats"], counts=[float(count)] * self.num_outputs,
+                             R=ms["R"] if carry else None, Z=ms["Z"] if carry else None, side=self._wsum_dev)
+        self._wsum_host = [gamma * w for w in self._wsum_host]
+        self._wsum_dev_host = [gamma * w for w in self._wsum_dev_host]
+        # derived from A (set_train_data's recipe, except that what is invariant under a scaling stays):
+        for op in ops:
+            op.root = op.inv_root = None            # L L^T described the undecayed matrix
+        for fac in self.__dict__.get("_spectral", {}).values():
+            fac.stale = True                         # rebuilt from the stencil when next asked
+        self._two_level_lose()                       # (its Gram matrix belongs to the undecayed statistics)
+        # the preconditioner (_memo["precond"]) stays: its eigenbasis depends on the NORMALISED density profile of cnt, which a scaling
+        # leaves alone, and its shift is wsum / norm at every use.  The mass the profile was taken at stays as well, so that "the data
+        # volume has doubled / halved since" keeps looking at the profile of a stream whose old points fade
+        # _stream_step_cache bakes pointers only (its shift is set at every step): it stays
+        if keep_mean_cache and not self._use_dense():
+            self._memo.pop("pending_rank_update", None)
+            self._memo.pop("root_space", None)
+        else:
+            self._dump_caches()
 
     def set_train_data(self, train_inputs, train_targets, train_noise_term):
         """:420-428 -- rebuild every statistic from scratch."""

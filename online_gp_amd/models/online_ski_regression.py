@@ -38,6 +38,7 @@ class OnlineSKIRegression(StreamingSKIWrapper):
             grid_size=[grid_size] * stem.output_dim,
             learn_additional_noise=True,
             num_path_probes=kwargs.get("num_path_probes", 0), path_seed=kwargs.get("path_seed", 0),
+            forgetting_factor=kwargs.get("forgetting_factor"),
         )
         self._setup(stem, gp, lr, init_x)
 
