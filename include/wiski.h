@@ -687,6 +687,38 @@ typedef struct wiski_decay_plan {
 int wiski_decay_stats_f32(const wiski_decay_plan* plan, double gamma, float* d_R, const float* d_Z, int64_t n_res, double* d_stats, int32_t nout, const double* h_count, double* d_side, int32_t nside, void* stream);
 int wiski_decay_stats_f64(const wiski_decay_plan* plan, double gamma, double* d_R, const double* d_Z, int64_t n_res, double* d_stats, int32_t nout, const double* h_count, double* d_side, int32_t nside, void* stream);
 
+/* ---- re-embedding of the streamed statistics on a grown / shifted / trimmed grid (regrid_stats.hip) ----
+ * The new grid has the spacing of `grid` and g_new[q] = grid->g[q] + below[q] + above[q] nodes per dim (negative: removed); the old node j of
+ * dim q is the new node j + below[q].  ONE launch copies every region of the plan, out of place: a region is k blocks of m nodes of w reals,
+ * element (c, node i, s) at src[c m w + i w + s] goes to dst[c m' w + i' w + s].  Every destination element is written exactly once -- zero
+ * where the old grid has no such node -- in destination order, 16-byte vectors where the phases allow (any alignment of src / dst to the
+ * element size is accepted); src is never written.  The layouts of the model:
+ *     half stencil, group 0          k = 1,          w = 4,  r0 = (7^d - 1) / 2            (src / dst: the stencil's first element)
+ *     half stencil, groups >= 1      k = (H - 4)/7,  w = 7,  r0 = 7 ((7^(d-1) - 1)/2 + 1)  (src + 4 m, dst + 4 m')
+ *     offset-major stencil rows      k = rows,       w = 1,  r0 = offset index of row 0    (0 for the full stencil, (7^d - 1)/2 for a half)
+ *     vectors [k][m] (b, cnt, ...)   k,              w = 1,  r0 = -1
+ *     probes [m][S]                  k = 1,          w = S,  r0 = -1
+ * r0 >= 0 names a stencil region: element (c, i, s) is A[i, i + off] for the offset index r0 + c w + s (base-7 digits, dim 0 first), and it is
+ * written as zero where that neighbour node lies outside the new grid (so that a trimmed A is the principal submatrix, in the same layout).
+ * report[i] >= 0 (a stencil region that contains the diagonal, offset index (7^d - 1)/2) asks for the drop report: the kernel ADDS to
+ * d_record[2 report] the number of source nodes without a destination whose A_ii != 0 and to d_record[2 report + 1] the sum of those A_ii
+ * (fp64; d_record holds WISKI_REGRID_MAX_REPORTS pairs and is zeroed by the caller).  `above` may be NULL (then g_new alone decides).
+ * WISKI_E_BADARG, with nothing launched: g_new[q] < 4; g_new[q] != g[q] + below[q] + above[q]; grids without a common node; a null or
+ * misaligned pointer; k or w < 1; a stencil region beyond offset index 7^d; a region whose src and dst overlap. */
+#define WISKI_REGRID_MAX_REGIONS 16
+#define WISKI_REGRID_MAX_REPORTS 8
+typedef struct wiski_regrid_plan {
+  const void* src[WISKI_REGRID_MAX_REGIONS];   /* DEVICE pointers to `real`s */
+  void* dst[WISKI_REGRID_MAX_REGIONS];
+  int64_t k[WISKI_REGRID_MAX_REGIONS];
+  int64_t r0[WISKI_REGRID_MAX_REGIONS];
+  int32_t w[WISKI_REGRID_MAX_REGIONS];
+  int32_t report[WISKI_REGRID_MAX_REGIONS];
+  int32_t count, reserved;
+} wiski_regrid_plan;
+int wiski_regrid_stats_f32(const wiski_grid* grid, const int32_t* below, const int32_t* above, const int32_t* g_new, const wiski_regrid_plan* plan, double* d_record, void* stream);
+int wiski_regrid_stats_f64(const wiski_grid* grid, const int32_t* below, const int32_t* above, const int32_t* g_new, const wiski_regrid_plan* plan, double* d_record, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 _SO = os.path.join(_CSRC, "libwiski_hip.so")
-_SOURCES = ["interp_gather.hip", "scatter_stats.hip", "solve.hip", "spectral.hip", "dense.hip", "collective.hip", "stream_step.hip", "spectral_basis.hip", "hyper_columns.hip", "two_level.hip", "hyper_step.hip", "lookahead.hip", "sample_paths.hip", "decay_stats.hip"]
+_SOURCES = ["interp_gather.hip", "scatter_stats.hip", "solve.hip", "spectral.hip", "dense.hip", "collective.hip", "stream_step.hip", "spectral_basis.hip", "hyper_columns.hip", "two_level.hip", "hyper_step.hip", "lookahead.hip", "sample_paths.hip", "decay_stats.hip", "regrid_stats.hip"]
 _HEADERS = ["wiski_common.h", "spmv_sym_dma.h", "spmv_sym_dma_mc.h", "spmm_sym_cols.h", "spmm_sym_bcast.h", "scatter_owner.h", "absorb.h", "dense_small.h", "dense_coop.h",
             os.path.join("..", "..", "include", "wiski.h")]
 MAX_DIM = 4
@@ -66,6 +66,16 @@ DECAY_MAX_OUTPUTS = 8
 
 class wiski_decay_plan(ctypes.Structure):
     _fields_ = [("ptr", ctypes.c_void_p * DECAY_MAX_REGIONS), ("n", ctypes.c_int64 * DECAY_MAX_REGIONS), ("factor", ctypes.c_double * DECAY_MAX_REGIONS),
+                ("count", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+REGRID_MAX_REGIONS = 16
+REGRID_MAX_REPORTS = 8
+
+
+class wiski_regrid_plan(ctypes.Structure):
+    _fields_ = [("src", ctypes.c_void_p * REGRID_MAX_REGIONS), ("dst", ctypes.c_void_p * REGRID_MAX_REGIONS), ("k", ctypes.c_int64 * REGRID_MAX_REGIONS),
+                ("r0", ctypes.c_int64 * REGRID_MAX_REGIONS), ("w", ctypes.c_int32 * REGRID_MAX_REGIONS), ("report", ctypes.c_int32 * REGRID_MAX_REGIONS),
                 ("count", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 

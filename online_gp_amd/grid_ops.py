@@ -60,6 +60,42 @@ class GridSpec:
     def ref(self):
         return ctypes.byref(self.c)
 
+    def shifted(self, below, above):
+        """The grid changed by whole nodes at unchanged spacing: ``below[q]`` nodes added in front of dim q and ``above[q]`` behind it
+        (ints or per-dim sequences, negative: removed).  Node arithmetic, ``g0' = g0 - below h``, ``h' = h``, ``g' = g + below + above``
+        -- nothing is recomputed from bounds, so the nodes both grids have coincide up to the rounding of one product and one sum (with
+        ``settings.float32_grid`` on, ``g0'`` is rounded to float32 as the constructor's grid is).  ``grid_bounds`` become the bounds from
+        which the constructor's recipe (``delta = (hi - lo) / (g - 2)``, ``linspace(lo - delta, hi + delta, g)``) builds this very grid:
+        ``lo' = g0' + h (g' - 1) / g'`` and ``hi' = g0' + h (g' - 1)^2 / g'``, so that ``GridSpec(new.grid_bounds, new.g)`` has the same
+        nodes up to rounding and ``shifted(0, 0)`` returns the old bounds.  (That recipe's spacing is ``delta g / (g - 1)``, not delta: lo
+        and hi lie a little outside node 1 and node g - 2, the box whose points are interior.)  The statistics of a model move with
+        ``regrid_stats``."""
+        a = [int(below)] * self.d if isinstance(below, int) else [int(v) for v in below]
+        b = [int(above)] * self.d if isinstance(above, int) else [int(v) for v in above]
+        if len(a) != self.d or len(b) != self.d:
+            raise ValueError(f"below / above need one entry per grid dim ({self.d})")
+        g = [gq + aq + bq for gq, aq, bq in zip(self.g, a, b)]
+        if min(g) < 4:
+            raise ValueError("cubic interpolation needs at least 4 grid points per dim")
+        if any(aq <= -gq or aq >= gn for gq, aq, gn in zip(self.g, a, g)):
+            raise ValueError("the shifted grid must share at least one node with the old one in every dim")
+        from . import settings
+
+        new = object.__new__(GridSpec)
+        new.d, new.g, new.h = self.d, g, list(self.h)
+        new.g0 = [g0 - aq * h for g0, aq, h in zip(self.g0, a, self.h)]
+        if settings.float32_grid.on():
+            new.g0 = [float(torch.tensor(v, dtype=torch.float32)) for v in new.g0]
+        new.grid_bounds = [[g0 + h * (gq - 1) / gq, g0 + h * (gq - 1) ** 2 / gq] for g0, h, gq in zip(new.g0, new.h, g)]
+        new.m = int(math.prod(g))
+        new.T, new.R = self.T, self.R
+        c = _hip.wiski_grid()
+        c.d = new.d
+        for q in range(new.d):
+            c.g[q], c.g0[q], c.h[q] = g[q], new.g0[q], new.h[q]
+        new.c = c
+        return new
+
     def grid_points(self, dtype=torch.float64, device="cpu"):
         """Per-dim 1-D grids (list of d tensors), as gpytorch's ``covar_module.grid``."""
         return [self.g0[q] + self.h[q] * torch.arange(self.g[q], dtype=dtype, device=device) for q in range(self.d)]
@@ -439,6 +475,80 @@ def decay_stats(gamma, regions, stats=None, counts=None, R=None, Z=None, side=No
                ctypes.c_int64(R.numel() if (first and R is not None) else 0), _hip.dptr(stats[o0:o1]) if o1 > o0 else None, ctypes.c_int32(o1 - o0), cnts,
                _hip.dptr(side[s0:s1]) if s1 > s0 else None, ctypes.c_int32(s1 - s0), _hip.stream_ptr(dev))
         _hip.check(rc, "wiski_decay_stats")
+
+
+def stencil_regrid_regions(old_grid, new_grid, src, dst, report=-1):
+    """The regions of ``regrid_stats`` that move one stencil: the native half stencil ``[H, m] -> [H, m']`` (group 0 as rows of 4, the
+    groups >= 1 as rows of 7, starting at 4 m / 4 m') or an offset-major full stencil ``[7^d, m] -> [7^d, m']``.  `report`: the slot of
+    the drop report this stencil's diagonal is counted in (-1: none)."""
+    R, m, m2 = old_grid.R, old_grid.m, new_grid.m
+    if src.dim() != 2 or dst.shape != (src.shape[0], m2) or src.shape[1] != m:
+        raise ValueError(f"stencil_regrid_regions: {tuple(src.shape)} -> {tuple(dst.shape)} is no stencil of a grid of {m} -> {m2} nodes")
+    if not is_half_stencil(old_grid, src):
+        return [(src, dst, R, 1, 0, report)]
+    H = (R + 1) // 2
+    regions = [(src.reshape(-1)[:4 * m], dst.reshape(-1)[:4 * m2], 1, 4, (R - 1) // 2, report)]
+    if H > 4:
+        regions.append((src.reshape(-1)[4 * m:], dst.reshape(-1)[4 * m2:], (H - 4) // 7, 7, 7 * ((R // 7 - 1) // 2 + 1), -1))
+    return regions
+
+
+def regrid_stats(old_grid, new_grid, below, regions):
+    """Re-embed statistics on a grid grown / shifted / trimmed by whole nodes (``wiski_regrid_stats``) in ONE launch, out of
+    place: `new_grid` is ``old_grid.shifted(below, above)``; every region ``(src, dst, k, w[, r0[, report]])`` holds k blocks of m nodes of
+    w reals, element (c, node i, s) at ``src[c m w + i w + s]`` goes to ``dst[c m' w + i' w + s]`` and every element of dst is written
+    exactly once (zero where the old grid has no such node; for a stencil region, ``r0 >= 0``: also where the entry's neighbour node is
+    outside the new grid).  src and dst are contiguous ROCm tensors (or flat views) of one dtype with ``k m w`` and ``k m' w`` elements.
+    ``report >= 0`` on the region that holds a stencil's diagonal asks for the drop report of that slot.  Returns ``(dropped_rows,
+    dropped_mass)``: per report slot, the number of removed nodes whose ``A_ii != 0`` and the sum of those ``A_ii`` (two lists; empty
+    without a report, else one host read).  Tables beyond the plan's 16 regions (or 8 report slots) take one launch per part."""
+    a = [int(below)] * old_grid.d if isinstance(below, int) else [int(v) for v in below]
+    if old_grid.d != new_grid.d or len(a) != old_grid.d:
+        raise _hip.WiskiError("regrid_stats: the grids and `below` must have one dimension")
+    regs = []
+    for reg in regions:
+        src, dst, k, w = reg[:4]
+        r0 = int(reg[4]) if len(reg) > 4 else -1
+        report = int(reg[5]) if len(reg) > 5 else -1
+        k, w = int(k), int(w)
+        if src.dtype != dst.dtype or src.device != dst.device or src.numel() != k * old_grid.m * w or dst.numel() != k * new_grid.m * w:
+            raise _hip.WiskiError(f"regrid_stats: region of {src.numel()} -> {dst.numel()} elements ({src.dtype} -> {dst.dtype}) does not match "
+                                  f"k = {k}, w = {w} on grids of {old_grid.m} -> {new_grid.m} nodes")
+        regs.append((src, dst, k, w, r0, report))
+    if not regs:
+        return [], []
+    dtype, dev = regs[0][0].dtype, regs[0][0].device
+    if any(r[0].dtype != dtype for r in regs):
+        raise _hip.WiskiError("regrid_stats: the regions must have one dtype")
+    nrep = max(r[5] for r in regs) + 1
+    record = torch.zeros((max(nrep, 1), 2), dtype=torch.float64, device=dev) if nrep > 0 else None
+    f = _hip.fn("wiski_regrid_stats", dtype)
+    c_below = (ctypes.c_int32 * old_grid.d)(*a)
+    c_above = (ctypes.c_int32 * old_grid.d)(*[gn - go - aq for gn, go, aq in zip(new_grid.g, old_grid.g, a)])
+    c_new = (ctypes.c_int32 * old_grid.d)(*new_grid.g)
+    i = 0
+    while i < len(regs):
+        plan = _hip.wiski_regrid_plan()
+        base = None                                          # first report slot of this launch
+        n = 0
+        while i < len(regs) and n < _hip.REGRID_MAX_REGIONS:
+            src, dst, k, w, r0, report = regs[i]
+            if report >= 0:
+                if base is None:
+                    base = report
+                if not (0 <= report - base < _hip.REGRID_MAX_REPORTS):
+                    break
+            plan.src[n], plan.dst[n], plan.k[n], plan.w[n], plan.r0[n] = _hip.dptr(src).value, _hip.dptr(dst).value, k, w, r0
+            plan.report[n] = report - base if report >= 0 else -1
+            n += 1
+            i += 1
+        plan.count = n
+        rc = f(old_grid.ref, c_below, c_above, c_new, ctypes.byref(plan), _hip.dptr(record[base:]) if base is not None else None, _hip.stream_ptr(dev))
+        _hip.check(rc, "wiski_regrid_stats")
+    if record is None:
+        return [], []
+    rec = record.tolist()
+    return [int(r[0]) for r in rec], [float(r[1]) for r in rec]
 
 
 def stencil_expand_add(grid, A_half, A_st):

@@ -302,6 +302,15 @@ class GridInterpolationKernel(Kernel):
         self.grid_sizes = list(self.grid_spec.g)
         self.grid_is_dynamic = False
 
+    def set_grid_spec(self, spec):
+        """Replace the inducing grid (``FixedNoiseOnlineSKIGP.regrid_``): geometry attributes follow, the cached lags are dropped."""
+        if spec.d != self.grid_spec.d:
+            raise ValueError("the new grid must have the dimension of the old one")
+        self.grid_spec = spec
+        self.grid_bounds = tuple((float(lo), float(hi)) for lo, hi in spec.grid_bounds)
+        self.grid_sizes = list(spec.g)
+        self.__dict__.pop("_lag_cat", None)
+
     @property
     def grid(self):
         p = next(self.base_kernel.parameters(), None)

@@ -133,6 +133,14 @@ class StreamingSKIWrapper(torch.nn.Module):
     def update(self, inputs, targets, update_stem=True, update_gp=True):
         inputs = self._as_rows(inputs)
         gp_targets, noise = self._encode(targets)
+        seen = self.gp.__dict__.get("_regrid_count", 0)
+        if self.gp.grow_grid:
+            # follow the features before anything looks at them; a captured hyper step belongs to the grid it was recorded on
+            with torch.no_grad():
+                self.gp.grow_to_cover_(self.stem(inputs))
+            if self.gp.__dict__.get("_regrid_count", 0) != seen:
+                self.__dict__["_graphed"] = None
+                seen = self.gp.__dict__["_regrid_count"]
         stem_loss = self._stem_step(inputs, gp_targets, noise) if update_stem else 0.0
         gp_loss = self._hyper_step() if update_gp else 0.0
         with torch.no_grad():
@@ -148,6 +156,8 @@ class StreamingSKIWrapper(torch.nn.Module):
         if torch.is_tensor(gp_loss):                 # the captured step's loss, read only now: the absorb above was queued behind the
             gs = self.__dict__.get("_graphed")       # graph without waiting for it (one GPU idle gap less per step)
             gp_loss = gs.read_loss() if gs is not None else float(gp_loss)
+        if self.gp.__dict__.get("_regrid_count", 0) != seen:     # the stem step moved the features and the absorb grew the grid once more
+            self.__dict__["_graphed"] = None
         return stem_loss, gp_loss
 
     def _ensure_eval(self):

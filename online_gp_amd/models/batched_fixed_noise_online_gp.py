@@ -90,9 +90,14 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         num_path_probes=0,
         path_seed=0,
         forgetting_factor=None,
+        grow_grid=False,
+        max_grid_size=None,
     ):
         super().__init__()
         assert train_inputs is not None or kernel_cache is not None
+        # following the stream (grow_to_cover_): every update first grows the grid by whole nodes until its batch is interior
+        self.grow_grid = bool(grow_grid)
+        self.max_grid_size = max_grid_size
         # exponential forgetting (forget_): every update scales the statistics by this factor before it absorbs its batch
         if forgetting_factor is not None:
             forgetting_factor = float(forgetting_factor)
@@ -1021,6 +1026,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         if noise is not None:
             noise = self._canon_noise(noise, Y)
         q = X.reshape(-1, self._grid.d).shape[0]
+        if self.grow_grid:
+            self.grow_to_cover_(X)                   # (exact: the functional form grows this model too, its posterior does not move)
         gamma = self.forgetting_factor if _decay else None
         if gamma == 1.0:
             gamma = None
@@ -1041,6 +1048,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             likelihood=self.likelihood,
             num_data=self.num_data + q,
             forgetting_factor=self.forgetting_factor,
+            grow_grid=self.grow_grid,
+            max_grid_size=self.max_grid_size,
         )
         new_gp._wsum_dev = self._wsum_dev.clone()
         new_gp._wsum_host = list(self._wsum_host)
@@ -1065,6 +1074,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         fallback -- but on large single-output grids the three launches go through ONE C-ABI call (``wiski_stream_step``) with
         the per-step host work reduced to bookkeeping.  Unit noise.  Returns the mean [n] (or None).  With a ``forgetting_factor``
         the statistics decay between the evaluation and the absorb (one more launch, ``wiski_decay_stats``)."""
+        if self.grow_grid:
+            self.grow_to_cover_(X)
         gamma = self.forgetting_factor
         if gamma is not None and gamma != 1.0:
             self._finish_pending()                   # the solve in flight belongs to the undecayed statistics
@@ -1503,6 +1514,117 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         if noise_term is None:
             noise_term = torch.ones_like(targets)
         return self.condition_on_observations(inputs, targets, noise_term, inplace=False, _decay=False)   # a what-if on the current state
+
+    # ------------------------------------------------------------ regridding --
+    def regrid_(self, below, above, drop="zero"):
+        """Grow, shift or trim the inducing grid by whole nodes, in place and exactly: ``below[q]`` nodes are added in
+        front of dim q and ``above[q]`` behind it (ints or per-dim sequences, negative: removed) at unchanged spacing,
+        ``GridSpec.shifted``.  A, b, cnt and the path probes are the old arrays at an index shift (new nodes hold zeros) and move in ONE
+        launch (``wiski_regrid_stats``); y^T D^-1 y, log|D|, ``num_data``, the noise-weight sums and the probes' seed / count stay.
+        Posterior, marginal likelihood and sample paths are unchanged to solver tolerance, and the model equals one built on the new grid
+        from all the data, as long as every absorbed point lies in an interior cell of both grids (points inside ``grid_bounds`` do).
+        Removing nodes no datum touches (A_ii = 0) is exact as well.
+
+        ``drop="zero"`` (default): if a removed node has A_ii != 0 a ValueError names the dims and the dropped mass, and the model is left
+        bit for bit as it was.  ``drop="any"`` commits anyway -- an APPROXIMATION: A becomes the principal submatrix on the kept nodes
+        (still PSD), b / cnt / probes lose the removed entries, the scalar statistics keep counting the points.
+
+        Everything derived from the grid size is dropped and rebuilt on next use (root pairs, spectral factors, two-level block,
+        preconditioner, streaming-step cache, PCG workspace, the warm-start state of the mean solve); the regime (dense / PCG) is
+        re-decided from the new m.  The kernel module receives the new grid: sibling models that share ``covar_module`` (functional
+        ``condition_on_observations``) must not be used afterwards.  Returns the model for ``drop="zero"`` (as ``forget_`` does) and
+        ``(model, dropped_mass)`` -- a float, summed over the outputs -- for ``drop="any"``."""
+        if drop not in ("zero", "any"):
+            raise ValueError(f'drop must be "zero" or "any", got {drop!r}')
+        old = self._grid
+        new = old.shifted(below, above)
+        a = [int(below)] * old.d if isinstance(below, int) else [int(v) for v in below]
+        bb = [gn - go - aq for gn, go, aq in zip(new.g, old.g, a)]
+        if not any(a) and not any(bb):
+            return self if drop == "zero" else (self, 0.0)
+        self._finish_pending()
+        self.leave_stencil_shard()
+        cache = self._kernel_cache
+        ops = _wtw_ops(cache["WtW"])
+        out, m2 = self.num_outputs, new.m
+        mk = lambda *shape: torch.empty(shape, dtype=self._dtype, device=self._device)      # (the kernel writes every element)
+        pack = self._stencil_pack(ops)
+        if pack is not None:
+            new_pack = mk(out, pack.shape[1], m2)         # the outputs' half stencils stay in one tensor
+            new_st = [new_pack[o] for o in range(out)]
+        else:
+            new_st = [mk(op.stencil.shape[0], m2) for op in ops]     # (an offset-major stencil is regridded in that layout)
+        regions = []
+        for o, op in enumerate(ops):
+            regions += grid_ops.stencil_regrid_regions(old, new, op.stencil.contiguous(), new_st[o], report=o)
+        b = cache["interpolation_cache"]
+        new_b = mk(out, m2, 1)
+        regions.append((b.contiguous(), new_b, out, 1))
+        new_cnt = None
+        if "_cnt" in cache:
+            new_cnt = mk(out, m2)
+            regions.append((cache["_cnt"].contiguous(), new_cnt, out, 1))
+        new_P = None
+        if "path_probes" in cache:
+            P = cache["path_probes"]
+            new_P = mk(m2, P.shape[1])
+            regions.append((P.contiguous(), new_P, 1, P.shape[1]))
+        rows, mass = grid_ops.regrid_stats(old, new, a, regions)
+        if sum(rows) > 0 and drop == "zero":
+            dims = [q for q in range(old.d) if a[q] < 0 or bb[q] < 0]
+            raise ValueError(f"regrid_: trimming dims {dims} (below {a}, above {bb}) would drop {sum(rows)} inducing nodes that carry data, "
+                             f"dropped mass sum A_ii = {sum(mass):.6g}; pass drop=\"any\" to cut anyway (an approximation)")
+        # ---- commit: swap the buffers, hand the new grid round, drop what was derived from the old size
+        new_ops = [StencilWtW(new, new_st[o]) for o in range(out)]
+        fresh = self._pack_cache(new_b, cache["_stats"], new_ops, new_cnt)
+        if new_cnt is None:
+            fresh.pop("_cnt")
+        if new_P is not None:
+            fresh.update(path_probes=new_P, path_seed=cache["path_seed"], path_count=cache["path_count"])
+        self._drop_spectral()
+        cache.clear()
+        cache.update(fresh)
+        self.covar_module.set_grid_spec(new)
+        self._grid = new
+        self._memo = {}                                # Toeplitz columns, preconditioner, prediction cache, root space, ...
+        for name in ("_stream_step_cache", "_two_level", "_profile_look", "_profile_look_host"):
+            self.__dict__.pop(name, None)
+        self._half_delta = None
+        self._pcg_ws = grid_ops.PCGWorkspace()
+        self._mean_state = None                        # (Z = Kt^-1 U does not embed: the next solve starts cold)
+        self._last_iters = None
+        self.__dict__["_regrid_count"] = self.__dict__.get("_regrid_count", 0) + 1
+        return self if drop == "zero" else (self, float(sum(mass)))
+
+    def grow_to_cover_(self, X, margin_nodes=1):
+        """The smallest whole-node growth (``regrid_``) after which every row of X [n, d] lies in an interior cell, at least
+        `margin_nodes` nodes away from the first and the last node of every dim; nothing happens (beyond one fused min / max and one host
+        read) when X already does.  Rows that are not finite are ignored (the absorb flags them as out of bounds).  If a dim would
+        exceed ``max_grid_size`` (an int or one per dim) the model's out-of-bounds RuntimeError is raised and nothing changes.
+        Returns the model."""
+        grid = self._grid
+        k = max(1, int(margin_nodes))
+        X = X.detach().reshape(-1, grid.d)
+        if X.shape[0] == 0:
+            return self
+        lo, hi = torch.aminmax(X.double(), dim=0)
+        ext = torch.stack((lo, hi)).tolist()
+        below, above = [0] * grid.d, [0] * grid.d
+        for q in range(grid.d):
+            xmin, xmax = ext[0][q], ext[1][q]
+            if not (math.isfinite(xmin) and math.isfinite(xmax)):
+                continue
+            below[q] = max(0, math.ceil((grid.g0[q] - xmin) / grid.h[q]) + k)               # xmin >= new node k
+            above[q] = max(0, math.ceil((xmax - grid.g0[q]) / grid.h[q]) - grid.g[q] + 1 + k)     # xmax <= new node g' - 1 - k
+        if not any(below) and not any(above):
+            return self
+        cap = self.max_grid_size
+        if cap is not None:
+            cap = [int(cap)] * grid.d if isinstance(cap, int) else [int(v) for v in cap]
+            if any(g + a + b > c for g, a, b, c in zip(grid.g, below, above, cap)):
+                self._raise_out_of_bounds(1)
+        self.regrid_(below, above)
+        return self
 
     # ------------------------------------------------------------ forgetting --
     def forget_(self, gamma):

@@ -272,6 +272,12 @@ class BatchedFantasyModel:
     def train(self, mode=True):
         return self
 
+    def regrid_(self, *args, **kwargs):
+        raise NotImplementedError("a batch of fantasy models shares its base model's grid and statistics: regrid the base model "
+                                  "(FixedNoiseOnlineSKIGP.regrid_) and fantasize again")
+
+    grow_to_cover_ = regrid_
+
 
 class _MultiOutputFantasyModel(BatchedFantasyModel):
     """num_outputs > 1: one single-output core per output (see BatchedFantasyModel)."""

@@ -35,7 +35,8 @@ class OnlineSKIClassifier(StreamingSKIWrapper):
         gp_targets, noise = self._encode(init_y)
         gp = FixedNoiseOnlineSKIGP(feats, gp_targets.to(feats.dtype), noise.to(feats.dtype),
                                    grid_bounds=torch.tensor([[-grid_bound, grid_bound]] * stem.output_dim),
-                                   grid_size=[grid_size] * stem.output_dim, forgetting_factor=kwargs.get("forgetting_factor"))
+                                   grid_size=[grid_size] * stem.output_dim, forgetting_factor=kwargs.get("forgetting_factor"),
+                                   grow_grid=kwargs.get("grow_grid", False), max_grid_size=kwargs.get("max_grid_size"))
         self._setup(stem, gp, lr, init_x)
 
     # ----- hooks of the streaming protocol

@@ -39,6 +39,7 @@ class OnlineSKIRegression(StreamingSKIWrapper):
             learn_additional_noise=True,
             num_path_probes=kwargs.get("num_path_probes", 0), path_seed=kwargs.get("path_seed", 0),
             forgetting_factor=kwargs.get("forgetting_factor"),
+            grow_grid=kwargs.get("grow_grid", False), max_grid_size=kwargs.get("max_grid_size"),
         )
         self._setup(stem, gp, lr, init_x)
 
