@@ -365,6 +365,39 @@ int wiski_stream_step_f64(const wiski_grid* grid, const wiski_stream_args_f64* a
 int wiski_scatter_stats_multi_f32(const wiski_grid* grid, const float* d_x, const float* d_y, const float* d_wa, const float* d_wb, const float* d_noise, int64_t n, int32_t nout, int64_t y_stride, int64_t w_stride, float* d_b, float* d_A_half, int64_t A_stride, float* d_cnt, const float* d_u, float* d_res, double* d_stats, int32_t* d_err, void* stream);
 int wiski_scatter_stats_multi_f64(const wiski_grid* grid, const double* d_x, const double* d_y, const double* d_wa, const double* d_wb, const double* d_noise, int64_t n, int32_t nout, int64_t y_stride, int64_t w_stride, double* d_b, double* d_A_half, int64_t A_stride, double* d_cnt, const double* d_u, double* d_res, double* d_stats, int32_t* d_err, void* stream);
 
+/* Derivative observations: values and gradients of f in ONE absorb launch.  Every point carries C = d + 1 scalar
+ * observations, d_y / d_wa / d_wb / d_noise / d_mean_out being [n][C]: channel 0 is f(x_p), channel 1 + q is df/dx_q (x_p).  Under
+ * the SKI model the latter is one more linear observation whose row of W is the value row with dim q's four weights replaced by
+ * k'(.) / h_q (zero where dim q's cell is a one-hot boundary cell: the rows wiski_gather_grad differentiates with).  Per point
+ *   b[a] += sum_c v_c[a] wb_c y_c,   A[a, b] += sum_c wa_c v_c[a] v_c[b],   stats += (sum_c wb_c y_c^2, sum_c log noise_c),
+ * the sum over c formed on chip, so that a point with a full gradient issues the T (T + 1) / 2 tap-pair atomics of a point with a
+ * value alone.  An absent channel is wa = wb = 0, noise = 1.  A present derivative channel in a boundary cell has a zero row: it
+ * adds its wb y^2 and log noise only (the model calls it pure noise).  A point outside the grid is dropped for every channel and
+ * counted once in d_err.  d_cnt (optional; feeds the preconditioner's density model only) += wa_0 v_0[a] + sum_{c >= 1} wa_c v_c[a]^2.
+ * The carry (optional, d_u with d_res and / or d_mean_out): d_mean_out[p][c] = v_c . u, the predictive mean and gradient of the
+ * point before the update, and d_res[a] += sum_c v_c[a] (wb_c y_c - wa_c (v_c . u)).  Symmetric half stencil, atomic form, d = 1..4. */
+int wiski_scatter_stats_grad_f32(const wiski_grid* grid, const float* d_x, const float* d_y, const float* d_wa, const float* d_wb, const float* d_noise, int64_t n, float* d_b, float* d_A_half, float* d_cnt, const float* d_u, float* d_res, float* d_mean_out, double* d_stats, int32_t* d_err, void* stream);
+int wiski_scatter_stats_grad_f64(const wiski_grid* grid, const double* d_x, const double* d_y, const double* d_wa, const double* d_wb, const double* d_noise, int64_t n, double* d_b, double* d_A_half, double* d_cnt, const double* d_u, double* d_res, double* d_mean_out, double* d_stats, int32_t* d_err, void* stream);
+
+/* The absorb with every option it has, as one record: what each wiski_scatter_stats_* entry above fills a part of.  Pointers are
+ * device pointers to float (wiski_absorb_f32) or double (wiski_absorb_f64) unless typed; a zeroed record with the points, d_b,
+ * d_stats, d_err and nout = 1 set is the plain absorb.  half: d_A is the symmetric half stencil (else offset-major); channels: 0,
+ * or d + 1 (wiski_scatter_stats_grad); g_hi = 0: every stencil group, else the groups [g_lo, g_hi) (wiski_scatter_stats_step_sharded);
+ * nout / *_stride as wiski_scatter_stats_multi.  Combinations no form of the absorb implements return WISKI_E_BADARG before
+ * anything is launched -- channels, for one, with a full stencil, a guard, zero regions, a shard or nout > 1. */
+typedef struct wiski_absorb_args {
+  const void* d_x; const void* d_y; const void* d_wa; const void* d_wb; const void* d_noise; int64_t n;
+  void* d_b; void* d_A; int32_t half; int32_t channels; void* d_cnt; double* d_stats; int32_t* d_err;
+  const void* d_u; void* d_res; void* d_mean_out;
+  void* z1; int64_t n1_bytes; void* z2; int64_t n2_bytes;
+  const void* d_guard; int64_t guard_expect;
+  void* d_bin; int64_t bin_bytes;
+  int32_t g_lo; int32_t g_hi; int32_t nout; int32_t reserved;
+  int64_t y_stride; int64_t w_stride; int64_t A_stride;
+} wiski_absorb_args;
+int wiski_absorb_f32(const wiski_grid* grid, const wiski_absorb_args* args, void* stream);
+int wiski_absorb_f64(const wiski_grid* grid, const wiski_absorb_args* args, void* stream);
+
 /* The two halves of a stencil-sharded step on their own (wiski_stream_step uses them when args->shard is set): the absorb
  * restricted to the stencil groups [g_lo, g_hi) (same arguments as wiski_scatter_stats_step; always the atomic form), and
  * wiski_pcg_async with every A . v product summed over the ranks of `shard`. */

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 _SO = os.path.join(_CSRC, "libwiski_hip.so")
 _SOURCES = ["interp_gather.hip", "scatter_stats.hip", "solve.hip", "spectral.hip", "dense.hip", "collective.hip", "stream_step.hip", "spectral_basis.hip", "hyper_columns.hip", "two_level.hip", "hyper_step.hip", "lookahead.hip", "sample_paths.hip", "decay_stats.hip", "regrid_stats.hip"]
-_HEADERS = ["wiski_common.h", "spmv_sym_dma.h", "spmv_sym_dma_mc.h", "spmm_sym_cols.h", "spmm_sym_bcast.h", "scatter_owner.h", "absorb.h", "dense_small.h", "dense_coop.h",
+_HEADERS = ["wiski_common.h", "spmv_sym_dma.h", "spmv_sym_dma_mc.h", "spmm_sym_cols.h", "spmm_sym_bcast.h", "scatter_owner.h", "scatter_grad.h", "absorb.h", "dense_small.h", "dense_coop.h",
             os.path.join("..", "..", "include", "wiski.h")]
 MAX_DIM = 4
 
@@ -77,6 +77,17 @@ class wiski_regrid_plan(ctypes.Structure):
     _fields_ = [("src", ctypes.c_void_p * REGRID_MAX_REGIONS), ("dst", ctypes.c_void_p * REGRID_MAX_REGIONS), ("k", ctypes.c_int64 * REGRID_MAX_REGIONS),
                 ("r0", ctypes.c_int64 * REGRID_MAX_REGIONS), ("w", ctypes.c_int32 * REGRID_MAX_REGIONS), ("report", ctypes.c_int32 * REGRID_MAX_REGIONS),
                 ("count", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class wiski_absorb_args(ctypes.Structure):
+    """The absorb's full argument record (include/wiski.h); a zeroed one with the points, d_b, d_stats, d_err and nout = 1 is the plain absorb."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("d_x", "d_y", "d_wa", "d_wb", "d_noise")] + [("n", ctypes.c_int64)] + [
+        ("d_b", ctypes.c_void_p), ("d_A", ctypes.c_void_p), ("half", ctypes.c_int32), ("channels", ctypes.c_int32), ("d_cnt", ctypes.c_void_p),
+        ("d_stats", ctypes.c_void_p), ("d_err", ctypes.c_void_p), ("d_u", ctypes.c_void_p), ("d_res", ctypes.c_void_p), ("d_mean_out", ctypes.c_void_p),
+        ("z1", ctypes.c_void_p), ("n1_bytes", ctypes.c_int64), ("z2", ctypes.c_void_p), ("n2_bytes", ctypes.c_int64),
+        ("d_guard", ctypes.c_void_p), ("guard_expect", ctypes.c_int64), ("d_bin", ctypes.c_void_p), ("bin_bytes", ctypes.c_int64),
+        ("g_lo", ctypes.c_int32), ("g_hi", ctypes.c_int32), ("nout", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("y_stride", ctypes.c_int64), ("w_stride", ctypes.c_int64), ("A_stride", ctypes.c_int64)]
 
 
 def sources():

@@ -18,10 +18,10 @@ template <typename real>
 struct AbsorbArgs {
   // points
   const real* x = nullptr;      // [n, d] coordinates; a point outside the grid is flagged in err and contributes nothing at all
-  const real* y = nullptr;      // [n] targets
-  const real* wa = nullptr;     // [n] weight a point enters A, cnt and the carried residual with
-  const real* wb = nullptr;     // [n] weight it enters b and y^T D^-1 y with
-  const real* noise = nullptr;  // [n] its noise: stats[1] += log noise
+  const real* y = nullptr;      // [n] targets                                                       ([n][channels] with channels)
+  const real* wa = nullptr;     // [n] weight a point enters A, cnt and the carried residual with    (likewise)
+  const real* wb = nullptr;     // [n] weight it enters b and y^T D^-1 y with                        (likewise)
+  const real* noise = nullptr;  // [n] its noise: stats[1] += log noise                              (likewise)
   int64_t n = 0;                // 0: nothing happens, whatever the other fields hold
   // targets
   real* b = nullptr;            // [m]
@@ -33,7 +33,7 @@ struct AbsorbArgs {
   // carry
   const real* u = nullptr;      // [m] current posterior mean on the grid
   real* res = nullptr;          // [m] res += W^T (wb y - wa (W u)): keeps res = b - z - A u exact under the increment
-  real* mean_out = nullptr;     // [n] w_p . u, the predictive mean of the batch BEFORE this update (saves the gather launch of a step)
+  real* mean_out = nullptr;     // [n] w_p . u, the predictive mean of the batch BEFORE this update (saves the gather launch of a step); [n][channels] with channels
   // zero regions: two word arrays of the solve that follows in the same streaming step (its scalar block, its partial vector)
   void* z1 = nullptr;
   int64_t n1_bytes = 0;         // multiples of 4
@@ -51,6 +51,10 @@ struct AbsorbArgs {
   // batch: several independent outputs in one launch -- same points, per-output y / weights / targets / statistics at `bt`
   int nout = 1;
   ScatterBatch bt;
+  // channels: 0, or d + 1 scalar observations per point -- its value and its d partial derivatives, each with its own y / wa / wb /
+  // noise (an absent one: wa = wb = 0, noise = 1) -- summed on chip into one atomic per tap pair (scatter_grad.h).  Single-output
+  // half-stencil atomic form only, with cnt and the carry; no guard, zero regions, shard or owner form
+  int channels = 0;
 
   bool sharded() const { return g_lo > 0 || g_hi < (1 << 30); }
 };

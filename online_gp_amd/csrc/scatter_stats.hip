@@ -325,6 +325,7 @@ __global__ __launch_bounds__(256) void k_scatter_stats_sym(GridDev<real> G, cons
 }
 
 #include "scatter_owner.h"
+#include "scatter_grad.h"
 
 // Unpacks the row-interleaved half stencil into a full offset-major stencil full[o][i] = A[i, i + off(o)]
 // (diagnostics, tests, and models handed a full-stencil cache):
@@ -390,7 +391,7 @@ static int64_t owner_min_points() {
 
 // Every combination of AbsorbArgs an absorb refuses, each with its reason.  Nothing has been launched when this returns.
 template <typename real>
-static int absorb_validate(const AbsorbArgs<real>& a) {
+static int absorb_validate(const AbsorbArgs<real>& a, int d) {
   if (a.n == 0) return WISKI_OK;                       // nothing to absorb: not even the pointers are looked at
   if (!a.x || !a.y || !a.wa || !a.wb || !a.noise || !a.b || !a.stats || !a.err) return WISKI_E_BADARG;   // what every form reads and writes
   if (a.mean_out == nullptr && (a.u != nullptr) != (a.res != nullptr)) return WISKI_E_BADARG;            // a carry without the mean is the pair (u, res)
@@ -401,6 +402,8 @@ static int absorb_validate(const AbsorbArgs<real>& a) {
   if (a.sharded() && !a.half) return WISKI_E_BADARG;                                                     // stencil groups are groups of the half stencil
   // batched outputs: the plain half-stencil absorb (with cnt and the carry pair) only
   if (a.nout < 1 || (a.nout > 1 && (!a.half || a.mean_out || a.n1_bytes || a.n2_bytes || a.guard))) return WISKI_E_BADARG;
+  // channels (value + d partials per point, scatter_grad.h): d + 1 of them, on the plain single-output half-stencil absorb only
+  if (a.channels && (a.channels != d + 1 || !a.half || a.guard || a.n1_bytes || a.n2_bytes || a.sharded() || a.nout > 1)) return WISKI_E_BADARG;
   return WISKI_OK;
 }
 
@@ -413,7 +416,7 @@ static size_t owner_lds_bytes(const GridDev<real>& G) { return ((size_t)G.g[2] *
 
 template <typename real>
 static bool owner_applies(const GridDev<real>& G, const AbsorbArgs<real>& a) {
-  if (a.sharded() || a.nout != 1 || !a.half || G.d != 3 || !a.bin || !a.cnt || !a.A) return false;
+  if (a.sharded() || a.nout != 1 || a.channels || !a.half || G.d != 3 || !a.bin || !a.cnt || !a.A) return false;
   if (G.g[2] > 64 || G.g[0] <= 3 || G.g[1] <= 3 || G.g[2] <= 3 || a.n >= (int64_t)1 << 31) return false;
   if (a.n < owner_min_points() || a.bin_bytes < owner_work_bytes<real>(G, a.n)) return false;
   static int lds_max = -1;
@@ -482,8 +485,9 @@ int absorb(const wiski_grid* grid, const AbsorbArgs<real>& a, void* stream) {
   // validation comes first: no branch below may start mutating statistics on arguments another branch would have refused
   GridDev<real> G;
   int rc = make_grid_dev<real>(grid, &G);
-  if (rc == WISKI_OK) rc = absorb_validate(a);
+  if (rc == WISKI_OK) rc = absorb_validate(a, G.d);
   if (rc != WISKI_OK || a.n == 0) return rc;
+  if (a.channels) return launch_grad(G, a, (hipStream_t)stream);
   return owner_applies(G, a) ? launch_owner(G, a, (hipStream_t)stream) : launch_atomic(G, a, (hipStream_t)stream);
 }
 template int absorb<float>(const wiski_grid*, const AbsorbArgs<float>&, void*);
@@ -498,7 +502,34 @@ static AbsorbArgs<real> absorb_args(const real* x, const real* y, const real* wa
   a.b = b; a.A = A; a.half = half; a.stats = stats; a.err = err;
   return a;
 }
+// the public record (wiski_absorb_args, include/wiski.h) as the typed one
+template <typename real>
+static AbsorbArgs<real> absorb_args(const wiski_absorb_args& p) {
+  AbsorbArgs<real> a = absorb_args((const real*)p.d_x, (const real*)p.d_y, (const real*)p.d_wa, (const real*)p.d_wb, (const real*)p.d_noise, p.n, (real*)p.d_b,
+                                   (real*)p.d_A, p.half != 0, p.d_stats, p.d_err);
+  a.cnt = (real*)p.d_cnt; a.u = (const real*)p.d_u; a.res = (real*)p.d_res; a.mean_out = (real*)p.d_mean_out;
+  a.z1 = p.z1; a.n1_bytes = p.n1_bytes; a.z2 = p.z2; a.n2_bytes = p.n2_bytes; a.guard = p.d_guard; a.guard_expect = p.guard_expect;
+  a.bin = p.d_bin; a.bin_bytes = p.bin_bytes;
+  if (p.g_hi > 0) { a.g_lo = p.g_lo; a.g_hi = p.g_hi; }
+  a.nout = p.nout; a.bt.y_stride = p.y_stride; a.bt.w_stride = p.w_stride; a.bt.A_stride = p.A_stride;
+  a.channels = p.channels;
+  return a;
+}
 extern "C" {
+int wiski_absorb_f32(const wiski_grid* g, const wiski_absorb_args* p, void* s) { return p ? absorb(g, absorb_args<float>(*p), s) : WISKI_E_BADARG; }
+int wiski_absorb_f64(const wiski_grid* g, const wiski_absorb_args* p, void* s) { return p ? absorb(g, absorb_args<double>(*p), s) : WISKI_E_BADARG; }
+int wiski_scatter_stats_grad_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, void* s) {
+  AbsorbArgs<float> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
+  a.cnt = cnt; a.u = u; a.res = res; a.mean_out = mean_out;
+  a.channels = g ? g->d + 1 : 0;
+  return absorb(g, a, s);
+}
+int wiski_scatter_stats_grad_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, void* s) {
+  AbsorbArgs<double> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
+  a.cnt = cnt; a.u = u; a.res = res; a.mean_out = mean_out;
+  a.channels = g ? g->d + 1 : 0;
+  return absorb(g, a, s);
+}
 int wiski_scatter_stats_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A, double* stats, int32_t* err, void* s) {
   return absorb(g, absorb_args(x, y, wa, wb, noise, n, b, A, false, stats, err), s);
 }

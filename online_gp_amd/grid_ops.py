@@ -415,6 +415,23 @@ def scatter_stats_multi(grid, x, Yt, wa, wb, noise, b, A_pack, cnt, stats, err, 
     _hip.check(rc, "wiski_scatter_stats_multi")
 
 
+def scatter_stats_grad(grid, x, Y, wa, wb, noise, b, A_half, cnt, stats, err, u=None, res=None, mean_out=None):
+    """Values and gradients in ONE absorb launch (``wiski_scatter_stats_grad``): Y / wa / wb / noise (and mean_out)
+    are [n, d + 1] -- column 0 the observation of f, column 1 + q that of df/dx_q; an absent one has wa = wb = 0, noise = 1.
+    (b, A_half, cnt, stats) accumulate in place; with u given, mean_out receives the predictive mean and gradient of every point
+    before the update and res the carried residual's increment."""
+    x = _x2d(x, grid)
+    n, C = x.shape[0], grid.d + 1
+    for name, t in (("Y", Y), ("wa", wa), ("wb", wb), ("noise", noise), ("mean_out", mean_out)):
+        if t is not None and (tuple(t.shape) != (n, C) or t.dtype != x.dtype):
+            raise ValueError(f"scatter_stats_grad: {name} must be [{n}, {C}] {x.dtype}, got {tuple(t.shape)} {t.dtype}")
+    rc = _hip.fn("wiski_scatter_stats_grad", x.dtype)(grid.ref, _hip.dptr(x), _hip.dptr(Y.contiguous()), _hip.dptr(wa.contiguous()),
+                                                      _hip.dptr(wb.contiguous()), _hip.dptr(noise.contiguous()), ctypes.c_int64(n), _hip.dptr(b),
+                                                      _hip.dptr(A_half), _hip.dptr(cnt), _hip.dptr(u), _hip.dptr(res), _hip.dptr(mean_out),
+                                                      _hip.dptr(stats), _hip.dptr(err), _hip.stream_ptr(x.device))
+    _hip.check(rc, "wiski_scatter_stats_grad")
+
+
 def scatter_probes(grid, x, wa, first_index, seed, P, err):
     """P [m, S] += the probe increments sum_i sqrt(wa_i) eps(first_index + i, s) w(x_i) of the points x [q, d]
     (``wiski_scatter_probes``; wa [q] or None = unit weights; the normals are a function of (seed, global point index, s):

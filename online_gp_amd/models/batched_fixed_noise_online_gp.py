@@ -1008,12 +1008,21 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         return MultivariateNormal(mean_o, cov)
 
     # -------------------------------------------------------------- updates --
-    def condition_on_observations(self, X, Y, noise=None, inplace=False, _decay=True):
+    def condition_on_observations(self, X, Y, noise=None, inplace=False, _decay=True, *, grad_Y=None, grad_noise=None, grad_mask=None):
         """a7, :258-285.  inplace: the statistics buffers are updated where they
         live (O(4^{2d}) atomics per point); otherwise they are cloned first and a
         sibling model sharing covar_module / likelihood is returned.  With a ``forgetting_factor`` the statistics -- of the clone,
         in the functional form -- decay once before the batch is absorbed (not for fantasies: batched conditioning,
-        ``get_fantasy_model``)."""
+        ``get_fantasy_model``).
+
+        ``grad_Y`` [n, d]: observations of the gradient of f at X, absorbed with the values in the same launch (DESIGN.md 3.15);
+        ``Y=None`` then means gradient-only.  ``grad_noise`` [n, d] or [n]: their noise (None: the value observation's, or unit
+        noise); ``grad_mask`` bool [n, d]: which partials were observed (None: all).  ``num_data`` grows by the number of scalar
+        observations.  Single output, unbatched X."""
+        if grad_Y is not None:
+            return self._condition_on_gradients(X, Y, noise, inplace, _decay, grad_Y, grad_noise, grad_mask)
+        if grad_noise is not None or grad_mask is not None:
+            raise ValueError("grad_noise / grad_mask describe grad_Y, which was not given")
         if X.dim() > 2 or Y.dim() > 2:
             # batch-expanded conditioning (what OSB.fantasize asks for, OSB:51-61): a batch of conditioned copies
             if inplace:
@@ -1041,12 +1050,23 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             self._seed_rank_updated_cache(self, old_pc, X, noise, Y)
             return None
         new_cache = self._clone_cache(self._kernel_cache)
+        new_gp = self._sibling(new_cache, self.num_data + q)
+        if gamma is not None:
+            new_gp._decay(gamma, self.num_data)          # the clone's buffers: the parent keeps its statistics bit for bit
+        new_gp._absorb(new_cache, X, Y, noise, init=False)
+        self._sibling_mean_state(new_gp)
+        self._seed_rank_updated_cache(new_gp, old_pc, X, noise, Y)
+        return new_gp
+
+    def _sibling(self, new_cache, num_data):
+        """The model the functional form returns, before its batch is absorbed: this model's modules, `new_cache` (a clone of the
+        kernel cache), this model's noise-weight sums."""
         new_gp = type(self)(
             covar_module=self.covar_module,
             kernel_cache=new_cache,
             learn_additional_noise=self.has_learnable_noise,
             likelihood=self.likelihood,
-            num_data=self.num_data + q,
+            num_data=num_data,
             forgetting_factor=self.forgetting_factor,
             grow_grid=self.grow_grid,
             max_grid_size=self.max_grid_size,
@@ -1055,16 +1075,108 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         new_gp._wsum_host = list(self._wsum_host)
         new_gp._wsum_dev_host = list(self._wsum_dev_host)
         new_gp._wsum_dirty = self._wsum_dirty
-        if gamma is not None:
-            new_gp._decay(gamma, self.num_data)          # the clone's buffers: the parent keeps its statistics bit for bit
-        new_gp._absorb(new_cache, X, Y, noise, init=False)
+        return new_gp
+
+    def _sibling_mean_state(self, new_gp):
+        """After the sibling's absorb: it starts its mean solve warm from a copy of this model's state, and in this model's mode."""
         if self._mean_state is not None:
             new_gp._mean_state = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in self._mean_state.items()}
             new_gp._mean_state["R_ok"] = False          # the copied residual predates the increment just absorbed
         if not self.training:
             new_gp.eval()
-        self._seed_rank_updated_cache(new_gp, old_pc, X, noise, Y)
+
+    # ---------------------------------------------- derivative observations --
+    def _condition_on_gradients(self, X, Y, noise, inplace, _decay, grad_Y, grad_noise, grad_mask):
+        """condition_on_observations with grad_Y: the batch becomes [n, d + 1] channel tensors -- column 0 the value,
+        column 1 + q the partial in dim q, each with its noise and a presence flag -- and one launch absorbs them."""
+        d = self._grid.d
+        if self.num_outputs > 1:
+            raise NotImplementedError("derivative observations are implemented for a single output")
+        if X.dim() > 2 or grad_Y.dim() > 2 or (Y is not None and Y.dim() > 2):
+            raise NotImplementedError("derivative observations cannot be fantasised: batched conditioning (X [..., n, d]) takes values only")
+        if "path_probes" in self._kernel_cache:
+            raise NotImplementedError("a model with path probes cannot absorb derivative observations (its probes follow value rows only)")
+        X = X.reshape(-1, d).to(self._device, self._dtype).contiguous()
+        n = X.shape[0]
+        dev, dt = self._device, self._dtype
+        if tuple(grad_Y.shape) != (n, d):
+            raise ValueError(f"grad_Y must be [{n}, {d}], got {tuple(grad_Y.shape)}")
+        Yc = torch.zeros((n, d + 1), dtype=dt, device=dev)
+        Nc = torch.ones((n, d + 1), dtype=dt, device=dev)
+        present = torch.ones((n, d + 1), dtype=torch.bool, device=dev)
+        Yc[:, 1:] = grad_Y.to(dev, dt)
+        if Y is None:
+            present[:, 0] = False
+        else:
+            Yc[:, 0] = Y.to(dev, dt).reshape(n)
+            if noise is not None:
+                Nc[:, 0] = noise.to(dev, dt).reshape(n)
+        if grad_noise is None:
+            Nc[:, 1:] = Nc[:, :1]                        # the value observation's noise (unit noise without one)
+        else:
+            gn = grad_noise.to(dev, dt)
+            Nc[:, 1:] = gn[:, None] if gn.dim() == 1 else gn
+        if grad_mask is not None:
+            if tuple(grad_mask.shape) != (n, d):
+                raise ValueError(f"grad_mask must be [{n}, {d}], got {tuple(grad_mask.shape)}")
+            present[:, 1:] = grad_mask.to(dev, torch.bool)
+        q = n * (d + 1 if Y is not None else d) if grad_mask is None else int(present.sum())     # scalar observations
+        if self.grow_grid:
+            self.grow_to_cover_(X)
+        gamma = self.forgetting_factor if _decay else None
+        if gamma == 1.0:
+            gamma = None
+        if inplace:
+            if gamma is not None:
+                self.forget_(gamma)
+            self._absorb_grad(self._kernel_cache, X, Yc, Nc, present)
+            self.num_data = self.num_data + q
+            self._dump_caches()
+            return None
+        new_cache = self._clone_cache(self._kernel_cache)
+        new_gp = self._sibling(new_cache, self.num_data + q)
+        if gamma is not None:
+            new_gp._decay(gamma, self.num_data)
+        new_gp._absorb_grad(new_cache, X, Yc, Nc, present)
+        self._sibling_mean_state(new_gp)
         return new_gp
+
+    def _absorb_grad(self, cache, X, Yc, Nc, present, half_delta=None):
+        """_absorb for [n, d + 1] channel tensors (values Yc, noises Nc, bool present), one launch (wiski_scatter_stats_grad).  The
+        carried residual follows when the mean state is current.  What a derivative row cannot be followed through is given up
+        rather than updated: the spectral factor is marked stale (it rebuilds from the stencil, exactly), the two-level block is
+        lost, a carried root pair is dropped, and no rank update is prepared."""
+        if half_delta is not None:
+            raise NotImplementedError("derivative observations do not follow the data-parallel statistics exchange (half_delta)")
+        if self.num_outputs > 1 or "path_probes" in cache:
+            raise NotImplementedError("derivative observations: single output, no path probes")
+        op = _wtw_ops(cache["WtW"])[0]
+        if not grid_ops.is_half_stencil(self._grid, op.stencil) or "_cnt" not in cache:
+            raise NotImplementedError("derivative observations need the native half-stencil cache (a full stencil was handed over)")
+        self._finish_pending()
+        mine = cache is self._kernel_cache
+        if mine:
+            self.leave_stencil_shard()
+        zero, one = torch.zeros((), dtype=self._dtype, device=self._device), torch.ones((), dtype=self._dtype, device=self._device)
+        wb = torch.where(present, 1.0 / Nc, zero)
+        wa = torch.where(present, self._weight_a(Nc, False), zero)
+        no = torch.where(present, Nc, one)               # an absent channel: wa = wb = 0, noise = 1 -- nothing anywhere
+        Yc = torch.where(present, Yc, zero)
+        ms = self._mean_state
+        carry = mine and ms is not None and ms.get("R_ok", False) and settings.residual_carry_over.on()
+        if mine and ms is not None and not carry:
+            ms["R_ok"] = False
+        grid_ops.scatter_stats_grad(self._grid, X, Yc, wa, wb, no, cache["interpolation_cache"][0, :, 0], op.stencil, cache["_cnt"][0],
+                                    cache["_stats"][0], self._err, u=ms["U"][0] if carry else None, res=ms["R"][0] if carry else None)
+        op.root = op.inv_root = None                     # L L^T described the matrix without these rows
+        if mine:
+            self._two_level_lose()
+            for fac in self.__dict__.get("_spectral", {}).values():
+                fac.stale = True
+            # the noise-weight sum (preconditioner shift only) is the mass of cnt, to which a derivative channel adds its diagonal
+            self._wsum_dev = cache["_cnt"].sum(dim=1, dtype=torch.float64)
+            self._wsum_host = [0.0] * self.num_outputs
+            self._wsum_dirty = True
 
     def stream_step(self, X, Y, want_mean=True):
         """evaluate -> absorb -> refresh for one streamed batch (the reference driver's online step at batch granularity,
