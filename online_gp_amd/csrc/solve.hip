@@ -2,7 +2,7 @@
 //   stencil SpMV  : WtW @ V                (URLT:47-48) on the block-stencil form
 //   Kron-Toeplitz : Kuu @ V                (BFN:334-348,363-366)
 //   PCG           : (Kt^-1 + A)^-1 RHS     (CG branch of BFN:368-383)
-#include "wiski_common.h"
+#include "pcg.h"
 
 #include <hip/hip_ext.h>
 
@@ -1934,150 +1934,194 @@ __global__ __launch_bounds__(256) void k_shard_reduce(int m4, int m, const real*
   }
 }
 
-static inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+// ------------------------------------------------------- the solve: pcg() ---
+// pcg_validate (every refusal) -> PcgPlan (kernels, grids, buffers: host arithmetic only) -> pcg_start (zero regions + starting
+// residual) -> pcg_iterate (the CG loop and its polls).  The contract is PcgArgs, the workspace PcgLayout (pcg.h).
 
-static int64_t pcg_ws_bytes(int m, int k, int max_iter, int es) {
-  int64_t vec = align_up((int64_t)k * m * es, 256);
-  int64_t scal = align_up(PcgScal::doubles(k, max_iter) * 8, 256);
-  return (6 + 8 + 6) * vec + scal;
+// which kernels a solve of (G, args) runs
+struct PcgPath {
+  bool wide;       // m % 4 == 0: the 16-byte vector kernels and the partial-vector SpMVs
+  bool sym;        // half stencil
+  bool spectral;   // eigen tables given: the separable preconditioner, else P = Kt
+  bool fused_cg;   // ... through the fused d = 3 front end (spectral.hip)
+  bool sharded;
+  template <typename real>
+  PcgPath(const GridDev<real>& G, const PcgArgs<real>& a)
+      : wide(G.m % 4 == 0), sym(a.a_sym), spectral(a.evec != nullptr && a.eval != nullptr), fused_cg(spectral && wide && spectral_fused_ok<real>(G)),
+        sharded(wiski_shard_active(a.shard)) {}
+};
+
+// Every combination of PcgArgs a solve refuses.  Nothing has been queued, no handle field written and no poll buffer taken when
+// this returns.
+template <typename real>
+static int pcg_validate(const GridDev<real>& G, const PcgArgs<real>& a, const PcgPath& path) {
+  if (!a.A || !a.RHS || !a.U || !a.Z || !a.work || a.k < 1 || a.max_iter < 1) return WISKI_E_BADARG;
+  if (a.mode != 0 && !a.handle) return WISKI_E_BADARG;                       // START / RESUME live in a handle
+  if (a.mode == 2 && a.handle->state != 1) return WISKI_E_BADARG;            // nothing was started on this one
+  if (!path.spectral && !a.tcol) return WISKI_E_BADARG;                      // no preconditioner at all
+  if (a.work_bytes < PcgLayout<real>::bytes(G.m, a.k, a.max_iter)) return WISKI_E_WORKSPACE;
+  if (path.sharded) {
+    // one column on the wide half-stencil kernels, a rank inside the communicator, and a way to sum over the ranks
+    if (!path.sym || !path.wide || a.k != 1 || a.shard->rank < 0 || a.shard->rank >= a.shard->nranks) return WISKI_E_BADARG;
+    if (!a.shard->comm && !a.shard->allreduce) return WISKI_E_BADARG;
+  }
+  if (a.mode != 2 && a.warm == 2 && !a.R) return WISKI_E_BADARG;             // the carried residual is the caller's R
+  // the exact block lives in the fused fp32 slab kernels (k > 1: launch_slab checks the scratch)
+  if (a.two_level && !(path.fused_cg && sizeof(real) == 4)) return WISKI_E_BADARG;
+  return WISKI_OK;
+}
+
+// number of partial vectors the wide SpMV leaves behind (0: the one-vector kernels of m % 4 != 0); on the half stencil the last
+// one is the atomically accumulated transposed term: zero on entry, re-zeroed by every consumer (*zl)
+template <typename real>
+static int pcg_partials(const GridDev<real>& G, int k, bool sym, int* zl) {
+  *zl = 0;
+  if (G.m % 4 != 0) return 0;
+  return sym ? sym_partials<real>(G, k, zl) : spmv_nch(G.d);
 }
 
 template <typename real>
-static int pcg_impl(const wiski_grid* grid, const real* d_A, const real* d_tcol, real kscale, const real* d_evec, const real* d_evec2, const real* d_eval,
-                    real shift, const real* d_RHS, int32_t k, real* d_U, real* d_Z, int32_t warm, double tol, int32_t max_iter,
-                    int32_t check_every, int32_t first_check, void* d_work, int64_t work_bytes, int32_t* h_iters, double* h_relres,
-                    const int32_t* d_err, int32_t* h_err, int32_t a_sym, real* d_R, void* stream, wiski_pcg_async* as = nullptr,
-                    int32_t amode = 0, const wiski_shard* shard = nullptr, const wiski_twolevel* two_level = nullptr) {
-  // shard (wiski_shard, nranks > 1): d_A holds only this rank's groups of the half stencil; every A . v product is this rank's
-  // share, summed over the ranks by ONE all-reduce of an m-vector (+ the p . Ap slots) per product on the solve's stream.
-  // Everything else -- preconditioner, vector updates, scalars -- is replicated, so all ranks take identical iterations.
-  // amode (with `as`): 0 = run to convergence; 1 = START: queue the iterations up to the first convergence poll, queue the
-  // poll and return WISKI_PENDING without waiting for it; 2 = RESUME a started solve (same arguments): wait for that poll
-  // (normally long over), finish with synchronous polls if it was not converged.  Nothing but the resume call may use
-  // (U, Z, R, workspace) in between.
-  GridDev<real> G;
-  int rc = make_grid_dev<real>(grid, &G);
-  if (rc) return rc;
-  if (!d_A || !d_RHS || !d_U || !d_Z || !d_work || k < 1 || max_iter < 1) return WISKI_E_BADARG;
-  if (amode != 0 && !as) return WISKI_E_BADARG;
-  const bool resume = amode == 2;
-  if (resume && as->state != 1) return WISKI_E_BADARG;
-  const bool spectral = d_evec != nullptr && d_eval != nullptr;
-  if (!spectral && !d_tcol) return WISKI_E_BADARG;
-  if (work_bytes < pcg_ws_bytes(G.m, k, max_iter, (int)sizeof(real))) return WISKI_E_WORKSPACE;
-  if (check_every < 1) check_every = 10;
-  hipStream_t s = (hipStream_t)stream;
-  const int m = G.m;
-  const int64_t vec = align_up((int64_t)k * m * sizeof(real), 256);
-  char* w = (char*)d_work;
-  real* r = d_R ? d_R : (real*)(w + 0 * vec);   // caller-owned residual: survives the call (carry-over for warm = 2)
-  real* y = (real*)(w + 1 * vec);
-  real* p = (real*)(w + 2 * vec);
-  real* pt = (real*)(w + 3 * vec);
-  real* hp = (real*)(w + 4 * vec);
-  real* tmp = (real*)(w + 5 * vec);
-  real* part = (real*)(w + 6 * vec);
-  real* ty = (real*)(w + 14 * vec);
-  real* sa = (real*)(w + 16 * vec);
-  real* sb = (real*)(w + 18 * vec);
-  PcgScal S{(double*)(w + 20 * vec), k, (double*)(w + 20 * vec) + PcgScal::scalars(k, max_iter)};
-  const bool wide = (m % 4) == 0;
-  const bool sym = a_sym != 0;
-  // number of partial vectors the wide SpMV leaves behind; on the half stencil the last one is the
-  // atomically accumulated transposed term: zero here, re-zeroed by every consumer (zl)
-  int zl = 0;
-  const int nch = wide ? (sym ? sym_partials<real>(G, k, &zl) : spmv_nch(G.d)) : 0;
-  const bool sharded = wiski_shard_active(shard);
+struct PcgPlan {
+  const GridDev<real>& G;
+  const PcgArgs<real>& a;
+  const PcgPath path;
+  const hipStream_t s;
+  const int m, k;
+  const PcgLayout<real> L;
+  real* r;                      // the residual: the caller's R (survives the call: carry-over for warm = 2) or workspace scratch
+  int nch, zl;                  // pcg_partials of the local product
   SymDmaParts stab{};
-  int sh_lo = 0, sh_hi = 0;                      // this replica's groups (stencil-sharded solves)
-  bool sh_dma = false;                           // its products run on the LDS-DMA kernel (part table) / on the LDS-window kernel (group range)
-  if (sharded) {
-    if (!sym || !wide || k != 1 || shard->rank < 0 || shard->rank >= shard->nranks) return WISKI_E_BADARG;
-    if (!shard->comm && !shard->allreduce) return WISKI_E_BADARG;
-    shard_group_range(sym_groups(G.d), shard->rank, shard->nranks, &sh_lo, &sh_hi);   // may be empty (more ranks than groups): zeros
-    sh_dma = sym_use_dma<real>(G, k);
-    if (sh_dma) shard_parts_d3(sh_lo, sh_hi, &stab);
+  int sh_lo = 0, sh_hi = 0;     // this replica's groups (stencil-sharded solves)
+  bool sh_dma = false;          // its products run on the LDS-DMA kernel (part table) / on the LDS-window kernel (group range)
+  real* cpart;                  // what the consumers of a product read: the partial vectors of the local launch, or the all-reduced sum
+  int cnch, czl;
+  dim3 egrid, vgrid;            // the vector kernels' grids: one element / one 16-byte group per thread, grid-stride
+  const double tol2;
+  bool init_in_fwd;             // fp32 fused path with a carried residual: the norms are formed by the first forward transform of r
+
+  PcgPlan(const GridDev<real>& G_, const PcgArgs<real>& a_, const PcgPath& path_, hipStream_t s_)
+      : G(G_), a(a_), path(path_), s(s_), m(G_.m), k(a_.k), L(G_.m, a_.k, a_.max_iter, a_.work), tol2(a_.tol * a_.tol) {
+    r = a.R ? a.R : L.r;
+    nch = pcg_partials<real>(G, k, path.sym, &zl);
+    if (path.sharded) {
+      shard_group_range(sym_groups(G.d), a.shard->rank, a.shard->nranks, &sh_lo, &sh_hi);   // may be empty (more ranks than groups): zeros
+      sh_dma = sym_use_dma<real>(G, k);
+      if (sh_dma) shard_parts_d3(sh_lo, sh_hi, &stab);
+    }
+    cpart = path.sharded ? L.hp : L.part;
+    cnch = path.sharded ? 1 : nch;
+    czl = path.sharded ? 0 : zl;
+    // Blocks per column of the vector kernels (grid-stride loops).  Every block ends with one fp64 atomic per norm on the
+    // column's scalar, the scalars of 16 columns share a 128-byte line, and same-line atomics serialise at the memory side
+    // (~12 ns each): 489 blocks x 64 columns made k_pcg_init 138 us on a 32 MB sweep.  m / 4096 blocks, 32..256.
+    int bcap = m / 4096;
+    bcap = bcap < 32 ? 32 : (bcap > 256 ? 256 : bcap);
+    if (k < 16 && bcap < 1024 / k) bcap = 1024 / k;     // few columns: the sweep wants the parallelism more than the atomics cost
+    int eb = (m + 255) / 256;
+    if (eb > bcap) eb = bcap;
+    egrid = dim3((unsigned)eb, (unsigned)k);
+    int vb = (m / 4 + 255) / 256;
+    if (vb < 1) vb = 1;
+    if (vb > bcap) vb = bcap;
+    vgrid = dim3((unsigned)vb, (unsigned)k);
+    init_in_fwd = a.mode != 2 && a.warm == 2 && sizeof(real) == 4 && path.fused_cg;
   }
-  // what the consumers of a product read: the partial vectors of the local launch, or the all-reduced sum
-  real* cpart = sharded ? hp : part;
-  const int cnch = sharded ? 1 : nch, czl = sharded ? 0 : zl;
-  auto spmv_wide = [&](const real* v, const real* add, real beta, double* dots) -> int {
-    if (!sharded)
-      return sym ? launch_spmv4_sym<real>(G, d_A, v, k, part, add, beta, dots, s) : launch_spmv4<real>(G, d_A, v, k, part, add, beta, dots, s);
+
+  // A . v on the wide kernels: partial vectors in L.part, or (sharded) this rank's share summed into L.hp and all-reduced
+  int product_wide(const real* v, const real* add, real beta, double* dots) const {
+    real* part = L.part;
+    if (!path.sharded)
+      return path.sym ? launch_spmv4_sym<real>(G, a.A, v, k, part, add, beta, dots, s) : launch_spmv4<real>(G, a.A, v, k, part, add, beta, dots, s);
     int np = 0;                                   // partial vectors this rank's launch wrote
     if (sh_dma) {
       if (stab.n) {
-        if (int r1 = launch_spmv4_sym<real>(G, d_A, v, k, part, add, beta, dots, s, &stab)) return r1;
+        if (int r1 = launch_spmv4_sym<real>(G, a.A, v, k, part, add, beta, dots, s, &stab)) return r1;
       }
       np = stab.n;
     } else if (sh_hi > sh_lo) {
-      if (int r1 = launch_spmv4_sym<real>(G, d_A, v, k, part, add, beta, dots, s, nullptr, sh_lo, sh_hi)) return r1;
+      if (int r1 = launch_spmv4_sym<real>(G, a.A, v, k, part, add, beta, dots, s, nullptr, sh_lo, sh_hi)) return r1;
       np = nch - 1;
     }
     const int m4 = m / 4;
     hipLaunchKernelGGL((k_shard_reduce<real>), dim3((unsigned)((m4 + 255) / 256)), dim3(256), 0, s, m4, m, (const real*)part, np,
-                       part + (int64_t)(nch - 1) * k * m, hp);
+                       part + (int64_t)(nch - 1) * k * m, L.hp);
     if (hipGetLastError() != hipSuccess) return WISKI_E_LAUNCH;
     const int64_t nd = dots ? (int64_t)k * PCG_DOT_COL : 0;
+    const wiski_shard* shard = a.shard;
     if (shard->comm) {
-      if constexpr (sizeof(real) == 4) return wiski_allreduce_stats_f32(shard->comm, nullptr, 0, (float*)hp, m, nullptr, 0, dots, nd, s);
-      else return wiski_allreduce_stats_f64(shard->comm, nullptr, 0, (double*)hp, m, nullptr, 0, dots, nd, s);
+      if constexpr (sizeof(real) == 4) return wiski_allreduce_stats_f32(shard->comm, nullptr, 0, (float*)L.hp, m, nullptr, 0, dots, nd, s);
+      else return wiski_allreduce_stats_f64(shard->comm, nullptr, 0, (double*)L.hp, m, nullptr, 0, dots, nd, s);
     }
-    return shard->allreduce(shard->ctx, hp, (int64_t)m, (int32_t)sizeof(real), dots, nd, s);
-  };
-  auto spmv_narrow = [&](const real* v, const real* add, real beta, real* out, double* dots) {
-    return sym ? launch_spmv_sym<real>(G, d_A, v, k, add, beta, out, dots, s) : launch_spmv<real>(G, d_A, v, k, add, beta, out, dots, s);
-  };
-  if (!resume && as && as->prezeroed) {
-    as->prezeroed = 0;      // wiski_stream_step had the step's first kernel zero both regions (wiski_pcg_zero_regions)
-  } else if (!resume) {
-    const int64_t nscal = PcgScal::doubles(k, max_iter), nvec = zl ? (int64_t)k * m : 0;
+    return shard->allreduce(shard->ctx, L.hp, (int64_t)m, (int32_t)sizeof(real), dots, nd, s);
+  }
+  // beta add + A . v: on the wide kernels as product_wide leaves it (the consumer sums), else finished in L.hp
+  int product(const real* v, const real* add, real beta, double* dots) const {
+    if (path.wide) return product_wide(v, add, beta, dots);
+    return path.sym ? launch_spmv_sym<real>(G, a.A, v, k, add, beta, L.hp, dots, s) : launch_spmv<real>(G, a.A, v, k, add, beta, L.hp, dots, s);
+  }
+};
+
+// One vector kernel K<real, VEC> of a plan on its grid: the 16-byte form (VEC = 4) where m % 4 == 0, else the element form.
+#define PCG_VEC_LAUNCH(plan, K, ...)                                                                          \
+  do {                                                                                                        \
+    if ((plan).path.wide) hipLaunchKernelGGL((K<real, 4>), (plan).vgrid, dim3(256), 0, (plan).s, __VA_ARGS__); \
+    else hipLaunchKernelGGL((K<real, 1>), (plan).egrid, dim3(256), 0, (plan).s, __VA_ARGS__);                  \
+  } while (0)
+
+// Zero regions (unless an earlier kernel of the streaming step zeroed them), then r0 and the norms ||rhs||^2, ||r0||^2.
+template <typename real>
+static int pcg_start(const PcgPlan<real>& plan) {
+  const PcgArgs<real>& a = plan.a;
+  const PcgLayout<real>& L = plan.L;
+  const hipStream_t s = plan.s;
+  const int m = plan.m, k = plan.k;
+  if (a.handle && a.handle->prezeroed) {
+    a.handle->prezeroed = 0;      // wiski_stream_step had the step's first kernel zero both regions (pcg_zero_regions)
+  } else {
+    const int64_t nscal = L.zero1_count(), nvec = L.zero2_count(plan.zl);
     int64_t zb = ((nscal > nvec ? nscal : nvec) + 255) / 256;
     if (zb > 1024) zb = 1024;
-    hipLaunchKernelGGL((k_pcg_zero<real>), dim3((unsigned)zb), dim3(256), 0, s, S.base, nscal, part + (int64_t)(nch > 0 ? nch - 1 : 0) * k * m, nvec);
+    hipLaunchKernelGGL((k_pcg_zero<real>), dim3((unsigned)zb), dim3(256), 0, s, L.zero1(), nscal, L.zero2(plan.nch), nvec);
   }
-  const double tol2 = tol * tol;
-  // Blocks per column of the vector kernels (grid-stride loops).  Every block ends with one fp64 atomic per norm on the
-  // column's scalar, the scalars of 16 columns share a 128-byte line, and same-line atomics serialise at the memory side
-  // (~12 ns each): 489 blocks x 64 columns made k_pcg_init 138 us on a 32 MB sweep.  m / 4096 blocks, 32..256.
-  int bcap = m / 4096;
-  bcap = bcap < 32 ? 32 : (bcap > 256 ? 256 : bcap);
-  if (k < 16 && bcap < 1024 / k) bcap = 1024 / k;     // few columns: the sweep wants the parallelism more than the atomics cost
-  int eb = (m + 255) / 256;
-  if (eb > bcap) eb = bcap;
-  dim3 egrid((unsigned)eb, (unsigned)k);
-  int vb = (m / 4 + 255) / 256;
-  if (vb < 1) vb = 1;
-  if (vb > bcap) vb = bcap;
-  dim3 vgrid((unsigned)vb, (unsigned)k);   // 16-byte groups, grid-stride
-
-  // fp32 fused path with a carried residual: the norms are formed by the first forward transform of r (apply = 2 below)
-  const bool init_in_fwd = !resume && warm == 2 && sizeof(real) == 4 && spectral && wide && spectral_fused_ok<real>(G);
-  if (resume) {
-    // the start call queued everything up to (and including) the poll of iteration as->it
-  } else if (warm == 2 && init_in_fwd) {
-    if (!d_R) return WISKI_E_BADARG;
-  } else if (warm == 2) {
-    // r0 carried over by the caller in d_R (wiski_scatter_stats_cnt's d_res): no A u product
-    if (!d_R) return WISKI_E_BADARG;
-    if (wide) hipLaunchKernelGGL((k_pcg_init<real, 4>), vgrid, dim3(256), 0, s, m, d_RHS, (const real*)nullptr, (real*)nullptr, 0, 0, 1, r, S);
-    else hipLaunchKernelGGL((k_pcg_init<real, 1>), egrid, dim3(256), 0, s, m, d_RHS, (const real*)nullptr, (real*)nullptr, 0, 0, 1, r, S);
-  } else if (warm) {
+  if (a.warm == 2 && plan.init_in_fwd) {
+    // the first fused forward transform of r forms the norms
+  } else if (a.warm == 2) {
+    // r0 carried over by the caller in R (wiski_scatter_stats_cnt's d_res): no A u product
+    PCG_VEC_LAUNCH(plan, k_pcg_init, m, a.RHS, (const real*)nullptr, (real*)nullptr, 0, 0, 1, plan.r, L.S);
+  } else if (a.warm) {
     // r0 = rhs - (z + A u)
-    if (wide) {
-      rc = spmv_wide(d_U, nullptr, (real)0, nullptr);
-      if (rc) return rc;
-      hipLaunchKernelGGL((k_pcg_init<real, 4>), vgrid, dim3(256), 0, s, m, d_RHS, (const real*)d_Z, cpart, cnch, czl, 0, r, S);
+    if (plan.path.wide) {
+      if (int rc = plan.product(a.U, nullptr, (real)0, nullptr)) return rc;
+      hipLaunchKernelGGL((k_pcg_init<real, 4>), plan.vgrid, dim3(256), 0, s, m, a.RHS, (const real*)a.Z, plan.cpart, plan.cnch, plan.czl, 0, plan.r, L.S);
     } else {
-      rc = spmv_narrow(d_U, d_Z, (real)1, hp, nullptr);
-      if (rc) return rc;
-      hipLaunchKernelGGL((k_pcg_init<real, 1>), egrid, dim3(256), 0, s, m, d_RHS, (const real*)hp, (real*)nullptr, 0, 0, 0, r, S);
+      if (int rc = plan.product(a.U, a.Z, (real)1, nullptr)) return rc;
+      hipLaunchKernelGGL((k_pcg_init<real, 1>), plan.egrid, dim3(256), 0, s, m, a.RHS, (const real*)L.hp, (real*)nullptr, 0, 0, 0, plan.r, L.S);
     }
   } else {
-    if (hipMemsetAsync(d_U, 0, (size_t)k * m * sizeof(real), s) != hipSuccess) return WISKI_E_LAUNCH;
-    if (hipMemsetAsync(d_Z, 0, (size_t)k * m * sizeof(real), s) != hipSuccess) return WISKI_E_LAUNCH;
-    hipLaunchKernelGGL((k_pcg_init<real, 1>), egrid, dim3(256), 0, s, m, d_RHS, (const real*)nullptr, (real*)nullptr, 0, 0, 0, r, S);
+    if (hipMemsetAsync(a.U, 0, (size_t)k * m * sizeof(real), s) != hipSuccess) return WISKI_E_LAUNCH;
+    if (hipMemsetAsync(a.Z, 0, (size_t)k * m * sizeof(real), s) != hipSuccess) return WISKI_E_LAUNCH;
+    hipLaunchKernelGGL((k_pcg_init<real, 1>), plan.egrid, dim3(256), 0, s, m, a.RHS, (const real*)nullptr, (real*)nullptr, 0, 0, 0, plan.r, L.S);
   }
+  return WISKI_OK;
+}
+
+// The CG loop and its convergence polls, from iteration 0 or (RESUME) from the poll the start call left in flight.
+template <typename real>
+static int pcg_iterate(const PcgPlan<real>& plan) {
+  const GridDev<real>& G = plan.G;
+  const PcgArgs<real>& a = plan.a;
+  const PcgLayout<real>& L = plan.L;
+  const PcgScal& S = L.S;
+  const hipStream_t s = plan.s;
+  const int m = plan.m, k = plan.k, max_iter = a.max_iter;
+  const double tol2 = plan.tol2;
+  const bool spectral = plan.path.spectral;
+  real *const r = plan.r, *const p = L.p, *const pt = L.pt, *const hp = L.hp, *const cpart = plan.cpart;
+  const int cnch = plan.cnch, czl = plan.czl;
+  wiski_pcg_async* const as = a.handle;
+  int mode = a.mode, first_check = a.first_check;
+  const int check_every = a.check_every < 1 ? 10 : a.check_every;
+  int rc = WISKI_OK;
 
   std::vector<double> h_rn0(k), h_rn(k);
   double err_seen = 0;
@@ -2108,10 +2152,10 @@ static int pcg_impl(const wiski_grid* grid, const real* d_A, const real* d_tcol,
     long long seq = queued_seq;
     if (!seq) {
       seq = ++P.seq;
-      hipLaunchKernelGGL(k_pcg_publish, dim3(1), dim3(64), 0, s, S, slot, P.d, d_err, seq, tol2, P.g);
+      hipLaunchKernelGGL(k_pcg_publish, dim3(1), dim3(64), 0, s, S, slot, P.d, a.d_err, seq, tol2, P.g);
     }
     if (hipGetLastError() != hipSuccess) return WISKI_E_LAUNCH;
-    if (amode == 1) {
+    if (mode == 1) {
       as->state = 1;
       as->it = slot;
       as->seq = seq;
@@ -2130,7 +2174,8 @@ static int pcg_impl(const wiski_grid* grid, const real* d_A, const real* d_tcol,
 
   int it = 0;
   bool done = false;
-  if (resume) {
+  if (mode == 2) {
+    // the start call queued everything up to (and including) the poll of iteration as->it
     it = as->it;
     as->state = 0;
     if (int prc = poll_wait(P, as->seq, s)) return prc;
@@ -2138,38 +2183,36 @@ static int pcg_impl(const wiski_grid* grid, const real* d_A, const real* d_tcol,
     as->guard_ok = (long long)P.h[2 + 2 * k] == as->seq ? 1 : 0;   // did an absorb guarded by this poll run? (wiski_pcg_async_guard)
     done = converged();
     first_check = it;          // from here on: a poll after every check_every-th further iteration
-    amode = 0;
+    mode = 0;
   }
   if (first_check < 1) first_check = check_every;
   if (first_check > max_iter) first_check = max_iter;
   // host convergence polls: after `first_check` iterations, then every `check_every`
   auto due = [&](int i) { return i == max_iter || i == first_check || (i > first_check && (i - first_check) % check_every == 0); };
-  const bool fused_cg = spectral && wide && spectral_fused_ok<real>(G);
-  if (two_level && !(fused_cg && sizeof(real) == 4)) return WISKI_E_BADARG;   // the exact block lives in the fused fp32 slab kernels (k > 1: launch_slab checks the scratch)
   bool pending = false;   // fused path: update_x of iteration it-1 not applied yet
   // publish: fold the convergence poll of iteration `it` into this update; returns its sequence number (0: nothing launched)
   auto flush_update = [&](bool publish = false) -> long long {
     long long seq = 0;
     if (pending) {
       if (publish) seq = ++P.seq;
-      hipLaunchKernelGGL((k_pcg_update_x<real, 4>), vgrid, dim3(256), 0, s, m, it - 1, tol2, (const real*)p, (const real*)pt, (const real*)hp,
-                         cpart, cnch, czl, d_U, d_Z, r, S, publish ? P.d : (double*)nullptr, d_err, seq, P.g);
+      hipLaunchKernelGGL((k_pcg_update_x<real, 4>), plan.vgrid, dim3(256), 0, s, m, it - 1, tol2, (const real*)p, (const real*)pt, (const real*)hp,
+                         cpart, cnch, czl, a.U, a.Z, r, S, publish ? P.d : (double*)nullptr, a.d_err, seq, P.g);
       pending = false;
     }
     return seq;
   };
   while (!done && it < max_iter) {
-    if (fused_cg) {
+    if (plan.path.fused_cg) {
       // fp32: 4 launches per iteration: [update_x(it-1) + mode-0 fwd] -> slab (+rho) -> [mode-0 bwd + update_p] -> SpMV (+p.Hp)
       // fp64: the update is its own launch (5 per iteration)
       constexpr bool fuse_upd = sizeof(real) == 4;
       if (!fuse_upd) flush_update();
-      const bool init_now = init_in_fwd && it == 0;
-      rc = launch_spectral_fused_cg<real>(G, d_evec, d_evec2, d_eval, kscale, shift, r, k, sa, sb, it, pending ? 1 : 0, tol2, p, pt, cpart, cnch, czl,
-                                          d_U, d_Z, S, s, init_now ? d_RHS : (const real*)nullptr, two_level);
+      const bool init_now = plan.init_in_fwd && it == 0;
+      rc = launch_spectral_fused_cg<real>(G, a.evec, a.evec2, a.eval, a.kscale, a.shift, r, k, L.sa, L.sb, it, pending ? 1 : 0, tol2, p, pt, cpart, cnch,
+                                          czl, a.U, a.Z, S, s, init_now ? a.RHS : (const real*)nullptr, a.two_level);
       pending = false;
       if (rc) return rc;
-      rc = spmv_wide(p, pt, (real)1, S.php(it));
+      rc = plan.product_wide(p, pt, (real)1, S.php(it));
       if (rc) return rc;
       pending = true;
       ++it;
@@ -2181,36 +2224,25 @@ static int pcg_impl(const wiski_grid* grid, const real* d_A, const real* d_tcol,
       }
       continue;
     }
-    // y = Kt r, rho(it) = r.y
+    // y = P r, rho(it) = r.y; then p = y + beta p, pt = t + beta pt
     if (spectral) {
-      // [t | y] = spectral preconditioner applied to r, rho(it) = r.y
-      rc = launch_spectral_precond<real>(G, d_evec, d_evec2, d_eval, kscale, shift, r, k, sa, sb, ty, S.rho(it), s);
+      // [t | y] = spectral preconditioner applied to r
+      rc = launch_spectral_precond<real>(G, a.evec, a.evec2, a.eval, a.kscale, a.shift, r, k, L.sa, L.sb, L.ty, S.rho(it), s);
       if (rc) return rc;
-      if (wide)
-        hipLaunchKernelGGL((k_pcg_update_p<real, 4>), vgrid, dim3(256), 0, s, m, it, tol2, (const real*)(ty + (int64_t)k * m), (const real*)ty, p,
-                           pt, S);
-      else
-        hipLaunchKernelGGL((k_pcg_update_p<real, 1>), egrid, dim3(256), 0, s, m, it, tol2, (const real*)(ty + (int64_t)k * m), (const real*)ty, p,
-                           pt, S);
+      PCG_VEC_LAUNCH(plan, k_pcg_update_p, m, it, tol2, (const real*)(L.ty + (int64_t)k * m), (const real*)L.ty, p, pt, S);
     } else {
-      // y = Kt r, rho(it) = r.y
-      rc = launch_kron<real>(G, d_tcol, r, k, kscale, tmp, y, r, S.rho(it), s);
+      // y = Kt r, t = r
+      rc = launch_kron<real>(G, a.tcol, r, k, a.kscale, L.tmp, L.y, r, S.rho(it), s);
       if (rc) return rc;
-      if (wide) hipLaunchKernelGGL((k_pcg_update_p<real, 4>), vgrid, dim3(256), 0, s, m, it, tol2, (const real*)y, (const real*)r, p, pt, S);
-      else hipLaunchKernelGGL((k_pcg_update_p<real, 1>), egrid, dim3(256), 0, s, m, it, tol2, (const real*)y, (const real*)r, p, pt, S);
+      PCG_VEC_LAUNCH(plan, k_pcg_update_p, m, it, tol2, (const real*)L.y, (const real*)r, p, pt, S);
     }
     // hp = pt + A p, php(it) = p.hp
-    if (wide) rc = spmv_wide(p, pt, (real)1, S.php(it));
-    else rc = spmv_narrow(p, pt, (real)1, hp, S.php(it));
+    rc = plan.product(p, pt, (real)1, S.php(it));
     if (rc) return rc;
     const bool pub = due(it + 1);
     const long long useq = pub ? ++P.seq : 0;
-    if (wide)
-      hipLaunchKernelGGL((k_pcg_update_x<real, 4>), vgrid, dim3(256), 0, s, m, it, tol2, (const real*)p, (const real*)pt, (const real*)hp,
-                         cpart, cnch, czl, d_U, d_Z, r, S, pub ? P.d : (double*)nullptr, d_err, useq, P.g);
-    else
-      hipLaunchKernelGGL((k_pcg_update_x<real, 1>), egrid, dim3(256), 0, s, m, it, tol2, (const real*)p, (const real*)pt, (const real*)hp,
-                         cpart, cnch, czl, d_U, d_Z, r, S, pub ? P.d : (double*)nullptr, d_err, useq, P.g);
+    PCG_VEC_LAUNCH(plan, k_pcg_update_x, m, it, tol2, (const real*)p, (const real*)pt, (const real*)hp, cpart, cnch, czl, a.U, a.Z, r, S,
+                   pub ? P.d : (double*)nullptr, a.d_err, useq, P.g);
     ++it;
     if (due(it)) {
       rc = fetch(it, useq);
@@ -2225,12 +2257,29 @@ static int pcg_impl(const wiski_grid* grid, const real* d_A, const real* d_tcol,
     rc = fetch(0);
     if (rc) return rc;
   }
-  if (h_iters) *h_iters = it;
-  if (h_err) *h_err = (int32_t)err_seen;   // raw flag word: bit 0 = any point outside the grid, bits 1.. = count of such training points
-  if (h_relres)
-    for (int c = 0; c < k; ++c) h_relres[c] = h_rn0[c] > 0 ? sqrt(h_rn[c] / h_rn0[c]) : 0.0;
+  if (a.h_iters) *a.h_iters = it;
+  if (a.h_err) *a.h_err = (int32_t)err_seen;   // raw flag word: bit 0 = any point outside the grid, bits 1.. = count of such training points
+  if (a.h_relres)
+    for (int c = 0; c < k; ++c) a.h_relres[c] = h_rn0[c] > 0 ? sqrt(h_rn[c] / h_rn0[c]) : 0.0;
   return done ? WISKI_OK : WISKI_E_NOTCONV;
 }
+#undef PCG_VEC_LAUNCH
+
+template <typename real>
+int pcg(const wiski_grid* grid, const PcgArgs<real>& a, void* stream) {
+  // validation comes first: nothing is queued and no handle field written on arguments a later step would have refused
+  GridDev<real> G;
+  int rc = make_grid_dev<real>(grid, &G);
+  if (rc) return rc;
+  const PcgPath path(G, a);
+  rc = pcg_validate(G, a, path);
+  if (rc) return rc;
+  const PcgPlan<real> plan(G, a, path, (hipStream_t)stream);
+  if (a.mode != 2) rc = pcg_start(plan);     // RESUME: the start call queued everything up to its poll
+  return rc ? rc : pcg_iterate(plan);
+}
+template int pcg<float>(const wiski_grid*, const PcgArgs<float>&, void*);
+template int pcg<double>(const wiski_grid*, const PcgArgs<double>&, void*);
 
 template <typename real>
 static int spmv_impl(const wiski_grid* grid, const real* d_A, const real* d_V, int32_t k, const real* d_add, real beta, real* d_out, void* stream) {
@@ -2297,32 +2346,60 @@ static int kron_impl(const wiski_grid* grid, const real* d_tcol, const real* d_V
   return launch_kron<real>(G, d_tcol, d_V, k, scale, d_tmp, d_out, nullptr, nullptr, (hipStream_t)stream);
 }
 
-// The two regions a solve zeroes before its first kernel (scalars + dot-slot ring; the atomically accumulated partial
-// vector of the half-stencil SpMV), for a caller that has an earlier kernel do it: same layout arithmetic as pcg_impl.
+// The two regions a solve zeroes before its first kernel (PcgLayout), for a caller that has an earlier kernel do it.
 template <typename real>
-static int pcg_zero_regions_impl(const wiski_grid* grid, int32_t k, int32_t max_iter, void* d_work, int32_t a_sym, void** p1, int64_t* n1, void** p2,
-                                 int64_t* n2) {
+int pcg_zero_regions(const wiski_grid* grid, int k, int max_iter, void* work, bool a_sym, void** p1, int64_t* n1_bytes, void** p2, int64_t* n2_bytes) {
   GridDev<real> G;
   int rc = make_grid_dev<real>(grid, &G);
   if (rc) return rc;
-  if (!d_work || !p1 || !n1 || !p2 || !n2 || k < 1 || max_iter < 1) return WISKI_E_BADARG;
-  const int m = G.m;
-  const int64_t vec = align_up((int64_t)k * m * sizeof(real), 256);
-  char* w = (char*)d_work;
-  real* part = (real*)(w + 6 * vec);
+  if (!work || !p1 || !n1_bytes || !p2 || !n2_bytes || k < 1 || max_iter < 1) return WISKI_E_BADARG;
+  const PcgLayout<real> L(G.m, k, max_iter, work);
   int zl = 0;
-  const bool wide = (m % 4) == 0;
-  const int nch = wide ? (a_sym ? sym_partials<real>(G, k, &zl) : spmv_nch(G.d)) : 0;
-  *p1 = w + 20 * vec;
-  *n1 = PcgScal::doubles(k, max_iter) * (int64_t)sizeof(double);
-  *p2 = part + (int64_t)(nch > 0 ? nch - 1 : 0) * k * m;
-  *n2 = zl ? (int64_t)k * m * (int64_t)sizeof(real) : 0;
+  const int nch = pcg_partials<real>(G, k, a_sym, &zl);
+  *p1 = L.zero1();
+  *n1_bytes = L.zero1_count() * (int64_t)sizeof(double);
+  *p2 = L.zero2(nch);
+  *n2_bytes = L.zero2_count(zl) * (int64_t)sizeof(real);
+  return WISKI_OK;
+}
+template int pcg_zero_regions<float>(const wiski_grid*, int, int, void*, bool, void**, int64_t*, void**, int64_t*);
+template int pcg_zero_regions<double>(const wiski_grid*, int, int, void*, bool, void**, int64_t*, void**, int64_t*);
+
+int pcg_guard(const wiski_pcg_async* as, const void** d_guard, int64_t* expect) {
+  if (!as || !d_guard || !expect || as->state != 1 || !as->poll) return WISKI_E_BADARG;
+  const WiskiPoll* P = static_cast<const WiskiPoll*>(as->poll);
+  if (!P->g) return WISKI_E_BADARG;
+  *d_guard = P->g;
+  *expect = as->seq;
   return WISKI_OK;
 }
 
+// The C ABI's argument list of a solve (include/wiski.h), once with types and once bare, and the record it fills: the wiski_pcg*
+// entry points differ only in what follows `stream`.
+#define PCG_ABI(real)                                                                                                                                           \
+  const real* A, const real* tcol, real kscale, const real* evec, const real* evec2, const real* eval, real shift, const real* RHS, int32_t k, real* U, real* Z, \
+      int32_t warm, double tol, int32_t max_iter, int32_t check_every, int32_t first_check, void* work, int64_t wb, int32_t* iters, double* relres,             \
+      const int32_t* d_err, int32_t* h_err, int32_t a_sym, real* R
+#define PCG_ABI_NAMES \
+  A, tcol, kscale, evec, evec2, eval, shift, RHS, k, U, Z, warm, tol, max_iter, check_every, first_check, work, wb, iters, relres, d_err, h_err, a_sym, R
+template <typename real>
+static PcgArgs<real> pcg_args(PCG_ABI(real), wiski_pcg_async* as = nullptr, int32_t amode = 0, const wiski_shard* shard = nullptr,
+                              const wiski_twolevel* two_level = nullptr) {
+  PcgArgs<real> a;
+  a.A = A; a.a_sym = a_sym != 0; a.RHS = RHS; a.k = k;
+  a.tcol = tcol; a.kscale = kscale; a.evec = evec; a.evec2 = evec2; a.eval = eval; a.shift = shift; a.two_level = two_level;
+  a.U = U; a.Z = Z; a.R = R; a.warm = warm;
+  a.tol = tol; a.max_iter = max_iter; a.check_every = check_every; a.first_check = first_check;
+  a.work = work; a.work_bytes = wb;
+  a.h_iters = iters; a.h_relres = relres; a.d_err = d_err; a.h_err = h_err;
+  a.handle = as; a.mode = amode;
+  a.shard = shard;
+  return a;
+}
+
 extern "C" {
-int wiski_pcg_zero_regions_f32(const wiski_grid* g, int32_t k, int32_t max_iter, void* work, int32_t a_sym, void** p1, int64_t* n1, void** p2, int64_t* n2) { return pcg_zero_regions_impl<float>(g, k, max_iter, work, a_sym, p1, n1, p2, n2); }
-int wiski_pcg_zero_regions_f64(const wiski_grid* g, int32_t k, int32_t max_iter, void* work, int32_t a_sym, void** p1, int64_t* n1, void** p2, int64_t* n2) { return pcg_zero_regions_impl<double>(g, k, max_iter, work, a_sym, p1, n1, p2, n2); }
+int wiski_pcg_zero_regions_f32(const wiski_grid* g, int32_t k, int32_t max_iter, void* work, int32_t a_sym, void** p1, int64_t* n1, void** p2, int64_t* n2) { return pcg_zero_regions<float>(g, k, max_iter, work, a_sym != 0, p1, n1, p2, n2); }
+int wiski_pcg_zero_regions_f64(const wiski_grid* g, int32_t k, int32_t max_iter, void* work, int32_t a_sym, void** p1, int64_t* n1, void** p2, int64_t* n2) { return pcg_zero_regions<double>(g, k, max_iter, work, a_sym != 0, p1, n1, p2, n2); }
 int wiski_stencil_spmv_f32(const wiski_grid* g, const float* A, const float* V, int32_t k, const float* add, float beta, float* out, void* s) { return spmv_impl<float>(g, A, V, k, add, beta, out, s); }
 int wiski_stencil_spmv_f64(const wiski_grid* g, const double* A, const double* V, int32_t k, const double* add, double beta, double* out, void* s) { return spmv_impl<double>(g, A, V, k, add, beta, out, s); }
 int wiski_stencil_spmv_sym_f32(const wiski_grid* g, const float* A, const float* V, int32_t k, const float* add, float beta, float* out, void* s) { return spmv_sym_impl<float>(g, A, V, k, add, beta, out, s); }
@@ -2337,31 +2414,16 @@ int64_t wiski_pcg_workspace_bytes(const wiski_grid* grid, int32_t k, int32_t max
   if (!grid || grid->d < 1 || grid->d > WISKI_MAX_DIM || k < 1 || max_iter < 1) return WISKI_E_BADARG;
   int64_t m = 1;
   for (int q = 0; q < grid->d; ++q) m *= grid->g[q];
-  return pcg_ws_bytes((int)m, k, max_iter, elem_size);
+  return PcgLayout<float>::bytes((int)m, k, max_iter, elem_size);
 }
-int wiski_pcg_async_f32(const wiski_grid* g, const float* A, const float* tcol, float kscale, const float* evec, const float* evec2, const float* eval, float shift, const float* RHS, int32_t k, float* U, float* Z, int32_t warm, double tol, int32_t max_iter, int32_t check_every, int32_t first_check, void* work, int64_t wb, int32_t* iters, double* relres, const int32_t* d_err, int32_t* h_err, int32_t a_sym, float* R, void* s, wiski_pcg_async* as, int32_t amode) {
-  return pcg_impl<float>(g, A, tcol, kscale, evec, evec2, eval, shift, RHS, k, U, Z, warm, tol, max_iter, check_every, first_check, work, wb, iters, relres, d_err, h_err, a_sym, R, s, as, amode);
-}
-int wiski_pcg_async_f64(const wiski_grid* g, const double* A, const double* tcol, double kscale, const double* evec, const double* evec2, const double* eval, double shift, const double* RHS, int32_t k, double* U, double* Z, int32_t warm, double tol, int32_t max_iter, int32_t check_every, int32_t first_check, void* work, int64_t wb, int32_t* iters, double* relres, const int32_t* d_err, int32_t* h_err, int32_t a_sym, double* R, void* s, wiski_pcg_async* as, int32_t amode) {
-  return pcg_impl<double>(g, A, tcol, kscale, evec, evec2, eval, shift, RHS, k, U, Z, warm, tol, max_iter, check_every, first_check, work, wb, iters, relres, d_err, h_err, a_sym, R, s, as, amode);
-}
-int wiski_pcg_sharded_f32(const wiski_grid* g, const float* A, const float* tcol, float kscale, const float* evec, const float* evec2, const float* eval, float shift, const float* RHS, int32_t k, float* U, float* Z, int32_t warm, double tol, int32_t max_iter, int32_t check_every, int32_t first_check, void* work, int64_t wb, int32_t* iters, double* relres, const int32_t* d_err, int32_t* h_err, int32_t a_sym, float* R, void* s, wiski_pcg_async* as, int32_t amode, const wiski_shard* shard) {
-  return pcg_impl<float>(g, A, tcol, kscale, evec, evec2, eval, shift, RHS, k, U, Z, warm, tol, max_iter, check_every, first_check, work, wb, iters, relres, d_err, h_err, a_sym, R, s, as, amode, shard);
-}
-int wiski_pcg_twolevel_f32(const wiski_grid* g, const float* A, const float* tcol, float kscale, const float* evec, const float* evec2, const float* eval, float shift, const float* RHS, int32_t k, float* U, float* Z, int32_t warm, double tol, int32_t max_iter, int32_t check_every, int32_t first_check, void* work, int64_t wb, int32_t* iters, double* relres, const int32_t* d_err, int32_t* h_err, int32_t a_sym, float* R, void* s, wiski_pcg_async* as, int32_t amode, const wiski_shard* shard, const wiski_twolevel* two_level) {
-  return pcg_impl<float>(g, A, tcol, kscale, evec, evec2, eval, shift, RHS, k, U, Z, warm, tol, max_iter, check_every, first_check, work, wb, iters, relres, d_err, h_err, a_sym, R, s, as, amode, shard, two_level);
-}
-// One application of the fused preconditioner (iteration 0 of the CG front end without an update to fold in): p = y = P r,
-// pt = t = Kt^-1 y, rho += r . y.
-int wiski_precond_apply_f32(const wiski_grid* grid, const float* evec, const float* evec2, const float* eval, float kscale, float shift, const float* d_r, float* w0, float* w1, float* d_y, float* d_t, double* d_rho, const wiski_twolevel* two_level, void* stream) {
-  GridDev<float> G;
-  if (int rc = make_grid_dev<float>(grid, &G)) return rc;
-  if (!evec || !eval || !d_r || !w0 || !w1 || !d_y || !d_t || !d_rho || !spectral_fused_ok<float>(G) || G.m % 4) return WISKI_E_BADARG;
-  PcgScal S{d_rho - 1, 1, nullptr};          // rho(0) = base + k (1 + 2 * 0) = d_rho; nothing else of S is touched at it = 0, apply = 0
-  return launch_spectral_fused_cg<float>(G, evec, evec2, eval, kscale, shift, const_cast<float*>(d_r), 1, w0, w1, 0, 0, 0.0, d_y, d_t, (float*)nullptr, 0, 0,
-                                         (float*)nullptr, (float*)nullptr, S, (hipStream_t)stream, (const float*)nullptr, two_level);
-}
-// ... of k grid vectors at once (the multi-column kernels): d_r, d_y, d_t [k][m], w0 k m reals, w1 2 k m reals, d_rho [k] doubles (+=).
+int wiski_pcg_async_f32(const wiski_grid* g, PCG_ABI(float), void* s, wiski_pcg_async* as, int32_t amode) { return pcg(g, pcg_args<float>(PCG_ABI_NAMES, as, amode), s); }
+int wiski_pcg_async_f64(const wiski_grid* g, PCG_ABI(double), void* s, wiski_pcg_async* as, int32_t amode) { return pcg(g, pcg_args<double>(PCG_ABI_NAMES, as, amode), s); }
+int wiski_pcg_sharded_f32(const wiski_grid* g, PCG_ABI(float), void* s, wiski_pcg_async* as, int32_t amode, const wiski_shard* shard) { return pcg(g, pcg_args<float>(PCG_ABI_NAMES, as, amode, shard), s); }
+int wiski_pcg_sharded_f64(const wiski_grid* g, PCG_ABI(double), void* s, wiski_pcg_async* as, int32_t amode, const wiski_shard* shard) { return pcg(g, pcg_args<double>(PCG_ABI_NAMES, as, amode, shard), s); }
+int wiski_pcg_twolevel_f32(const wiski_grid* g, PCG_ABI(float), void* s, wiski_pcg_async* as, int32_t amode, const wiski_shard* shard, const wiski_twolevel* two_level) { return pcg(g, pcg_args<float>(PCG_ABI_NAMES, as, amode, shard, two_level), s); }
+// One application of the fused preconditioner (iteration 0 of the CG front end without an update to fold in) to k grid vectors
+// (k > 1: the multi-column kernels): p = y = P r, pt = t = Kt^-1 y, rho += r . y.  d_r, d_y, d_t [k][m], w0 k m reals, w1 2 k m
+// reals, d_rho [k] doubles (+=).
 int wiski_precond_apply_cols_f32(const wiski_grid* grid, const float* evec, const float* evec2, const float* eval, float kscale, float shift, const float* d_r, int32_t k, float* w0, float* w1, float* d_y, float* d_t, double* d_rho, const wiski_twolevel* two_level, void* stream) {
   GridDev<float> G;
   if (int rc = make_grid_dev<float>(grid, &G)) return rc;
@@ -2370,8 +2432,8 @@ int wiski_precond_apply_cols_f32(const wiski_grid* grid, const float* evec, cons
   return launch_spectral_fused_cg<float>(G, evec, evec2, eval, kscale, shift, const_cast<float*>(d_r), k, w0, w1, 0, 0, 0.0, d_y, d_t, (float*)nullptr, 0, 0,
                                          (float*)nullptr, (float*)nullptr, S, (hipStream_t)stream, (const float*)nullptr, two_level);
 }
-int wiski_pcg_sharded_f64(const wiski_grid* g, const double* A, const double* tcol, double kscale, const double* evec, const double* evec2, const double* eval, double shift, const double* RHS, int32_t k, double* U, double* Z, int32_t warm, double tol, int32_t max_iter, int32_t check_every, int32_t first_check, void* work, int64_t wb, int32_t* iters, double* relres, const int32_t* d_err, int32_t* h_err, int32_t a_sym, double* R, void* s, wiski_pcg_async* as, int32_t amode, const wiski_shard* shard) {
-  return pcg_impl<double>(g, A, tcol, kscale, evec, evec2, eval, shift, RHS, k, U, Z, warm, tol, max_iter, check_every, first_check, work, wb, iters, relres, d_err, h_err, a_sym, R, s, as, amode, shard);
+int wiski_precond_apply_f32(const wiski_grid* grid, const float* evec, const float* evec2, const float* eval, float kscale, float shift, const float* d_r, float* w0, float* w1, float* d_y, float* d_t, double* d_rho, const wiski_twolevel* two_level, void* stream) {
+  return wiski_precond_apply_cols_f32(grid, evec, evec2, eval, kscale, shift, d_r, 1, w0, w1, d_y, d_t, d_rho, two_level, stream);
 }
 int wiski_shard_groups(int32_t d, int32_t rank, int32_t nranks, int32_t* g_lo, int32_t* g_hi) {
   if (d < 1 || d > WISKI_MAX_DIM || nranks < 1 || rank < 0 || rank >= nranks || !g_lo || !g_hi) return WISKI_E_BADARG;
@@ -2393,18 +2455,7 @@ int wiski_pcg_async_free(wiski_pcg_async* as) {
   as->state = 0;
   return WISKI_OK;
 }
-int wiski_pcg_async_guard(const wiski_pcg_async* as, const void** d_guard, int64_t* expect) {
-  if (!as || !d_guard || !expect || as->state != 1 || !as->poll) return WISKI_E_BADARG;
-  const WiskiPoll* P = static_cast<const WiskiPoll*>(as->poll);
-  if (!P->g) return WISKI_E_BADARG;
-  *d_guard = P->g;
-  *expect = as->seq;
-  return WISKI_OK;
-}
-int wiski_pcg_f32(const wiski_grid* g, const float* A, const float* tcol, float kscale, const float* evec, const float* evec2, const float* eval, float shift, const float* RHS, int32_t k, float* U, float* Z, int32_t warm, double tol, int32_t max_iter, int32_t check_every, int32_t first_check, void* work, int64_t wb, int32_t* iters, double* relres, const int32_t* d_err, int32_t* h_err, int32_t a_sym, float* R, void* s) {
-  return pcg_impl<float>(g, A, tcol, kscale, evec, evec2, eval, shift, RHS, k, U, Z, warm, tol, max_iter, check_every, first_check, work, wb, iters, relres, d_err, h_err, a_sym, R, s);
-}
-int wiski_pcg_f64(const wiski_grid* g, const double* A, const double* tcol, double kscale, const double* evec, const double* evec2, const double* eval, double shift, const double* RHS, int32_t k, double* U, double* Z, int32_t warm, double tol, int32_t max_iter, int32_t check_every, int32_t first_check, void* work, int64_t wb, int32_t* iters, double* relres, const int32_t* d_err, int32_t* h_err, int32_t a_sym, double* R, void* s) {
-  return pcg_impl<double>(g, A, tcol, kscale, evec, evec2, eval, shift, RHS, k, U, Z, warm, tol, max_iter, check_every, first_check, work, wb, iters, relres, d_err, h_err, a_sym, R, s);
-}
+int wiski_pcg_async_guard(const wiski_pcg_async* as, const void** d_guard, int64_t* expect) { return pcg_guard(as, d_guard, expect); }
+int wiski_pcg_f32(const wiski_grid* g, PCG_ABI(float), void* s) { return pcg(g, pcg_args<float>(PCG_ABI_NAMES), s); }
+int wiski_pcg_f64(const wiski_grid* g, PCG_ABI(double), void* s) { return pcg(g, pcg_args<double>(PCG_ABI_NAMES), s); }
 }

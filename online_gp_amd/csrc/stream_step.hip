@@ -1,13 +1,14 @@
 // One streaming step behind ONE C-ABI call: the launches of
 //   predictive mean of the incoming batch + absorb   wiski_scatter_stats_step (BFN:206-210, BFN:155-171 + URLT:58; carries the residual)
-//   warm-started refresh of the mean                 wiski_pcg                (CG branch of BFN:368-383)
+//   warm-started refresh of the mean                 pcg()                    (CG branch of BFN:368-383)
 // are queued back to back on the caller's stream without returning to the host language in between (the Python
 // front-end left the GPU idle for ~30 us between the gather and the scatter and ~40 us after the solver's last poll).
 // With a deferred solve pending, the absorb of the NEXT batch is queued before the host has read that solve's convergence
 // poll, guarded on the device by the poll's own verdict (wiski_pcg_async_guard): the GPU goes from the last iteration
 // straight into the absorb instead of idling through the host's poll round trip (~20 us of a 220 us step).
-// Pure host code: it only sequences the entry points above.
+// Pure host code: it fills the two argument records (absorb.h, pcg.h) and sequences absorb() and pcg().
 #include "absorb.h"
+#include "pcg.h"
 
 template <typename real>
 struct StreamArgs;
@@ -27,10 +28,7 @@ static int absorb_batch(const wiski_grid* g, const typename StreamArgs<real>::ty
   r.res = carry ? a->d_R : nullptr;
   if (!r.mean_out) return absorb(g, r, s);
   if (zero) {
-    int rc;
-    if constexpr (sizeof(real) == 4) rc = wiski_pcg_zero_regions_f32(g, 1, a->max_iter, a->d_work, 1, &r.z1, &r.n1_bytes, &r.z2, &r.n2_bytes);
-    else rc = wiski_pcg_zero_regions_f64(g, 1, a->max_iter, a->d_work, 1, &r.z1, &r.n1_bytes, &r.z2, &r.n2_bytes);
-    if (rc) return rc;
+    if (int rc = pcg_zero_regions<real>(g, 1, a->max_iter, a->d_work, true, &r.z1, &r.n1_bytes, &r.z2, &r.n2_bytes)) return rc;
   }
   if (wiski_shard_active(a->shard)) {
     int32_t glo = 0, ghi = 0;
@@ -41,17 +39,19 @@ static int absorb_batch(const wiski_grid* g, const typename StreamArgs<real>::ty
   }
   return absorb(g, r, s);
 }
-static int pcg1(const wiski_grid* g, const wiski_stream_args_f32* a, int warm, int first_check, int32_t* it, double* rr, int32_t* herr, void* s,
-                wiski_pcg_async* as, int mode) {
-  return wiski_pcg_twolevel_f32(g, a->d_A_half, a->d_tcol, a->kscale, a->d_evec, a->d_evec2, a->d_eval, a->shift, a->d_b, 1, a->d_U, a->d_Z, warm, a->tol,
-                                a->max_iter, a->check_every, first_check, a->d_work, a->work_bytes, it, rr, a->d_err, herr, 1, a->d_R, s, as, mode, a->shard,
-                                a->two_level);
-}
-static int pcg1(const wiski_grid* g, const wiski_stream_args_f64* a, int warm, int first_check, int32_t* it, double* rr, int32_t* herr, void* s,
-                wiski_pcg_async* as, int mode) {
-  if (a->two_level) return WISKI_E_BADARG;
-  return wiski_pcg_sharded_f64(g, a->d_A_half, a->d_tcol, a->kscale, a->d_evec, a->d_evec2, a->d_eval, a->shift, a->d_b, 1, a->d_U, a->d_Z, warm, a->tol,
-                               a->max_iter, a->check_every, first_check, a->d_work, a->work_bytes, it, rr, a->d_err, herr, 1, a->d_R, s, as, mode, a->shard);
+// The refresh of the stream's mean: (Kt^-1 + A_half) U = b, one column, warm from (U, Z) -- with `carry` from the residual R the
+// absorb kept current.  Reports and deferred-poll mode are the caller's.
+template <typename real>
+static PcgArgs<real> solve_args(const typename StreamArgs<real>::type* a, int carry, int first_check) {
+  PcgArgs<real> p;
+  p.A = a->d_A_half; p.a_sym = true; p.RHS = a->d_b; p.k = 1;
+  p.tcol = a->d_tcol; p.kscale = a->kscale; p.evec = a->d_evec; p.evec2 = a->d_evec2; p.eval = a->d_eval; p.shift = a->shift; p.two_level = a->two_level;
+  p.U = a->d_U; p.Z = a->d_Z; p.R = a->d_R; p.warm = carry ? 2 : 1;
+  p.tol = a->tol; p.max_iter = a->max_iter; p.check_every = a->check_every; p.first_check = first_check;
+  p.work = a->d_work; p.work_bytes = a->work_bytes;
+  p.d_err = a->d_err;
+  p.shard = a->shard;
+  return p;
 }
 
 template <typename real>
@@ -63,6 +63,8 @@ static int stream_step_impl(const wiski_grid* grid, const typename StreamArgs<re
   if (wiski_shard_active(a->shard) && q > 0 && !d_mean_out) return WISKI_E_BADARG;   // the sharded absorb is the mean-emitting kernel
   int rc = WISKI_OK;
   if (h_resumed) *h_resumed = 0;
+  PcgArgs<real> solve = solve_args<real>(a, carry, first_check);   // this stream's solve, reporting into the caller's outputs
+  solve.h_iters = h_iters; solve.h_relres = h_relres; solve.h_err = h_err; solve.handle = as;
   AbsorbArgs<real> batch;                    // the points of this call; absorb_batch adds the targets
   batch.x = d_x; batch.y = d_y; batch.wa = d_wa; batch.wb = d_wb; batch.noise = d_noise; batch.n = q; batch.mean_out = d_mean_out;
   bool absorbed = false;                     // the speculative absorb below has run
@@ -76,7 +78,7 @@ static int stream_step_impl(const wiski_grid* grid, const typename StreamArgs<re
     if (q > 0 && d_mean_out) {
       const void* guard = nullptr;
       int64_t expect = 0;
-      if (wiski_pcg_async_guard(as, &guard, &expect) == WISKI_OK) {
+      if (pcg_guard(as, &guard, &expect) == WISKI_OK) {
         AbsorbArgs<real> spec_batch = batch;
         spec_batch.guard = guard; spec_batch.guard_expect = expect;
         rc = absorb_batch<real>(grid, a, spec_batch, carry, 1, stream);
@@ -85,9 +87,10 @@ static int stream_step_impl(const wiski_grid* grid, const typename StreamArgs<re
       }
     }
     {
-      typename StreamArgs<real>::type ar = *a;     // RESUME with the shift the solve was started with (a->shift is the NEXT solve's)
-      ar.shift = (real)as->shift;
-      rc = pcg1(grid, &ar, 2, first_check, h_iters, h_relres, h_err, stream, as, 2);
+      PcgArgs<real> resume = solve;                // RESUME with the shift the solve was started with (a->shift is the NEXT solve's)
+      resume.shift = (real)as->shift;
+      resume.mode = 2;
+      rc = pcg(grid, resume, stream);
     }
     if (h_resumed) *h_resumed = 1;
     if (rc != WISKI_OK && rc != WISKI_E_NOTCONV) return rc;
@@ -112,19 +115,19 @@ static int stream_step_impl(const wiski_grid* grid, const typename StreamArgs<re
       if (rc) return rc;
     }
   }
-  if (!as) return pcg1(grid, a, carry ? 2 : 1, first_check, h_iters, h_relres, h_err, stream, nullptr, 0);
+  if (!as) return pcg(grid, solve, stream);
   if (defer) {
-    int32_t it2 = 0, e2 = 0;
-    double r2 = 0;
     as->shift = (double)a->shift;
-    rc = pcg1(grid, a, carry ? 2 : 1, first_check, &it2, &r2, &e2, stream, as, 1);      // outputs of THIS solve arrive with the next call
+    solve.h_iters = nullptr; solve.h_relres = nullptr; solve.h_err = nullptr;           // outputs of THIS solve arrive with the next call
+    solve.mode = 1;
+    rc = pcg(grid, solve, stream);
     return rc == WISKI_PENDING ? (resumed_rc == WISKI_E_NOTCONV ? WISKI_E_NOTCONV : WISKI_PENDING) : rc;
   }
   // deferral switched off with a solve pending: the outputs below describe THIS step's synchronous solve; the resumed
   // one (finished above) is reported as *h_resumed = 2 -- "resumed, but its numbers were overwritten" -- and a resumed
   // solve that stopped at max_iter still surfaces through the return code
   if (h_resumed && *h_resumed == 1) *h_resumed = 2;
-  rc = pcg1(grid, a, carry ? 2 : 1, first_check, h_iters, h_relres, h_err, stream, as, 0);
+  rc = pcg(grid, solve, stream);
   return rc == WISKI_OK && resumed_rc == WISKI_E_NOTCONV ? WISKI_E_NOTCONV : rc;
 }
 

@@ -813,19 +813,9 @@ class StreamStep:
 
 
 def precond_apply(grid, eig, kscale, shift, r, two_level=None):
-    """One application of the fused fp32 preconditioner to the grid vector r (``wiski_precond_apply``): (y = P r, t = Kt^-1 y, r . y)."""
-    evec, evals, evec2 = (tuple(eig) + (None,))[:3]
-    r = r.contiguous()
-    m = grid.m
-    w0 = torch.empty(m, dtype=r.dtype, device=r.device)
-    w1 = torch.empty(2 * m, dtype=r.dtype, device=r.device)
-    y, t = torch.empty_like(r), torch.empty_like(r)
-    rho = torch.zeros(2, dtype=torch.float64, device=r.device)
-    rc = _hip.lib().wiski_precond_apply_f32(grid.ref, _hip.dptr(evec), _hip.dptr(evec2), _hip.dptr(evals), ctypes.c_float(kscale), ctypes.c_float(shift),
-                                            _hip.dptr(r), _hip.dptr(w0), _hip.dptr(w1), _hip.dptr(y), _hip.dptr(t), ctypes.c_void_p(rho.data_ptr() + 8),
-                                            ctypes.byref(two_level) if two_level is not None else None, _hip.stream_ptr(r.device))
-    _hip.check(rc, "wiski_precond_apply")
-    return y, t, rho[1]
+    """One application of the fused fp32 preconditioner to the grid vector r: (y = P r, t = Kt^-1 y, r . y) -- `precond_apply_cols` of one row."""
+    Y, T, rho = precond_apply_cols(grid, eig, kscale, shift, r.reshape(1, grid.m), two_level=two_level)
+    return Y.reshape(r.shape), T.reshape(r.shape), rho[0]
 
 
 def precond_apply_cols(grid, eig, kscale, shift, R, two_level=None):
@@ -880,6 +870,16 @@ def kron_eigen(grid, tcol, profiles=None, host_out=None):
     return mk(X), mk(vals), mk(Z)
 
 
+def _pcg_abi(dtype, *, grid, A, a_sym, RHS, k, tcol, kscale, evec, evec2, eval, shift, U, Z, R, warm, tol, max_iter, check_every, first_check,
+             work, work_bytes, h_iters, h_relres, d_err, h_err, stream):
+    """What every ``wiski_pcg*`` entry point starts with (include/wiski.h), from fields named and grouped as in the solve's record
+    (csrc/pcg.h: PcgArgs) -- the one place the ABI's order is written down."""
+    cr, i32, p = _hip.creal(dtype), (lambda v: ctypes.c_int32(int(v))), _hip.dptr
+    return (grid.ref, p(A), p(tcol), cr(kscale), p(evec), p(evec2), p(eval), cr(shift), p(RHS), i32(k), p(U), p(Z), i32(warm), ctypes.c_double(tol),
+            i32(max_iter), i32(check_every), i32(first_check), p(work), ctypes.c_int64(work_bytes), ctypes.byref(h_iters), h_relres, p(d_err),
+            ctypes.byref(h_err), i32(a_sym), p(R), stream)
+
+
 def pcg(grid, A_st, tcol, kscale, RHS, U=None, Z=None, warm=False, tol=1e-6, max_iter=1000, check_every=10, workspace=None,
         raise_on_fail=False, eigen=None, shift=0.0, first_check=0, err=None, inplace=False, R=None, two_level=None):
     """Solve (Kt^-1 + A) U = RHS, Kt = kscale*Kuu.  Returns (U, Z, iters, relres).
@@ -903,13 +903,11 @@ def pcg(grid, A_st, tcol, kscale, RHS, U=None, Z=None, warm=False, tol=1e-6, max
     iters = ctypes.c_int32(0)
     h_err = ctypes.c_int32(0)
     relres = (ctypes.c_double * k)()
-    cr = _hip.creal(RHS2.dtype)
     evec, evals, evec2 = (tuple(eigen) + (None,))[:3] if eigen is not None else (None, None, None)
-    common = (grid.ref, _hip.dptr(A_st), _hip.dptr(tcol.contiguous()), cr(kscale), _hip.dptr(evec), _hip.dptr(evec2), _hip.dptr(evals),
-              cr(shift), _hip.dptr(RHS2), ctypes.c_int32(k),
-              _hip.dptr(U), _hip.dptr(Z), ctypes.c_int32(int(warm)), ctypes.c_double(tol), ctypes.c_int32(max_iter),
-              ctypes.c_int32(check_every), ctypes.c_int32(first_check), _hip.dptr(buf), ctypes.c_int64(need), ctypes.byref(iters), relres, _hip.dptr(err), ctypes.byref(h_err),
-              ctypes.c_int32(1 if is_half_stencil(grid, A_st) else 0), _hip.dptr(R), _hip.stream_ptr(RHS2.device))
+    common = _pcg_abi(RHS2.dtype, grid=grid, A=A_st, a_sym=is_half_stencil(grid, A_st), RHS=RHS2, k=k,
+                      tcol=tcol.contiguous(), kscale=kscale, evec=evec, evec2=evec2, eval=evals, shift=shift,
+                      U=U, Z=Z, R=R, warm=warm, tol=tol, max_iter=max_iter, check_every=check_every, first_check=first_check,
+                      work=buf, work_bytes=need, h_iters=iters, h_relres=relres, d_err=err, h_err=h_err, stream=_hip.stream_ptr(RHS2.device))
     if two_level is not None and (k == 1 or (two_level.d_mc and k <= two_level.mc_cols)) and RHS2.dtype == torch.float32 and evec is not None:
         rc = _hip.lib().wiski_pcg_twolevel_f32(*common, None, ctypes.c_int32(0), None, ctypes.byref(two_level))
     else:

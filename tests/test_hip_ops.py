@@ -446,6 +446,134 @@ def test_pcg_against_oracle_and_warm_start(d, g, tdt, ndt, tol, spectral, half):
     assert np.abs(U2.double().cpu().numpy() - Uref).max() < tol * np.abs(Uref).max()
 
 
+def _pcg_case(d, g, tdt, ndt, n, k, handle=None, shard=None):
+    """One small system for the C-ABI tests of the solve: (named fields of grid_ops._pcg_abi with fresh NaN-filled U / Z, Uref, a keep-alive list)."""
+    import ctypes
+
+    from online_gp_amd import _hip, grid_ops
+
+    grid, X, y, noise, B2, rng = _setup(d, g, tdt, ndt, n=n)
+    B2.absorb(X.astype(np.float64), y.astype(np.float64), noise.astype(np.float64), init=True)
+    RHS = np.stack([B2.b] + [rng.standard_normal(grid.m) for _ in range(k - 1)])
+    tc = _t(B2.tcol, tdt)
+    A = grid_ops.half_stencil_from_offset_major(grid, _t(B2.A, tdt)[(grid.R - 1) // 2:].contiguous())
+    evec, evals = grid_ops.kron_eigen(grid, tc)
+    max_iter = 500
+    work, need = grid_ops.PCGWorkspace().get(grid, k, max_iter, tdt, torch.device("cuda", torch.cuda.current_device()))
+    nan = lambda: torch.full((k, grid.m), float("nan"), device="cuda", dtype=tdt)
+    f = dict(grid=grid, A=A, a_sym=1, RHS=_t(RHS, tdt), k=k, tcol=tc, kscale=1.0 / B2.sigma2, evec=evec, evec2=None, eval=evals, shift=n / grid.m,
+             U=nan(), Z=nan(), R=None, warm=0, tol=1e-10 if tdt == torch.float64 else 1e-6, max_iter=max_iter, check_every=5, first_check=0,
+             work=work, work_bytes=need, h_iters=ctypes.c_int32(-1), h_relres=(ctypes.c_double * k)(), d_err=None, h_err=ctypes.c_int32(0),
+             stream=_hip.stream_ptr(work.device))
+    return f, B2, RHS
+
+
+@pytest.mark.parametrize("tdt,ndt", [(torch.float32, np.float32), (torch.float64, np.float64)])
+def test_pcg_refusal_table(tdt, ndt):
+    """Every argument combination the solve refuses, through the C ABI (d = 3, g = 8, half stencil of 5 points), with the code each
+    returns -- and all of them before anything is queued or a handle field written: U and Z keep their NaN fill, the workspace its
+    byte pattern, the handle prezeroed = 1 and state = 0.  (Before pcg_validate existed, `warm = 2 without R` was refused after the
+    zeroing launch, with `prezeroed` consumed, and `two_level without eigen tables` after the cold start had cleared U and Z.)"""
+    import ctypes
+
+    from online_gp_amd import _hip, grid_ops
+
+    BADARG, WORKSPACE, i32 = -1, -3, ctypes.c_int32
+    cases = {dt: _pcg_case(3, 8, dt, nd, 5, 2)[0] for dt, nd in ((torch.float32, np.float32), (torch.float64, np.float64))}
+    for f in cases.values():
+        f["work"].fill_(0x5A)
+        f["k"] = 1                                                        # (buffers and workspace have room for the k = 2 case)
+    f = cases[tdt]
+    need1 = int(_hip.lib().wiski_pcg_workspace_bytes(f["grid"].ref, i32(1), i32(f["max_iter"]), i32(f["U"].element_size())))
+    handle = grid_ops._PcgAsync()
+    handle.prezeroed = 1
+    cb = grid_ops.ALLREDUCE_FN(lambda *a: -2)                             # never called: every sharded case below is refused
+    shard = lambda rank=0, nranks=2, fn=cb: ctypes.byref(grid_ops._Shard(rank, nranks, None, fn, None))
+    block = grid_ops.TwoLevelStruct()
+    block.r = 1
+    h = ctypes.byref(handle)
+
+    def call(entry, *tail, dt=tdt, **over):
+        return _hip.fn(entry, dt)(*grid_ops._pcg_abi(dt, **dict(cases[dt], **over)), *tail)
+
+    table = [(f"pcg {n} NULL", call("wiski_pcg", **{n: None}), BADARG) for n in ("A", "RHS", "U", "Z", "work")]
+    table += [("pcg k = 0", call("wiski_pcg", k=0), BADARG), ("pcg max_iter = 0", call("wiski_pcg", max_iter=0), BADARG),
+              ("pcg work_bytes one short", call("wiski_pcg", work_bytes=need1 - 1), WORKSPACE),
+              ("pcg no eigen tables, no tcol", call("wiski_pcg", evec=None, eval=None, tcol=None), BADARG),
+              ("pcg warm = 2, no R", call("wiski_pcg", warm=2), BADARG),
+              ("async warm = 2, no R", call("wiski_pcg_async", h, i32(0), warm=2), BADARG),
+              ("async mode 1, no handle", call("wiski_pcg_async", None, i32(1)), BADARG),
+              ("async mode 2, no handle", call("wiski_pcg_async", None, i32(2)), BADARG),
+              ("async mode 2, idle handle", call("wiski_pcg_async", h, i32(2)), BADARG),
+              ("sharded a_sym = 0", call("wiski_pcg_sharded", h, i32(0), shard(), a_sym=0), BADARG),
+              ("sharded k = 2", call("wiski_pcg_sharded", h, i32(0), shard(), k=2), BADARG),
+              ("sharded rank = nranks", call("wiski_pcg_sharded", h, i32(0), shard(rank=2), k=1), BADARG),
+              ("sharded no comm, no allreduce", call("wiski_pcg_sharded", h, i32(0), shard(fn=grid_ops.ALLREDUCE_FN())), BADARG),
+              ("twolevel_f32 block, no eigen tables", call("wiski_pcg_twolevel", h, i32(0), None, ctypes.byref(block), dt=torch.float32, evec=None, eval=None),
+               BADARG)]
+    # wiski_stream_step_f64 with a two-level block (q = 0, no handle: the call is the solve alone)
+    g64 = cases[torch.float64]
+    sa = grid_ops._StreamArgs64()
+    R64 = torch.zeros_like(g64["U"])
+    sa.d_A_half, sa.d_b, sa.d_U, sa.d_Z, sa.d_R, sa.d_tcol = [g64[n].data_ptr() for n in ("A", "RHS", "U", "Z")] + [R64.data_ptr(), g64["tcol"].data_ptr()]
+    sa.kscale, sa.shift, sa.tol, sa.max_iter, sa.check_every = g64["kscale"], g64["shift"], g64["tol"], g64["max_iter"], 5
+    sa.d_evec, sa.d_eval, sa.d_work, sa.work_bytes = g64["evec"].data_ptr(), g64["eval"].data_ptr(), g64["work"].data_ptr(), g64["work_bytes"]
+    sa.two_level = ctypes.addressof(block)
+    it, rr, he, resumed = i32(0), ctypes.c_double(0), i32(0), i32(0)
+    rc = _hip.fn("wiski_stream_step", torch.float64)(g64["grid"].ref, ctypes.byref(sa), None, None, None, None, None, ctypes.c_int64(0), None, i32(1), i32(0),
+                                                    ctypes.byref(it), ctypes.byref(rr), ctypes.byref(he), g64["stream"], None, i32(0), ctypes.byref(resumed))
+    table.append(("stream_step_f64 two_level", rc, BADARG))
+    torch.cuda.synchronize()
+    for what, rc, want in table:
+        print(f"refusal[{'f32' if tdt == torch.float32 else 'f64'}] {what}: {rc}")
+    assert [(what, rc, want) for what, rc, want in table if rc != want] == []
+    untouched = {f"{n} {dt}": bool(torch.isnan(c[n]).all()) for dt, c in cases.items() for n in ("U", "Z")}
+    untouched.update({f"work {dt}": bool((c["work"] == 0x5A).all()) for dt, c in cases.items()})
+    untouched.update(prezeroed=handle.prezeroed == 1, state=handle.state == 0)
+    print("untouched:", untouched)
+    assert all(untouched.values()), untouched
+
+
+@pytest.mark.parametrize("k", [1, 3])
+@pytest.mark.parametrize("d,g", [(2, 12), (3, 8)])
+@pytest.mark.parametrize("tdt,ndt,tol", [(torch.float64, np.float64, 1e-8), (torch.float32, np.float32, 2e-3)])
+def test_pcg_entry_points_agree(tdt, ndt, tol, d, g, k):
+    """The same system (m % 4 == 0, half stencil of 200 points, spectral preconditioner, cold start) through every entry point of
+    the solve -- wiski_pcg, wiski_pcg_async mode 0, START (first_check = 3) + RESUME, wiski_pcg_sharded without a shard and, fp32,
+    wiski_pcg_twolevel without its extras: each U against the dense oracle solve at the tolerance of
+    test_pcg_against_oracle_and_warm_start; START returns WISKI_PENDING and leaves state = 1, RESUME state = 0 and iters >= 3."""
+    import ctypes
+
+    from online_gp_amd import _hip, grid_ops
+
+    PENDING, i32 = 1, ctypes.c_int32
+    f, B2, RHS = _pcg_case(d, g, tdt, ndt, 200, k)
+    Uref = B2.solve(RHS, tol=1e-13)[0]
+    fresh = lambda: dict(U=torch.full_like(f["U"], float("nan")), Z=torch.full_like(f["Z"], float("nan")))
+
+    def solve(entry, *tail, **over):
+        a = {**f, **fresh(), **over}
+        return _hip.fn(entry, tdt)(*grid_ops._pcg_abi(tdt, **a), *tail), a["U"]
+
+    handles = [grid_ops._PcgAsync(), grid_ops._PcgAsync()]
+    got = {"pcg": solve("wiski_pcg"), "async mode 0": solve("wiski_pcg_async", ctypes.byref(handles[0]), i32(0)),
+           "sharded, no shard": solve("wiski_pcg_sharded", None, i32(0), None)}
+    if tdt == torch.float32:
+        got["twolevel, no extras"] = solve("wiski_pcg_twolevel", None, i32(0), None, None)
+    uz = fresh()
+    rc, _ = solve("wiski_pcg_async", ctypes.byref(handles[1]), i32(1), first_check=3, **uz)
+    assert rc == PENDING and handles[1].state == 1
+    f["h_iters"].value = -1
+    got["start + resume"] = solve("wiski_pcg_async", ctypes.byref(handles[1]), i32(2), first_check=3, **uz)
+    assert handles[1].state == 0 and f["h_iters"].value >= 3, (handles[1].state, f["h_iters"].value)
+    for hd in handles:
+        assert _hip.lib().wiski_pcg_async_free(ctypes.byref(hd)) == 0
+    scale = np.abs(Uref).max()
+    errs = {what: (rc, np.abs(U.double().cpu().numpy() - Uref).max() / scale) for what, (rc, U) in got.items()}
+    print("entry points:", errs)
+    assert all(rc == 0 and e < tol for rc, e in errs.values()), errs
+
+
 def test_wt_columns():
     from online_gp_amd import grid_ops
 
