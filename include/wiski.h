@@ -398,6 +398,25 @@ typedef struct wiski_absorb_args {
 int wiski_absorb_f32(const wiski_grid* grid, const wiski_absorb_args* args, void* stream);
 int wiski_absorb_f64(const wiski_grid* grid, const wiski_absorb_args* args, void* stream);
 
+/* Outlier-robust absorb: every point is Huber-weighted against the posterior BEFORE the batch, inside the launch that absorbs it
+ * (DESIGN.md 3.16).  The arguments of wiski_scatter_stats_grad (for a value per point: d_y / d_wa / d_wb / d_noise / d_mean_out
+ * are [n]) plus d_inv_scale [n], huber_c and d_omega_out [n].  With u the posterior mean on the grid,
+ *   z_p = (y_p - w_p . u) inv_scale_p,   omega_p = min(1, huber_c / |z_p|)      (exactly 1 for |z_p| <= huber_c),
+ * and the point enters A, cnt and the carried residual with omega_p wa_p, b and sum wb y^2 with omega_p wb_p, log|D| with
+ * log(noise_p / omega_p): the absorb of the same point at noise noise_p / omega_p, so everything downstream stays an exact GP.
+ * d_omega_out receives omega_p (0 for a point outside the grid, which is flagged, counted and dropped as everywhere);
+ * inv_scale_p = 0 exempts a point.  Required: d_u, d_A_half, d_cnt, d_omega_out, d_inv_scale, a finite huber_c > 0; d_res and
+ * d_mean_out are optional.  Symmetric half stencil, atomic form, one output, d = 1..4; anything else is WISKI_E_BADARG before
+ * a launch.
+ * wiski_absorb_args has NOT grown a robust group: it is passed by pointer without a size field, and callers built against
+ * today's header hand over records of today's size.  The robust form is reached through these entries only.
+ * wiski_absorb_robust takes the record plus the three robust arguments; it exists so that every combination absorb_validate
+ * refuses (a guard, zero regions, a shard, an owner workspace, nout > 1, channels, a full stencil) can be reached and tested. */
+int wiski_scatter_stats_robust_f32(const wiski_grid* grid, const float* d_x, const float* d_y, const float* d_wa, const float* d_wb, const float* d_noise, int64_t n, float* d_b, float* d_A_half, float* d_cnt, const float* d_u, float* d_res, float* d_mean_out, double* d_stats, int32_t* d_err, const float* d_inv_scale, float huber_c, float* d_omega_out, void* stream);
+int wiski_scatter_stats_robust_f64(const wiski_grid* grid, const double* d_x, const double* d_y, const double* d_wa, const double* d_wb, const double* d_noise, int64_t n, double* d_b, double* d_A_half, double* d_cnt, const double* d_u, double* d_res, double* d_mean_out, double* d_stats, int32_t* d_err, const double* d_inv_scale, double huber_c, double* d_omega_out, void* stream);
+int wiski_absorb_robust_f32(const wiski_grid* grid, const wiski_absorb_args* args, const float* d_inv_scale, float huber_c, float* d_omega_out, void* stream);
+int wiski_absorb_robust_f64(const wiski_grid* grid, const wiski_absorb_args* args, const double* d_inv_scale, double huber_c, double* d_omega_out, void* stream);
+
 /* The two halves of a stencil-sharded step on their own (wiski_stream_step uses them when args->shard is set): the absorb
  * restricted to the stencil groups [g_lo, g_hi) (same arguments as wiski_scatter_stats_step; always the atomic form), and
  * wiski_pcg_async with every A . v product summed over the ranks of `shard`. */

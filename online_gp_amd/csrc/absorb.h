@@ -3,6 +3,9 @@
 // may be asked to do, as ONE named record.  Every member defaults to "off"; the extern "C" entry points of scatter_stats.hip
 // and the streaming step (stream_step.hip) fill the fields they expose and call absorb().  Which combinations are refused is
 // absorb_validate() in scatter_stats.hip; whoever writes another form of the absorb has to honour every group below.
+// Three kernels stand behind it: the atomic form (k_scatter_stats[_sym]; the owner form where its workspace is given and applies),
+// the derivative-observation form (`channels`, scatter_grad.h) and the outlier-robust form (`inv_scale`, scatter_robust.h).  The
+// last two implement the plain single-output half-stencil absorb with cnt and the carry and refuse every other group.
 #pragma once
 #include "wiski_common.h"
 
@@ -55,6 +58,14 @@ struct AbsorbArgs {
   // noise (an absent one: wa = wb = 0, noise = 1) -- summed on chip into one atomic per tap pair (scatter_grad.h).  Single-output
   // half-stencil atomic form only, with cnt and the carry; no guard, zero regions, shard or owner form
   int channels = 0;
+  // robust: inv_scale != NULL Huber-weights every point against the posterior before the batch (scatter_robust.h):
+  //   z = (y - w_p . u) inv_scale,  omega = min(1, huber_c / |z|);  wa, wb enter as omega wa, omega wb, log noise as log(noise / omega)
+  // -- the absorb of the point at noise / omega.  inv_scale_p = 0 exempts a point (omega = 1).  Needs u, A, cnt, omega_out and a
+  // finite huber_c > 0; res and mean_out stay optional.  Single-output half-stencil atomic form only: no channels, guard, zero
+  // regions, shard or owner workspace
+  const real* inv_scale = nullptr;  // [n] 1 / scale of each point's innovation
+  real huber_c = 0;
+  real* omega_out = nullptr;        // [n] the weight each point entered with; 0 for a point outside the grid
 
   bool sharded() const { return g_lo > 0 || g_hi < (1 << 30); }
 };

@@ -6,6 +6,7 @@
 // update; here each streamed point touches exactly its 4^d x 4^d stencil block.
 #include "absorb.h"
 #include <atomic>
+#include <cmath>
 #include <cstdlib>
 
 // The half-stencil atomics of k_scatter_stats_sym.  Cache-policy bits on the fp32 atomic (sc1, nt, sc1 nt) leave A_h no better
@@ -326,6 +327,7 @@ __global__ __launch_bounds__(256) void k_scatter_stats_sym(GridDev<real> G, cons
 
 #include "scatter_owner.h"
 #include "scatter_grad.h"
+#include "scatter_robust.h"
 
 // Unpacks the row-interleaved half stencil into a full offset-major stencil full[o][i] = A[i, i + off(o)]
 // (diagnostics, tests, and models handed a full-stencil cache):
@@ -394,6 +396,15 @@ template <typename real>
 static int absorb_validate(const AbsorbArgs<real>& a, int d) {
   if (a.n == 0) return WISKI_OK;                       // nothing to absorb: not even the pointers are looked at
   if (!a.x || !a.y || !a.wa || !a.wb || !a.noise || !a.b || !a.stats || !a.err) return WISKI_E_BADARG;   // what every form reads and writes
+  if (a.inv_scale) {
+    // robust (scatter_robust.h): the weights need u; A, cnt and omega_out are written unconditionally; the plain single-output
+    // half-stencil atomic form only.  res and mean_out are optional here: u alone is a complete request
+    if (!a.u || !a.half || !a.A || !a.cnt || !a.omega_out || a.nout != 1 || a.channels) return WISKI_E_BADARG;
+    if (a.guard || a.n1_bytes || a.n2_bytes || a.z1 || a.z2 || a.sharded() || a.bin || a.bin_bytes) return WISKI_E_BADARG;
+    if (!(a.huber_c > (real)0) || !std::isfinite(a.huber_c)) return WISKI_E_BADARG;
+    return WISKI_OK;
+  }
+  if (a.omega_out || a.huber_c != (real)0) return WISKI_E_BADARG;                                        // the robust group without inv_scale
   if (a.mean_out == nullptr && (a.u != nullptr) != (a.res != nullptr)) return WISKI_E_BADARG;            // a carry without the mean is the pair (u, res)
   if ((a.res && !a.u) || (a.mean_out && !a.u) || (a.u && !a.half)) return WISKI_E_BADARG;                // residual carry-over / mean: need u, half-stencil form only
   if (a.guard && !a.half) return WISKI_E_BADARG;                                                         // so is the guard
@@ -487,6 +498,7 @@ int absorb(const wiski_grid* grid, const AbsorbArgs<real>& a, void* stream) {
   int rc = make_grid_dev<real>(grid, &G);
   if (rc == WISKI_OK) rc = absorb_validate(a, G.d);
   if (rc != WISKI_OK || a.n == 0) return rc;
+  if (a.inv_scale) return launch_robust(G, a, (hipStream_t)stream);
   if (a.channels) return launch_grad(G, a, (hipStream_t)stream);
   return owner_applies(G, a) ? launch_owner(G, a, (hipStream_t)stream) : launch_atomic(G, a, (hipStream_t)stream);
 }
@@ -528,6 +540,30 @@ int wiski_scatter_stats_grad_f64(const wiski_grid* g, const double* x, const dou
   AbsorbArgs<double> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
   a.cnt = cnt; a.u = u; a.res = res; a.mean_out = mean_out;
   a.channels = g ? g->d + 1 : 0;
+  return absorb(g, a, s);
+}
+int wiski_scatter_stats_robust_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, const float* inv_scale, float huber_c, float* omega_out, void* s) {
+  AbsorbArgs<float> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
+  a.cnt = cnt; a.u = u; a.res = res; a.mean_out = mean_out;
+  a.inv_scale = inv_scale; a.huber_c = huber_c; a.omega_out = omega_out;
+  return inv_scale ? absorb(g, a, s) : WISKI_E_BADARG;
+}
+int wiski_scatter_stats_robust_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, const double* inv_scale, double huber_c, double* omega_out, void* s) {
+  AbsorbArgs<double> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
+  a.cnt = cnt; a.u = u; a.res = res; a.mean_out = mean_out;
+  a.inv_scale = inv_scale; a.huber_c = huber_c; a.omega_out = omega_out;
+  return inv_scale ? absorb(g, a, s) : WISKI_E_BADARG;
+}
+int wiski_absorb_robust_f32(const wiski_grid* g, const wiski_absorb_args* p, const float* inv_scale, float huber_c, float* omega_out, void* s) {
+  if (!p || !inv_scale) return WISKI_E_BADARG;
+  AbsorbArgs<float> a = absorb_args<float>(*p);
+  a.inv_scale = inv_scale; a.huber_c = huber_c; a.omega_out = omega_out;
+  return absorb(g, a, s);
+}
+int wiski_absorb_robust_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* inv_scale, double huber_c, double* omega_out, void* s) {
+  if (!p || !inv_scale) return WISKI_E_BADARG;
+  AbsorbArgs<double> a = absorb_args<double>(*p);
+  a.inv_scale = inv_scale; a.huber_c = huber_c; a.omega_out = omega_out;
   return absorb(g, a, s);
 }
 int wiski_scatter_stats_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A, double* stats, int32_t* err, void* s) {

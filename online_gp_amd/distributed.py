@@ -190,6 +190,10 @@ class ShardedStatsUpdater:
             # a decay is one local launch per replica and would commute with the all-reduce, but the deltas in flight and the stencil shards
             # would have to decay with it: single-GPU for now
             raise NotImplementedError("ShardedStatsUpdater does not decay the statistics: build the model with forgetting_factor=None")
+        if getattr(model, "robust_c", None) is not None:
+            # the Huber weights of a shard are taken where it is absorbed; the followers on the other ranks (noise-weight sum, probes,
+            # two-level block) would need them gathered beside the statistics: single-GPU for now
+            raise NotImplementedError("ShardedStatsUpdater does not carry robust weights: build the model with robust_c=None")
         self.model = model
         self.group = group
         self.exchange = exchange

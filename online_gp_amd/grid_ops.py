@@ -432,6 +432,30 @@ def scatter_stats_grad(grid, x, Y, wa, wb, noise, b, A_half, cnt, stats, err, u=
     _hip.check(rc, "wiski_scatter_stats_grad")
 
 
+def scatter_stats_robust(grid, x, y, wa, wb, noise, inv_scale, c, b, A_half, cnt, stats, err, u, res=None, mean_out=None):
+    """The outlier-robust absorb in ONE launch (``wiski_scatter_stats_robust``): every point is Huber-weighted
+    against the posterior mean ``u`` [m] before the batch, z = (y - w . u) inv_scale, omega = min(1, c / |z|), and enters
+    (b, A_half, cnt, stats) -- and the carried residual ``res``, if given -- as the same point at noise / omega.  ``inv_scale``
+    [n] (0 exempts a point).  Returns omega [n] (0 for a point outside the grid); ``mean_out`` [n] receives w . u."""
+    x = _x2d(x, grid)
+    n = x.shape[0]
+    for name, t in (("y", y), ("wa", wa), ("wb", wb), ("noise", noise), ("inv_scale", inv_scale), ("mean_out", mean_out)):
+        if t is not None and (tuple(t.shape) != (n,) or t.dtype != x.dtype):
+            raise ValueError(f"scatter_stats_robust: {name} must be [{n}] {x.dtype}, got {tuple(t.shape)} {t.dtype}")
+    if u is None or tuple(u.shape) != (grid.m,) or u.dtype != x.dtype:
+        raise ValueError(f"scatter_stats_robust: u must be the grid mean [{grid.m}] {x.dtype}")
+    omega = torch.empty(n, dtype=x.dtype, device=x.device)
+    if n == 0:
+        return omega
+    rc = _hip.fn("wiski_scatter_stats_robust", x.dtype)(grid.ref, _hip.dptr(x), _hip.dptr(y.contiguous()), _hip.dptr(wa.contiguous()),
+                                                        _hip.dptr(wb.contiguous()), _hip.dptr(noise.contiguous()), ctypes.c_int64(n), _hip.dptr(b),
+                                                        _hip.dptr(A_half), _hip.dptr(cnt), _hip.dptr(u), _hip.dptr(res), _hip.dptr(mean_out),
+                                                        _hip.dptr(stats), _hip.dptr(err), _hip.dptr(inv_scale.contiguous()),
+                                                        _hip.creal(x.dtype)(float(c)), _hip.dptr(omega), _hip.stream_ptr(x.device))
+    _hip.check(rc, "wiski_scatter_stats_robust")
+    return omega
+
+
 def scatter_probes(grid, x, wa, first_index, seed, P, err):
     """P [m, S] += the probe increments sum_i sqrt(wa_i) eps(first_index + i, s) w(x_i) of the points x [q, d]
     (``wiski_scatter_probes``; wa [q] or None = unit weights; the normals are a function of (seed, global point index, s):

@@ -92,6 +92,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         forgetting_factor=None,
         grow_grid=False,
         max_grid_size=None,
+        robust_c=None,
+        robust_scale="noise",
     ):
         super().__init__()
         assert train_inputs is not None or kernel_cache is not None
@@ -104,6 +106,17 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             if not (0.0 < forgetting_factor <= 1.0):
                 raise ValueError(f"forgetting_factor must lie in (0, 1], got {forgetting_factor}")
         self.forgetting_factor = forgetting_factor
+        # outlier-robust streaming (_absorb_robust): every streamed batch is Huber-weighted at this threshold against
+        # the posterior before it.  None: every path is what it is without the feature
+        if robust_c is not None:
+            robust_c = float(robust_c)
+            if not (robust_c > 0.0 and math.isfinite(robust_c)):
+                raise ValueError(f"robust_c must be a finite positive number, got {robust_c}")
+        if robust_scale not in ("noise", "predictive"):
+            raise ValueError(f"robust_scale must be 'noise' or 'predictive', got {robust_scale!r}")
+        self.robust_c = robust_c
+        self.robust_scale = robust_scale
+        self.last_robust_weights = None              # omega [q] of the last robustly absorbed batch, on the device
 
         if train_targets is not None:
             if train_targets.dim() == 1:
@@ -119,6 +132,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             device, dtype = ic.device, ic.dtype
             num_dims = None
         self.num_outputs = num_outputs
+        if robust_c is not None and num_outputs > 1:
+            raise NotImplementedError("robust_c is implemented for a single output (the robust absorb weights one target per point)")
         _batch_shape = torch.Size([num_outputs]) if num_outputs > 1 else torch.Size()
         # probe vectors of the posterior sample paths (sample_paths): S of them, rounded up to even (the generator
         # makes Box-Muller pairs); they live in the kernel cache beside b and follow it through every hand-over
@@ -282,6 +297,9 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         innovation W^T (wb y - wa (W U)) of the carried residual, to be all-reduced and added to R alongside."""
         if "path_probes" in cache and half_delta is not None:
             raise NotImplementedError("path probes do not follow the data-parallel statistics exchange")
+        if self.robust_c is not None and half_delta is not None:
+            raise NotImplementedError("robust_c does not follow the data-parallel statistics exchange (half_delta): the Huber weights of a "
+                                      "shard would be taken on one rank and the other ranks' followers never see them")
         self._finish_pending()
         if cache is self._kernel_cache:
             self.leave_stencil_shard()               # the generic absorb writes every group
@@ -1015,10 +1033,18 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         in the functional form -- decay once before the batch is absorbed (not for fantasies: batched conditioning,
         ``get_fantasy_model``).
 
+        With ``robust_c`` set on the model, an unbatched batch is Huber-weighted against the posterior before it (after growing and
+        decaying) and absorbed at noise ``noise_i / omega_i`` in the same launch (``_absorb_robust``, DESIGN.md 3.16);
+        ``last_robust_weights`` -- of the returned model, in the functional form -- then holds ``omega`` [q].  Batched X (fantasies)
+        ignores ``robust_c``: fantasised targets come from the model itself.  ``"noise"`` scaling (1 / sqrt(sigma2 noise_i)) presumes
+        a model that already tracks the signal; ``"predictive"`` adds the posterior variance at X (one more solve).
+
         ``grad_Y`` [n, d]: observations of the gradient of f at X, absorbed with the values in the same launch (DESIGN.md 3.15);
         ``Y=None`` then means gradient-only.  ``grad_noise`` [n, d] or [n]: their noise (None: the value observation's, or unit
         noise); ``grad_mask`` bool [n, d]: which partials were observed (None: all).  ``num_data`` grows by the number of scalar
         observations.  Single output, unbatched X."""
+        if grad_Y is not None and self.robust_c is not None:
+            raise NotImplementedError("robust_c weights value observations only: a model built with it takes no grad_Y")
         if grad_Y is not None:
             return self._condition_on_gradients(X, Y, noise, inplace, _decay, grad_Y, grad_noise, grad_mask)
         if grad_noise is not None or grad_mask is not None:
@@ -1040,6 +1066,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         gamma = self.forgetting_factor if _decay else None
         if gamma == 1.0:
             gamma = None
+        if self.robust_c is not None:
+            return self._condition_robust(X, Y, noise, inplace, gamma, q)
         if gamma is not None and inplace:
             self.forget_(gamma)
         old_pc = None if gamma is not None else self._rank_update_source(q)      # (a rank-q update starts from the factor of the undecayed A)
@@ -1070,6 +1098,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             forgetting_factor=self.forgetting_factor,
             grow_grid=self.grow_grid,
             max_grid_size=self.max_grid_size,
+            robust_c=self.robust_c,
+            robust_scale=self.robust_scale,
         )
         new_gp._wsum_dev = self._wsum_dev.clone()
         new_gp._wsum_host = list(self._wsum_host)
@@ -1177,6 +1207,84 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             self._wsum_dev = cache["_cnt"].sum(dim=1, dtype=torch.float64)
             self._wsum_host = [0.0] * self.num_outputs
             self._wsum_dirty = True
+
+    # ------------------------------------------------- outlier-robust absorb --
+    def _condition_robust(self, X, Y, noise, inplace, gamma, q):
+        """condition_on_observations of a model with robust_c, once the grid has grown: decay, weigh, absorb.  The
+        weights are taken against the posterior of the statistics the batch is added to -- the decayed ones under forgetting."""
+        if inplace:
+            if gamma is not None:
+                self.forget_(gamma)
+            self._absorb_robust(self._kernel_cache, X, Y, noise, self)
+            self.num_data = self.num_data + q
+            self._dump_caches()
+            return None
+        new_cache = self._clone_cache(self._kernel_cache)
+        new_gp = self._sibling(new_cache, self.num_data + q)
+        src = self                                   # without a decay the clone's posterior is this model's, usually already solved
+        if gamma is not None:
+            new_gp._decay(gamma, self.num_data)          # the clone's buffers: the parent keeps its statistics bit for bit
+            self._sibling_mean_state(new_gp)             # (warm start of the solve the weights need)
+            src = new_gp
+        new_gp._absorb_robust(new_cache, X, Y, noise, src)
+        new_gp._dump_caches()                            # (the prediction cache the weights were read from predates the batch)
+        if src is self:
+            self._sibling_mean_state(new_gp)
+        elif not self.training:
+            new_gp.eval()
+        return new_gp
+
+    def _robust_inputs(self, X, noise):
+        """(u [m], inv_scale [n]) of a batch under THIS model's current posterior: the grid mean from the prediction cache (every
+        regime keeps one), and 1 / sqrt(sigma2 noise_i) ("noise") or 1 / sqrt(var_i + sigma2 noise_i) ("predictive", var_i the
+        posterior variance at x_i: one more solve on the paths every posterior call takes)."""
+        u = self.prediction_cache["pred_mean"][0, :, 0]
+        s2 = self._sigma2(0)
+        scale2 = noise.clamp_min(1e-7) * s2                  # (the floor _weight_a gives the noise of an update)
+        if self.robust_scale == "predictive":
+            with torch.no_grad(), settings.skip_posterior_variances(False):
+                var = self._eval_forward(X).variance.reshape(-1).to(self._dtype)
+            scale2 = scale2 + var.clamp_min(0.0)
+        return u, scale2.rsqrt()
+
+    def _absorb_robust(self, cache, X, Y, noise, src):
+        """_absorb of one value-only batch with Huber weights, one launch (wiski_scatter_stats_robust).  `src`: the model whose
+        posterior the weights are taken against -- this one, or in the functional form without a decay the parent, whose statistics
+        the clone still equals.  Everything that follows the stream point by point receives the effective weights wa omega and
+        wb omega: a carried root pair, the spectral factor, the path probes, the noise-weight sum.  The two-level block is given up
+        (a model with robust_c never takes the fused streaming step that feeds it) and the dense rank-update seed is skipped: the
+        next posterior is factored afresh."""
+        if self.num_outputs > 1:
+            raise NotImplementedError("robust_c is implemented for a single output")
+        op = _wtw_ops(cache["WtW"])[0]
+        if not grid_ops.is_half_stencil(self._grid, op.stencil) or "_cnt" not in cache:
+            raise NotImplementedError("robust_c needs the native half-stencil cache (a full stencil was handed over)")
+        X = X.reshape(-1, self._grid.d).to(self._device, self._dtype).contiguous()
+        y = Y.to(self._device, self._dtype).reshape(-1).contiguous()
+        n = X.shape[0]
+        unit = noise is None
+        no, wa, wb = self._batch_weights(None if unit else noise.to(self._device, self._dtype).reshape(-1).contiguous(), False, n)
+        u, inv_scale = src._robust_inputs(X, no)             # (finishes whatever is pending, leaves a stencil shard)
+        self._finish_pending()
+        self.leave_stencil_shard()
+        ms = self._mean_state if src is self else None
+        carry = ms is not None and ms.get("R_ok", False) and settings.residual_carry_over.on() and ms["U"][0].data_ptr() == u.data_ptr()
+        if self._mean_state is not None and not carry:
+            self._mean_state["R_ok"] = False
+        omega = grid_ops.scatter_stats_robust(self._grid, X, y, wa, wb, no, inv_scale, self.robust_c, cache["interpolation_cache"][0, :, 0],
+                                              op.stencil, cache["_cnt"][0], cache["_stats"][0], self._err, u, res=ms["R"][0] if carry else None)
+        self.last_robust_weights = omega
+        if n == 0:
+            return
+        wa_eff, wb_eff = wa * omega, wb * omega              # a point outside the grid: omega = 0, nothing anywhere
+        self._two_level_lose()                               # (its block is rebuilt from the stencil where one is wanted again)
+        if getattr(op, "root", None) is not None:
+            Wd = grid_ops.wt_columns(self._grid, X, self._err)
+            op.update_roots_((Wd * wa_eff.sqrt()[:, None]).t().contiguous())
+        self._spectral_absorb(0, X, wa_eff, y * wb_eff)
+        self._wsum_add(0, n, wa_eff)
+        if "path_probes" in cache:
+            self._absorb_probes(cache, X, wa_eff)
 
     def stream_step(self, X, Y, want_mean=True):
         """evaluate -> absorb -> refresh for one streamed batch (the reference driver's online step at batch granularity,
@@ -1384,7 +1492,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
 
     def _stream_fast_state(self, X, Y):
         """(prepared StreamStep, mean state, preconditioner state) when the one-call streaming step applies, else None."""
-        if (self.num_outputs != 1 or self._use_dense() or settings.spectral_preconditioner.off() or settings.residual_carry_over.off()
+        if (self.robust_c is not None or self.num_outputs != 1 or self._use_dense() or settings.spectral_preconditioner.off() or settings.residual_carry_over.off()
                 or X.dim() != 2 or not X.is_cuda or X.dtype != self._dtype or not X.is_contiguous() or Y.dtype != self._dtype):
             return None
         ms = self._mean_state

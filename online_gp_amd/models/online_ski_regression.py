@@ -2,6 +2,7 @@
 (counterpart of online_gp/models/online_ski_regression.py:16-197, experiments/regression.py:38-138):
 
     OnlineSKIRegression(stem, init_x, init_y, lr, grid_size, grid_bound, covar_module=None, **kw)
+        (**kw: num_path_probes, path_seed, forgetting_factor, grow_grid, max_grid_size, robust_c, robust_scale -- passed to the GP)
     .fit(x, y, num_epochs, test_dataset=None) -> list of per-epoch dicts
     .update(x, y, update_stem=True, update_gp=True) -> (stem_loss, gp_loss)
     .evaluate(x, y) -> (rmse, nll)        .predict(x) -> (mean [n, out], var [n, out])
@@ -40,6 +41,7 @@ class OnlineSKIRegression(StreamingSKIWrapper):
             num_path_probes=kwargs.get("num_path_probes", 0), path_seed=kwargs.get("path_seed", 0),
             forgetting_factor=kwargs.get("forgetting_factor"),
             grow_grid=kwargs.get("grow_grid", False), max_grid_size=kwargs.get("max_grid_size"),
+            robust_c=kwargs.get("robust_c"), robust_scale=kwargs.get("robust_scale", "noise"),
         )
         self._setup(stem, gp, lr, init_x)
 
