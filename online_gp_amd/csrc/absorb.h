@@ -5,7 +5,9 @@
 // absorb_validate() in scatter_stats.hip; whoever writes another form of the absorb has to honour every group below.
 // Three kernels stand behind it: the atomic form (k_scatter_stats[_sym]; the owner form where its workspace is given and applies),
 // the derivative-observation form (`channels`, scatter_grad.h) and the outlier-robust form (`inv_scale`, scatter_robust.h).  The
-// last two implement the plain single-output half-stencil absorb with cnt and the carry and refuse every other group.
+// last two implement the plain single-output half-stencil absorb with cnt and the carry and refuse every other group.  What the
+// three half-stencil kernels do per point -- the tap tables, the per-tap atomics, the pair loop that encodes the row-interleaved
+// layout, the two scalars -- is stated once, in scatter_half.h.
 #pragma once
 #include "wiski_common.h"
 

@@ -9,8 +9,7 @@
 // order of the points nor on the order of the atomics.
 #pragma once
 
-// The lane mapping, the LDS tables, the pair list and the row-interleaved half-stencil layout are those of k_scatter_stats_sym:
-// one wave per point, four points per block, lane = (a2, b2, pair slot).  No guard, zero regions, shard or batch (absorb_validate).
+// The point sweep is that of k_scatter_stats_sym (scatter_half.h).  No guard, zero regions, shard or batch (absorb_validate).
 //
 // The two scalars cannot come from scatter_stats_pass: its designated blocks would need the omega of points other blocks weight
 // in the same launch, and nothing orders a read of omega_out behind those writes.  Each wave therefore keeps, in fp64, the
@@ -23,129 +22,49 @@ __global__ __launch_bounds__(256) void k_scatter_stats_robust(GridDev<real> G, c
                                                               real* __restrict__ cnt, const real* __restrict__ u, real* __restrict__ res,
                                                               real* __restrict__ mean_out, const real* __restrict__ inv_scale, real huber_c,
                                                               real* __restrict__ omega_out) {
-  constexpr int T = 1 << (2 * D);
-  constexpr int TP = T / 4;                      // tap prefixes (leading d-1 digits)
-  constexpr int NPAIR = TP * (TP + 1) / 2;       // prefix pairs with pb >= pa
-  constexpr int TPL = T > 64 ? T / 64 : 1;       // taps per lane when filling the per-point tables
-  __shared__ real s_val[4][T];
-  __shared__ int s_idx[4][T];
-  __shared__ int s_pair[NPAIR];                  // pa | pb << 8 | g << 16
+  using H = HalfTaps<D>;
+  __shared__ real s_val[4][H::T];
+  __shared__ int s_idx[4][H::T];
+  __shared__ int s_pair[H::NPAIR];
   __shared__ double s_red[16];
   const int lane = threadIdx.x & 63, loc = threadIdx.x >> 6;
-  // the prefix pairs in the order k_scatter_stats_sym lists them (closed form: scatter_grad.h)
-  for (int idx = threadIdx.x; idx < TP * TP; idx += 256) {
-    const int pa = idx / TP, pb = idx % TP;
-    int ca = 0, cb = 0;
-#pragma unroll
-    for (int q = 0; q < D - 1; ++q) {
-      ca = ca * 7 + ((pa >> (2 * (D - 2 - q))) & 3);
-      cb = cb * 7 + ((pb >> (2 * (D - 2 - q))) & 3);
-    }
-    if (pb >= pa) s_pair[pa * TP - pa * (pa - 1) / 2 + (pb - pa)] = pa | (pb << 8) | ((cb - ca) << 16);
-  }
+  half_pair_list<D>(s_pair, reinterpret_cast<int*>(s_red), 0, 1 << 30);         // the whole stencil: H::NPAIR pairs
   bool bad = false;
   double c_acc = 0, ld_acc = 0;                  // lane 0: this wave's share of the two scalars
-  const int64_t m = G.m;
   for (int64_t base = (int64_t)blockIdx.x * 4; base < n; base += (int64_t)gridDim.x * 4) {
     const int64_t p = base + loc;
     const bool valid = p < n;
-    bool inside = false;
-    int j0[D];
-    real w[D][4];
+    int j0[D], flat_t[H::TPL];
+    real w[D][4], val_t[H::TPL][1], yw[1], wac[1], wu[1], innov[1];
+    const bool inside = half_point_setup<real, D>(G, x, p, n, lane == 0, err, bad, j0, w);
     real yp = 0, wap = 0, wbp = 0, isp = 0;
     if (valid) {
-      real xp[D];
-#pragma unroll
-      for (int q = 0; q < D; ++q) xp[q] = x[p * D + q];
-      inside = point_stencil<real, D>(G, xp, j0, w);
-      if (!inside) flag_outside(err, lane == 0, bad);
       yp = y[p];
       wap = wa[p];
       wbp = wb[p];
       isp = inv_scale[p];
-    } else {
-#pragma unroll
-      for (int q = 0; q < D; ++q) {
-        j0[q] = 0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) w[q][c] = 0;
-      }
     }
-    int flat_t[TPL];
-    real val_t[TPL];
-    real wu = (real)0;                            // this lane's share of w_p . u
-#pragma unroll
-    for (int t = 0; t < TPL; ++t) {
-      const int a = lane + t * 64;
-      flat_t[t] = 0;
-      val_t[t] = (real)0;
-      if (a < T) {
-        int flat = 0;
-        real v = (real)1;
-#pragma unroll
-        for (int q = 0; q < D; ++q) {
-          const int c = (a >> (2 * (D - 1 - q))) & 3;
-          flat += (j0[q] + c) * G.stride[q];
-          v *= w[q][c];
-        }
-        s_val[loc][a] = v;
-        s_idx[loc][a] = flat;
-        flat_t[t] = flat;
-        val_t[t] = v;
-        if (v != (real)0) wu += v * u[flat];
-      }
-    }
-    wu = wave_reduce_sum<real>(wu);               // the predictive mean of the point before the batch, in every lane
+    half_tap_table<real, D, 1>(G, j0, w, nullptr, lane, u, s_val[loc], s_idx[loc], flat_t, val_t, wu);   // wu: the predictive mean of the point before the batch
     // the Huber weight, the same in every lane; a point outside the grid has zero rows and reports omega = 0
-    const real az = fabs((yp - wu) * isp);
+    const real az = fabs((yp - wu[0]) * isp);
     const real omega = az > huber_c ? huber_c / az : (real)1;
-    wap *= omega;
     wbp *= omega;
-    const real innov = yp * wbp - wap * wu;       // res += W^T (wb y - wa (W u)), with the weights the point enters with
+    wac[0] = wap * omega;
+    yw[0] = yp * wbp;
+    half_carry<real, 1>(u, yw, wac, wu, mean_out, p, lane == 0 && valid, innov);   // with the weights the point enters with
     if (lane == 0 && valid) {
-      if (mean_out) mean_out[p] = wu;
       omega_out[p] = inside ? omega : (real)0;
       if (inside) {
         c_acc += (double)yp * (double)yp * (double)wbp;
         ld_acc += log((double)noise[p] / (double)omega);
       }
     }
-#pragma unroll
-    for (int t = 0; t < TPL; ++t) {
-      if (valid && val_t[t] != (real)0) {
-        atomic_add_real(b + flat_t[t], val_t[t] * yp * wbp);
-        atomic_add_real(cnt + flat_t[t], val_t[t] * wap);
-        if (res) atomic_add_real(res + flat_t[t], val_t[t] * innov);
-      }
-    }
+    half_tap_atomics<real, D, 1>(valid, flat_t, val_t, yw, wac, innov, b, cnt, res);
     __syncthreads();
-    if (valid) {
-      const int a2 = lane & 3, b2 = (lane >> 2) & 3, ps = lane >> 4;
-#pragma unroll 2
-      for (int t0 = 0; t0 < NPAIR; t0 += 4) {
-        const int t = t0 + ps;
-        if (t < NPAIR) {
-          const int pk = s_pair[t];
-          const int g = pk >> 16;
-          const int a = (pk & 0xff) * 4 + a2;
-          const real v = wap * s_val[loc][a] * s_val[loc][((pk >> 8) & 0xff) * 4 + b2];
-          const int64_t row = s_idx[loc][a];
-          if (g == 0) {
-            if (b2 >= a2 && v != (real)0) stencil_atomic(A + row * 4 + (b2 - a2), v);
-          } else if (v != (real)0) {
-            stencil_atomic(A + (int64_t)(7 * g - 3) * m + row * 7 + (b2 - a2 + 3), v);
-          }
-        }
-      }
-    }
+    if (valid) half_pair_loop<real, D, 1>(lane, H::NPAIR, s_pair, s_val[loc], s_idx[loc], wac, 1, A, G.m);
     __syncthreads();
   }
-  const double c_tot = block_reduce_sum(c_acc, s_red);
-  const double ld_tot = block_reduce_sum(ld_acc, s_red);
-  if (threadIdx.x == 0 && (c_tot != 0 || ld_tot != 0)) {
-    unsafeAtomicAdd(stats + 0, c_tot);
-    unsafeAtomicAdd(stats + 1, ld_tot);
-  }
+  stats_atomic_pair(c_acc, ld_acc, stats, s_red);
   if (bad) atomicOr(err, 1);
 }
 

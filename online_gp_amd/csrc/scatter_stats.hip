@@ -5,15 +5,10 @@
 // The reference densifies W^T (m x q) and adds a dense m x m outer product per
 // update; here each streamed point touches exactly its 4^d x 4^d stencil block.
 #include "absorb.h"
+#include "scatter_half.h"
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
-
-// The half-stencil atomics of k_scatter_stats_sym.  Cache-policy bits on the fp32 atomic (sc1, nt, sc1 nt) leave A_h no better
-// placed for the SpMV that follows -- SpMV dispatches right after the absorb / absorb kernel: default 18.0-18.2 us / 66.6-67.4 us,
-// sc1 18.1-18.4 / 67.7, nt 18.3-18.4 / 69.3, sc1 nt 18.2-18.3 / 68.7 -- so it is the plain fire-and-forget add.
-__device__ __forceinline__ void stencil_atomic(float* p, float v) { unsafeAtomicAdd(p, v); }
-__device__ __forceinline__ void stencil_atomic(double* p, double v) { unsafeAtomicAdd(p, v); }
 
 // What the point-sweeping kernels of an absorb (k_scatter_stats_sym, k_bin_points) do before their first point.  False: a guarded
 // launch (AbsorbArgs::guard) that is not to happen.  Otherwise the two zero regions are cleared on the way, grid-strided.
@@ -24,46 +19,6 @@ __device__ __forceinline__ bool absorb_prologue(const long long* __restrict__ gu
   for (int64_t e = (int64_t)blockIdx.x * nt + threadIdx.x; e < n1; e += (int64_t)nb * nt) z1[e] = 0u;
   for (int64_t e = (int64_t)blockIdx.x * nt + threadIdx.x; e < n2; e += (int64_t)nb * nt) z2[e] = 0u;
   return true;
-}
-
-// A point outside the grid raises the flag and contributes nothing at all (zero weights; no y^2 / log-noise term either, so a
-// caller that catches the error keeps statistics that agree with A and b).  `count`: the one lane that counts the point --
-// bits 1..: number of training points dropped; bit 0 (any point outside) is set from `bad` when the kernel ends.
-__device__ __forceinline__ void flag_outside(int32_t* __restrict__ err, bool count, bool& bad) {
-  bad = true;
-  if (count) atomicAdd(err, 2);
-}
-
-// stats[0] += sum wb y^2, stats[1] += sum log(noise) over the points inside the grid.  Atomics of many blocks on one address
-// serialise at the memory side (~12 ns each): with one pair per block the 1 024 blocks of a q = 4 096 absorb spent 25 us of
-// their 87 us queueing on these two doubles.  So a few designated blocks sweep the points once more (x, y, wb, noise: 24 B per
-// point) and issue one pair each.
-template <typename real, int D>
-__device__ __forceinline__ void scatter_stats_pass(const GridDev<real>& G, const real* __restrict__ x, const real* __restrict__ y,
-                                                   const real* __restrict__ wb, const real* __restrict__ noise, int64_t n,
-                                                   double* __restrict__ stats, double* s_red) {
-  int64_t want = n / 512;
-  want = want < 1 ? 1 : (want > 64 ? 64 : want);
-  const int ns = (int64_t)gridDim.x < want ? (int)gridDim.x : (int)want;
-  if ((int)blockIdx.x >= ns) return;                       // block-uniform
-  double c_acc = 0, ld_acc = 0;
-  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)ns * blockDim.x) {
-    real xp[D], w[D][4];
-    int j0[D];
-#pragma unroll
-    for (int q = 0; q < D; ++q) xp[q] = x[p * D + q];
-    if (point_stencil<real, D>(G, xp, j0, w)) {
-      const double yp = (double)y[p];
-      c_acc += yp * yp * (double)wb[p];
-      ld_acc += log((double)noise[p]);
-    }
-  }
-  const double c_tot = block_reduce_sum(c_acc, s_red);
-  const double ld_tot = block_reduce_sum(ld_acc, s_red);
-  if (threadIdx.x == 0 && (c_tot != 0 || ld_tot != 0)) {
-    unsafeAtomicAdd(stats + 0, c_tot);
-    unsafeAtomicAdd(stats + 1, ld_tot);
-  }
 }
 
 // GRP = min(T, 64) lanes cooperate on one point (lane <-> tap a); each lane
@@ -122,7 +77,7 @@ __global__ __launch_bounds__(256) void k_scatter_stats(GridDev<real> G, const re
       real v = (real)1;
 #pragma unroll
       for (int q = 0; q < D; ++q) {
-        const int c = (a >> (2 * (D - 1 - q))) & 3;
+        const int c = tap_digit<D>(a, q);
         flat += (j0[q] + c) * G.stride[q];
         code = code * 7 + c;
         v *= w[q][c];
@@ -151,7 +106,7 @@ __global__ __launch_bounds__(256) void k_scatter_stats(GridDev<real> G, const re
               const int bb = (bb0 & ~3) | ((bb0 + (sub + t * GRP)) & 3);
               int codeb = 0;
 #pragma unroll
-              for (int q = 0; q < D; ++q) codeb = codeb * 7 + ((bb >> (2 * (D - 1 - q))) & 3);
+              for (int q = 0; q < D; ++q) codeb = codeb * 7 + tap_digit<D>(bb, q);
               const real vb = s_val[loc][bb];
               if (vb != (real)0) atomic_add_real(Arow + (int64_t)(obase + codeb) * G.m, va * vb);
             }
@@ -165,18 +120,8 @@ __global__ __launch_bounds__(256) void k_scatter_stats(GridDev<real> G, const re
   if (bad) atomicOr(err, 1);
 }
 
-// Symmetric half-stencil accumulation (the model's native W^T D^-1 W storage), "row-interleaved" layout:
-// with P = the leading d-1 stencil digits of an offset and s its innermost digit, only offsets >= centre
-// are kept, grouped by g = P - P_centre:
-//   group 0      :  A_h[4 i + (s - 3)]                 s = 3..6   (4 reals per row; s = 3 is the diagonal)
-//   group g >= 1 :  A_h[(7 g - 3) m + 7 i + s]         s = 0..6   (7 reals per row)
-// -- (7^d + 1)/2 * m reals in total, the same as a row-major [(7^d+1)/2][m] half stencil.  The layout is
-// chosen for this kernel: one wave per point, lane = (a2, b2, pair slot) with a2/b2 the innermost tap
-// digits of taps a/b, looping over the (prefix_a <= prefix_b) pairs four at a time.  The 16 (a2, b2)
-// combinations of a pair land in one 88-byte span (rows i..i+3 x 7 slots), so a wave instruction touches
-// ~9 cache lines with ~7 lanes each instead of 16 lines with 4 lanes (offset-major layout) -- measured
-// 72 us vs 208 us per 4096 uniform points at 50^3 (the memory-side atomic units are transaction-bound).
-// The stencil SpMV re-tiles the 7-wide rows through LDS (solve.hip).
+// Symmetric half-stencil accumulation (the model's native W^T D^-1 W storage; the row-interleaved layout and the point sweep are
+// scatter_half.h), with everything the plain form carries besides: the guard, the zero regions, stencil shards, batched outputs.
 template <typename real, int D>
 __global__ __launch_bounds__(256) void k_scatter_stats_sym(GridDev<real> G, const real* __restrict__ x, const real* __restrict__ y,
                                                            const real* __restrict__ wa, const real* __restrict__ wb,
@@ -198,127 +143,29 @@ __global__ __launch_bounds__(256) void k_scatter_stats_sym(GridDev<real> G, cons
     if (res) res += o * bt.vec_stride;
   }
   if (!absorb_prologue(guard, guard_expect, z1, n1, z2, n2, blockDim.x, gridDim.x)) return;
-  constexpr int T = 1 << (2 * D);
-  constexpr int TP = T / 4;                      // tap prefixes (leading d-1 digits)
-  constexpr int NPAIR = TP * (TP + 1) / 2;       // prefix pairs with code(pb) >= code(pa)
-  constexpr int TPL = T > 64 ? T / 64 : 1;       // taps per lane when filling the per-point tables
-  __shared__ real s_val[4][T];
-  __shared__ int s_idx[4][T];
-  __shared__ int s_pair[NPAIR];                  // pa | pb << 8 | g << 16
-  __shared__ int s_scan[4];
+  using H = HalfTaps<D>;
+  __shared__ real s_val[4][H::T];
+  __shared__ int s_idx[4][H::T];
+  __shared__ int s_pair[H::NPAIR];
   __shared__ double s_red[16];
   const int lane = threadIdx.x & 63, loc = threadIdx.x >> 6;
-  int npair = 0;
-  {  // compact list of the valid prefix pairs (block-cooperative stream compaction)
-    int running = 0;
-    for (int base = 0; base < TP * TP; base += 256) {
-      const int idx = base + threadIdx.x;
-      const int pa = idx / TP, pb = idx % TP;
-      int ca = 0, cb = 0;
-#pragma unroll
-      for (int q = 0; q < D - 1; ++q) {
-        ca = ca * 7 + ((pa >> (2 * (D - 2 - q))) & 3);
-        cb = cb * 7 + ((pb >> (2 * (D - 2 - q))) & 3);
-      }
-      const bool ok = idx < TP * TP && cb >= ca && cb - ca >= g_lo && cb - ca < g_hi;
-      const unsigned long long mask = __ballot(ok);
-      if (lane == 0) s_scan[loc] = __popcll(mask);
-      __syncthreads();
-      int off = running;
-      for (int w = 0; w < loc; ++w) off += s_scan[w];
-      if (ok) s_pair[off + __popcll(mask & ((1ull << lane) - 1ull))] = pa | (pb << 8) | ((cb - ca) << 16);
-      running += s_scan[0] + s_scan[1] + s_scan[2] + s_scan[3];
-      __syncthreads();
-    }
-    npair = running;                              // block-uniform: NPAIR for the whole stencil, fewer for a shard
-  }
+  const int npair = half_pair_list<D>(s_pair, reinterpret_cast<int*>(s_red), g_lo, g_hi);
   bool bad = false;
-  const int64_t m = G.m;
   for (int64_t base = (int64_t)blockIdx.x * 4; base < n; base += (int64_t)gridDim.x * 4) {
     const int64_t p = base + loc;
     const bool valid = p < n;
-    int j0[D];
-    real w[D][4];
-    real yp = 0, wap = 0, wbp = 0;
+    int j0[D], flat_t[H::TPL];
+    real w[D][4], val_t[H::TPL][1], yw[1] = {0}, wac[1] = {0}, wu[1], innov[1];
+    half_point_setup<real, D>(G, x, p, n, lane == 0 && blockIdx.y == 0, err, bad, j0, w);      // (a dropped point counts once, not once per output)
     if (valid) {
-      real xp[D];
-#pragma unroll
-      for (int q = 0; q < D; ++q) xp[q] = x[p * D + q];
-      if (!point_stencil<real, D>(G, xp, j0, w)) flag_outside(err, lane == 0 && blockIdx.y == 0, bad);      // (a dropped point counts once, not once per output)
-      yp = y[p];
-      wap = wa[p];
-      wbp = wb[p];
-    } else {
-#pragma unroll
-      for (int q = 0; q < D; ++q) {
-        j0[q] = 0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) w[q][c] = 0;
-      }
+      yw[0] = y[p] * wb[p];
+      wac[0] = wa[p];
     }
-    int flat_t[TPL];
-    real val_t[TPL];
-    real wu = (real)0;                            // this lane's share of w_p . u
-#pragma unroll
-    for (int t = 0; t < TPL; ++t) {
-      const int a = lane + t * 64;
-      flat_t[t] = 0;
-      val_t[t] = (real)0;
-      if (a < T) {
-        int flat = 0;
-        real v = (real)1;
-#pragma unroll
-        for (int q = 0; q < D; ++q) {
-          const int c = (a >> (2 * (D - 1 - q))) & 3;
-          flat += (j0[q] + c) * G.stride[q];
-          v *= w[q][c];
-        }
-        s_val[loc][a] = v;
-        s_idx[loc][a] = flat;
-        flat_t[t] = flat;
-        val_t[t] = v;
-        if (u && v != (real)0) wu += v * u[flat];
-      }
-    }
-    // residual carry-over (optional): res += W^T (wb y - wa (W u)) keeps res = b - z - A u exact under the
-    // increment (b, A) += (W^T wb y, W^T wa W), so the next warm-started solve needs no A u product
-    // w_p . u is also the predictive mean of the point under the posterior BEFORE this update (u = the current posterior mean
-    // on the grid): mean_out makes the separate gather launch of a streaming step unnecessary
-    real innov = yp * wbp;
-    if (u) {
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) wu += __shfl_xor(wu, off, 64);
-      innov -= wap * wu;
-      if (mean_out && lane == 0 && valid) mean_out[p] = wu;
-    }
-#pragma unroll
-    for (int t = 0; t < TPL; ++t) {
-      if (valid && val_t[t] != (real)0) {
-        atomic_add_real(b + flat_t[t], val_t[t] * yp * wbp);
-        if (cnt) atomic_add_real(cnt + flat_t[t], val_t[t] * wap);     // row sums of the increment (preconditioner density model)
-        if (res) atomic_add_real(res + flat_t[t], val_t[t] * innov);
-      }
-    }
+    half_tap_table<real, D, 1>(G, j0, w, nullptr, lane, u, s_val[loc], s_idx[loc], flat_t, val_t, wu);
+    half_carry<real, 1>(u, yw, wac, wu, mean_out, p, lane == 0 && valid, innov);
+    half_tap_atomics<real, D, 1>(valid, flat_t, val_t, yw, wac, innov, b, cnt, res);
     __syncthreads();
-    if (valid && A) {
-      const int a2 = lane & 3, b2 = (lane >> 2) & 3, ps = lane >> 4;
-#pragma unroll 2
-      for (int t0 = 0; t0 < npair; t0 += 4) {
-        const int t = t0 + ps;
-        if (t < npair) {
-          const int pk = s_pair[t];
-          const int g = pk >> 16;
-          const int a = (pk & 0xff) * 4 + a2;
-          const real v = wap * s_val[loc][a] * s_val[loc][((pk >> 8) & 0xff) * 4 + b2];
-          const int64_t row = s_idx[loc][a];
-          if (g == 0) {
-            if (b2 >= a2 && v != (real)0) stencil_atomic(A + row * 4 + (b2 - a2), v);
-          } else if (v != (real)0) {
-            stencil_atomic(A + (int64_t)(7 * g - 3) * m + row * 7 + (b2 - a2 + 3), v);
-          }
-        }
-      }
-    }
+    if (valid && A) half_pair_loop<real, D, 1>(lane, npair, s_pair, s_val[loc], s_idx[loc], wac, 1, A, G.m);
     __syncthreads();
   }
   scatter_stats_pass<real, D>(G, x, y, wb, noise, n, stats, s_red);
@@ -514,120 +361,105 @@ static AbsorbArgs<real> absorb_args(const real* x, const real* y, const real* wa
   a.b = b; a.A = A; a.half = half; a.stats = stats; a.err = err;
   return a;
 }
+// cnt and the carry, as the entry points that take them list them
+template <typename real>
+static void absorb_carry(AbsorbArgs<real>& a, real* cnt, const real* u, real* res, real* mean_out = nullptr) {
+  a.cnt = cnt; a.u = u; a.res = res; a.mean_out = mean_out;
+}
+// the zero regions and the guard of a streaming step
+template <typename real>
+static void absorb_step(AbsorbArgs<real>& a, void* z1, int64_t n1, void* z2, int64_t n2, const void* guard, int64_t guard_expect) {
+  a.z1 = z1; a.n1_bytes = n1; a.z2 = z2; a.n2_bytes = n2; a.guard = guard; a.guard_expect = guard_expect;
+}
 // the public record (wiski_absorb_args, include/wiski.h) as the typed one
 template <typename real>
 static AbsorbArgs<real> absorb_args(const wiski_absorb_args& p) {
   AbsorbArgs<real> a = absorb_args((const real*)p.d_x, (const real*)p.d_y, (const real*)p.d_wa, (const real*)p.d_wb, (const real*)p.d_noise, p.n, (real*)p.d_b,
                                    (real*)p.d_A, p.half != 0, p.d_stats, p.d_err);
-  a.cnt = (real*)p.d_cnt; a.u = (const real*)p.d_u; a.res = (real*)p.d_res; a.mean_out = (real*)p.d_mean_out;
-  a.z1 = p.z1; a.n1_bytes = p.n1_bytes; a.z2 = p.z2; a.n2_bytes = p.n2_bytes; a.guard = p.d_guard; a.guard_expect = p.guard_expect;
+  absorb_carry(a, (real*)p.d_cnt, (const real*)p.d_u, (real*)p.d_res, (real*)p.d_mean_out);
+  absorb_step(a, p.z1, p.n1_bytes, p.z2, p.n2_bytes, p.d_guard, p.guard_expect);
   a.bin = p.d_bin; a.bin_bytes = p.bin_bytes;
   if (p.g_hi > 0) { a.g_lo = p.g_lo; a.g_hi = p.g_hi; }
   a.nout = p.nout; a.bt.y_stride = p.y_stride; a.bt.w_stride = p.w_stride; a.bt.A_stride = p.A_stride;
   a.channels = p.channels;
   return a;
 }
+
+// The bodies of the extern "C" entry points below (include/wiski.h documents each), once for both scalar types.
+template <typename real>
+static int entry_absorb(const wiski_grid* g, const wiski_absorb_args* p, void* s) { return p ? absorb(g, absorb_args<real>(*p), s) : WISKI_E_BADARG; }
+template <typename real>
+static int entry_grad(const wiski_grid* g, const real* x, const real* y, const real* wa, const real* wb, const real* noise, int64_t n, real* b, real* A_half, real* cnt, const real* u, real* res, real* mean_out, double* stats, int32_t* err, void* s) {
+  AbsorbArgs<real> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
+  absorb_carry(a, cnt, u, res, mean_out);
+  a.channels = g ? g->d + 1 : 0;
+  return absorb(g, a, s);
+}
+template <typename real>
+static int entry_robust(const wiski_grid* g, AbsorbArgs<real> a, const real* inv_scale, real huber_c, real* omega_out, void* s) {
+  a.inv_scale = inv_scale; a.huber_c = huber_c; a.omega_out = omega_out;
+  return inv_scale ? absorb(g, a, s) : WISKI_E_BADARG;
+}
+template <typename real>
+static int entry_scatter_robust(const wiski_grid* g, const real* x, const real* y, const real* wa, const real* wb, const real* noise, int64_t n, real* b, real* A_half, real* cnt, const real* u, real* res, real* mean_out, double* stats, int32_t* err, const real* inv_scale, real huber_c, real* omega_out, void* s) {
+  AbsorbArgs<real> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
+  absorb_carry(a, cnt, u, res, mean_out);
+  return entry_robust(g, a, inv_scale, huber_c, omega_out, s);
+}
+template <typename real>
+static int entry_absorb_robust(const wiski_grid* g, const wiski_absorb_args* p, const real* inv_scale, real huber_c, real* omega_out, void* s) {
+  return p ? entry_robust(g, absorb_args<real>(*p), inv_scale, huber_c, omega_out, s) : WISKI_E_BADARG;
+}
+template <typename real>
+static int entry_plain(const wiski_grid* g, const real* x, const real* y, const real* wa, const real* wb, const real* noise, int64_t n, real* b, real* A, bool half, double* stats, int32_t* err, void* s) {
+  return absorb(g, absorb_args(x, y, wa, wb, noise, n, b, A, half, stats, err), s);
+}
+template <typename real>
+static int entry_cnt(const wiski_grid* g, const real* x, const real* y, const real* wa, const real* wb, const real* noise, int64_t n, real* b, real* A, int32_t half, real* cnt, const real* u, real* res, double* stats, int32_t* err, void* s) {
+  AbsorbArgs<real> a = absorb_args(x, y, wa, wb, noise, n, b, A, half != 0, stats, err);
+  absorb_carry(a, cnt, u, res);
+  return absorb(g, a, s);
+}
+// the streaming step; `bin`: its owner workspace (plain step), [g_lo, g_hi): its stencil shard (sharded step)
+template <typename real>
+static int entry_step(const wiski_grid* g, const real* x, const real* y, const real* wa, const real* wb, const real* noise, int64_t n, real* b, real* A_half, real* cnt, const real* u, real* res, real* mean_out, double* stats, int32_t* err, void* z1, int64_t n1, void* z2, int64_t n2, const void* guard, int64_t guard_expect, void* bin, int64_t bin_bytes, int32_t g_lo, int32_t g_hi, void* s) {
+  AbsorbArgs<real> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
+  absorb_carry(a, cnt, u, res, mean_out);
+  absorb_step(a, z1, n1, z2, n2, guard, guard_expect);
+  a.bin = bin; a.bin_bytes = bin_bytes;
+  a.g_lo = g_lo; a.g_hi = g_hi;
+  return absorb(g, a, s);
+}
+template <typename real>
+static int entry_multi(const wiski_grid* g, const real* x, const real* y, const real* wa, const real* wb, const real* noise, int64_t n, int32_t nout, int64_t y_stride, int64_t w_stride, real* b, real* A_half, int64_t A_stride, real* cnt, const real* u, real* res, double* stats, int32_t* err, void* s) {
+  AbsorbArgs<real> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
+  absorb_carry(a, cnt, u, res);
+  a.nout = nout; a.bt.y_stride = y_stride; a.bt.w_stride = w_stride; a.bt.A_stride = A_stride;
+  return absorb(g, a, s);
+}
+constexpr int32_t G_ALL = 1 << 30;                     // AbsorbArgs::g_hi of an unsharded absorb
+
 extern "C" {
-int wiski_absorb_f32(const wiski_grid* g, const wiski_absorb_args* p, void* s) { return p ? absorb(g, absorb_args<float>(*p), s) : WISKI_E_BADARG; }
-int wiski_absorb_f64(const wiski_grid* g, const wiski_absorb_args* p, void* s) { return p ? absorb(g, absorb_args<double>(*p), s) : WISKI_E_BADARG; }
-int wiski_scatter_stats_grad_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, void* s) {
-  AbsorbArgs<float> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
-  a.cnt = cnt; a.u = u; a.res = res; a.mean_out = mean_out;
-  a.channels = g ? g->d + 1 : 0;
-  return absorb(g, a, s);
-}
-int wiski_scatter_stats_grad_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, void* s) {
-  AbsorbArgs<double> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
-  a.cnt = cnt; a.u = u; a.res = res; a.mean_out = mean_out;
-  a.channels = g ? g->d + 1 : 0;
-  return absorb(g, a, s);
-}
-int wiski_scatter_stats_robust_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, const float* inv_scale, float huber_c, float* omega_out, void* s) {
-  AbsorbArgs<float> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
-  a.cnt = cnt; a.u = u; a.res = res; a.mean_out = mean_out;
-  a.inv_scale = inv_scale; a.huber_c = huber_c; a.omega_out = omega_out;
-  return inv_scale ? absorb(g, a, s) : WISKI_E_BADARG;
-}
-int wiski_scatter_stats_robust_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, const double* inv_scale, double huber_c, double* omega_out, void* s) {
-  AbsorbArgs<double> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
-  a.cnt = cnt; a.u = u; a.res = res; a.mean_out = mean_out;
-  a.inv_scale = inv_scale; a.huber_c = huber_c; a.omega_out = omega_out;
-  return inv_scale ? absorb(g, a, s) : WISKI_E_BADARG;
-}
-int wiski_absorb_robust_f32(const wiski_grid* g, const wiski_absorb_args* p, const float* inv_scale, float huber_c, float* omega_out, void* s) {
-  if (!p || !inv_scale) return WISKI_E_BADARG;
-  AbsorbArgs<float> a = absorb_args<float>(*p);
-  a.inv_scale = inv_scale; a.huber_c = huber_c; a.omega_out = omega_out;
-  return absorb(g, a, s);
-}
-int wiski_absorb_robust_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* inv_scale, double huber_c, double* omega_out, void* s) {
-  if (!p || !inv_scale) return WISKI_E_BADARG;
-  AbsorbArgs<double> a = absorb_args<double>(*p);
-  a.inv_scale = inv_scale; a.huber_c = huber_c; a.omega_out = omega_out;
-  return absorb(g, a, s);
-}
-int wiski_scatter_stats_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A, double* stats, int32_t* err, void* s) {
-  return absorb(g, absorb_args(x, y, wa, wb, noise, n, b, A, false, stats, err), s);
-}
-int wiski_scatter_stats_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A, double* stats, int32_t* err, void* s) {
-  return absorb(g, absorb_args(x, y, wa, wb, noise, n, b, A, false, stats, err), s);
-}
-int wiski_scatter_stats_sym_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, double* stats, int32_t* err, void* s) {
-  return absorb(g, absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err), s);
-}
-int wiski_scatter_stats_sym_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* stats, int32_t* err, void* s) {
-  return absorb(g, absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err), s);
-}
-int wiski_scatter_stats_cnt_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A, int32_t half, float* cnt, const float* u, float* res, double* stats, int32_t* err, void* s) {
-  AbsorbArgs<float> a = absorb_args(x, y, wa, wb, noise, n, b, A, half != 0, stats, err);
-  a.cnt = cnt; a.u = u; a.res = res;
-  return absorb(g, a, s);
-}
-int wiski_scatter_stats_cnt_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A, int32_t half, double* cnt, const double* u, double* res, double* stats, int32_t* err, void* s) {
-  AbsorbArgs<double> a = absorb_args(x, y, wa, wb, noise, n, b, A, half != 0, stats, err);
-  a.cnt = cnt; a.u = u; a.res = res;
-  return absorb(g, a, s);
-}
-int wiski_scatter_stats_step_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, void* z1, int64_t n1, void* z2, int64_t n2, const void* guard, int64_t guard_expect, void* bin, int64_t bin_bytes, void* s) {
-  AbsorbArgs<float> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
-  a.cnt = cnt; a.u = u; a.res = res; a.mean_out = mean_out;
-  a.z1 = z1; a.n1_bytes = n1; a.z2 = z2; a.n2_bytes = n2; a.guard = guard; a.guard_expect = guard_expect;
-  a.bin = bin; a.bin_bytes = bin_bytes;
-  return absorb(g, a, s);
-}
-int wiski_scatter_stats_step_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, void* z1, int64_t n1, void* z2, int64_t n2, const void* guard, int64_t guard_expect, void* bin, int64_t bin_bytes, void* s) {
-  AbsorbArgs<double> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
-  a.cnt = cnt; a.u = u; a.res = res; a.mean_out = mean_out;
-  a.z1 = z1; a.n1_bytes = n1; a.z2 = z2; a.n2_bytes = n2; a.guard = guard; a.guard_expect = guard_expect;
-  a.bin = bin; a.bin_bytes = bin_bytes;
-  return absorb(g, a, s);
-}
-int wiski_scatter_stats_step_sharded_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, void* z1, int64_t n1, void* z2, int64_t n2, const void* guard, int64_t guard_expect, int32_t g_lo, int32_t g_hi, void* s) {
-  AbsorbArgs<float> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
-  a.cnt = cnt; a.u = u; a.res = res; a.mean_out = mean_out;
-  a.z1 = z1; a.n1_bytes = n1; a.z2 = z2; a.n2_bytes = n2; a.guard = guard; a.guard_expect = guard_expect;
-  a.g_lo = g_lo; a.g_hi = g_hi;
-  return absorb(g, a, s);
-}
-int wiski_scatter_stats_step_sharded_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, void* z1, int64_t n1, void* z2, int64_t n2, const void* guard, int64_t guard_expect, int32_t g_lo, int32_t g_hi, void* s) {
-  AbsorbArgs<double> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
-  a.cnt = cnt; a.u = u; a.res = res; a.mean_out = mean_out;
-  a.z1 = z1; a.n1_bytes = n1; a.z2 = z2; a.n2_bytes = n2; a.guard = guard; a.guard_expect = guard_expect;
-  a.g_lo = g_lo; a.g_hi = g_hi;
-  return absorb(g, a, s);
-}
-int wiski_scatter_stats_multi_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, int32_t nout, int64_t y_stride, int64_t w_stride, float* b, float* A_half, int64_t A_stride, float* cnt, const float* u, float* res, double* stats, int32_t* err, void* s) {
-  AbsorbArgs<float> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
-  a.cnt = cnt; a.u = u; a.res = res;
-  a.nout = nout; a.bt.y_stride = y_stride; a.bt.w_stride = w_stride; a.bt.A_stride = A_stride;
-  return absorb(g, a, s);
-}
-int wiski_scatter_stats_multi_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, int32_t nout, int64_t y_stride, int64_t w_stride, double* b, double* A_half, int64_t A_stride, double* cnt, const double* u, double* res, double* stats, int32_t* err, void* s) {
-  AbsorbArgs<double> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
-  a.cnt = cnt; a.u = u; a.res = res;
-  a.nout = nout; a.bt.y_stride = y_stride; a.bt.w_stride = w_stride; a.bt.A_stride = A_stride;
-  return absorb(g, a, s);
-}
+int wiski_absorb_f32(const wiski_grid* g, const wiski_absorb_args* p, void* s) { return entry_absorb<float>(g, p, s); }
+int wiski_absorb_f64(const wiski_grid* g, const wiski_absorb_args* p, void* s) { return entry_absorb<double>(g, p, s); }
+int wiski_scatter_stats_grad_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, void* s) { return entry_grad(g, x, y, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, s); }
+int wiski_scatter_stats_grad_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, void* s) { return entry_grad(g, x, y, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, s); }
+int wiski_scatter_stats_robust_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, const float* inv_scale, float huber_c, float* omega_out, void* s) { return entry_scatter_robust(g, x, y, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, inv_scale, huber_c, omega_out, s); }
+int wiski_scatter_stats_robust_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, const double* inv_scale, double huber_c, double* omega_out, void* s) { return entry_scatter_robust(g, x, y, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, inv_scale, huber_c, omega_out, s); }
+int wiski_absorb_robust_f32(const wiski_grid* g, const wiski_absorb_args* p, const float* inv_scale, float huber_c, float* omega_out, void* s) { return entry_absorb_robust(g, p, inv_scale, huber_c, omega_out, s); }
+int wiski_absorb_robust_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* inv_scale, double huber_c, double* omega_out, void* s) { return entry_absorb_robust(g, p, inv_scale, huber_c, omega_out, s); }
+int wiski_scatter_stats_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A, double* stats, int32_t* err, void* s) { return entry_plain(g, x, y, wa, wb, noise, n, b, A, false, stats, err, s); }
+int wiski_scatter_stats_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A, double* stats, int32_t* err, void* s) { return entry_plain(g, x, y, wa, wb, noise, n, b, A, false, stats, err, s); }
+int wiski_scatter_stats_sym_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, double* stats, int32_t* err, void* s) { return entry_plain(g, x, y, wa, wb, noise, n, b, A_half, true, stats, err, s); }
+int wiski_scatter_stats_sym_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* stats, int32_t* err, void* s) { return entry_plain(g, x, y, wa, wb, noise, n, b, A_half, true, stats, err, s); }
+int wiski_scatter_stats_cnt_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A, int32_t half, float* cnt, const float* u, float* res, double* stats, int32_t* err, void* s) { return entry_cnt(g, x, y, wa, wb, noise, n, b, A, half, cnt, u, res, stats, err, s); }
+int wiski_scatter_stats_cnt_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A, int32_t half, double* cnt, const double* u, double* res, double* stats, int32_t* err, void* s) { return entry_cnt(g, x, y, wa, wb, noise, n, b, A, half, cnt, u, res, stats, err, s); }
+int wiski_scatter_stats_step_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, void* z1, int64_t n1, void* z2, int64_t n2, const void* guard, int64_t guard_expect, void* bin, int64_t bin_bytes, void* s) { return entry_step(g, x, y, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, z1, n1, z2, n2, guard, guard_expect, bin, bin_bytes, 0, G_ALL, s); }
+int wiski_scatter_stats_step_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, void* z1, int64_t n1, void* z2, int64_t n2, const void* guard, int64_t guard_expect, void* bin, int64_t bin_bytes, void* s) { return entry_step(g, x, y, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, z1, n1, z2, n2, guard, guard_expect, bin, bin_bytes, 0, G_ALL, s); }
+int wiski_scatter_stats_step_sharded_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, void* z1, int64_t n1, void* z2, int64_t n2, const void* guard, int64_t guard_expect, int32_t g_lo, int32_t g_hi, void* s) { return entry_step(g, x, y, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, z1, n1, z2, n2, guard, guard_expect, (void*)nullptr, 0, g_lo, g_hi, s); }
+int wiski_scatter_stats_step_sharded_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, void* z1, int64_t n1, void* z2, int64_t n2, const void* guard, int64_t guard_expect, int32_t g_lo, int32_t g_hi, void* s) { return entry_step(g, x, y, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, z1, n1, z2, n2, guard, guard_expect, (void*)nullptr, 0, g_lo, g_hi, s); }
+int wiski_scatter_stats_multi_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, int32_t nout, int64_t y_stride, int64_t w_stride, float* b, float* A_half, int64_t A_stride, float* cnt, const float* u, float* res, double* stats, int32_t* err, void* s) { return entry_multi(g, x, y, wa, wb, noise, n, nout, y_stride, w_stride, b, A_half, A_stride, cnt, u, res, stats, err, s); }
+int wiski_scatter_stats_multi_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, int32_t nout, int64_t y_stride, int64_t w_stride, double* b, double* A_half, int64_t A_stride, double* cnt, const double* u, double* res, double* stats, int32_t* err, void* s) { return entry_multi(g, x, y, wa, wb, noise, n, nout, y_stride, w_stride, b, A_half, A_stride, cnt, u, res, stats, err, s); }
 int64_t wiski_scatter_bin_bytes(const wiski_grid* g, int64_t n, int32_t elem_size) {
   if (!g || g->d != 3 || n < 0 || (elem_size != 4 && elem_size != 8)) return -1;
   return elem_size == 4 ? owner_work_bytes<float>(*g, n) : owner_work_bytes<double>(*g, n);

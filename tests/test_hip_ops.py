@@ -391,6 +391,126 @@ def test_scatter_stats(d, g, tdt, ndt, tol):
     assert np.allclose(stats.cpu().numpy(), B2.c_ld, rtol=max(tol, 1e-12) * 10)
 
 
+SWEEP_GRIDS = {1: [8], 2: [5, 7], 3: [6, 5, 4], 4: [5, 4, 4, 4]}
+SWEEP_N = 37                                                      # not a multiple of the 4 points per block
+
+
+def _sweep_case(d, tdt, outside=False):
+    """Points, weights and a grid vector u for the half-stencil point sweep; with `outside`, point 5 lies outside the grid."""
+    from online_gp_amd import grid_ops
+
+    rng = np.random.default_rng(40 + d)
+    grid = grid_ops.GridSpec([[-1.0, 1.0]] * d, SWEEP_GRIDS[d])
+    mk = lambda a: torch.as_tensor(a, device="cuda", dtype=tdt)
+    X = rng.uniform(-1, 1, (SWEEP_N, d))
+    if outside:
+        X[5] = 3.0
+    noise = mk(rng.uniform(0.5, 2.0, SWEEP_N))
+    return grid, mk(X), mk(rng.standard_normal(SWEEP_N)), 1.0 / noise, noise, mk(rng.standard_normal(grid.m))
+
+
+def _sweep_buffers(grid, tdt, n=SWEEP_N):
+    z = lambda *s: torch.zeros(s, device="cuda", dtype=tdt)
+    return dict(A=z((grid.R + 1) // 2 * grid.m), b=z(grid.m), cnt=z(grid.m), res=z(grid.m), stats=torch.zeros(2, device="cuda", dtype=torch.float64),
+                mean=torch.full((n,), float("nan"), device="cuda", dtype=tdt))
+
+
+def _plain_absorb(grid, X, y, w, noise, u, buf, tdt, g_lo=0, g_hi=0):
+    """wiski_absorb with the full argument record: the plain half-stencil form with cnt, the carry and mean_out; g_hi > 0 shards.
+    Returns the error word."""
+    import ctypes
+
+    from online_gp_amd import _hip, grid_ops
+
+    p = lambda t: _hip.dptr(t).value
+    err = grid_ops.new_err_flag("cuda")
+    a = _hip.wiski_absorb_args(d_x=p(X), d_y=p(y), d_wa=p(w), d_wb=p(w), d_noise=p(noise), n=X.shape[0], d_b=p(buf["b"]), d_A=p(buf["A"]), half=1,
+                               d_cnt=p(buf["cnt"]), d_stats=p(buf["stats"]), d_err=p(err), d_u=p(u), d_res=p(buf["res"]), d_mean_out=p(buf["mean"]),
+                               g_lo=g_lo, g_hi=g_hi, nout=1)
+    assert _hip.fn("wiski_absorb", tdt)(grid.ref, ctypes.byref(a), _hip.stream_ptr(X.device)) == 0
+    return int(err.item())
+
+
+def _close(got, ref, tol):
+    return float((got.double() - ref.double()).abs().max()) <= tol * float(ref.double().abs().max())
+
+
+@pytest.mark.parametrize("d", [1, 2, 3, 4])
+@pytest.mark.parametrize("tdt,ndt,tol", DTYPES)
+def test_absorb_shards_tile_the_half_stencil(d, tdt, ndt, tol):
+    """wiski_absorb once per shard of a partition of the stencil groups [0, G), G = (7^(d-1) + 1) / 2, into three uneven ranges (one
+    starts at 0, one holds a single group; d = 1 has one group): a shard writes A only inside its half_stencil_group_slices, there
+    it equals the unsharded A, and b, cnt, res, the statistics, mean_out and the error word are those of the unsharded absorb."""
+    from online_gp_amd import grid_ops
+
+    grid, X, y, w, noise, u = _sweep_case(d, tdt)
+    G = (7 ** (d - 1) + 1) // 2
+    k = G // 3 + 1
+    parts = [(0, k), (k, k + 1), (k + 1, G)] if d > 1 else [(0, 1)]
+    assert parts[0][0] == 0 and parts[-1][1] == G and all(a[1] == b[0] for a, b in zip(parts, parts[1:])) and all(hi > lo for lo, hi in parts)
+    whole = _sweep_buffers(grid, tdt)
+    assert _plain_absorb(grid, X, y, w, noise, u, whole, tdt) == 0
+    amax = float(whole["A"].double().abs().max())
+    covered = torch.zeros(whole["A"].numel(), dtype=torch.bool, device="cuda")
+    for lo, hi in parts:
+        part = _sweep_buffers(grid, tdt)
+        assert _plain_absorb(grid, X, y, w, noise, u, part, tdt, lo, hi) == 0
+        inside = torch.zeros_like(covered)
+        for s, e in grid_ops.half_stencil_group_slices(grid, lo, hi):
+            inside[s:e] = True
+        assert not bool((covered & inside).any())
+        covered |= inside
+        assert not bool((part["A"][~inside] != 0).any()), (lo, hi)
+        assert float((part["A"][inside].double() - whole["A"][inside].double()).abs().max()) <= tol * amax, (lo, hi)
+        for key in ("b", "cnt", "res", "stats", "mean"):
+            assert _close(part[key], whole[key], tol), (key, lo, hi)
+    assert bool(covered.all())
+
+
+@pytest.mark.parametrize("d", [2, 4])
+@pytest.mark.parametrize("tdt,ndt,tol", DTYPES)
+def test_three_absorb_forms_agree_where_they_overlap(d, tdt, ndt, tol):
+    """The same points, weights and u through the plain form, the robust form with inv_scale = 0 (every omega = 1) and the derivative
+    form with only channel 0 present (the others wa = wb = 0, noise = 1): the same A, b, cnt, res, statistics and mean_out.  Point 5
+    lies outside the grid: err = 3 in each, omega_out = 0, mean_out = 0, and the sums are those of the batch without it."""
+    from online_gp_amd import grid_ops
+
+    grid, X, y, w, noise, u = _sweep_case(d, tdt, outside=True)
+    C, n = d + 1, SWEEP_N
+    plain = _sweep_buffers(grid, tdt)
+    assert _plain_absorb(grid, X, y, w, noise, u, plain, tdt) == 3
+
+    robust = _sweep_buffers(grid, tdt)
+    err = grid_ops.new_err_flag("cuda")
+    omega = grid_ops.scatter_stats_robust(grid, X, y, w, w, noise, torch.zeros_like(y), 1.5, robust["b"], robust["A"], robust["cnt"], robust["stats"], err, u,
+                                          res=robust["res"], mean_out=robust["mean"])
+    assert int(err.item()) == 3
+    expect = torch.ones_like(y)
+    expect[5] = 0
+    assert torch.equal(omega, expect)
+
+    grad = _sweep_buffers(grid, tdt)
+    col0 = lambda v, fill: torch.cat([v[:, None], torch.full((n, d), fill, device="cuda", dtype=tdt)], dim=1).contiguous()
+    mean_c = torch.full((n, C), float("nan"), device="cuda", dtype=tdt)
+    err = grid_ops.new_err_flag("cuda")
+    grid_ops.scatter_stats_grad(grid, X, col0(y, 0.0), col0(w, 0.0), col0(w, 0.0), col0(noise, 1.0), grad["b"], grad["A"], grad["cnt"], grad["stats"], err, u=u,
+                                res=grad["res"], mean_out=mean_c)
+    assert int(err.item()) == 3
+    grad["mean"] = mean_c[:, 0].contiguous()
+    assert float(mean_c[5].abs().max()) == 0.0
+
+    keep = torch.arange(n, device="cuda") != 5
+    without = _sweep_buffers(grid, tdt, n - 1)
+    assert _plain_absorb(grid, X[keep].contiguous(), y[keep].contiguous(), w[keep].contiguous(), noise[keep].contiguous(), u, without, tdt) == 0
+    assert float(plain["mean"][5]) == 0.0 and float(robust["mean"][5]) == 0.0
+    for key in ("A", "b", "cnt", "res", "stats"):
+        assert _close(without[key], plain[key], tol), key
+    assert _close(without["mean"], plain["mean"][keep], tol)
+    for name, form in (("robust", robust), ("grad", grad)):
+        for key in ("A", "b", "cnt", "res", "stats", "mean"):
+            assert _close(form[key], plain[key], tol), (name, key)
+
+
 @pytest.mark.parametrize("half", [False, True])
 @pytest.mark.parametrize("d,g", CASES + [(2, 9), (3, 16)])
 @pytest.mark.parametrize("tdt,ndt,tol", DTYPES)
