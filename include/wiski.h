@@ -157,6 +157,24 @@ int wiski_stencil_expand_add_f64(const wiski_grid* grid, double* d_A_half, doubl
 int wiski_wt_columns_f32(const wiski_grid* grid, const float* d_x, int64_t n, float* d_out, int32_t* d_err, void* stream);
 int wiski_wt_columns_f64(const wiski_grid* grid, const double* d_x, int64_t n, double* d_out, int32_t* d_err, void* stream);
 
+/* Jet rows J(x) = [w(x); d_1 w(x); ...; d_d w(x)], C = d + 1 channels (csrc/jet_rows.h): channel 0 is the value row, channel 1 + q has
+ * dim q's four weights replaced by k'(s) / h_q and is identically zero where dim q's cell is a one-hot boundary cell (as
+ * wiski_gather_grad).  A point outside the grid has all C rows zero and sets bit 0 of *d_err (as wiski_gather).  All three: n = 0 is a
+ * no-op; a null pointer, k < 1, rows_per_point < 0 or ldm < m is WISKI_E_BADARG without a launch.
+ * wiski_jet_quadform: d_out[p][c][c'] = sum_ab J_c(x_p)[a] d_M[idx_a][idx_b] J_c'(x_p)[b] for a row-major d_M [m][ldm] (ldm >= m), d_out
+ *   [n][C][C].  Reads the 4^d x 4^d sub-block of the point's taps only; fp64 accumulation; the lower triangle is a copy of the upper. */
+int wiski_jet_quadform_f32(const wiski_grid* grid, const float* d_x, int64_t n, const float* d_M, int64_t ldm, float* d_out, int32_t* d_err, void* stream);
+int wiski_jet_quadform_f64(const wiski_grid* grid, const double* d_x, int64_t n, const double* d_M, int64_t ldm, double* d_out, int32_t* d_err, void* stream);
+/* wiski_wt_columns_jet: row p C + c of the caller-zeroed d_out [n C][m] receives J_c(x_p) (plain stores); row p C is the column that
+ *   wiski_wt_columns writes for x_p, bit for bit. */
+int wiski_wt_columns_jet_f32(const wiski_grid* grid, const float* d_x, int64_t n, float* d_out, int32_t* d_err, void* stream);
+int wiski_wt_columns_jet_f64(const wiski_grid* grid, const double* d_x, int64_t n, double* d_out, int32_t* d_err, void* stream);
+/* wiski_gather_jet: rows_per_point = 0: d_V [k][m] is shared by all points, d_out[p][j][c] = J_c(x_p) . d_V[j], d_out [n][k][C].
+ *   rows_per_point = B >= 1: d_V [n B][m], d_out[p][j][c] = J_c(x_p) . d_V[p B + j], d_out [n][B][C] (k is not used beyond k >= 1).
+ *   fp64 accumulation. */
+int wiski_gather_jet_f32(const wiski_grid* grid, const float* d_x, int64_t n, const float* d_V, int32_t k, int32_t rows_per_point, float* d_out, int32_t* d_err, void* stream);
+int wiski_gather_jet_f64(const wiski_grid* grid, const double* d_x, int64_t n, const double* d_V, int32_t k, int32_t rows_per_point, double* d_out, int32_t* d_err, void* stream);
+
 /* replaces WtW._matmul (URLT:47-48) on the stencil form:
  * d_out[c] = beta * d_add[c] + A_st . d_V[c]   (d_add may be NULL). */
 int wiski_stencil_spmv_f32(const wiski_grid* grid, const float* d_A_st, const float* d_V, int32_t k, const float* d_add, float beta, float* d_out, void* stream);

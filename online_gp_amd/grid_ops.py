@@ -608,6 +608,48 @@ def wt_columns(grid, x, err):
     return out
 
 
+def wt_columns_jet(grid, x, err):
+    """The jet rows J_c(x_p) as dense columns: [n C, m], row p C + c (C = d + 1; ``wiski_wt_columns_jet``)."""
+    x = _x2d(x, grid)
+    out = torch.zeros((x.shape[0] * (grid.d + 1), grid.m), dtype=x.dtype, device=x.device)
+    rc = _hip.fn("wiski_wt_columns_jet", x.dtype)(grid.ref, _hip.dptr(x), ctypes.c_int64(x.shape[0]), _hip.dptr(out), _hip.dptr(err),
+                                                  _hip.stream_ptr(x.device))
+    _hip.check(rc, "wiski_wt_columns_jet")
+    return out
+
+
+def jet_quadform(grid, x, M, err):
+    """out[p, c, c'] = J_c(x_p)^T M J_c'(x_p) for a dense row-major M [m, >= m] (leading dimension ``M.stride(0)``): [n, C, C],
+    exactly symmetric (``wiski_jet_quadform``)."""
+    x = _x2d(x, grid)
+    assert M.dim() == 2 and M.shape[0] == grid.m and M.shape[1] >= grid.m and M.stride(1) == 1 and M.dtype == x.dtype
+    C = grid.d + 1
+    out = torch.empty((x.shape[0], C, C), dtype=x.dtype, device=x.device)
+    if not M.is_cuda:
+        raise _hip.WiskiError("online_gp_amd ops need ROCm device tensors (no CPU fallback)")
+    rc = _hip.fn("wiski_jet_quadform", x.dtype)(grid.ref, _hip.dptr(x), ctypes.c_int64(x.shape[0]), ctypes.c_void_p(M.data_ptr()),
+                                                ctypes.c_int64(M.stride(0)), _hip.dptr(out), _hip.dptr(err), _hip.stream_ptr(x.device))
+    _hip.check(rc, "wiski_jet_quadform")
+    return out
+
+
+def gather_jet(grid, x, V, err, rows_per_point=0):
+    """Value and gradient gather in one launch (``wiski_gather_jet``): out[p, j, c] = J_c(x_p) . V[j] for V [k, m] shared by all
+    points (rows_per_point = 0; [n, k, C]), or J_c(x_p) . V[p B + j] for V [n B, m] (rows_per_point = B; [n, B, C])."""
+    x = _x2d(x, grid)
+    V = V.contiguous()
+    if V.dim() == 1:
+        V = V[None]
+    n, B = x.shape[0], int(rows_per_point)
+    assert V.shape[1] == grid.m and V.dtype == x.dtype and (B == 0 or V.shape[0] == n * B)
+    k = B if B > 0 else V.shape[0]
+    out = torch.empty((n, k, grid.d + 1), dtype=x.dtype, device=x.device)
+    rc = _hip.fn("wiski_gather_jet", x.dtype)(grid.ref, _hip.dptr(x), ctypes.c_int64(n), _hip.dptr(V), ctypes.c_int32(max(k, 1)), ctypes.c_int32(B),
+                                              _hip.dptr(out), _hip.dptr(err), _hip.stream_ptr(x.device))
+    _hip.check(rc, "wiski_gather_jet")
+    return out
+
+
 def is_half_stencil(grid, A_st):
     """True for the symmetric half-stencil layout [(R+1)/2, m], False for the full [R, m] one."""
     rows = A_st.shape[-2]

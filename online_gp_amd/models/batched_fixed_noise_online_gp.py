@@ -1025,6 +1025,35 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             cov = BatchOperator(covs)
         return MultivariateNormal(mean_o, cov)
 
+    def posterior_jet(self, X, joint=False):
+        """Joint Gaussian posterior of ``f`` and ``grad f`` at X [n, d]: a :class:`~online_gp_amd.lazy.jet.JetPosterior`
+        with ``mean`` [n, d + 1] and ``covariance`` [n, d + 1, d + 1] -- or, with ``joint``, the [n (d + 1), n (d + 1)] covariance
+        between all points, point-major.  Channel 0 is the value (its variance is that of ``posterior(X)``), channel 1 + q the
+        partial derivative in dim q, which is identically zero in a boundary cell of dim q.  Answered through the prediction cache in
+        every regime (a model inside a stencil shard leaves it, as for every solve).  Outputs are detached: the cubic interpolant is
+        C^1 only, so a derivative of the jet with respect to X jumps at the cell faces.  One output, unbatched X."""
+        from ..lazy.jet import JetCovariance, JetPosterior
+
+        if self.num_outputs > 1:
+            raise NotImplementedError("posterior_jet is implemented for a single output")
+        if X.dim() > 2:
+            raise NotImplementedError("posterior_jet takes unbatched points [n, d]")
+        grid = self._grid
+        Xf = X.detach().reshape(-1, grid.d).to(self._device, self._dtype).contiguous()
+        with torch.no_grad():
+            pc = self.prediction_cache
+            mean = grid_ops.gather_jet(grid, Xf, pc["pred_mean"][0, :, 0], self._err)[:, 0, :]
+            if settings.deferred_bounds_check.off():
+                flag = grid_ops.read_flag(self._err)
+                if flag:
+                    self._raise_out_of_bounds(flag)
+            sigma2 = self._hyper()[0][1] if self.has_learnable_noise else 1.0
+            op = JetCovariance(pc["pred_cov"], Xf, sigma2, self._err, chunk=settings.variance_chunk.value())
+            cov = op.joint() if joint else op.blocks()
+        post = JetPosterior(mean, cov, joint)
+        post.cg_iters = op.cg_iters
+        return post
+
     # -------------------------------------------------------------- updates --
     def condition_on_observations(self, X, Y, noise=None, inplace=False, _decay=True, *, grad_Y=None, grad_noise=None, grad_mask=None):
         """a7, :258-285.  inplace: the statistics buffers are updated where they

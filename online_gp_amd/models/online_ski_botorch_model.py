@@ -72,6 +72,11 @@ class OnlineSKIBotorchModel(FixedNoiseOnlineSKIGP):
         noise = self.likelihood.noise.mean().detach().expand(Y_fantasized.shape[1:])
         return self.condition_on_observations(X=X, Y=Y_fantasized, noise=noise)
 
+    def posterior_jet(self, X, joint=False):
+        """Joint posterior of f and its gradient at X [n, d] (``FixedNoiseOnlineSKIGP.posterior_jet``)."""
+        self.eval()
+        return super().posterior_jet(X.to(self._dtype), joint=joint)
+
     def posterior(self, X, observation_noise=False, **kwargs):
         self.eval()
         X = X.to(self._dtype)

@@ -62,6 +62,17 @@ class OnlineSKIRegression(StreamingSKIWrapper):
         sigma2 = self.gp.likelihood.second_noise.detach().reshape(1, -1)
         return mean.reshape(-1, self.target_dim), var.reshape(-1, self.target_dim) + sigma2
 
+    def predict_gradient(self, inputs):
+        """(mean [n, d], covariance [n, d, d]) of the gradient of the latent function at the inputs (``posterior_jet`` of the GP).
+        Only with the ``Identity`` stem: behind a learned stem the GP's gradient is with respect to the features, not the inputs."""
+        from .stems import Identity
+
+        if not isinstance(self.stem, Identity):
+            raise NotImplementedError("predict_gradient needs the Identity stem (the GP differentiates with respect to its own inputs)")
+        self._ensure_eval()
+        jet = self.gp.posterior_jet(self._as_rows(inputs))
+        return jet.grad_mean, jet.grad_covariance
+
     def evaluate(self, inputs, targets):
         """(rmse, nll): means over batches of 1024 of the per-batch RMSE and mean Gaussian NLL; one host sync."""
         inputs = self._as_rows(inputs)
