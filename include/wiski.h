@@ -363,6 +363,8 @@ typedef struct wiski_stream_args_f32 {
   void* d_bin; int64_t bin_bytes;                 /* optional binning workspace of the absorb (wiski_scatter_bin_bytes), or NULL / 0 */
   const wiski_shard* shard;                      /* NULL, or: this replica owns a share of the half stencil (see wiski_shard) */
   const wiski_twolevel* two_level;               /* NULL, or: exact block on the dominant modes in the preconditioner (see wiski_twolevel) */
+  int32_t keep[3];                               /* eigenmodes per dimension the preconditioner transforms (the last keep[q] columns of the
+                                                  * eigen tables; on all others t = r and y = 0), or all 0: every mode.  See wiski_precond_keep_ok */
 } wiski_stream_args_f32;
 typedef struct wiski_stream_args_f64 {
   double* d_A_half; double* d_b; double* d_cnt; double* d_stats; int32_t* d_err;
@@ -372,6 +374,7 @@ typedef struct wiski_stream_args_f64 {
   void* d_bin; int64_t bin_bytes;
   const wiski_shard* shard;
   const wiski_twolevel* two_level;               /* must be NULL (the two-level block exists for the fused fp32 path only) */
+  int32_t keep[3];                               /* must be 0 (the truncated transforms exist for the fused fp32 path only) */
 } wiski_stream_args_f64;
 int wiski_stream_step_f32(const wiski_grid* grid, const wiski_stream_args_f32* args, const float* d_x, const float* d_y, const float* d_wa, const float* d_wb, const float* d_noise, int64_t q, float* d_mean_out, int32_t carry, int32_t first_check, int32_t* h_iters, double* h_relres, int32_t* h_err, void* stream, wiski_pcg_async* handle, int32_t defer, int32_t* h_resumed);
 int wiski_stream_step_f64(const wiski_grid* grid, const wiski_stream_args_f64* args, const double* d_x, const double* d_y, const double* d_wa, const double* d_wb, const double* d_noise, int64_t q, double* d_mean_out, int32_t carry, int32_t first_check, int32_t* h_iters, double* h_relres, int32_t* h_err, void* stream, wiski_pcg_async* handle, int32_t defer, int32_t* h_resumed);
@@ -462,6 +465,16 @@ int wiski_twolevel_refresh_f32(const wiski_grid* grid, const float* d_x, int64_t
  * d_y = P r, d_t = Kt^-1 P r, *d_rho (device double) += r . P r, for one m-vector d_r; d_w0 (m reals) and d_w1 (2 m reals)
  * are scratch.  two_level as above or NULL.  d = 3, every g_q <= 64, g_1 g_2 % 4 == 0. */
 int wiski_precond_apply_f32(const wiski_grid* grid, const float* d_evec, const float* d_evec2, const float* d_eval, float kscale, float shift, const float* d_r, float* d_w0, float* d_w1, float* d_y, float* d_t, double* d_rho, const wiski_twolevel* two_level, void* stream);
+/* The same application on the kept eigenmodes only: keep[q] = number of modes of dimension q (the last columns of the eigen tables:
+ * eigenvalues ascend) that are transformed; every other mode passes t = r and contributes nothing to y.  Exact to below fp32
+ * resolution when shift * lambda / (1 + shift * lambda) < 2^-30 on every dropped mode.  Each keep[q] a multiple of 4 in
+ * [4, min(g_q, 24)], the selected modes of two_level inside the box, and wiski_precond_keep_ok(grid, keep, two_level != NULL) == 1
+ * (a backward workgroup holds the whole coefficient cube twice -- 16 or 24 rows of keep[1] * keep[2] + 16 floats each -- beside its
+ * images within 144 KB of LDS: (16, 16, 16) fits, (20, 20, 20) does not);
+ * keep all 0: exactly wiski_precond_apply_f32.  wiski_stream_args_f32.keep hands the same counts to the streaming step's solve;
+ * there they are refused (WISKI_E_BADARG) with fp64, off the fused path or outside these bounds. */
+int wiski_precond_apply_keep_f32(const wiski_grid* grid, const float* d_evec, const float* d_evec2, const float* d_eval, float kscale, float shift, const float* d_r, float* d_w0, float* d_w1, float* d_y, float* d_t, double* d_rho, const wiski_twolevel* two_level, const int32_t* keep, void* stream);
+int wiski_precond_keep_ok(const wiski_grid* grid, const int32_t* keep, int32_t with_two_level);
 /* The same for k grid vectors at once (the multi-column kernels of the 64-column variance / probe solves): d_r, d_y, d_t [k][m],
  * d_w0 k m reals, d_w1 2 k m reals, d_rho [k] doubles (+=).  two_level with k > 1 needs its d_mc scratch (k <= mc_cols). */
 int wiski_precond_apply_cols_f32(const wiski_grid* grid, const float* d_evec, const float* d_evec2, const float* d_eval, float kscale, float shift, const float* d_r, int32_t k, float* d_w0, float* d_w1, float* d_y, float* d_t, double* d_rho, const wiski_twolevel* two_level, void* stream);

@@ -21,6 +21,8 @@ struct PcgArgs {
   const real* eval = nullptr;     // per-dim eigenvalues D_q >= 0, concatenated
   real shift = (real)0;           // density scale of the separable model
   const wiski_twolevel* two_level = nullptr;   // exact block on the dominant modes: fused fp32 path (d = 3, m % 4 == 0, eigen tables) only
+  int keep[3] = {0, 0, 0};        // eigenmodes per dimension the preconditioner transforms (the rest: t = r, y = 0 -- spectral_keep.h); 0: all.
+                                  // fused fp32 path, k = 1, multiples of 4 up to min(g_q, 24)
   // iterate
   real* U = nullptr;              // [k][m] solution, in place
   real* Z = nullptr;              // [k][m] its pre-image, U = Kt Z

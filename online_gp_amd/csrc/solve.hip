@@ -1968,6 +1968,14 @@ static int pcg_validate(const GridDev<real>& G, const PcgArgs<real>& a, const Pc
   if (a.mode != 2 && a.warm == 2 && !a.R) return WISKI_E_BADARG;             // the carried residual is the caller's R
   // the exact block lives in the fused fp32 slab kernels (k > 1: launch_slab checks the scratch)
   if (a.two_level && !(path.fused_cg && sizeof(real) == 4)) return WISKI_E_BADARG;
+  // kept-mode counts: all three or none, one fp32 column on the fused path, within the truncated kernels' cap and LDS budget
+  if (a.keep[0] != 0 || a.keep[1] != 0 || a.keep[2] != 0) {
+    if constexpr (sizeof(real) == 4) {
+      if (!path.fused_cg || a.k != 1 || !spectral_keep_ok(G, a.keep, a.two_level != nullptr)) return WISKI_E_BADARG;
+    } else {
+      return WISKI_E_BADARG;
+    }
+  }
   return WISKI_OK;
 }
 
@@ -2209,7 +2217,7 @@ static int pcg_iterate(const PcgPlan<real>& plan) {
       if (!fuse_upd) flush_update();
       const bool init_now = plan.init_in_fwd && it == 0;
       rc = launch_spectral_fused_cg<real>(G, a.evec, a.evec2, a.eval, a.kscale, a.shift, r, k, L.sa, L.sb, it, pending ? 1 : 0, tol2, p, pt, cpart, cnch,
-                                          czl, a.U, a.Z, S, s, init_now ? a.RHS : (const real*)nullptr, a.two_level);
+                                          czl, a.U, a.Z, S, s, init_now ? a.RHS : (const real*)nullptr, a.two_level, a.keep);
       pending = false;
       if (rc) return rc;
       rc = plan.product_wide(p, pt, (real)1, S.php(it));
@@ -2434,6 +2442,25 @@ int wiski_precond_apply_cols_f32(const wiski_grid* grid, const float* evec, cons
 }
 int wiski_precond_apply_f32(const wiski_grid* grid, const float* evec, const float* evec2, const float* eval, float kscale, float shift, const float* d_r, float* w0, float* w1, float* d_y, float* d_t, double* d_rho, const wiski_twolevel* two_level, void* stream) {
   return wiski_precond_apply_cols_f32(grid, evec, evec2, eval, kscale, shift, d_r, 1, w0, w1, d_y, d_t, d_rho, two_level, stream);
+}
+// wiski_precond_apply_f32 on the kept modes only (keep[3]; all zero: exactly wiski_precond_apply_f32); counts a solve would refuse are refused
+int wiski_precond_apply_keep_f32(const wiski_grid* grid, const float* evec, const float* evec2, const float* eval, float kscale, float shift, const float* d_r, float* w0, float* w1, float* d_y, float* d_t, double* d_rho, const wiski_twolevel* two_level, const int32_t* keep, void* stream) {
+  GridDev<float> G;
+  if (int rc = make_grid_dev<float>(grid, &G)) return rc;
+  if (!evec || !eval || !d_r || !w0 || !w1 || !d_y || !d_t || !d_rho || !keep || !spectral_fused_ok<float>(G) || G.m % 4) return WISKI_E_BADARG;
+  const int kp[3] = {keep[0], keep[1], keep[2]};
+  const bool any = kp[0] != 0 || kp[1] != 0 || kp[2] != 0;
+  if (any && !spectral_keep_ok(G, kp, two_level != nullptr)) return WISKI_E_BADARG;
+  PcgScal S{d_rho - 1, 1, nullptr};          // rho(0) = base + 1
+  return launch_spectral_fused_cg<float>(G, evec, evec2, eval, kscale, shift, const_cast<float*>(d_r), 1, w0, w1, 0, 0, 0.0, d_y, d_t, (float*)nullptr, 0, 0,
+                                         (float*)nullptr, (float*)nullptr, S, (hipStream_t)stream, (const float*)nullptr, two_level, any ? kp : (const int*)nullptr);
+}
+// 1 when a solve on `grid` accepts these kept-mode counts (cap, multiples of 4, the backward kernel's LDS budget), else 0
+int wiski_precond_keep_ok(const wiski_grid* grid, const int32_t* keep, int32_t with_two_level) {
+  GridDev<float> G;
+  if (!keep || make_grid_dev<float>(grid, &G)) return 0;
+  const int kp[3] = {keep[0], keep[1], keep[2]};
+  return spectral_fused_ok<float>(G) && G.m % 4 == 0 && spectral_keep_ok(G, kp, with_two_level != 0) ? 1 : 0;
 }
 int wiski_shard_groups(int32_t d, int32_t rank, int32_t nranks, int32_t* g_lo, int32_t* g_hi) {
   if (d < 1 || d > WISKI_MAX_DIM || nranks < 1 || rank < 0 || rank >= nranks || !g_lo || !g_hi) return WISKI_E_BADARG;

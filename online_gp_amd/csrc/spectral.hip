@@ -1509,7 +1509,11 @@ __global__ __launch_bounds__(128) void k_spec_mode0_bwd_updp(GridDev<real> G, co
   }
 }
 
+#include "spectral_keep.h"   // the truncated one-column form: k_keep_fwd / k_keep_bwd, launch_spectral_keep_cg
+
 // ------------------------------------------------------------ host side ---
+bool spectral_keep_ok(const GridDev<float>& G, const int* keep, bool two_level) { return keep_counts_ok(G, keep, two_level); }
+
 template <typename real>
 bool spectral_fused_ok(const GridDev<real>& G) {
   if (G.d != 3) return false;
@@ -1542,11 +1546,21 @@ int launch_spectral_fused(const GridDev<real>& G, const real* evec, const real* 
 // One CG iteration's preconditioner + vector updates in three launches: mode-0 forward (fp32: with the previous
 // iteration's u / z / r update folded into its tile load when `apply`), slab (+ rho), mode-0 backward with p / pt updated
 // in the store.  fp64 callers apply the update with a separate k_pcg_update_x launch and pass apply = 0.
+// keep (fp32, k = 1): kept eigenmodes per dimension -- the same application by the truncated kernels of spectral_keep.h
+// (two launches: forward with the update, then cube + backward with the direction update); NULL or keep[0] == 0: the full transforms.
 template <typename real>
 int launch_spectral_fused_cg(const GridDev<real>& G, const real* evec, const real* evec2, const real* evals, real kscale, real shift, real* r,
                              int k, real* w0, real* w1, int it, int apply, double tol2, real* p, real* pt, real* part, int nch, int zl, real* u,
-                             real* z, PcgScal S, hipStream_t s, const real* rhs0, const wiski_twolevel* two_level) {
+                             real* z, PcgScal S, hipStream_t s, const real* rhs0, const wiski_twolevel* two_level, const int* keep) {
   const int g0 = G.g[0], g1 = G.g[1];
+  if (keep && keep[0] != 0) {
+    if constexpr (sizeof(real) == 4) {
+      if (k != 1) return WISKI_E_BADARG;
+      return launch_spectral_keep_cg(G, evec, evec2, evals, kscale, shift, r, w1, it, apply, tol2, p, pt, part, nch, zl, u, z, S, s, rhs0, two_level, keep);
+    } else {
+      return WISKI_E_BADARG;
+    }
+  }
   if (!evec2) evec2 = evec;
   const real* V0 = evec;
   const real* V1 = evec + g0 * g0;
@@ -1571,10 +1585,10 @@ int launch_spectral_fused_cg(const GridDev<real>& G, const real* evec, const rea
 template bool spectral_fused_ok<float>(const GridDev<float>&);
 template int launch_spectral_fused_cg<float>(const GridDev<float>&, const float*, const float*, const float*, float, float, float*, int, float*,
                                              float*, int, int, double, float*, float*, float*, int, int, float*, float*, PcgScal, hipStream_t,
-                                             const float*, const wiski_twolevel*);
+                                             const float*, const wiski_twolevel*, const int*);
 template int launch_spectral_fused_cg<double>(const GridDev<double>&, const double*, const double*, const double*, double, double, double*, int,
                                               double*, double*, int, int, double, double*, double*, double*, int, int, double*, double*, PcgScal,
-                                              hipStream_t, const double*, const wiski_twolevel*);
+                                              hipStream_t, const double*, const wiski_twolevel*, const int*);
 template bool spectral_fused_ok<double>(const GridDev<double>&);
 template int launch_spectral_fused<float>(const GridDev<float>&, const float*, const float*, const float*, float, float, const float*, int, float*,
                                           float*, float*, double*, hipStream_t);

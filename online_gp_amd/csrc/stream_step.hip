@@ -46,6 +46,7 @@ static PcgArgs<real> solve_args(const typename StreamArgs<real>::type* a, int ca
   PcgArgs<real> p;
   p.A = a->d_A_half; p.a_sym = true; p.RHS = a->d_b; p.k = 1;
   p.tcol = a->d_tcol; p.kscale = a->kscale; p.evec = a->d_evec; p.evec2 = a->d_evec2; p.eval = a->d_eval; p.shift = a->shift; p.two_level = a->two_level;
+  for (int q = 0; q < 3; ++q) p.keep[q] = a->keep[q];
   p.U = a->d_U; p.Z = a->d_Z; p.R = a->d_R; p.warm = carry ? 2 : 1;
   p.tol = a->tol; p.max_iter = a->max_iter; p.check_every = a->check_every; p.first_check = first_check;
   p.work = a->d_work; p.work_bytes = a->work_bytes;

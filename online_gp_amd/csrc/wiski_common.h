@@ -303,4 +303,8 @@ int launch_spectral_fused(const GridDev<real>& G, const real* evec, const real* 
 template <typename real>
 int launch_spectral_fused_cg(const GridDev<real>& G, const real* evec, const real* evec2, const real* evals, real kscale, real shift, real* r,
                              int k, real* w0, real* w1, int it, int apply, double tol2, real* p, real* pt, real* part, int nch, int zl, real* u,
-                             real* z, PcgScal S, hipStream_t s, const real* rhs0 = nullptr, const wiski_twolevel* two_level = nullptr);
+                             real* z, PcgScal S, hipStream_t s, const real* rhs0 = nullptr, const wiski_twolevel* two_level = nullptr,
+                             const int* keep = nullptr);
+// ... with `keep` counts (fp32, one column): would a solve on G accept them?  (multiples of 4 in [4, min(g_q, 24)], the backward
+// kernel's cubes within its LDS budget -- spectral_keep.h)
+bool spectral_keep_ok(const GridDev<float>& G, const int* keep, bool two_level);

@@ -730,7 +730,8 @@ class _StreamArgs32(ctypes.Structure):
                 ("d_tcol", ctypes.c_void_p), ("kscale", ctypes.c_float), ("d_evec", ctypes.c_void_p), ("d_evec2", ctypes.c_void_p),
                 ("d_eval", ctypes.c_void_p), ("shift", ctypes.c_float), ("tol", ctypes.c_double), ("max_iter", ctypes.c_int32),
                 ("check_every", ctypes.c_int32), ("d_work", ctypes.c_void_p), ("work_bytes", ctypes.c_int64),
-                ("d_bin", ctypes.c_void_p), ("bin_bytes", ctypes.c_int64), ("shard", ctypes.c_void_p), ("two_level", ctypes.c_void_p)]
+                ("d_bin", ctypes.c_void_p), ("bin_bytes", ctypes.c_int64), ("shard", ctypes.c_void_p), ("two_level", ctypes.c_void_p),
+                ("keep", ctypes.c_int32 * 3)]
 
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
@@ -841,6 +842,12 @@ class StreamStep:
         self._two_level = tl
         self.args.two_level = ctypes.addressof(tl) if tl is not None else None
 
+    def set_keep(self, keep):
+        """keep: the eigenmodes per dimension the solve's preconditioner transforms (`keep_counts`), or None: all of them."""
+        k = tuple(int(v) for v in keep) if keep is not None else (0, 0, 0)
+        if tuple(self.args.keep) != k:
+            self.args.keep[:] = k
+
     def set_solver(self, kscale, eig, shift, tol, check_every):
         a = self.args
         evec, evals, evec2 = (tuple(eig) + (None,))[:3]
@@ -884,6 +891,69 @@ def precond_apply(grid, eig, kscale, shift, r, two_level=None):
     return Y.reshape(r.shape), T.reshape(r.shape), rho[0]
 
 
+KEEP_EPS = 2.0 ** -30      # modes whose w = a lam / (1 + a lam) is below this pass the preconditioner untransformed (t = r, y = 0)
+
+
+def keep_counts(D_host, kscale, shift, eps=KEEP_EPS):
+    """Which eigenmodes the separable preconditioner has to transform (csrc/spectral_keep.h).  D_host: per-dim eigenvalues, ascending
+    (``kron_eigen(..., host_out)["D"]``).  K_q = number of indices of dim q with w = a lam / (1 + a lam) > eps, a = shift,
+    lam = kscale D_q[j] prod_{p != q} max D_p (the other dims at their largest eigenvalue); eigenvalues below g_q 2^-52 of the dim's
+    largest are eigensolver noise and count as zero.  Returns (K, lo, hi): the counts rounded up to multiples of 4 -- or None
+    where the rule keeps everything, nothing, or a dim whose size is no multiple of 4 in full -- and the interval lo < shift <= hi
+    on which the unrounded counts stay what they are (so a caller recomputes only when the shift leaves it)."""
+    import numpy as np
+
+    if not (shift > 0 and kscale > 0):
+        return None, 0.0, 0.0
+    tau = eps / (1.0 - eps)                         # w > eps  <=>  a lam > tau
+    dmax = [float(D[-1]) for D in D_host]
+    if min(dmax) <= 0:
+        return None, 0.0, 0.0
+    K, lo, hi = [], 0.0, np.inf
+    for q, D in enumerate(D_host):
+        g = len(D)
+        d = np.where(D < g * 2.0 ** -52 * dmax[q], 0.0, D)
+        c = kscale * float(np.prod([dmax[p] for p in range(len(D_host)) if p != q]))
+        first = int(np.searchsorted(d, tau / (shift * c), side="right"))        # first kept index
+        K.append(g - first)
+        if first < g:
+            lo = max(lo, tau / (c * d[first]))
+        if first > 0 and d[first - 1] > 0:
+            hi = min(hi, tau / (c * d[first - 1]))
+    out = []
+    for q, D in enumerate(D_host):
+        g, k4 = len(D), -(-K[q] // 4) * 4
+        if K[q] < 1 or (k4 > g and g % 4 != 0):
+            return None, lo, hi
+        out.append(min(k4, g))
+    if all(k == len(D) for k, D in zip(out, D_host)):
+        return None, lo, hi
+    return tuple(out), lo, hi
+
+
+def keep_accepts(grid, keep, two_level=False):
+    """Would a solve on `grid` take these kept-mode counts (wiski_precond_keep_ok: cap 24 per dim, coefficient cubes within the backward
+    kernel's LDS budget)?"""
+    return bool(_hip.lib().wiski_precond_keep_ok(grid.ref, (ctypes.c_int32 * 3)(*[int(v) for v in keep]), ctypes.c_int32(int(bool(two_level)))))
+
+
+def precond_apply_keep(grid, eig, kscale, shift, r, keep, two_level=None):
+    """`precond_apply` on the kept modes only (``wiski_precond_apply_keep_f32``); keep = None or zeros: the full transforms."""
+    evec, evals, evec2 = (tuple(eig) + (None,))[:3]
+    r = r.contiguous()
+    m = r.numel()
+    w0 = torch.empty(m, dtype=r.dtype, device=r.device)
+    w1 = torch.empty(2 * m, dtype=r.dtype, device=r.device)
+    y, t = torch.empty_like(r), torch.empty_like(r)
+    rho = torch.zeros(1, dtype=torch.float64, device=r.device)
+    kp = (ctypes.c_int32 * 3)(*([int(v) for v in keep] if keep is not None else [0, 0, 0]))
+    rc = _hip.lib().wiski_precond_apply_keep_f32(grid.ref, _hip.dptr(evec), _hip.dptr(evec2), _hip.dptr(evals), ctypes.c_float(kscale), ctypes.c_float(shift),
+                                                 _hip.dptr(r), _hip.dptr(w0), _hip.dptr(w1), _hip.dptr(y), _hip.dptr(t), _hip.dptr(rho),
+                                                 ctypes.byref(two_level) if two_level is not None else None, kp, _hip.stream_ptr(r.device))
+    _hip.check(rc, "wiski_precond_apply_keep")
+    return y, t, rho[0]
+
+
 def precond_apply_cols(grid, eig, kscale, shift, R, two_level=None):
     """`precond_apply` for the k rows of R [k, m] through the multi-column kernels (``wiski_precond_apply_cols``): (Y, T, rho [k])."""
     evec, evals, evec2 = (tuple(eig) + (None,))[:3]
@@ -900,14 +970,17 @@ def precond_apply_cols(grid, eig, kscale, shift, R, two_level=None):
     return Y, T, rho
 
 
-def kron_eigen(grid, tcol, profiles=None, host_out=None):
+def kron_eigen(grid, tcol, profiles=None, host_out=None, dtype=None):
     """Per-dim (generalized) eigen-decomposition of the d small symmetric-Toeplitz Kronecker
     factors (host side, fp64, O(d g^3) -- done when the hyper-parameters or the data-density
     profile change, not per streaming update).
 
     profiles=None:  K_q = V_q diag(lam_q) V_q^T                         -> (evec, evals)
     profiles=[t_q]: K_q = X_q D_q X_q^T with X_q^T diag(t_q) X_q = I     -> (evec = X, evals = D, evec2 = Z = diag(t) X)
-    Eigenvalues are clamped >= 0.  Feeds wiski_pcg's preconditioner (K^-1 + a kron diag(t_q))^-1."""
+    Eigenvalues are clamped >= 0.  Feeds wiski_pcg's preconditioner (K^-1 + a kron diag(t_q))^-1.
+    dtype: of the returned tables (default: tcol's).  fp32 tables from fp64 columns keep the super-exponential tail of a smooth
+    prior's spectrum down to the eigensolver's own noise (~1e-16 of the largest eigenvalue); columns rounded to fp32 first bury
+    it under ~1e-9 of rounding noise, half of it positive -- modes that `keep_counts` would then have to keep."""
     import numpy as np
 
     tc = tcol.detach().to("cpu", torch.float64).numpy()
@@ -927,7 +1000,7 @@ def kron_eigen(grid, tcol, profiles=None, host_out=None):
             Z.append((U * rt[:, None]).reshape(-1))
         vals.append(np.clip(w, 0.0, None))
         off += g
-    mk = lambda parts: torch.as_tensor(np.concatenate(parts)).to(tcol.device, tcol.dtype)
+    mk = lambda parts: torch.as_tensor(np.concatenate(parts)).to(tcol.device, dtype or tcol.dtype)
     if host_out is not None:              # fp64 host copies (per dim: eigenvectors [g, g] column = mode, eigenvalues ascending)
         host_out["X"] = [x.reshape(g, g) for x, g in zip(X, grid.g)]
         host_out["D"] = [v.copy() for v in vals]

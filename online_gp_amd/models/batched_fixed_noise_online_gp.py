@@ -563,7 +563,14 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
                 st["it0"] = None
             else:
                 host = {}
-                eig = grid_ops.kron_eigen(self._grid, tcol, profiles=profiles, host_out=host)
+                # where the truncated preconditioner can engage (_keep_for_step: one output, d = 3, fp32) decompose the fp64 columns:
+                # the tables are fp32 either way and reproduce the prior factor as closely as before
+                # (tests/test_precond_keep_host.py::test_tables_from_fp64_columns_reproduce_the_factor_as_closely).  Columns rounded to fp32
+                # first carry ~1e-9 of rounding noise in their spectrum, which the truncation rule would have to keep as if it were
+                # prior (grid_ops.kron_eigen).  Everything else decomposes what it always did
+                fine = settings.truncated_preconditioner.on() and tcol.dtype == torch.float32 and self.num_outputs == 1 and self._grid.d == 3
+                src = self._hyper()[o][2] if fine else tcol
+                eig = grid_ops.kron_eigen(self._grid, src, profiles=profiles, host_out=host, dtype=tcol.dtype)
                 st = {"ver": ver, "wsum": wsum, "eig": eig, "norm": norm, "profiles": profiles, "it0": None, "eig_host": host}
                 self._memo["precond"][o] = st
         return st["eig"], wsum / st["norm"]
@@ -1358,6 +1365,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         fc, probe = self._first_poll(last)
         carry = ms.get("R_ok", False) and self._refresh_count % 16 != 0
         step.args.shift = float(self._wsum[0]) / pst["norm"]
+        step.set_keep(self._keep_for_step(step, pst))
         y1 = Y.reshape(-1)
         y1 = y1 if y1.is_contiguous() else y1.contiguous()
         if "_spectral" in self.__dict__:
@@ -1382,6 +1390,33 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             self._absorb_probes(self._kernel_cache, X, None)       # one extra launch; none without probes
         self._note_solve(ms, res, fc, probe)
         return mean
+
+    def _keep_for_step(self, step, pst):
+        """The eigenmodes the step's preconditioner transforms (grid_ops.keep_counts; None: all).  The counts depend on the eigenvalues
+        and on the shift only: they are kept with the interval of shifts on which they hold and recomputed when the shift leaves it.
+        Host data that every replica of a sharded step holds alike, so the ranks stay in lock-step."""
+        if (settings.truncated_preconditioner.off() or self._dtype != torch.float32 or self._grid.d != 3 or self.num_outputs != 1
+                or "eig_host" not in pst):
+            return None
+        kscale, shift = float(step.args.kscale), float(step.args.shift)
+        memo = pst.get("keep")
+        if memo is None or memo[0] != kscale or not (memo[1] < shift <= memo[2]):
+            K, lo, hi = grid_ops.keep_counts(pst["eig_host"]["D"], kscale, shift)
+            if K is not None and not grid_ops.keep_accepts(self._grid, K, two_level=True):
+                K = None                                   # above the cap / the cube does not fit the middle kernel
+            memo = pst["keep"] = (kscale, lo, hi, K)
+        K = memo[3]
+        if K is not None and getattr(step, "_two_level", None) is not None:
+            tr = self.__dict__.get("_two_level")
+            blk = tr.block if tr is not None else None
+            if blk is None:
+                return None
+            low = blk.__dict__.get("_idx_low")
+            if low is None:
+                low = blk._idx_low = tuple(int(v) for v in blk.idx_host.min(axis=1))
+            if any(low[q] < self._grid.g[q] - K[q] for q in range(3)):
+                return None                                # a selected mode of the exact block lies outside the box
+        return K
 
     # ------------------------------------------------- two-level preconditioner --
     def _two_level_applies(self):

@@ -231,6 +231,15 @@ class two_level_preconditioner(_feature_flag):
     _state = True
 
 
+class truncated_preconditioner(_feature_flag):
+    """One-column fp32 streaming solves transform only the eigenmodes on which the separable preconditioner differs from the
+    identity by more than 2^-30 (``grid_ops.keep_counts``, csrc/spectral_keep.h): a box of K_0 x K_1 x K_2 modes instead of the whole
+    grid, in two launches none of which waits on another workgroup.  Engages only where the rule drops modes and the box fits
+    the kernels (smooth priors on grids much finer than the lengthscale); off, or where it does not engage: the full transforms."""
+
+    _state = True
+
+
 class two_level_rank(_value_context):
     """Modes in the exact block of the two-level preconditioner (<= 480).  50^3, road-like stream: 128 / 192 / 256 / 384 modes
     need 3.28 / 3.02 / 3.02 / 3.02 iterations per step (2.0 late in the stream); the refresh costs grow with the square."""
