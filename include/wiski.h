@@ -612,7 +612,10 @@ int wiski_hyper_columns_f64(const wiski_hyper_plan* plan, const wiski_grid* grid
 int wiski_hyper_mid_f32(const double* d_bMb, const double* d_logdet, const float* d_s2, const double* d_c, const double* d_ld, const double* d_n, double* d_out, double* d_loss, void* stream);
 int wiski_hyper_mid_f64(const double* d_bMb, const double* d_logdet, const double* d_s2, const double* d_c, const double* d_ld, const double* d_n, double* d_out, double* d_loss, void* stream);
 /* Chain rule to the raw parameters (d_gell, d_gscale from wiski_stationary_columns_grad, sigma2's from d_mid / d_gkap) and torch.optim.Adam's update
- * (no weight decay, no amsgrad) of every parameter of the plan, its moments and step counters. */
+ * (no weight decay, no amsgrad) of every parameter of the plan, its moments and step counters.  The plan is held to what wiski_hyper_columns asks of it
+ * (count 1..6, exactly one lengthscale and one noise, scalar scale factors, roles 0..2, kinds 0..1, at most 64 elements; only the lengthscale's numel
+ * against the grid dimension is not known here) and, on top, needs the moments and counters (step_numel 1 or numel) of every entry and d_scale / d_gscale
+ * when it has a role-1 entry: anything else is WISKI_E_BADARG and nothing is launched. */
 int wiski_hyper_adam_f32(const wiski_hyper_plan* plan, const float* d_scale, const float* d_s2, const float* d_gell, const float* d_gscale, const double* d_mid, const double* d_gkap, const double* d_n, double lr, double beta1, double beta2, double eps, void* stream);
 int wiski_hyper_adam_f64(const wiski_hyper_plan* plan, const double* d_scale, const double* d_s2, const double* d_gell, const double* d_gscale, const double* d_mid, const double* d_gkap, const double* d_n, double lr, double beta1, double beta2, double eps, void* stream);
 /* count <= 12 fp64 segments dst[s][0 .. n[s]) = src[s][..] and one scalar store, in ONE launch (the staging of a factor state into the static

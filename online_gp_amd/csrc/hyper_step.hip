@@ -170,13 +170,15 @@ __global__ void k_hyper_adam(wiski_hyper_plan plan, const real* __restrict__ sca
     }
 }
 
+// the one validation of a plan, for both entry points: exactly one lengthscale (numel 1 or d; d < 0: the caller does not know the grid, any
+// numel), exactly one noise, scalar output-scale factors, at most 64 elements (one thread per element, one wave)
 static int plan_ok(const wiski_hyper_plan* plan, int d) {
   if (!plan || plan->count < 1 || plan->count > WISKI_HYPER_MAX_PARAMS) return 0;
   int total = 0, nell = 0, nnoise = 0;
   for (int i = 0; i < plan->count; ++i) {
     const wiski_hyper_param& p = plan->p[i];
     if (!p.raw || p.numel < 1 || p.role < 0 || p.role > 2 || p.kind < 0 || p.kind > 1) return 0;
-    if (p.role == 0) { if (nell || (p.numel != 1 && p.numel != d)) return 0; nell = p.numel; }
+    if (p.role == 0) { if (nell || (d >= 0 && p.numel != 1 && p.numel != d)) return 0; nell = p.numel; }
     else if (p.numel != 1) return 0;
     if (p.role == 2) ++nnoise;
     total += p.numel;
@@ -202,14 +204,7 @@ static int hyper_columns_impl(const wiski_hyper_plan* plan, const wiski_grid* gr
 template <typename real>
 static int hyper_adam_impl(const wiski_hyper_plan* plan, const real* d_scale, const real* d_s2, const real* d_gell, const real* d_gscale, const double* d_mid,
                            const double* d_gkap, const double* d_n, double lr, double beta1, double beta2, double eps, void* stream) {
-  if (!plan || plan->count < 1 || plan->count > WISKI_HYPER_MAX_PARAMS || !d_s2 || !d_gell || !d_mid || !d_gkap || !d_n) return WISKI_E_BADARG;
-  int total = 0;
-  for (int i = 0; i < plan->count; ++i) {
-    const wiski_hyper_param& p = plan->p[i];
-    if (!p.raw || p.numel < 1 || p.role < 0 || p.role > 2 || p.kind < 0 || p.kind > 1 || (p.role != 0 && p.numel != 1)) return WISKI_E_BADARG;
-    total += p.numel;
-  }
-  if (total > 64) return WISKI_E_BADARG;                  // (one thread per element, one wave)
+  if (!plan_ok(plan, -1) || !d_s2 || !d_gell || !d_mid || !d_gkap || !d_n) return WISKI_E_BADARG;
   for (int i = 0; i < plan->count; ++i) {
     const wiski_hyper_param& p = plan->p[i];
     if (!p.exp_avg || !p.exp_avg_sq || !p.step || (p.step_numel != 1 && p.step_numel != p.numel)) return WISKI_E_BADARG;
