@@ -438,6 +438,34 @@ int wiski_scatter_stats_robust_f64(const wiski_grid* grid, const double* d_x, co
 int wiski_absorb_robust_f32(const wiski_grid* grid, const wiski_absorb_args* args, const float* d_inv_scale, float huber_c, float* d_omega_out, void* stream);
 int wiski_absorb_robust_f64(const wiski_grid* grid, const wiski_absorb_args* args, const double* d_inv_scale, double huber_c, double* d_omega_out, void* stream);
 
+/* Sliding-window absorb: the statistics of exactly the points in a device-resident ring.  The statistics are
+ * sums, so a point leaves them by being absorbed once more with its weights negated.  The ring is five device arrays of `cap`
+ * slots in the working precision -- d_x [cap, d], d_y, d_wa, d_wb, d_noise [cap] -- and `head`, kept by the host, is the slot of
+ * the launch's first entering point.  An EMPTY slot holds wa = wb = 0, noise = 1 and a finite x: the caller creates the ring that
+ * way.  In ONE launch, for entering point j of n, the wave of slot s = (head + j) mod cap
+ *   1. reads the old occupant of s,
+ *   2. writes the entering point into s -- a point outside the grid is flagged and counted in d_err as everywhere, contributes
+ *      nothing, and is stored VOID: wa = wb = 0, noise = 1, y = 0, x = NaN (a point no grid contains, a grown one included),
+ *   3. absorbs the entering point with (+wa, +wb); d_mean_out[j] is its predictive mean before the update,
+ *   4. absorbs the old occupant, if it holds weight, with (-wa, -wb); a void or empty slot gives nothing back.
+ * stats += (sum wb y^2, sum log noise) of the points that entered minus those of the points that left.  *d_void_left += the
+ * number of overwritten slots that were void, so that a caller can keep its point count without reading the ring.  n <= cap is
+ * required (the slots of one launch are then distinct: a slot has one reader and one writer, the same wave), as are d_u, d_A_half,
+ * d_cnt and d_void_left; d_res and d_mean_out are optional.  Both sweeps use the same u, so the result does not depend on the
+ * order of points or atomics.  The caller advances head by n (mod cap) afterwards.  Symmetric half stencil, atomic form, one
+ * output, d = 1..4; anything else -- n > cap, head outside [0, cap), a missing ring array -- is WISKI_E_BADARG before a launch.
+ * As with the robust form, wiski_absorb_args has NOT grown a ring group (it is passed by pointer without a size field), and
+ * wiski_absorb_window takes the record plus the ring so that every combination absorb_validate refuses (a guard, zero regions, a
+ * shard, an owner workspace, nout > 1, channels, a full stencil) can be reached and tested. */
+typedef struct wiski_window_ring {
+  void* d_x; void* d_y; void* d_wa; void* d_wb; void* d_noise;
+  int64_t cap; int64_t head;
+} wiski_window_ring;
+int wiski_scatter_stats_window_f32(const wiski_grid* grid, const float* d_x, const float* d_y, const float* d_wa, const float* d_wb, const float* d_noise, int64_t n, const wiski_window_ring* ring, float* d_b, float* d_A_half, float* d_cnt, const float* d_u, float* d_res, float* d_mean_out, double* d_stats, int32_t* d_err, int32_t* d_void_left, void* stream);
+int wiski_scatter_stats_window_f64(const wiski_grid* grid, const double* d_x, const double* d_y, const double* d_wa, const double* d_wb, const double* d_noise, int64_t n, const wiski_window_ring* ring, double* d_b, double* d_A_half, double* d_cnt, const double* d_u, double* d_res, double* d_mean_out, double* d_stats, int32_t* d_err, int32_t* d_void_left, void* stream);
+int wiski_absorb_window_f32(const wiski_grid* grid, const wiski_absorb_args* args, const wiski_window_ring* ring, int32_t* d_void_left, void* stream);
+int wiski_absorb_window_f64(const wiski_grid* grid, const wiski_absorb_args* args, const wiski_window_ring* ring, int32_t* d_void_left, void* stream);
+
 /* The two halves of a stencil-sharded step on their own (wiski_stream_step uses them when args->shard is set): the absorb
  * restricted to the stencil groups [g_lo, g_hi) (same arguments as wiski_scatter_stats_step; always the atomic form), and
  * wiski_pcg_async with every A . v product summed over the ranks of `shard`. */

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 _SO = os.path.join(_CSRC, "libwiski_hip.so")
 _SOURCES = ["interp_gather.hip", "scatter_stats.hip", "solve.hip", "spectral.hip", "dense.hip", "collective.hip", "stream_step.hip", "spectral_basis.hip", "hyper_columns.hip", "two_level.hip", "hyper_step.hip", "lookahead.hip", "sample_paths.hip", "decay_stats.hip", "regrid_stats.hip"]
-_HEADERS = ["wiski_common.h", "spmv_sym_dma.h", "spmv_sym_dma_mc.h", "spmm_sym_cols.h", "spmm_sym_bcast.h", "scatter_half.h", "scatter_owner.h", "scatter_grad.h", "scatter_robust.h", "absorb.h", "dense_small.h", "dense_coop.h",
+_HEADERS = ["wiski_common.h", "spmv_sym_dma.h", "spmv_sym_dma_mc.h", "spmm_sym_cols.h", "spmm_sym_bcast.h", "scatter_half.h", "scatter_owner.h", "scatter_grad.h", "scatter_robust.h", "scatter_window.h", "absorb.h", "dense_small.h", "dense_coop.h",
             os.path.join("..", "..", "include", "wiski.h")]
 MAX_DIM = 4
 
@@ -88,6 +88,11 @@ class wiski_absorb_args(ctypes.Structure):
         ("d_guard", ctypes.c_void_p), ("guard_expect", ctypes.c_int64), ("d_bin", ctypes.c_void_p), ("bin_bytes", ctypes.c_int64),
         ("g_lo", ctypes.c_int32), ("g_hi", ctypes.c_int32), ("nout", ctypes.c_int32), ("reserved", ctypes.c_int32),
         ("y_stride", ctypes.c_int64), ("w_stride", ctypes.c_int64), ("A_stride", ctypes.c_int64)]
+
+
+class wiski_window_ring(ctypes.Structure):
+    """The device-resident ring of a sliding-window absorb (include/wiski.h): five arrays of `cap` slots and the host-kept head."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("d_x", "d_y", "d_wa", "d_wb", "d_noise")] + [("cap", ctypes.c_int64), ("head", ctypes.c_int64)]
 
 
 def sources():

@@ -3,11 +3,11 @@
 // may be asked to do, as ONE named record.  Every member defaults to "off"; the extern "C" entry points of scatter_stats.hip
 // and the streaming step (stream_step.hip) fill the fields they expose and call absorb().  Which combinations are refused is
 // absorb_validate() in scatter_stats.hip; whoever writes another form of the absorb has to honour every group below.
-// Three kernels stand behind it: the atomic form (k_scatter_stats[_sym]; the owner form where its workspace is given and applies),
-// the derivative-observation form (`channels`, scatter_grad.h) and the outlier-robust form (`inv_scale`, scatter_robust.h).  The
-// last two implement the plain single-output half-stencil absorb with cnt and the carry and refuse every other group.  What the
-// three half-stencil kernels do per point -- the tap tables, the per-tap atomics, the pair loop that encodes the row-interleaved
-// layout, the two scalars -- is stated once, in scatter_half.h.
+// Four kernels stand behind it: the atomic form (k_scatter_stats[_sym]; the owner form where its workspace is given and applies),
+// the derivative-observation form (`channels`, scatter_grad.h), the outlier-robust form (`inv_scale`, scatter_robust.h) and the
+// sliding-window form (`ring_*`, scatter_window.h).  The last three implement the plain single-output half-stencil absorb with cnt
+// and the carry and refuse every other group.  What the four half-stencil kernels do per point -- the tap tables, the per-tap
+// atomics, the pair loop that encodes the row-interleaved layout, the two scalars -- is stated once, in scatter_half.h.
 #pragma once
 #include "wiski_common.h"
 
@@ -68,8 +68,22 @@ struct AbsorbArgs {
   const real* inv_scale = nullptr;  // [n] 1 / scale of each point's innovation
   real huber_c = 0;
   real* omega_out = nullptr;        // [n] the weight each point entered with; 0 for a point outside the grid
+  // ring: ring_x != NULL makes the absorb a sliding window (scatter_window.h): entering point j is absorbed, stored in slot
+  // (ring_head + j) mod ring_cap, and the point that slot held is taken out again with its weights negated, all in one launch.
+  // An empty slot holds wa = wb = 0, noise = 1; a point outside the grid is stored void (wa = wb = 0, noise = 1, y = 0, x = NaN) and
+  // void_left counts the void slots that were overwritten.  Needs all five arrays, ring_cap >= 1, 0 <= ring_head < ring_cap,
+  // n <= ring_cap (the slots of a launch are distinct), u, A, cnt and void_left; res and mean_out stay optional.  Single-output
+  // half-stencil atomic form only: no channels, inv_scale, guard, zero regions, shard or owner workspace
+  real* ring_x = nullptr;           // [ring_cap, d]
+  real* ring_y = nullptr;           // [ring_cap]
+  real* ring_wa = nullptr;          // [ring_cap]
+  real* ring_wb = nullptr;          // [ring_cap]
+  real* ring_noise = nullptr;       // [ring_cap]
+  int64_t ring_cap = 0, ring_head = 0;
+  int32_t* void_left = nullptr;     // += number of overwritten slots that were void
 
   bool sharded() const { return g_lo > 0 || g_hi < (1 << 30); }
+  bool windowed() const { return ring_x || ring_y || ring_wa || ring_wb || ring_noise || ring_cap || ring_head || void_left; }
 };
 
 // Validates, then queues the absorb on `stream`: WISKI_OK, WISKI_E_BADARG (nothing was launched) or WISKI_E_LAUNCH.

@@ -175,6 +175,7 @@ __global__ __launch_bounds__(256) void k_scatter_stats_sym(GridDev<real> G, cons
 #include "scatter_owner.h"
 #include "scatter_grad.h"
 #include "scatter_robust.h"
+#include "scatter_window.h"
 
 // Unpacks the row-interleaved half stencil into a full offset-major stencil full[o][i] = A[i, i + off(o)]
 // (diagnostics, tests, and models handed a full-stencil cache):
@@ -243,6 +244,17 @@ template <typename real>
 static int absorb_validate(const AbsorbArgs<real>& a, int d) {
   if (a.n == 0) return WISKI_OK;                       // nothing to absorb: not even the pointers are looked at
   if (!a.x || !a.y || !a.wa || !a.wb || !a.noise || !a.b || !a.stats || !a.err) return WISKI_E_BADARG;   // what every form reads and writes
+  if (a.windowed()) {
+    // window (scatter_window.h): a whole ring with head inside it and no more entering points than slots, so that the slots of
+    // the launch are distinct; u, A, cnt and void_left are used unconditionally; the plain single-output half-stencil atomic
+    // form only, and not the robust one either.  res and mean_out are optional
+    if (!a.ring_x || !a.ring_y || !a.ring_wa || !a.ring_wb || !a.ring_noise || !a.void_left) return WISKI_E_BADARG;
+    if (a.ring_cap < 1 || a.ring_head < 0 || a.ring_head >= a.ring_cap || a.n > a.ring_cap) return WISKI_E_BADARG;
+    if (!a.u || !a.half || !a.A || !a.cnt || a.nout != 1 || a.channels) return WISKI_E_BADARG;
+    if (a.inv_scale || a.omega_out || a.huber_c != (real)0) return WISKI_E_BADARG;
+    if (a.guard || a.n1_bytes || a.n2_bytes || a.z1 || a.z2 || a.sharded() || a.bin || a.bin_bytes) return WISKI_E_BADARG;
+    return WISKI_OK;
+  }
   if (a.inv_scale) {
     // robust (scatter_robust.h): the weights need u; A, cnt and omega_out are written unconditionally; the plain single-output
     // half-stencil atomic form only.  res and mean_out are optional here: u alone is a complete request
@@ -345,6 +357,7 @@ int absorb(const wiski_grid* grid, const AbsorbArgs<real>& a, void* stream) {
   int rc = make_grid_dev<real>(grid, &G);
   if (rc == WISKI_OK) rc = absorb_validate(a, G.d);
   if (rc != WISKI_OK || a.n == 0) return rc;
+  if (a.windowed()) return launch_window(G, a, (hipStream_t)stream);
   if (a.inv_scale) return launch_robust(G, a, (hipStream_t)stream);
   if (a.channels) return launch_grad(G, a, (hipStream_t)stream);
   return owner_applies(G, a) ? launch_owner(G, a, (hipStream_t)stream) : launch_atomic(G, a, (hipStream_t)stream);
@@ -411,6 +424,23 @@ static int entry_absorb_robust(const wiski_grid* g, const wiski_absorb_args* p, 
   return p ? entry_robust(g, absorb_args<real>(*p), inv_scale, huber_c, omega_out, s) : WISKI_E_BADARG;
 }
 template <typename real>
+static int entry_window(const wiski_grid* g, AbsorbArgs<real> a, const wiski_window_ring* r, int32_t* void_left, void* s) {
+  if (!r) return WISKI_E_BADARG;
+  a.ring_x = (real*)r->d_x; a.ring_y = (real*)r->d_y; a.ring_wa = (real*)r->d_wa; a.ring_wb = (real*)r->d_wb; a.ring_noise = (real*)r->d_noise;
+  a.ring_cap = r->cap; a.ring_head = r->head; a.void_left = void_left;
+  return a.ring_x ? absorb(g, a, s) : WISKI_E_BADARG;
+}
+template <typename real>
+static int entry_scatter_window(const wiski_grid* g, const real* x, const real* y, const real* wa, const real* wb, const real* noise, int64_t n, const wiski_window_ring* r, real* b, real* A_half, real* cnt, const real* u, real* res, real* mean_out, double* stats, int32_t* err, int32_t* void_left, void* s) {
+  AbsorbArgs<real> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
+  absorb_carry(a, cnt, u, res, mean_out);
+  return entry_window(g, a, r, void_left, s);
+}
+template <typename real>
+static int entry_absorb_window(const wiski_grid* g, const wiski_absorb_args* p, const wiski_window_ring* r, int32_t* void_left, void* s) {
+  return p ? entry_window(g, absorb_args<real>(*p), r, void_left, s) : WISKI_E_BADARG;
+}
+template <typename real>
 static int entry_plain(const wiski_grid* g, const real* x, const real* y, const real* wa, const real* wb, const real* noise, int64_t n, real* b, real* A, bool half, double* stats, int32_t* err, void* s) {
   return absorb(g, absorb_args(x, y, wa, wb, noise, n, b, A, half, stats, err), s);
 }
@@ -448,6 +478,10 @@ int wiski_scatter_stats_robust_f32(const wiski_grid* g, const float* x, const fl
 int wiski_scatter_stats_robust_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, const double* inv_scale, double huber_c, double* omega_out, void* s) { return entry_scatter_robust(g, x, y, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, inv_scale, huber_c, omega_out, s); }
 int wiski_absorb_robust_f32(const wiski_grid* g, const wiski_absorb_args* p, const float* inv_scale, float huber_c, float* omega_out, void* s) { return entry_absorb_robust(g, p, inv_scale, huber_c, omega_out, s); }
 int wiski_absorb_robust_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* inv_scale, double huber_c, double* omega_out, void* s) { return entry_absorb_robust(g, p, inv_scale, huber_c, omega_out, s); }
+int wiski_scatter_stats_window_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, const wiski_window_ring* ring, float* b, float* A_half, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, int32_t* void_left, void* s) { return entry_scatter_window(g, x, y, wa, wb, noise, n, ring, b, A_half, cnt, u, res, mean_out, stats, err, void_left, s); }
+int wiski_scatter_stats_window_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, const wiski_window_ring* ring, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, int32_t* void_left, void* s) { return entry_scatter_window(g, x, y, wa, wb, noise, n, ring, b, A_half, cnt, u, res, mean_out, stats, err, void_left, s); }
+int wiski_absorb_window_f32(const wiski_grid* g, const wiski_absorb_args* p, const wiski_window_ring* ring, int32_t* void_left, void* s) { return entry_absorb_window<float>(g, p, ring, void_left, s); }
+int wiski_absorb_window_f64(const wiski_grid* g, const wiski_absorb_args* p, const wiski_window_ring* ring, int32_t* void_left, void* s) { return entry_absorb_window<double>(g, p, ring, void_left, s); }
 int wiski_scatter_stats_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A, double* stats, int32_t* err, void* s) { return entry_plain(g, x, y, wa, wb, noise, n, b, A, false, stats, err, s); }
 int wiski_scatter_stats_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A, double* stats, int32_t* err, void* s) { return entry_plain(g, x, y, wa, wb, noise, n, b, A, false, stats, err, s); }
 int wiski_scatter_stats_sym_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, double* stats, int32_t* err, void* s) { return entry_plain(g, x, y, wa, wb, noise, n, b, A_half, true, stats, err, s); }

@@ -194,6 +194,9 @@ class ShardedStatsUpdater:
             # the Huber weights of a shard are taken where it is absorbed; the followers on the other ranks (noise-weight sum, probes,
             # two-level block) would need them gathered beside the statistics: single-GPU for now
             raise NotImplementedError("ShardedStatsUpdater does not carry robust weights: build the model with robust_c=None")
+        if getattr(model, "window", None) is not None:
+            # what leaves the window must leave every replica, and a replica's ring would hold its own shard only: single-GPU for now
+            raise NotImplementedError("ShardedStatsUpdater does not carry a sliding window: build the model with window=None")
         self.model = model
         self.group = group
         self.exchange = exchange

@@ -7,6 +7,8 @@ import ctypes
 import math
 import warnings
 
+import numpy as np
+
 import torch
 
 from . import _hip
@@ -454,6 +456,110 @@ def scatter_stats_robust(grid, x, y, wa, wb, noise, inv_scale, c, b, A_half, cnt
                                                         _hip.creal(x.dtype)(float(c)), _hip.dptr(omega), _hip.stream_ptr(x.device))
     _hip.check(rc, "wiski_scatter_stats_robust")
     return omega
+
+
+class WindowRing:
+    """The device-resident ring of a sliding window (``wiski_window_ring``): x [cap, d], y / wa / wb / noise [cap]
+    in the working precision, and on the host ``head`` -- the slot the next entering point takes -- and ``fill``, the number of
+    slots written so far (at most cap).  An empty slot holds wa = wb = 0, noise = 1; a void one (its point lay outside the grid
+    when it entered) the same with x = NaN.  ``void_left`` [1] int32 counts, on the device, the void slots overwritten so far.
+    ``unit`` (host, bool [cap]) is the owner's note of the slots it wrote at unit noise (the model keeps their weight sum on the host),
+    ``explicit`` [cap] the device mask of the slots written with explicit noise (1, else 0) and ``explicit_host`` its host copy;
+    ``mark`` writes all three.  An empty slot is in neither set."""
+
+    def __init__(self, cap, d, dtype, device):
+        cap = int(cap)
+        if cap < 1:
+            raise ValueError(f"WindowRing: cap must be at least 1, got {cap}")
+        self.cap, self.d, self.head, self.fill = cap, int(d), 0, 0
+        self.x = torch.zeros((cap, self.d), dtype=dtype, device=device)
+        self.y = torch.zeros(cap, dtype=dtype, device=device)
+        self.wa = torch.zeros(cap, dtype=dtype, device=device)
+        self.wb = torch.zeros(cap, dtype=dtype, device=device)
+        self.noise = torch.ones(cap, dtype=dtype, device=device)
+        self.void_left = torch.zeros(1, dtype=torch.int32, device=device)
+        self.unit = np.zeros(cap, dtype=bool)
+        self.explicit = torch.zeros(cap, dtype=dtype, device=device)
+        self.explicit_host = np.zeros(cap, dtype=bool)
+
+    def tensors(self):
+        return self.x, self.y, self.wa, self.wb, self.noise
+
+    def clone(self):
+        new = object.__new__(WindowRing)
+        new.cap, new.d, new.head, new.fill = self.cap, self.d, self.head, self.fill
+        new.x, new.y, new.wa, new.wb, new.noise = (t.clone() for t in self.tensors())
+        new.void_left = self.void_left.clone()
+        new.unit = self.unit.copy()
+        new.explicit, new.explicit_host = self.explicit.clone(), self.explicit_host.copy()
+        return new
+
+    def to(self, device):
+        new = self.clone()
+        new.x, new.y, new.wa, new.wb, new.noise = (t.to(device) for t in new.tensors())
+        new.void_left, new.explicit = new.void_left.to(device), new.explicit.to(device)
+        return new
+
+    def clear(self):
+        """Every slot empty again."""
+        self.head = self.fill = 0
+        for t in (self.x, self.y, self.wa, self.wb, self.void_left):
+            t.zero_()
+        self.noise.fill_(1)
+        self.unit[:] = False
+        self.explicit.zero_()
+        self.explicit_host[:] = False
+
+    def spans(self, n):
+        """The slots head .. head + n - 1 (mod cap), n <= cap, as one or two slices."""
+        end = self.head + n
+        return [slice(self.head, end)] if end <= self.cap else [slice(self.head, self.cap), slice(0, end - self.cap)]
+
+    def mark(self, spans, unit):
+        """Note the slots of `spans` as written at unit noise, or with explicit noise (host flags and device mask; no host read)."""
+        for sl in spans:
+            self.unit[sl] = unit
+            self.explicit_host[sl] = not unit
+            self.explicit[sl] = 0 if unit else 1
+
+    def advance(self, n):
+        self.head = (self.head + n) % self.cap
+        self.fill = min(self.cap, self.fill + n)
+
+    def order(self):
+        """Slot indices of the written slots, oldest first (a host list)."""
+        first = self.head if self.fill == self.cap else 0
+        return [(first + i) % self.cap for i in range(self.fill)]
+
+    def ref(self, head=None):
+        return _hip.wiski_window_ring(*(t.data_ptr() for t in self.tensors()), self.cap, self.head if head is None else int(head))
+
+
+def scatter_stats_window(grid, x, y, wa, wb, noise, ring, b, A_half, cnt, stats, err, u, res=None, mean_out=None):
+    """The sliding-window absorb in ONE launch (``wiski_scatter_stats_window``): the n <= ring.cap points enter
+    (b, A_half, cnt, stats) -- and the carried residual ``res``, if given -- and the slots ring.head, ring.head + 1, ... (mod cap)
+    of ``ring``; what those slots held leaves the statistics again, with its weights negated.  ``u`` [m]: the posterior mean on the
+    grid both sweeps are taken against (any vector when neither ``res`` nor ``mean_out`` is asked for); ``mean_out`` [n] receives
+    w . u of the entering points.  Advances ``ring.head`` and ``ring.fill``."""
+    x = _x2d(x, grid)
+    n = x.shape[0]
+    for name, t in (("y", y), ("wa", wa), ("wb", wb), ("noise", noise), ("mean_out", mean_out)):
+        if t is not None and (tuple(t.shape) != (n,) or t.dtype != x.dtype):
+            raise ValueError(f"scatter_stats_window: {name} must be [{n}] {x.dtype}, got {tuple(t.shape)} {t.dtype}")
+    if u is None or tuple(u.shape) != (grid.m,) or u.dtype != x.dtype:
+        raise ValueError(f"scatter_stats_window: u must be a grid vector [{grid.m}] {x.dtype}")
+    if ring.d != grid.d or ring.x.dtype != x.dtype or ring.x.device != x.device:
+        raise ValueError(f"scatter_stats_window: the ring holds {ring.d}-d {ring.x.dtype} points on {ring.x.device}")
+    if n == 0:
+        return
+    r = ring.ref()
+    rc = _hip.fn("wiski_scatter_stats_window", x.dtype)(grid.ref, _hip.dptr(x), _hip.dptr(y.contiguous()), _hip.dptr(wa.contiguous()),
+                                                        _hip.dptr(wb.contiguous()), _hip.dptr(noise.contiguous()), ctypes.c_int64(n), ctypes.byref(r),
+                                                        _hip.dptr(b), _hip.dptr(A_half), _hip.dptr(cnt), _hip.dptr(u), _hip.dptr(res),
+                                                        _hip.dptr(mean_out), _hip.dptr(stats), _hip.dptr(err), _hip.dptr(ring.void_left),
+                                                        _hip.stream_ptr(x.device))
+    _hip.check(rc, "wiski_scatter_stats_window")
+    ring.advance(n)
 
 
 def scatter_probes(grid, x, wa, first_index, seed, P, err):

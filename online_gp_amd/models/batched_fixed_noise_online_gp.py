@@ -94,6 +94,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         max_grid_size=None,
         robust_c=None,
         robust_scale="noise",
+        window=None,
+        window_rebuild_every=None,
     ):
         super().__init__()
         assert train_inputs is not None or kernel_cache is not None
@@ -117,6 +119,28 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         self.robust_c = robust_c
         self.robust_scale = robust_scale
         self.last_robust_weights = None              # omega [q] of the last robustly absorbed batch, on the device
+        # sliding window (_absorb_window): the model is the GP of exactly the last `window` points; every update absorbs
+        # its batch, stores it in a device-resident ring and takes out what the ring's slots held, in one launch
+        if window is not None:
+            if isinstance(window, bool) or int(window) != window or int(window) < 1:
+                raise ValueError(f"window must be an integer >= 1, got {window!r}")
+            window = int(window)
+            if forgetting_factor is not None:
+                raise NotImplementedError("window and forgetting_factor are alternatives: a hard window lets a point go after `window` points, "
+                                          "forgetting inflates its noise for ever -- build the model with one of them")
+            if robust_c is not None:
+                raise NotImplementedError("window does not combine with robust_c: the ring stores the weights a point entered with, and no "
+                                          "kernel both weighs and retires in one launch")
+        if window_rebuild_every is not None:
+            if window is None:
+                raise ValueError("window_rebuild_every needs window")
+            if isinstance(window_rebuild_every, bool) or int(window_rebuild_every) != window_rebuild_every or int(window_rebuild_every) < 1:
+                raise ValueError(f"window_rebuild_every must be an integer >= 1, got {window_rebuild_every!r}")
+            window_rebuild_every = int(window_rebuild_every)
+        self.window = window
+        self.window_rebuild_every = window_rebuild_every
+        self._win_voids = 0                          # void slots of the ring, as far as check_bounds() has been told
+        self._win_updates = 0
 
         if train_targets is not None:
             if train_targets.dim() == 1:
@@ -134,6 +158,11 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         self.num_outputs = num_outputs
         if robust_c is not None and num_outputs > 1:
             raise NotImplementedError("robust_c is implemented for a single output (the robust absorb weights one target per point)")
+        if window is not None and num_outputs > 1:
+            raise NotImplementedError("window is implemented for a single output (the ring stores one target per point)")
+        if window is not None and (int(num_path_probes) > 0 or (kernel_cache is not None and "path_probes" in kernel_cache)):
+            raise NotImplementedError("window does not combine with path probes (num_path_probes > 0): a probe increment is random and "
+                                      "cannot be taken out again from the ring")
         _batch_shape = torch.Size([num_outputs]) if num_outputs > 1 else torch.Size()
         # probe vectors of the posterior sample paths (sample_paths): S of them, rounded up to even (the generator
         # makes Box-Muller pairs); they live in the kernel cache beside b and follow it through every hand-over
@@ -189,8 +218,16 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
 
         if kernel_cache is None:
             self._kernel_cache = self._fresh_cache()
-            self._absorb(self._kernel_cache, train_inputs, train_targets, train_noise_term, init=True)
+            if window is not None:
+                self._kernel_cache["_ring"] = grid_ops.WindowRing(window, self._grid.d, dtype, device)
+                self._window_restart(train_inputs, train_targets, train_noise_term)
+            else:
+                self._absorb(self._kernel_cache, train_inputs, train_targets, train_noise_term, init=True)
         else:
+            if window is not None and (kernel_cache.get("_ring") is None or kernel_cache["_ring"].cap != window):
+                raise ValueError(f"window={window}, but the kernel cache handed over carries "
+                                 + ("no ring: statistics do not remember their points" if kernel_cache.get("_ring") is None
+                                    else f"a ring of {kernel_cache['_ring'].cap} slots"))
             self._kernel_cache = kernel_cache
             facs = kernel_cache.get("_spectral")
             if facs:
@@ -257,6 +294,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         new = self._pack_cache(cache["interpolation_cache"].clone(), stats, new_ops, cnt)
         if "path_probes" in cache:                      # a child's increments never reach the parent's buffer
             new.update(path_probes=cache["path_probes"].clone(), path_seed=cache["path_seed"], path_count=cache["path_count"])
+        if cache.get("_ring") is not None:              # the window's points follow the statistics they are the points of
+            new["_ring"] = cache["_ring"].clone()
         facs = cache.get("_spectral")
         if facs:
             new["_spectral"] = {o: fac.clone() for o, fac in facs.items() if fac.ref is not None and not fac.stale}
@@ -300,6 +339,9 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         if self.robust_c is not None and half_delta is not None:
             raise NotImplementedError("robust_c does not follow the data-parallel statistics exchange (half_delta): the Huber weights of a "
                                       "shard would be taken on one rank and the other ranks' followers never see them")
+        if self.window is not None and half_delta is not None:
+            raise NotImplementedError("window does not follow the data-parallel statistics exchange (half_delta): the ring of a replica "
+                                      "would hold its own shard only, and what leaves must leave every replica")
         self._finish_pending()
         if cache is self._kernel_cache:
             self.leave_stencil_shard()               # the generic absorb writes every group
@@ -440,6 +482,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         if self._wsum_dirty:
             self._wsum_dev_host = self._wsum_dev.tolist()
             self._wsum_dirty = False
+        if self.window is not None:                  # (a sum that points have left is zero up to rounding only)
+            return [max(0.0, h + d) for h, d in zip(self._wsum_host, self._wsum_dev_host)]
         return [h + d for h, d in zip(self._wsum_host, self._wsum_dev_host)]
 
     def check_bounds(self):
@@ -447,7 +491,19 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         grid (the kernels only set a device flag; this is the one host sync; the
         device part of the noise-weight sum rides on the same transfer)."""
         self._finish_pending()
-        if self._wsum_dirty:
+        if self.window is not None:
+            # the number of void slots that were overwritten rides on the same transfer: num_data is the ring's occupancy less the
+            # voids still in it (dropped at entry, not yet left)
+            ring = self._kernel_cache["_ring"]
+            vals = torch.cat([self._err.double(), ring.void_left.double(), self._wsum_dev]).tolist()
+            if self._wsum_dirty:
+                self._wsum_dev_host, self._wsum_dirty = vals[2:], False
+            flag, left = int(vals[0]), int(vals[1])
+            if left:
+                ring.void_left.zero_()
+                self._win_voids -= left
+                self.num_data = ring.fill - self._win_voids
+        elif self._wsum_dirty:
             vals = torch.cat([self._err.double(), self._wsum_dev]).tolist()
             self._wsum_dev_host, self._wsum_dirty = vals[1:], False
             flag = int(vals[0])
@@ -465,7 +521,19 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         self._err.zero_()
         self.__dict__.pop("_stream_step_cache", None)
         self._drop_spectral()          # rows of out-of-grid points were zero for the factor too, but a prepared state may be half-updated
-        if dropped:
+        if dropped and self.window is not None:
+            ring = self._kernel_cache["_ring"]
+            self._win_voids += dropped
+            self.num_data = ring.fill - self._win_voids
+            # the noise-weight sum is that of the ring (a void holds wa = 0): from now on the device keeps all of it
+            ring.unit[:] = False
+            ring.explicit.fill_(1)
+            ring.explicit_host[:] = True
+            self._wsum_host = [0.0]
+            self._wsum_dev = ring.wa.sum(dtype=torch.float64).reshape(1)
+            self._wsum_dirty = True
+            self._dump_caches()
+        elif dropped:
             self.num_data = self.num_data - dropped
             cnt = self._kernel_cache.get("_cnt")
             if cnt is not None:                       # row sums of W^T D^-1 W: sum_i cnt_i = sum over absorbed points of 1/noise
@@ -548,7 +616,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             if cnt is not None and wsum > 0:
                 c3 = cnt[o].reshape(self._grid.g).double()
                 margs = [c3.sum(dim=[r for r in range(self._grid.d) if r != q]) if self._grid.d > 1 else c3 for q in range(self._grid.d)]
-                margs = torch.stack([torch.nn.functional.pad(mg, (0, max(self._grid.g) - mg.numel())) for mg in margs]).cpu().numpy()
+                # (cnt of a cell whose points have all left a sliding window is zero up to rounding only: no negative density)
+                margs = torch.stack([torch.nn.functional.pad(mg, (0, max(self._grid.g) - mg.numel())) for mg in margs]).clamp_min(0).cpu().numpy()
                 if margs.max() > 0:
                     profiles, norm = [], 1.0
                     for q, gq in enumerate(self._grid.g):
@@ -626,6 +695,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         where the sharded step does not apply (then nothing changes): one output, native half stencil, m % 4 == 0, a grid beyond the
         dense regime.  Any d and both precisions: the d = 3 fp32 products run on the LDS-DMA kernel's part table, all others on
         the LDS-window kernel restricted to the replica's group range."""
+        if self.window is not None:
+            raise NotImplementedError("window does not combine with enter_stencil_shard: the window absorb writes every stencil group")
         op = _wtw_ops(self._kernel_cache["WtW"])[0]
         if (world <= 1 and not comm) or self.num_outputs != 1 or self._use_dense() or not op.is_half or self._grid.m % 4 or op.root is not None:
             return False
@@ -1075,12 +1146,19 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         ignores ``robust_c``: fantasised targets come from the model itself.  ``"noise"`` scaling (1 / sqrt(sigma2 noise_i)) presumes
         a model that already tracks the signal; ``"predictive"`` adds the posterior variance at X (one more solve).
 
+        With ``window=N`` set on the model, an unbatched batch enters the statistics and the model's ring of the last N points, and
+        the points whose slots it takes leave them again, in the same launch (``_absorb_window``): afterwards the model
+        is the GP of ``window_points()``, and ``num_data`` their number.  A batch larger than N is split on the host.  Fantasies
+        (batched X, ``get_fantasy_model``) add hypothetical points and retire nothing.
+
         ``grad_Y`` [n, d]: observations of the gradient of f at X, absorbed with the values in the same launch (DESIGN.md 3.15);
         ``Y=None`` then means gradient-only.  ``grad_noise`` [n, d] or [n]: their noise (None: the value observation's, or unit
         noise); ``grad_mask`` bool [n, d]: which partials were observed (None: all).  ``num_data`` grows by the number of scalar
         observations.  Single output, unbatched X."""
         if grad_Y is not None and self.robust_c is not None:
             raise NotImplementedError("robust_c weights value observations only: a model built with it takes no grad_Y")
+        if grad_Y is not None and self.window is not None:
+            raise NotImplementedError("window stores value observations only: a model built with it takes no grad_Y")
         if grad_Y is not None:
             return self._condition_on_gradients(X, Y, noise, inplace, _decay, grad_Y, grad_noise, grad_mask)
         if grad_noise is not None or grad_mask is not None:
@@ -1104,6 +1182,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             gamma = None
         if self.robust_c is not None:
             return self._condition_robust(X, Y, noise, inplace, gamma, q)
+        if self.window is not None and _decay:       # (_decay=False: a fantasy adds hypothetical points and retires nothing)
+            return self._condition_window(X, Y, noise, inplace)
         if gamma is not None and inplace:
             self.forget_(gamma)
         old_pc = None if gamma is not None else self._rank_update_source(q)      # (a rank-q update starts from the factor of the undecayed A)
@@ -1136,7 +1216,10 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             max_grid_size=self.max_grid_size,
             robust_c=self.robust_c,
             robust_scale=self.robust_scale,
+            window=self.window,
+            window_rebuild_every=self.window_rebuild_every,
         )
+        new_gp._win_voids, new_gp._win_updates = self._win_voids, self._win_updates
         new_gp._wsum_dev = self._wsum_dev.clone()
         new_gp._wsum_host = list(self._wsum_host)
         new_gp._wsum_dev_host = list(self._wsum_dev_host)
@@ -1321,6 +1404,141 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         self._wsum_add(0, n, wa_eff)
         if "path_probes" in cache:
             self._absorb_probes(cache, X, wa_eff)
+
+    # ------------------------------------------------------- sliding window --
+    def _condition_window(self, X, Y, noise, inplace):
+        """condition_on_observations of a model with window, once the grid has grown: the batch enters the statistics
+        and the ring, what the ring's slots held leaves.  The grid may grow under a window (grow_grid, a growing regrid_): the ring
+        holds coordinates, not node indices, so a stored point finds its nodes on the grown grid when it leaves -- which is also why
+        no node may be removed.  The functional form clones the ring with the cache."""
+        if inplace:
+            self._absorb_window(self._kernel_cache, X, Y, noise)
+            self._dump_caches()
+            self._window_rebuild_due()
+            return None
+        new_cache = self._clone_cache(self._kernel_cache)
+        new_gp = self._sibling(new_cache, self.num_data)
+        new_gp._absorb_window(new_cache, X, Y, noise)
+        self._sibling_mean_state(new_gp)
+        new_gp._window_rebuild_due()
+        return new_gp
+
+    def _window_rebuild_due(self):
+        self._win_updates += 1
+        if self.window_rebuild_every is not None and self._win_updates % self.window_rebuild_every == 0:
+            self.rebuild_window_()
+
+    def _window_restart(self, X, Y, noise):
+        """The statistics (zeroed by the caller) and the ring restart from the last `window` rows of (X, Y, noise), at the weights of a
+        model built from data (1 / noise, unfloored)."""
+        d = self._grid.d
+        X = X.reshape(-1, d)
+        Y = Y.reshape(X.shape[0], -1)
+        ring = self._kernel_cache["_ring"]
+        ring.clear()
+        self._win_voids = 0
+        lo = max(0, X.shape[0] - self.window)
+        self._absorb_window(self._kernel_cache, X[lo:], Y[lo:], None if noise is None else noise.reshape(X.shape[0], -1)[lo:], init=True)
+
+    def _absorb_window(self, cache, X, Y, noise, init=False):
+        """_absorb of one value-only batch through the ring, one launch per `window` points (wiski_scatter_stats_window): a batch larger
+        than the window is split on the host so that the slots of a launch are distinct.  The carried residual follows when the mean
+        state is current.  What cannot follow a point that leaves is given up rather than updated, as under a decay: a carried root
+        pair is dropped, the spectral factor marked stale (it rebuilds from the stencil, exactly), the two-level block lost, no rank
+        update prepared.  The noise-weight sum loses what left: on the host for the slots written at unit noise; for the others the
+        device part moves by the ring's wa over the launch's slots, after minus before -- O(batch) work, queued, no host read or copy."""
+        if self.num_outputs > 1:
+            raise NotImplementedError("window is implemented for a single output")
+        op = _wtw_ops(cache["WtW"])[0]
+        if not grid_ops.is_half_stencil(self._grid, op.stencil) or "_cnt" not in cache:
+            raise NotImplementedError("window needs the native half-stencil cache (a full stencil was handed over)")
+        ring = cache["_ring"]
+        self._finish_pending()
+        mine = cache is self._kernel_cache
+        if mine:
+            self.leave_stencil_shard()
+        X = X.reshape(-1, self._grid.d).to(self._device, self._dtype).contiguous()
+        y = Y.to(self._device, self._dtype).reshape(-1).contiguous()
+        n = X.shape[0]
+        unit = noise is None
+        no, wa, wb = self._batch_weights(None if unit else noise.to(self._device, self._dtype).reshape(-1).contiguous(), init, n)
+        ms = self._mean_state if mine else None
+        carry = not init and ms is not None and ms.get("R_ok", False) and settings.residual_carry_over.on()
+        if mine and self._mean_state is not None and not carry:
+            self._mean_state["R_ok"] = False
+        if carry:
+            u = ms["U"][0]
+        else:                                            # (the kernel takes both sweeps against some u; without res it goes nowhere)
+            u = self.__dict__.get("_win_zero_u")
+            if u is None or u.shape[0] != self._grid.m:
+                u = self.__dict__["_win_zero_u"] = torch.zeros(self._grid.m, dtype=self._dtype, device=self._device)
+        for lo in range(0, n, ring.cap):
+            hi = min(n, lo + ring.cap)
+            spans = ring.spans(hi - lo)
+            # what leaves the noise-weight sum: counted on the host for slots written at unit noise; for the others the ring's own wa,
+            # summed over the launch's slots BEFORE it overwrites them -- slices at host-known bounds, queued, never read back here
+            left_unit = sum(int(ring.unit[sl].sum()) for sl in spans)
+            left_dev = None
+            if any(bool(ring.explicit_host[sl].any()) for sl in spans):
+                left_dev = sum((ring.wa[sl] * ring.explicit[sl]).sum(dtype=torch.float64) for sl in spans)
+            self._wsum_host[0] += (float(hi - lo) if unit else 0.0) - float(left_unit)
+            ring.mark(spans, unit)
+            grid_ops.scatter_stats_window(self._grid, X[lo:hi], y[lo:hi], wa[lo:hi], wb[lo:hi], no[lo:hi], ring, cache["interpolation_cache"][0, :, 0],
+                                          op.stencil, cache["_cnt"][0], cache["_stats"][0], self._err, u, res=ms["R"][0] if carry else None)
+            if left_dev is not None or not unit:
+                delta = 0.0 if left_dev is None else -left_dev
+                if not unit:                             # what entered, as the ring now holds it (a point dropped at entry: 0)
+                    delta = delta + sum(ring.wa[sl].sum(dtype=torch.float64) for sl in spans)
+                self._wsum_dev[0] += delta
+                self._wsum_dirty = True
+        self.num_data = ring.fill - self._win_voids
+        if n == 0:
+            return
+        op.root = op.inv_root = None                     # L L^T described the matrix with the points that left
+        if mine:
+            self._two_level_lose()
+            for fac in self.__dict__.get("_spectral", {}).values():
+                fac.stale = True
+
+    def window_points(self):
+        """(X [k, d], Y [k], noise [k]) of the points the model is the GP of, oldest first; slots whose point was dropped at entry
+        (outside the grid) are omitted.  One host sync."""
+        if self.window is None:
+            raise RuntimeError("window_points: the model was built without window")
+        ring = self._kernel_cache["_ring"]
+        idx = torch.as_tensor(ring.order(), dtype=torch.long, device=self._device)
+        X = ring.x[idx]
+        keep = ~torch.isnan(X[:, 0])
+        return X[keep], ring.y[idx][keep], ring.noise[idx][keep]
+
+    def rebuild_window_(self):
+        """Zero the statistics and absorb the ring again, through the plain absorb (one launch): cancels the rounding that many
+        turnovers leave behind in fp32 (DESIGN.md 3.19 tabulates it) -- after it the statistics are those of a fresh model on
+        ``window_points()``.  Everything derived from A is rebuilt on next use; the next mean solve starts from the current mean but
+        recomputes its residual.  Returns the model."""
+        if self.window is None:
+            raise RuntimeError("rebuild_window_: the model was built without window")
+        self._finish_pending()
+        self.leave_stencil_shard()
+        cache = self._kernel_cache
+        ring = cache["_ring"]
+        op = _wtw_ops(cache["WtW"])[0]
+        for t in (cache["interpolation_cache"], cache["_stats"], cache["_cnt"], op.stencil):
+            t.zero_()
+        op.root = op.inv_root = None
+        # an empty or void slot holds no weight and noise 1: absorbed at any point inside the grid it adds nothing anywhere
+        dead = (ring.wa == 0) & (ring.wb == 0)
+        centre = torch.tensor([g0 + 0.5 * h * (g - 1) for g0, h, g in zip(self._grid.g0, self._grid.h, self._grid.g)], dtype=self._dtype, device=self._device)
+        X = torch.where(dead[:, None], centre[None, :], ring.x).contiguous()
+        grid_ops.scatter_stats_cnt(self._grid, X, ring.y, ring.wa, ring.wb, ring.noise, cache["interpolation_cache"][0, :, 0], op.stencil, True,
+                                   cache["_cnt"][0], cache["_stats"][0], self._err)
+        if self._mean_state is not None:
+            self._mean_state["R_ok"] = False
+        self._two_level_lose()
+        for fac in self.__dict__.get("_spectral", {}).values():
+            fac.stale = True
+        self._dump_caches()
+        return self
 
     def stream_step(self, X, Y, want_mean=True):
         """evaluate -> absorb -> refresh for one streamed batch (the reference driver's online step at batch granularity,
@@ -1556,7 +1774,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
 
     def _stream_fast_state(self, X, Y):
         """(prepared StreamStep, mean state, preconditioner state) when the one-call streaming step applies, else None."""
-        if (self.robust_c is not None or self.num_outputs != 1 or self._use_dense() or settings.spectral_preconditioner.off() or settings.residual_carry_over.off()
+        if (self.robust_c is not None or self.window is not None or self.num_outputs != 1 or self._use_dense() or settings.spectral_preconditioner.off() or settings.residual_carry_over.off()
                 or X.dim() != 2 or not X.is_cuda or X.dtype != self._dtype or not X.is_contiguous() or Y.dtype != self._dtype):
             return None
         ms = self._mean_state
@@ -1615,7 +1833,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         if look is None:
             c3 = cnt[0].reshape(g).double()
             margs = [c3.sum(dim=[r for r in range(self._grid.d) if r != q]) if self._grid.d > 1 else c3 for q in range(self._grid.d)]
-            margs = torch.stack([torch.nn.functional.pad(mg, (0, max(g) - mg.numel())) for mg in margs])
+            margs = torch.stack([torch.nn.functional.pad(mg, (0, max(g) - mg.numel())) for mg in margs]).clamp_min(0)
             host = self.__dict__.get("_profile_look_host")            # pinned once (a pinned allocation costs ~0.3 ms)
             if host is None or host.shape != margs.shape:
                 host = torch.empty(margs.shape, dtype=margs.dtype, pin_memory=True)
@@ -1826,6 +2044,9 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         bb = [gn - go - aq for gn, go, aq in zip(new.g, old.g, a)]
         if not any(a) and not any(bb):
             return self if drop == "zero" else (self, 0.0)
+        if self.window is not None and (any(v < 0 for v in a) or any(v < 0 for v in bb)):
+            raise NotImplementedError("window: regrid_ may only grow the grid -- a point of the ring whose nodes were removed could not "
+                                      "be taken out of the statistics again")
         self._finish_pending()
         self.leave_stencil_shard()
         cache = self._kernel_cache
@@ -1865,6 +2086,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             fresh.pop("_cnt")
         if new_P is not None:
             fresh.update(path_probes=new_P, path_seed=cache["path_seed"], path_count=cache["path_count"])
+        if cache.get("_ring") is not None:
+            fresh["_ring"] = cache["_ring"]              # coordinates, not node indices: the ring is the same on the grown grid
         self._drop_spectral()
         cache.clear()
         cache.update(fresh)
@@ -1926,6 +2149,9 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         gamma = float(gamma)
         if not (0.0 < gamma <= 1.0):
             raise ValueError(f"gamma must lie in (0, 1], got {gamma}")
+        if self.window is not None:
+            raise NotImplementedError("forget_ on a model with window: the ring keeps the weights its points entered with, and a point that "
+                                      "left after a decay would take out more than is still there -- the two are alternatives")
         if gamma != 1.0:
             if self.num_data is None:
                 raise RuntimeError("forget_ needs the number of absorbed points (log|D| moves by -n log gamma): hand num_data over with the kernel cache")
@@ -1994,8 +2220,11 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         self._wsum_dirty = False
         self._memo.pop("precond", None)
         self._drop_spectral()
-        self._absorb(cache, train_inputs, train_targets, noise, init=True)
-        self.num_data = train_inputs.reshape(-1, self._grid.d).shape[0]
+        if self.window is not None:
+            self._window_restart(train_inputs, train_targets, noise)     # the last `window` points only
+        else:
+            self._absorb(cache, train_inputs, train_targets, noise, init=True)
+            self.num_data = train_inputs.reshape(-1, self._grid.d).shape[0]
         self._mean_state = None
         self._dump_caches()
 
@@ -2022,6 +2251,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             self._kernel_cache = self._pack_cache(c["interpolation_cache"].to(device), stats, new_ops, c["_cnt"].to(device) if "_cnt" in c else None)
             if "path_probes" in c:
                 self._kernel_cache.update(path_probes=c["path_probes"].to(device), path_seed=c["path_seed"], path_count=c["path_count"])
+            if c.get("_ring") is not None:
+                self._kernel_cache["_ring"] = c["_ring"].to(device)
             self._device = torch.device(device)
             self._err = grid_ops.new_err_flag(device)
             self._mean_state = None

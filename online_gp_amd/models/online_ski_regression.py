@@ -2,7 +2,8 @@
 (counterpart of online_gp/models/online_ski_regression.py:16-197, experiments/regression.py:38-138):
 
     OnlineSKIRegression(stem, init_x, init_y, lr, grid_size, grid_bound, covar_module=None, **kw)
-        (**kw: num_path_probes, path_seed, forgetting_factor, grow_grid, max_grid_size, robust_c, robust_scale -- passed to the GP)
+        (**kw: num_path_probes, path_seed, forgetting_factor, grow_grid, max_grid_size, robust_c, robust_scale, window,
+        window_rebuild_every -- passed to the GP)
     .fit(x, y, num_epochs, test_dataset=None) -> list of per-epoch dicts
     .update(x, y, update_stem=True, update_gp=True) -> (stem_loss, gp_loss)
     .evaluate(x, y) -> (rmse, nll)        .predict(x) -> (mean [n, out], var [n, out])
@@ -42,6 +43,7 @@ class OnlineSKIRegression(StreamingSKIWrapper):
             forgetting_factor=kwargs.get("forgetting_factor"),
             grow_grid=kwargs.get("grow_grid", False), max_grid_size=kwargs.get("max_grid_size"),
             robust_c=kwargs.get("robust_c"), robust_scale=kwargs.get("robust_scale", "noise"),
+            window=kwargs.get("window"), window_rebuild_every=kwargs.get("window_rebuild_every"),
         )
         self._setup(stem, gp, lr, init_x)
 
