@@ -466,6 +466,31 @@ int wiski_scatter_stats_window_f64(const wiski_grid* grid, const double* d_x, co
 int wiski_absorb_window_f32(const wiski_grid* grid, const wiski_absorb_args* args, const wiski_window_ring* ring, int32_t* d_void_left, void* stream);
 int wiski_absorb_window_f64(const wiski_grid* grid, const wiski_absorb_args* args, const wiski_window_ring* ring, int32_t* d_void_left, void* stream);
 
+/* Interval and censored observations: y_p = f(x_p) + eps_p is only known to lie in [d_lo_p, d_hi_p].  Either end
+ * may be infinite (a one-sided bound: censored data, a probit label); lo == hi is an exact value.  Every point is moment-matched
+ * against the posterior BEFORE the batch, inside the launch that absorbs it (assumed-density filtering, all sites of a launch in
+ * parallel).  With mu = w_p . u, v = max(d_pvar_p, 0) the posterior variance of f at x_p, dn = sigma2 noise_p, s^2 = v + dn,
+ *   a = (lo - mu) / s,  b = (hi - mu) / s,  Z = Phi(b) - Phi(a),
+ *   alpha = (phi(a) - phi(b)) / (s Z),   beta = alpha^2 + (b phi(b) - a phi(a)) / (s^2 Z),
+ *   omega = min(1, dn beta / (1 - v beta)),   ytilde = mu + alpha / beta,
+ * evaluated in double in both precisions, and the point enters as the target ytilde at noise noise_p / omega_p: A, cnt and the
+ * carried residual with omega wa, b and sum wb y^2 with omega wb and ytilde, log|D| with log(noise / omega) -- so everything
+ * downstream is the exact GP of the pseudo-observations.  lo == hi gives ytilde = lo and omega = 1 exactly.  A point is SKIPPED --
+ * it enters nothing and is not flagged in d_err -- when omega < 1e-12 (WISKI_INTERVAL_OMEGA_MIN: (-inf, inf), a bound satisfied
+ * by many standard deviations), when beta is not positive and finite, when lo > hi or when a bound is NaN.
+ * Outputs, [n] each: d_ytilde_out (mu for a skipped point), d_omega_out (0 for a skipped point), d_logz_out (double in both
+ * precisions): log Z, the log predictive probability of the interval -- the Gaussian log density for lo == hi, -inf for lo > hi,
+ * NaN for a NaN bound.  A point outside the grid is flagged, counted and dropped as everywhere and reports (0, 0, 0).
+ * Arguments otherwise as wiski_scatter_stats_robust, without d_y.  Required: d_hi, d_pvar, d_u, d_A_half, d_cnt, the three
+ * outputs and a finite sigma2 > 0; d_res and d_mean_out are optional.  Symmetric half stencil, atomic form, one output, d = 1..4;
+ * anything else is WISKI_E_BADARG before a launch.  As with the robust form wiski_absorb_args has NOT grown: wiski_absorb_interval
+ * takes the record (its d_y is ignored) plus the interval arguments, so that every combination absorb_validate refuses (a guard,
+ * zero regions, a shard, an owner workspace, nout > 1, channels, a full stencil) can be reached and tested. */
+int wiski_scatter_stats_interval_f32(const wiski_grid* grid, const float* d_x, const float* d_lo, const float* d_hi, const float* d_pvar, double sigma2, const float* d_wa, const float* d_wb, const float* d_noise, int64_t n, float* d_b, float* d_A_half, float* d_cnt, const float* d_u, float* d_res, float* d_mean_out, double* d_stats, int32_t* d_err, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, void* stream);
+int wiski_scatter_stats_interval_f64(const wiski_grid* grid, const double* d_x, const double* d_lo, const double* d_hi, const double* d_pvar, double sigma2, const double* d_wa, const double* d_wb, const double* d_noise, int64_t n, double* d_b, double* d_A_half, double* d_cnt, const double* d_u, double* d_res, double* d_mean_out, double* d_stats, int32_t* d_err, double* d_ytilde_out, double* d_omega_out, double* d_logz_out, void* stream);
+int wiski_absorb_interval_f32(const wiski_grid* grid, const wiski_absorb_args* args, const float* d_lo, const float* d_hi, const float* d_pvar, double sigma2, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, void* stream);
+int wiski_absorb_interval_f64(const wiski_grid* grid, const wiski_absorb_args* args, const double* d_lo, const double* d_hi, const double* d_pvar, double sigma2, double* d_ytilde_out, double* d_omega_out, double* d_logz_out, void* stream);
+
 /* The two halves of a stencil-sharded step on their own (wiski_stream_step uses them when args->shard is set): the absorb
  * restricted to the stencil groups [g_lo, g_hi) (same arguments as wiski_scatter_stats_step; always the atomic form), and
  * wiski_pcg_async with every A . v product summed over the ranks of `shard`. */

@@ -3,10 +3,10 @@
 // may be asked to do, as ONE named record.  Every member defaults to "off"; the extern "C" entry points of scatter_stats.hip
 // and the streaming step (stream_step.hip) fill the fields they expose and call absorb().  Which combinations are refused is
 // absorb_validate() in scatter_stats.hip; whoever writes another form of the absorb has to honour every group below.
-// Four kernels stand behind it: the atomic form (k_scatter_stats[_sym]; the owner form where its workspace is given and applies),
-// the derivative-observation form (`channels`, scatter_grad.h), the outlier-robust form (`inv_scale`, scatter_robust.h) and the
-// sliding-window form (`ring_*`, scatter_window.h).  The last three implement the plain single-output half-stencil absorb with cnt
-// and the carry and refuse every other group.  What the four half-stencil kernels do per point -- the tap tables, the per-tap
+// Five kernels stand behind it: the atomic form (k_scatter_stats[_sym]; the owner form where its workspace is given and applies),
+// the derivative-observation form (`channels`, scatter_grad.h), the outlier-robust form (`inv_scale`, scatter_robust.h), the
+// sliding-window form (`ring_*`, scatter_window.h) and the interval form (`lo`, scatter_interval.h).  The last four implement the
+// plain single-output half-stencil absorb with cnt and the carry and refuse every other group.  What the five half-stencil kernels do per point -- the tap tables, the per-tap
 // atomics, the pair loop that encodes the row-interleaved layout, the two scalars -- is stated once, in scatter_half.h.
 #pragma once
 #include "wiski_common.h"
@@ -81,9 +81,22 @@ struct AbsorbArgs {
   real* ring_noise = nullptr;       // [ring_cap]
   int64_t ring_cap = 0, ring_head = 0;
   int32_t* void_left = nullptr;     // += number of overwritten slots that were void
+  // interval: lo != NULL makes every point an interval observation lo <= f(x) + eps <= hi, moment-matched against the posterior
+  // before the batch (scatter_interval.h): with mu = w_p . u, v = pvar, dn = sigma2 noise the site (ytilde, omega) follows from the
+  // Gaussian mass of [lo, hi] under N(mu, v + dn), and the point enters as the target ytilde at noise / omega; y is ignored.  A
+  // site with omega < WISKI_INTERVAL_OMEGA_MIN, lo > hi or a NaN bound is skipped: nothing anywhere, omega_out = 0, no flag in err.
+  // Needs hi, pvar, u, A, cnt, the three outputs and a finite sigma2 > 0; res and mean_out stay optional.  Single-output
+  // half-stencil atomic form only: no channels, inv_scale, ring, guard, zero regions, shard or owner workspace
+  const real* lo = nullptr;         // [n] lower ends (-inf: none)
+  const real* hi = nullptr;         // [n] upper ends (+inf: none); lo == hi: an exact value
+  const real* pvar = nullptr;       // [n] posterior variance of f at the point before the batch, in the units of y^2 (negative: 0)
+  double sigma2 = 0;                // the noise scale: the point's noise variance is sigma2 noise
+  real* ytilde_out = nullptr;       // [n] the pseudo-target each point entered with; the predictive mean for a skipped point
+  double* logz_out = nullptr;       // [n] log P(lo <= y <= hi) under the posterior before the batch  (omega_out: the robust group's field)
 
   bool sharded() const { return g_lo > 0 || g_hi < (1 << 30); }
   bool windowed() const { return ring_x || ring_y || ring_wa || ring_wb || ring_noise || ring_cap || ring_head || void_left; }
+  bool interval() const { return lo || hi || pvar || sigma2 != 0 || ytilde_out || logz_out; }
 };
 
 // Validates, then queues the absorb on `stream`: WISKI_OK, WISKI_E_BADARG (nothing was launched) or WISKI_E_LAUNCH.

@@ -176,6 +176,7 @@ __global__ __launch_bounds__(256) void k_scatter_stats_sym(GridDev<real> G, cons
 #include "scatter_grad.h"
 #include "scatter_robust.h"
 #include "scatter_window.h"
+#include "scatter_interval.h"
 
 // Unpacks the row-interleaved half stencil into a full offset-major stencil full[o][i] = A[i, i + off(o)]
 // (diagnostics, tests, and models handed a full-stencil cache):
@@ -243,7 +244,17 @@ static int64_t owner_min_points() {
 template <typename real>
 static int absorb_validate(const AbsorbArgs<real>& a, int d) {
   if (a.n == 0) return WISKI_OK;                       // nothing to absorb: not even the pointers are looked at
-  if (!a.x || !a.y || !a.wa || !a.wb || !a.noise || !a.b || !a.stats || !a.err) return WISKI_E_BADARG;   // what every form reads and writes
+  if (!a.x || (!a.y && !a.lo) || !a.wa || !a.wb || !a.noise || !a.b || !a.stats || !a.err) return WISKI_E_BADARG;   // what every form reads and writes (the interval form has no y)
+  if (a.interval()) {
+    // interval (scatter_interval.h): the whole group; the sites need u; A, cnt and the three outputs are written unconditionally;
+    // the plain single-output half-stencil atomic form only, and neither the robust nor the window one.  res and mean_out are optional
+    if (!a.lo || !a.hi || !a.pvar || !a.ytilde_out || !a.omega_out || !a.logz_out) return WISKI_E_BADARG;
+    if (!(a.sigma2 > 0) || !std::isfinite(a.sigma2)) return WISKI_E_BADARG;
+    if (!a.u || !a.half || !a.A || !a.cnt || a.nout != 1 || a.channels) return WISKI_E_BADARG;
+    if (a.inv_scale || a.huber_c != (real)0 || a.windowed()) return WISKI_E_BADARG;
+    if (a.guard || a.n1_bytes || a.n2_bytes || a.z1 || a.z2 || a.sharded() || a.bin || a.bin_bytes) return WISKI_E_BADARG;
+    return WISKI_OK;
+  }
   if (a.windowed()) {
     // window (scatter_window.h): a whole ring with head inside it and no more entering points than slots, so that the slots of
     // the launch are distinct; u, A, cnt and void_left are used unconditionally; the plain single-output half-stencil atomic
@@ -357,6 +368,7 @@ int absorb(const wiski_grid* grid, const AbsorbArgs<real>& a, void* stream) {
   int rc = make_grid_dev<real>(grid, &G);
   if (rc == WISKI_OK) rc = absorb_validate(a, G.d);
   if (rc != WISKI_OK || a.n == 0) return rc;
+  if (a.interval()) return launch_interval(G, a, (hipStream_t)stream);
   if (a.windowed()) return launch_window(G, a, (hipStream_t)stream);
   if (a.inv_scale) return launch_robust(G, a, (hipStream_t)stream);
   if (a.channels) return launch_grad(G, a, (hipStream_t)stream);
@@ -441,6 +453,22 @@ static int entry_absorb_window(const wiski_grid* g, const wiski_absorb_args* p, 
   return p ? entry_window(g, absorb_args<real>(*p), r, void_left, s) : WISKI_E_BADARG;
 }
 template <typename real>
+static int entry_interval(const wiski_grid* g, AbsorbArgs<real> a, const real* lo, const real* hi, const real* pvar, double sigma2, real* ytilde_out, real* omega_out, double* logz_out, void* s) {
+  a.y = nullptr;                                       // ignored by the form
+  a.lo = lo; a.hi = hi; a.pvar = pvar; a.sigma2 = sigma2; a.ytilde_out = ytilde_out; a.omega_out = omega_out; a.logz_out = logz_out;
+  return lo ? absorb(g, a, s) : WISKI_E_BADARG;
+}
+template <typename real>
+static int entry_scatter_interval(const wiski_grid* g, const real* x, const real* lo, const real* hi, const real* pvar, double sigma2, const real* wa, const real* wb, const real* noise, int64_t n, real* b, real* A_half, real* cnt, const real* u, real* res, real* mean_out, double* stats, int32_t* err, real* ytilde_out, real* omega_out, double* logz_out, void* s) {
+  AbsorbArgs<real> a = absorb_args(x, (const real*)nullptr, wa, wb, noise, n, b, A_half, true, stats, err);
+  absorb_carry(a, cnt, u, res, mean_out);
+  return entry_interval(g, a, lo, hi, pvar, sigma2, ytilde_out, omega_out, logz_out, s);
+}
+template <typename real>
+static int entry_absorb_interval(const wiski_grid* g, const wiski_absorb_args* p, const real* lo, const real* hi, const real* pvar, double sigma2, real* ytilde_out, real* omega_out, double* logz_out, void* s) {
+  return p ? entry_interval(g, absorb_args<real>(*p), lo, hi, pvar, sigma2, ytilde_out, omega_out, logz_out, s) : WISKI_E_BADARG;
+}
+template <typename real>
 static int entry_plain(const wiski_grid* g, const real* x, const real* y, const real* wa, const real* wb, const real* noise, int64_t n, real* b, real* A, bool half, double* stats, int32_t* err, void* s) {
   return absorb(g, absorb_args(x, y, wa, wb, noise, n, b, A, half, stats, err), s);
 }
@@ -482,6 +510,10 @@ int wiski_scatter_stats_window_f32(const wiski_grid* g, const float* x, const fl
 int wiski_scatter_stats_window_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, const wiski_window_ring* ring, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, int32_t* void_left, void* s) { return entry_scatter_window(g, x, y, wa, wb, noise, n, ring, b, A_half, cnt, u, res, mean_out, stats, err, void_left, s); }
 int wiski_absorb_window_f32(const wiski_grid* g, const wiski_absorb_args* p, const wiski_window_ring* ring, int32_t* void_left, void* s) { return entry_absorb_window<float>(g, p, ring, void_left, s); }
 int wiski_absorb_window_f64(const wiski_grid* g, const wiski_absorb_args* p, const wiski_window_ring* ring, int32_t* void_left, void* s) { return entry_absorb_window<double>(g, p, ring, void_left, s); }
+int wiski_scatter_stats_interval_f32(const wiski_grid* g, const float* x, const float* lo, const float* hi, const float* pvar, double sigma2, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return entry_scatter_interval(g, x, lo, hi, pvar, sigma2, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, ytilde_out, omega_out, logz_out, s); }
+int wiski_scatter_stats_interval_f64(const wiski_grid* g, const double* x, const double* lo, const double* hi, const double* pvar, double sigma2, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return entry_scatter_interval(g, x, lo, hi, pvar, sigma2, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, ytilde_out, omega_out, logz_out, s); }
+int wiski_absorb_interval_f32(const wiski_grid* g, const wiski_absorb_args* p, const float* lo, const float* hi, const float* pvar, double sigma2, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return entry_absorb_interval(g, p, lo, hi, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
+int wiski_absorb_interval_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* lo, const double* hi, const double* pvar, double sigma2, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return entry_absorb_interval(g, p, lo, hi, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
 int wiski_scatter_stats_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A, double* stats, int32_t* err, void* s) { return entry_plain(g, x, y, wa, wb, noise, n, b, A, false, stats, err, s); }
 int wiski_scatter_stats_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A, double* stats, int32_t* err, void* s) { return entry_plain(g, x, y, wa, wb, noise, n, b, A, false, stats, err, s); }
 int wiski_scatter_stats_sym_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, double* stats, int32_t* err, void* s) { return entry_plain(g, x, y, wa, wb, noise, n, b, A_half, true, stats, err, s); }

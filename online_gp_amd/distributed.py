@@ -378,8 +378,12 @@ class ShardedStatsUpdater:
                 self._delta["_cnt"].zero_()
         return self._delta
 
-    def update(self, X, Y, noise=None):
+    def update(self, X, Y, noise=None, *, lower=None, upper=None):
         from . import grid_ops
+
+        if lower is not None or upper is not None:
+            # the sites of a shard would be matched on one rank, and the other ranks' followers never see them: single-GPU for now
+            raise NotImplementedError("ShardedStatsUpdater does not carry interval observations (lower / upper): condition the model itself")
         from .models.batched_fixed_noise_online_gp import _wtw_ops
 
         m = self.model

@@ -458,6 +458,35 @@ def scatter_stats_robust(grid, x, y, wa, wb, noise, inv_scale, c, b, A_half, cnt
     return omega
 
 
+def scatter_stats_interval(grid, x, lower, upper, pvar, sigma2, wa, wb, noise, b, A_half, cnt, stats, err, u, res=None, mean_out=None):
+    """The interval-observation absorb in ONE launch (``wiski_scatter_stats_interval``): point i says
+    lower_i <= f(x_i) + eps_i <= upper_i (either end may be infinite; equal ends are an exact value).  It is moment-matched against
+    the posterior before the batch -- the grid mean ``u`` [m], the posterior variance ``pvar`` [n] of f at x, the noise
+    ``sigma2 * noise`` -- and enters (b, A_half, cnt, stats) -- and the carried residual ``res``, if given -- as the target ytilde_i
+    at noise_i / omega_i.  Returns (ytilde [n], omega [n], log_z [n] float64); a skipped point (nothing to say: omega below 1e-12,
+    lower > upper, a NaN bound) has omega = 0 and ytilde = w . u, a point outside the grid (0, 0, 0).  ``mean_out`` [n] receives w . u."""
+    x = _x2d(x, grid)
+    n = x.shape[0]
+    for name, t in (("lower", lower), ("upper", upper), ("pvar", pvar), ("wa", wa), ("wb", wb), ("noise", noise), ("mean_out", mean_out)):
+        if t is not None and (tuple(t.shape) != (n,) or t.dtype != x.dtype):
+            raise ValueError(f"scatter_stats_interval: {name} must be [{n}] {x.dtype}, got {tuple(t.shape)} {t.dtype}")
+    if u is None or tuple(u.shape) != (grid.m,) or u.dtype != x.dtype:
+        raise ValueError(f"scatter_stats_interval: u must be the grid mean [{grid.m}] {x.dtype}")
+    ytilde = torch.empty(n, dtype=x.dtype, device=x.device)
+    omega = torch.empty(n, dtype=x.dtype, device=x.device)
+    log_z = torch.empty(n, dtype=torch.float64, device=x.device)
+    if n == 0:
+        return ytilde, omega, log_z
+    rc = _hip.fn("wiski_scatter_stats_interval", x.dtype)(grid.ref, _hip.dptr(x), _hip.dptr(lower.contiguous()), _hip.dptr(upper.contiguous()),
+                                                          _hip.dptr(pvar.contiguous()), ctypes.c_double(float(sigma2)), _hip.dptr(wa.contiguous()),
+                                                          _hip.dptr(wb.contiguous()), _hip.dptr(noise.contiguous()), ctypes.c_int64(n), _hip.dptr(b),
+                                                          _hip.dptr(A_half), _hip.dptr(cnt), _hip.dptr(u), _hip.dptr(res), _hip.dptr(mean_out),
+                                                          _hip.dptr(stats), _hip.dptr(err), _hip.dptr(ytilde), _hip.dptr(omega), _hip.dptr(log_z),
+                                                          _hip.stream_ptr(x.device))
+    _hip.check(rc, "wiski_scatter_stats_interval")
+    return ytilde, omega, log_z
+
+
 class WindowRing:
     """The device-resident ring of a sliding window (``wiski_window_ring``): x [cap, d], y / wa / wb / noise [cap]
     in the working precision, and on the host ``head`` -- the slot the next entering point takes -- and ``fill``, the number of

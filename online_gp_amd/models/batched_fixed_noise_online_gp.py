@@ -74,6 +74,17 @@ def _default_tol(dtype):
     return 1e-6 if dtype == torch.float32 else 1e-10
 
 
+def interval_from_labels(labels):
+    """(lower, upper) of binary labels for the probit use of interval observations (DESIGN.md 3.20): a label in {0, 1} or {-1, +1}
+    says f(x) + eps > 0 (positive) or < 0, eps of unit noise -- a one-sided interval at 0.  Pass them to
+    ``condition_on_observations(X, None, noise=torch.ones(n), lower=lower, upper=upper)``."""
+    labels = torch.as_tensor(labels)
+    pos = labels > 0
+    dtype = labels.dtype if labels.is_floating_point() else torch.get_default_dtype()
+    zero = torch.zeros(labels.shape, dtype=dtype, device=labels.device)
+    return torch.where(pos, zero, zero - float("inf")), torch.where(pos, zero + float("inf"), zero)
+
+
 class FixedNoiseOnlineSKIGP(torch.nn.Module):
     def __init__(
         self,
@@ -119,6 +130,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         self.robust_c = robust_c
         self.robust_scale = robust_scale
         self.last_robust_weights = None              # omega [q] of the last robustly absorbed batch, on the device
+        # interval observations (_absorb_interval): (ytilde, omega, log_z) [q] of the last batch given as bounds
+        self.last_interval_sites = None
         # sliding window (_absorb_window): the model is the GP of exactly the last `window` points; every update absorbs
         # its batch, stores it in a device-resident ring and takes out what the ring's slots held, in one launch
         if window is not None:
@@ -1133,7 +1146,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         return post
 
     # -------------------------------------------------------------- updates --
-    def condition_on_observations(self, X, Y, noise=None, inplace=False, _decay=True, *, grad_Y=None, grad_noise=None, grad_mask=None):
+    def condition_on_observations(self, X, Y, noise=None, inplace=False, _decay=True, *, grad_Y=None, grad_noise=None, grad_mask=None,
+                                  lower=None, upper=None):
         """a7, :258-285.  inplace: the statistics buffers are updated where they
         live (O(4^{2d}) atomics per point); otherwise they are cloned first and a
         sibling model sharing covar_module / likelihood is returned.  With a ``forgetting_factor`` the statistics -- of the clone,
@@ -1154,7 +1168,19 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         ``grad_Y`` [n, d]: observations of the gradient of f at X, absorbed with the values in the same launch (DESIGN.md 3.15);
         ``Y=None`` then means gradient-only.  ``grad_noise`` [n, d] or [n]: their noise (None: the value observation's, or unit
         noise); ``grad_mask`` bool [n, d]: which partials were observed (None: all).  ``num_data`` grows by the number of scalar
-        observations.  Single output, unbatched X."""
+        observations.  Single output, unbatched X.
+
+        ``lower`` / ``upper`` [n] with ``Y=None``: interval and censored observations, lower_i <= f(x_i) + eps_i <= upper_i -- a missing
+        side is -inf / +inf, equal ends are an exact value (``_condition_interval``).  Every point is moment-matched
+        against the posterior before the batch (after growing and decaying) and absorbed as the pseudo-target ytilde_i at noise
+        ``noise_i / omega_i`` in the same launch; ``last_interval_sites`` -- of the returned model, in the functional form -- then
+        holds ``(ytilde, omega, log_z)``.  This is parallel assumed-density filtering: an approximation of the non-Gaussian
+        posterior, whose MLL is the Gaussian MLL of the pseudo-data; ``log_z.sum()`` is the prequential evidence of the batch.  A
+        point with nothing to say (omega = 0) enters nothing and does not count in ``num_data``.  Single output, unbatched X."""
+        if lower is not None or upper is not None:
+            if grad_Y is not None or grad_noise is not None or grad_mask is not None:
+                raise NotImplementedError("interval observations bound values only: lower / upper take no grad_Y")
+            return self._condition_interval(X, Y, noise, lower, upper, inplace, _decay)
         if grad_Y is not None and self.robust_c is not None:
             raise NotImplementedError("robust_c weights value observations only: a model built with it takes no grad_Y")
         if grad_Y is not None and self.window is not None:
@@ -1404,6 +1430,131 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         self._wsum_add(0, n, wa_eff)
         if "path_probes" in cache:
             self._absorb_probes(cache, X, wa_eff)
+
+    # ------------------------------------------------ interval observations --
+    def _condition_interval(self, X, Y, noise, lower, upper, inplace, _decay):
+        """condition_on_observations with lower / upper: grow, decay, moment-match, absorb.  The sites are taken
+        against the posterior of the statistics the batch is added to -- the decayed ones under forgetting."""
+        if Y is not None:
+            raise NotImplementedError("a batch is given as targets Y or as bounds lower / upper, not both (an exact value is lower == upper)")
+        if self.num_outputs > 1:
+            raise NotImplementedError("interval observations are implemented for a single output")
+        if self.robust_c is not None:
+            raise NotImplementedError("interval observations do not combine with robust_c: a site is a weight already, and no kernel applies both")
+        if self.window is not None:
+            raise NotImplementedError("interval observations do not combine with window: the ring stores targets, and a site depends on the "
+                                      "posterior it was matched against")
+        if X.dim() > 2:
+            raise NotImplementedError("batched conditioning (fantasies) takes targets, not bounds")
+        d = self._grid.d
+        X = X.reshape(-1, d)
+        n = X.shape[0]
+        inf = float("inf")
+        lo = torch.full((n,), -inf, dtype=self._dtype, device=self._device) if lower is None else lower.to(self._device, self._dtype).reshape(-1)
+        hi = torch.full((n,), inf, dtype=self._dtype, device=self._device) if upper is None else upper.to(self._device, self._dtype).reshape(-1)
+        if lo.shape[0] != n or hi.shape[0] != n:
+            raise ValueError(f"lower / upper must hold one bound per point ([{n}]), got {tuple(lo.shape)} and {tuple(hi.shape)}")
+        if noise is not None:
+            noise = noise.to(self._device, self._dtype).reshape(-1)
+            if noise.shape[0] != n:
+                raise ValueError(f"noise must hold one value per point ([{n}]), got {tuple(noise.shape)}")
+        if self.grow_grid:
+            self.grow_to_cover_(X)
+        gamma = self.forgetting_factor if _decay else None
+        if gamma == 1.0:
+            gamma = None
+        if inplace:
+            if gamma is not None:
+                self.forget_(gamma)
+            entered = self._absorb_interval(self._kernel_cache, X, lo, hi, noise, self)
+            self.num_data = self.num_data + entered
+            self._dump_caches()
+            return None
+        new_cache = self._clone_cache(self._kernel_cache)
+        new_gp = self._sibling(new_cache, self.num_data)
+        src = self                                   # without a decay the clone's posterior is this model's, usually already solved
+        if gamma is not None:
+            new_gp._decay(gamma, self.num_data)          # the clone's buffers: the parent keeps its statistics bit for bit
+            self._sibling_mean_state(new_gp)             # (warm start of the solve the sites need)
+            src = new_gp
+        new_gp.num_data = self.num_data + new_gp._absorb_interval(new_cache, X, lo, hi, noise, src)
+        new_gp._dump_caches()                            # (the prediction cache the sites were read from predates the batch)
+        if src is self:
+            self._sibling_mean_state(new_gp)
+        elif not self.training:
+            new_gp.eval()
+        return new_gp
+
+    def _absorb_interval(self, cache, X, lo, hi, noise, src, half_delta=None):
+        """_absorb of one batch of interval observations, one launch (wiski_scatter_stats_interval).  `src`: the model whose posterior
+        the sites are matched against -- this one, or in the functional form without a decay the parent, whose statistics the clone
+        still equals: its grid mean from the prediction cache and its posterior variance at X (one more solve on the paths every
+        posterior call takes).  Everything that follows the stream point by point receives the effective weights wa omega, wb omega
+        and the pseudo-targets: a carried root pair, the spectral factor, the path probes, the noise-weight sum.  The two-level block
+        is given up and the dense rank-update seed is skipped, as in _absorb_robust.  Returns the number of points num_data grows by:
+        those that entered, and those outside the grid (which _raise_out_of_bounds takes off again when the flag is read)."""
+        if half_delta is not None:
+            raise NotImplementedError("interval observations do not follow the data-parallel statistics exchange (half_delta): the sites of "
+                                      "a shard would be matched on one rank and the other ranks' followers never see them")
+        op = _wtw_ops(cache["WtW"])[0]
+        if not grid_ops.is_half_stencil(self._grid, op.stencil) or "_cnt" not in cache:
+            raise NotImplementedError("interval observations need the native half-stencil cache (a full stencil was handed over)")
+        X = X.reshape(-1, self._grid.d).to(self._device, self._dtype).contiguous()
+        n = X.shape[0]
+        no, wa, wb = self._batch_weights(None if noise is None else noise.contiguous(), False, n)
+        u = src.prediction_cache["pred_mean"][0, :, 0]       # (finishes whatever is pending, leaves a stencil shard)
+        with torch.no_grad(), settings.skip_posterior_variances(False):
+            pvar = src._eval_forward(X).variance.reshape(-1).to(self._dtype).contiguous()
+        self._finish_pending()
+        self.leave_stencil_shard()
+        ms = self._mean_state if src is self else None
+        carry = ms is not None and ms.get("R_ok", False) and settings.residual_carry_over.on() and ms["U"][0].data_ptr() == u.data_ptr()
+        if self._mean_state is not None and not carry:
+            self._mean_state["R_ok"] = False
+        flag0 = self._err.clone()
+        sites = grid_ops.scatter_stats_interval(self._grid, X, lo.contiguous(), hi.contiguous(), pvar, self._sigma2(0), wa, wb, no,
+                                                cache["interpolation_cache"][0, :, 0], op.stencil, cache["_cnt"][0], cache["_stats"][0], self._err, u,
+                                                res=ms["R"][0] if carry else None)
+        self.last_interval_sites = sites
+        if n == 0:
+            return 0
+        yt, omega, _ = sites
+        wa_eff, wb_eff = wa * omega, wb * omega              # a skipped point, a point outside the grid: omega = 0, nothing anywhere
+        self._two_level_lose()                               # (its block is rebuilt from the stencil where one is wanted again)
+        if getattr(op, "root", None) is not None:
+            Wd = grid_ops.wt_columns(self._grid, X, self._err)
+            op.update_roots_((Wd * wa_eff.sqrt()[:, None]).t().contiguous())
+        self._spectral_absorb(0, X, wa_eff, yt * wb_eff)
+        self._wsum_add(0, n, wa_eff)
+        if "path_probes" in cache:
+            self._absorb_probes(cache, X, wa_eff)
+        entered, dropped = torch.stack([(omega > 0).sum(), (self._err - flag0).reshape(-1)[0] >> 1]).tolist()
+        return int(entered) + int(dropped)
+
+    def interval_probability(self, X, lower, upper, noise=None):
+        """log P(lower_i <= f(x_i) + eps_i <= upper_i) [n] under the current posterior, eps_i ~ N(0, sigma2 noise_i) (``noise`` None:
+        unit noise); either bound may be None or infinite.  Plain torch on the posterior's mean and variance: the Gaussian mass of
+        the interval through ``torch.special.log_ndtr``, mirrored so that the difference is taken in the lower tail."""
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad(), settings.skip_posterior_variances(False):
+                mvn = self(X.to(self._device, self._dtype))
+                mean, var = mvn.mean.reshape(-1).double(), mvn.variance.reshape(-1).double()
+        finally:
+            if was_training:
+                self.train()
+        n = mean.shape[0]
+        inf = float("inf")
+        lo = torch.full((n,), -inf, dtype=torch.float64, device=mean.device) if lower is None else lower.to(mean.device, torch.float64).reshape(-1)
+        hi = torch.full((n,), inf, dtype=torch.float64, device=mean.device) if upper is None else upper.to(mean.device, torch.float64).reshape(-1)
+        dn = self._sigma2(0) * (1.0 if noise is None else noise.to(mean.device, torch.float64).reshape(-1))
+        s = (var.clamp_min(0.0) + dn).sqrt()
+        a, b = (lo - mean) / s, (hi - mean) / s
+        flip = a + b > 0
+        a, b = torch.where(flip, -b, a), torch.where(flip, -a, b)
+        la, lb = torch.special.log_ndtr(a), torch.special.log_ndtr(b)
+        return lb + torch.log1p(-torch.exp(la - lb))
 
     # ------------------------------------------------------- sliding window --
     def _condition_window(self, X, Y, noise, inplace):
