@@ -175,6 +175,24 @@ int wiski_wt_columns_jet_f64(const wiski_grid* grid, const double* d_x, int64_t 
 int wiski_gather_jet_f32(const wiski_grid* grid, const float* d_x, int64_t n, const float* d_V, int32_t k, int32_t rows_per_point, float* d_out, int32_t* d_err, void* stream);
 int wiski_gather_jet_f64(const wiski_grid* grid, const double* d_x, int64_t n, const double* d_V, int32_t k, int32_t rows_per_point, double* d_out, int32_t* d_err, void* stream);
 
+/* Box functionals c_b = int_box w(x) dx (csrc/box_rows.h): the Kronecker product of d per-dimension integrated rows.  Boxes d_lo, d_hi
+ * [B][d].  A box is clipped to the grid's extent (w = 0 outside); a dimension with lo == hi evaluates at that coordinate instead of
+ * integrating (its row is the value row of wiski_wt_columns, bit for bit, and its factor of the volume is 1).  A box not wholly
+ * inside the grid sets bit 0 of *d_err; a NaN bound or lo > hi also gives a zero row.  All three: B = 0 is a no-op; a null pointer,
+ * k < 1, rows_per_box < 0 or nsplit outside 1 .. 65535 is WISKI_E_BADARG without a launch.
+ * wiski_box_tables: d_tab [B][sum_q g_q] the per-dimension rows (every entry written, evaluated in fp64 and rounded once), d_range
+ *   [B][d][2] the node range [first, end) of each row's support, d_vol [B] the clipped volume (0 when nothing of the box is inside). */
+int wiski_box_tables_f32(const wiski_grid* grid, const float* d_lo, const float* d_hi, int64_t B, float* d_tab, int32_t* d_range, float* d_vol, int32_t* d_err, void* stream);
+int wiski_box_tables_f64(const wiski_grid* grid, const double* d_lo, const double* d_hi, int64_t B, double* d_tab, int32_t* d_range, double* d_vol, int32_t* d_err, void* stream);
+/* wiski_wt_columns_box: row b of the caller-zeroed d_out [B][m] receives c_b (plain stores over the support). */
+int wiski_wt_columns_box_f32(const wiski_grid* grid, const float* d_tab, const int32_t* d_range, int64_t B, float* d_out, void* stream);
+int wiski_wt_columns_box_f64(const wiski_grid* grid, const double* d_tab, const int32_t* d_range, int64_t B, double* d_out, void* stream);
+/* wiski_gather_box: rows_per_box = 0: d_V [k][m] is shared by all boxes, d_out[b][j] = c_b . d_V[j], d_out [B][k].  rows_per_box = R >= 1:
+ *   d_V [B R][m], d_out[b][j] = c_b . d_V[b R + j], d_out [B][R] (k is not used beyond k >= 1).  fp64 accumulation.  nsplit blocks share
+ *   the support of each (box, row); nsplit > 1 needs the workspace d_part [B rows][nsplit] doubles and adds a small second launch. */
+int wiski_gather_box_f32(const wiski_grid* grid, const float* d_tab, const int32_t* d_range, int64_t B, const float* d_V, int32_t k, int32_t rows_per_box, int32_t nsplit, double* d_part, float* d_out, void* stream);
+int wiski_gather_box_f64(const wiski_grid* grid, const double* d_tab, const int32_t* d_range, int64_t B, const double* d_V, int32_t k, int32_t rows_per_box, int32_t nsplit, double* d_part, double* d_out, void* stream);
+
 /* replaces WtW._matmul (URLT:47-48) on the stencil form:
  * d_out[c] = beta * d_add[c] + A_st . d_V[c]   (d_add may be NULL). */
 int wiski_stencil_spmv_f32(const wiski_grid* grid, const float* d_A_st, const float* d_V, int32_t k, const float* d_add, float beta, float* d_out, void* stream);

@@ -143,6 +143,7 @@ __global__ __launch_bounds__(256) void k_gather_ell(const int32_t* __restrict__ 
 
 #include "gather_ell_dma.h"
 #include "jet_rows.h"
+#include "box_rows.h"
 
 // ------------------------------------------------------------- W^T columns --
 // out[p][idx] += val for the T taps of query p (one dense m-column per query).

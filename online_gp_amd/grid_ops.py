@@ -785,6 +785,73 @@ def gather_jet(grid, x, V, err, rows_per_point=0):
     return out
 
 
+class BoxTables:
+    """Per-dimension integrated rows of B boxes (``wiski_box_tables``): ``tab`` [B, sum g_q], ``range`` int32 [B, d, 2] (the node range
+    of each row's support), ``vol`` [B] (the clipped volume).  ``tables[s:e]`` is the same for a run of the boxes."""
+
+    def __init__(self, tab, range_, vol):
+        self.tab, self.range, self.vol = tab, range_, vol
+        self.B = tab.shape[0]
+
+    def __getitem__(self, sl):
+        assert isinstance(sl, slice) and sl.step in (None, 1)
+        return BoxTables(self.tab[sl], self.range[sl], self.vol[sl])
+
+
+def box_tables(grid, lower, upper, err):
+    """Tables of the box functionals c_b = int_[lower_b, upper_b] w(x) dx for bounds [B, d] (``wiski_box_tables``)."""
+    lo, hi = _x2d(lower, grid), _x2d(upper, grid)
+    if lo.shape != hi.shape or lo.dtype != hi.dtype or lo.device != hi.device:
+        raise ValueError(f"lower {tuple(lo.shape)} {lo.dtype} and upper {tuple(hi.shape)} {hi.dtype} must match")
+    B = lo.shape[0]
+    tab = torch.empty((B, sum(grid.g)), dtype=lo.dtype, device=lo.device)
+    rng = torch.empty((B, grid.d, 2), dtype=torch.int32, device=lo.device)
+    vol = torch.empty((B,), dtype=lo.dtype, device=lo.device)
+    rc = _hip.fn("wiski_box_tables", lo.dtype)(grid.ref, _hip.dptr(lo), _hip.dptr(hi), ctypes.c_int64(B), _hip.dptr(tab), _hip.dptr(rng), _hip.dptr(vol),
+                                              _hip.dptr(err), _hip.stream_ptr(lo.device))
+    _hip.check(rc, "wiski_box_tables")
+    return BoxTables(tab, rng, vol)
+
+
+def wt_columns_box(grid, tables):
+    """The box functionals as dense columns: [B, m] (``wiski_wt_columns_box``)."""
+    tab = tables.tab
+    out = torch.zeros((tables.B, grid.m), dtype=tab.dtype, device=tab.device)
+    rc = _hip.fn("wiski_wt_columns_box", tab.dtype)(grid.ref, _hip.dptr(tab), _hip.dptr(tables.range), ctypes.c_int64(tables.B), _hip.dptr(out),
+                                                    _hip.stream_ptr(tab.device))
+    _hip.check(rc, "wiski_wt_columns_box")
+    return out
+
+
+BOX_GATHER_BLOCKS = 2048      # blocks that a box gather aims for: eight per compute unit of an MI355X
+
+
+def box_gather_nsplit(grid, pairs):
+    """Blocks per (box, row) of ``gather_box``: enough for BOX_GATHER_BLOCKS in all, at most one per 1024 entries of a domain-sized
+    support (256 lanes, four entries each) -- the host does not know the boxes' sizes, a small box leaves its extra blocks idle."""
+    return max(1, min(-(-BOX_GATHER_BLOCKS // max(int(pairs), 1)), -(-grid.m // 1024)))
+
+
+def gather_box(grid, tables, V, rows_per_box=0, nsplit=None):
+    """``wiski_gather_box``: out[b, j] = c_b . V[j] for V [k, m] shared by all boxes (rows_per_box = 0; [B, k]), or c_b . V[b R + j] for
+    V [B R, m] (rows_per_box = R; [B, R]).  nsplit: blocks per (box, row), ``box_gather_nsplit`` by default."""
+    tab = tables.tab
+    V = V.contiguous()
+    if V.dim() == 1:
+        V = V[None]
+    B, R = tables.B, int(rows_per_box)
+    assert V.shape[1] == grid.m and V.dtype == tab.dtype and (R == 0 or V.shape[0] == B * R)
+    k = R if R > 0 else V.shape[0]
+    out = torch.empty((B, k), dtype=tab.dtype, device=tab.device)
+    ns = box_gather_nsplit(grid, B * k) if nsplit is None else int(nsplit)
+    part = torch.empty((B * k * ns,), dtype=torch.float64, device=tab.device) if ns > 1 and B > 0 else None
+    rc = _hip.fn("wiski_gather_box", tab.dtype)(grid.ref, _hip.dptr(tab), _hip.dptr(tables.range), ctypes.c_int64(B), _hip.dptr(V),
+                                                ctypes.c_int32(max(k, 1)), ctypes.c_int32(R), ctypes.c_int32(ns), _hip.dptr(part), _hip.dptr(out),
+                                                _hip.stream_ptr(tab.device))
+    _hip.check(rc, "wiski_gather_box")
+    return out
+
+
 def is_half_stencil(grid, A_st):
     """True for the symmetric half-stencil layout [(R+1)/2, m], False for the full [R, m] one."""
     rows = A_st.shape[-2]

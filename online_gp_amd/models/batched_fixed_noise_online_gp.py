@@ -1145,6 +1145,43 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         post.cg_iters = op.cg_iters
         return post
 
+    def posterior_integral(self, lower, upper, joint=False, average=False):
+        """Gaussian posterior of the integral of ``f`` over the boxes ``[lower_b, upper_b]`` ([B, d] each): an
+        :class:`~online_gp_amd.lazy.quadrature.IntegralPosterior` with ``mean`` [B], ``variance`` [B], ``volume`` [B] and, with ``joint``,
+        the [B, B] ``covariance`` between the boxes.  Exact under the SKI model, one solve column per box whatever its size.  A
+        dimension with ``lower == upper`` is evaluated at that coordinate instead of integrated (line and plane integrals, marginal
+        curves; a box degenerate in every dimension is ``posterior`` at that point).  The interpolant is zero outside the grid, so
+        a box is clipped to the grid's extent -- and, as a point outside the grid does, a box not wholly inside raises unless
+        ``settings.deferred_bounds_check`` is on.  ``average``: the mean is divided by the clipped volume and the covariance by the
+        volumes' outer product (a box of zero clipped volume has mean 0 and variance 0).  Answered through the prediction cache in
+        every regime.  Outputs are detached.  One output, unbatched bounds.  The bounds are checked in the precision they are given
+        in and then cast to the model's: a box that the cast would collapse in some dimension (narrower than one ulp of the model's dtype)
+        is refused with ``ValueError`` rather than silently evaluated instead of integrated."""
+        from ..lazy.quadrature import BoxCovariance, IntegralPosterior, check_bounds_host, scale_by_volume
+
+        if self.num_outputs > 1:
+            raise NotImplementedError("posterior_integral is implemented for a single output")
+        grid = self._grid
+        lo, hi = check_bounds_host(lower, upper, grid.d, "posterior_integral", self._device, self._dtype)
+        with torch.no_grad():
+            pc = self.prediction_cache
+            tables = grid_ops.box_tables(grid, lo, hi, self._err)
+            mean = grid_ops.gather_box(grid, tables, pc["pred_mean"][0, :, 0])[:, 0]
+            if settings.deferred_bounds_check.off():
+                flag = grid_ops.read_flag(self._err)
+                if flag:
+                    self._raise_out_of_bounds(flag)
+            sigma2 = self._hyper()[0][1] if self.has_learnable_noise else 1.0
+            op = BoxCovariance(pc["pred_cov"], tables, sigma2, self._err, chunk=settings.variance_chunk.value())
+            cov = op.joint() if joint else op.diag()
+            if average:
+                s = scale_by_volume(tables.vol)
+                mean = mean * s
+                cov = cov * s[:, None] * s[None, :] if joint else cov * s * s
+        post = IntegralPosterior(mean, cov, tables.vol, joint)
+        post.cg_iters = op.cg_iters
+        return post
+
     # -------------------------------------------------------------- updates --
     def condition_on_observations(self, X, Y, noise=None, inplace=False, _decay=True, *, grad_Y=None, grad_noise=None, grad_mask=None,
                                   lower=None, upper=None):

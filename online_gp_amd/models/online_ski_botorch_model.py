@@ -77,6 +77,11 @@ class OnlineSKIBotorchModel(FixedNoiseOnlineSKIGP):
         self.eval()
         return super().posterior_jet(X.to(self._dtype), joint=joint)
 
+    def posterior_integral(self, lower, upper, joint=False, average=False):
+        """Posterior of the integral (or average) of f over boxes [B, d] (``FixedNoiseOnlineSKIGP.posterior_integral``)."""
+        self.eval()
+        return super().posterior_integral(lower, upper, joint=joint, average=average)      # (cast there, after the checks in the caller's precision)
+
     def posterior(self, X, observation_noise=False, **kwargs):
         self.eval()
         X = X.to(self._dtype)

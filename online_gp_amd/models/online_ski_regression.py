@@ -75,6 +75,17 @@ class OnlineSKIRegression(StreamingSKIWrapper):
         jet = self.gp.posterior_jet(self._as_rows(inputs))
         return jet.grad_mean, jet.grad_covariance
 
+    def predict_integral(self, lower, upper, joint=False, average=False):
+        """Posterior of the integral (``average``: the mean value) of the latent function over the boxes [lower_b, upper_b] ([B, d] each): the
+        ``IntegralPosterior`` of the GP's ``posterior_integral``.  Only with the ``Identity`` stem: behind a learned stem a box of inputs
+        is not a box of features."""
+        from .stems import Identity
+
+        if not isinstance(self.stem, Identity):
+            raise NotImplementedError("predict_integral needs the Identity stem (the GP integrates over its own inputs)")
+        self._ensure_eval()
+        return self.gp.posterior_integral(lower, upper, joint=joint, average=average)
+
     def evaluate(self, inputs, targets):
         """(rmse, nll): means over batches of 1024 of the per-batch RMSE and mean Gaussian NLL; one host sync."""
         inputs = self._as_rows(inputs)

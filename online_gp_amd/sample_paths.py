@@ -53,6 +53,22 @@ class GridSamplePaths:
         self._check()
         return out.t().reshape((self.num_paths,) + lead)
 
+    def integrate(self, lower, upper, average=False):
+        """Integral of every path over the boxes [lower_b, upper_b] ([B, d] each): [num_paths, B] -- exact for the
+        path f = w^T u, so consistent with its point evaluations; ``average`` divides by the volume of the box clipped to the grid's
+        extent.  A dimension with lower == upper is evaluated, not integrated.  Detached; a box not wholly inside the grid raises as a
+        point outside does."""
+        from .lazy.quadrature import check_bounds_host, scale_by_volume
+
+        lo, hi = check_bounds_host(lower, upper, self.grid.d, "integrate", self.values.device, self.values.dtype)
+        with torch.no_grad():
+            tables = grid_ops.box_tables(self.grid, lo, hi, self._err)
+            out = grid_ops.gather_box(self.grid, tables, self.values.detach())          # [B, num_paths]
+            if average:
+                out = out * scale_by_volume(tables.vol)[:, None]
+        self._check()
+        return out.t()
+
     def max_values(self, candidates):
         """max over the candidate points [..., d] of every path: [num_paths] (the discrete max-value sample of each path)."""
         with torch.no_grad():
