@@ -355,9 +355,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         if self.window is not None and half_delta is not None:
             raise NotImplementedError("window does not follow the data-parallel statistics exchange (half_delta): the ring of a replica "
                                       "would hold its own shard only, and what leaves must leave every replica")
-        self._finish_pending()
-        if cache is self._kernel_cache:
-            self.leave_stencil_shard()               # the generic absorb writes every group
+        mine = self._before_launch(cache)            # the generic absorb writes every group
         X = X.reshape(-1, self._grid.d).to(self._device, self._dtype).contiguous()
         Y = Y.to(self._device, self._dtype)
         if Y.dim() == 1:
@@ -373,7 +371,6 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         # residual carry-over: while the posterior-mean state (U, Z, R = b - Z - A U) is current, the scatter
         # keeps R exact under the increment, and the next refresh starts without an A U product
         ms = self._mean_state
-        mine = cache is self._kernel_cache
         if (mine or half_delta is not None) and self.num_outputs == 1:
             if half_delta is not None:
                 # the increment arrives by all-reduce: other ranks' points never pass here.  The updater hands the gathered coordinates over
@@ -387,12 +384,9 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
                     self._two_level_lose()
             else:
                 self._two_level_note(X, None if unit else self._weight_a(noise[:, 0], init), init=init)
-        carry = (mine and half_delta is None and not init and ms is not None and ms.get("R_ok", False)
-                 and settings.residual_carry_over.on())
         carry_delta = (half_delta is not None and res_delta is not None and not init and ms is not None and ms.get("R_ok", False)
                        and settings.residual_carry_over.on())
-        if mine and ms is not None and not carry:
-            ms["R_ok"] = False
+        carry = self._carried(mine, init or half_delta is not None) is not None
         if getattr(self, "_scratch_stats", None) is None:
             self._scratch_stats = torch.zeros(2, dtype=torch.float64, device=self._device)
         if half_delta is None and self._absorb_all_outputs(cache, X, Y, noise, init, ops, ms if carry else None):
@@ -413,17 +407,86 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
                 # the stencil is being rebuilt (set_train_data) or receives its increment later, after an all-reduce
                 # (data-parallel path): a carried root pair would describe the OLD matrix -- drop it, it is re-derived on demand
                 ops[o].root = ops[o].inv_root = None
-            if half_delta is None and getattr(ops[o], "root", None) is not None and n > 0:
-                # the reference's root pair, once somebody asked for it: L L^T follows A by a rank-n root update (URLT:62-119)
-                Wd = grid_ops.wt_columns(self._grid, X, self._err)                 # [n, m]
-                ops[o].update_roots_((Wd * wa.sqrt()[:, None]).t().contiguous())   # V = W^T diag(wa)^(1/2), BFN:163-168
-            if mine and n > 0:
-                self._spectral_absorb(o, X, None if unit else wa, yo if unit else yo * wb, init=init, bypass=half_delta is not None)
-            if mine or init:
-                self._wsum_add(o, n, None if unit else wa)
-        if "path_probes" in cache:                   # (single output: `wa` is the weight the points just entered A with)
-            self._absorb_probes(cache, X, None if unit else wa, init)
+            self._follow(cache, o, X, None if unit else wa, yo if unit else yo * wb, init=init, bypass=half_delta is not None)
         return carry_delta
+
+    # ---- what an absorb owes the things that follow the statistics: stated once, used by every observation form ----
+    def _before_launch(self, cache):
+        """Before a launch writes into `cache`: nothing is in flight, and the model's own stencil is whole (the launches of the
+        absorb forms write every group).  Returns whether `cache` is the model's own."""
+        self._finish_pending()
+        mine = cache is self._kernel_cache
+        if mine:
+            self.leave_stencil_shard()
+        return mine
+
+    def _native_half_op(self, cache, form, half_delta=None):
+        """The half-stencil operator of `cache` for a form whose launch writes the statistics themselves: a single output, the
+        native half-stencil cache with its row sums, no data-parallel exchange -- refused otherwise, in the form's name."""
+        if half_delta is not None:
+            raise NotImplementedError(f"{form}: no data-parallel statistics exchange (half_delta) -- the launch takes its weights on one rank "
+                                      "and writes the statistics themselves: there is no increment to all-reduce, and the other ranks' "
+                                      "followers would never see the weights")
+        if self.num_outputs > 1:
+            raise NotImplementedError(f"{form}: implemented for a single output")
+        op = _wtw_ops(cache["WtW"])[0]
+        if not grid_ops.is_half_stencil(self._grid, op.stencil) or "_cnt" not in cache:
+            raise NotImplementedError(f"{form}: the native half-stencil cache is needed (a full stencil was handed over)")
+        return op
+
+    def _canon_batch(self, X, y, noise, init=False):
+        """A single-output batch as the absorb kernels take it: (X [n, d], y [n] or None, noise, wa, wb) on the model's device, in its
+        dtype, contiguous; noise None: unit noise (_batch_weights)."""
+        X = X.reshape(-1, self._grid.d).to(self._device, self._dtype).contiguous()
+        if y is not None:
+            y = y.to(self._device, self._dtype).reshape(-1).contiguous()
+        if noise is not None:
+            noise = noise.to(self._device, self._dtype).reshape(-1).contiguous()
+        return (X, y) + self._batch_weights(noise, init, X.shape[0])
+
+    def _carried(self, mine, init=False, u=None):
+        """The carried-residual decision of a launch into the model's own cache (`mine`): the mean state whose R = b - Z - A U the
+        launch keeps exact under its increment -- it is current, the statistics are not being rebuilt (`init`), and, where the
+        launch reads a grid mean `u` of its own, that is this state's U itself -- or None, and then the state's residual is marked
+        as no longer carried (the next refresh recomputes it)."""
+        ms = self._mean_state
+        if ms is None:
+            return None
+        if (mine and not init and ms.get("R_ok", False) and settings.residual_carry_over.on()
+                and (u is None or ms["U"][0].data_ptr() == u.data_ptr())):
+            return ms
+        if mine:
+            ms["R_ok"] = False
+        return None
+
+    def _follow(self, cache, o, X, wa, wby, init=False, bypass=False):
+        """Follower policy "follow": every point of X has entered A of output o with the effective weight wa (None: unit) and b with
+        wby = wb_eff * y_eff.  Everything that follows the stream point by point receives the same: a carried root pair, the
+        spectral factor, the noise-weight sum, the path probes.  bypass: the increment reaches the stencil later, by all-reduce."""
+        n, mine = X.shape[0], cache is self._kernel_cache
+        op = _wtw_ops(cache["WtW"])[o]
+        if not bypass and getattr(op, "root", None) is not None and n > 0:
+            # the reference's root pair, once somebody asked for it: L L^T follows A by a rank-n root update (URLT:62-119)
+            Wd = grid_ops.wt_columns(self._grid, X, self._err)                                       # [n, m]
+            op.update_roots_((Wd if wa is None else Wd * wa.sqrt()[:, None]).t().contiguous())       # V = W^T diag(wa)^(1/2), BFN:163-168
+        if mine and n > 0:
+            self._spectral_absorb(o, X, wa, wby, init=init, bypass=bypass)
+        if mine or init:
+            self._wsum_add(o, n, wa)
+        if "path_probes" in cache:                   # (single output)
+            self._absorb_probes(cache, X, wa, init)
+
+    def _give_up(self, cache):
+        """Follower policy "give up": the launch changed A by something that cannot be followed point by point (a derivative row, a
+        point that left, a scaling).  A carried root pair is dropped (L L^T described the matrix before), and for the model's own
+        cache the two-level block is lost and the spectral factors are marked stale: each is rebuilt from the stencil, exactly,
+        where it is wanted again.  (On the factor, not the model: it travels with the kernel cache.)"""
+        for op in _wtw_ops(cache["WtW"]):
+            op.root = op.inv_root = None
+        if cache is self._kernel_cache:
+            self._two_level_lose()
+            for fac in self.__dict__.get("_spectral", {}).values():
+                fac.stale = True
 
     def _absorb_probes(self, cache, X, wa, init=False):
         """Every point that enters A enters the probes P with the same weight wa (None: unit) and its global index, so that
@@ -447,7 +510,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         pack = self._stencil_pack(ops)
         if pack is None:
             return False
-        unit, mine = noise is None, cache is self._kernel_cache
+        unit = noise is None
         Yt = Y.t().contiguous()                                   # [out, n]
         no, wa, wb = self._batch_weights(None if unit else noise.t().contiguous(), init, n)
         b = cache["interpolation_cache"][:, :, 0]
@@ -455,11 +518,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             return False
         grid_ops.scatter_stats_multi(self._grid, X, Yt, wa, wb, no, b, pack, cache["_cnt"], cache["_stats"], self._err,
                                      u=ms["U"] if ms else None, res=ms["R"] if ms else None)
-        for o in range(out):
-            if mine:
-                self._spectral_absorb(o, X, None if unit else wa[o], Yt[o] if unit else Yt[o] * wb[o], init=init)
-            if mine or init:
-                self._wsum_add(o, n, None if unit else wa[o])
+        for o in range(out):                                       # (no root pair, no probes: the spectral factor and the weight sum)
+            self._follow(cache, o, X, None if unit else wa[o], Yt[o] if unit else Yt[o] * wb[o], init=init)
         return True
 
     def _ones(self, n):
@@ -1240,29 +1300,65 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         q = X.reshape(-1, self._grid.d).shape[0]
         if self.grow_grid:
             self.grow_to_cover_(X)                   # (exact: the functional form grows this model too, its posterior does not move)
-        gamma = self.forgetting_factor if _decay else None
-        if gamma == 1.0:
-            gamma = None
+        gamma = self._gamma(_decay)
         if self.robust_c is not None:
-            return self._condition_robust(X, Y, noise, inplace, gamma, q)
+            # weigh, absorb: the weights are taken against the posterior of the statistics the batch is added to
+            return self._condition(lambda model, cache, src: model._absorb_robust(cache, X, Y, noise, src), inplace, gamma, reads_posterior=True)
         if self.window is not None and _decay:       # (_decay=False: a fantasy adds hypothetical points and retires nothing)
-            return self._condition_window(X, Y, noise, inplace)
-        if gamma is not None and inplace:
-            self.forget_(gamma)
+            # the batch enters the statistics and the ring, what the ring's slots held leaves.  The grid may grow
+            # under a window (grow_grid, a growing regrid_): the ring holds coordinates, not node indices, so a stored point finds its
+            # nodes on the grown grid when it leaves -- which is also why no node may be removed.  The functional form clones the ring
+            # with the cache
+            new_gp = self._condition(lambda model, cache, src: model._absorb_window(cache, X, Y, noise), inplace, None)
+            (self if inplace else new_gp)._window_rebuild_due()
+            return new_gp
         old_pc = None if gamma is not None else self._rank_update_source(q)      # (a rank-q update starts from the factor of the undecayed A)
+
+        def absorb(model, cache, src):
+            model._absorb(cache, X, Y, noise, init=False)
+            return q
+
+        new_gp = self._condition(absorb, inplace, gamma)
+        self._seed_rank_updated_cache(self if inplace else new_gp, old_pc, X, noise, Y)
+        return new_gp
+
+    def _gamma(self, decay=True):
+        """The factor an update decays the statistics by before it absorbs its batch, or None: no forgetting_factor, a factor of
+        one, or an update that is a what-if on the current state (decay False: fantasies)."""
+        gamma = self.forgetting_factor if decay else None
+        return None if gamma == 1.0 else gamma
+
+    def _condition(self, absorb, inplace, gamma, reads_posterior=False):
+        """The skeleton of condition_on_observations, for every observation form.  `absorb(model, cache, src)` absorbs the form's batch
+        into `cache`, the kernel cache of `model`, and returns what num_data grows by (None: the form keeps the count itself, as the
+        window does from its ring).  In place: decay, absorb, count, dump the caches.  Functional: the same on a sibling model with a
+        clone of the cache -- the clone's buffers decay, the parent keeps its statistics bit for bit -- which then starts its mean
+        solve warm from a copy of this model's state, in this model's mode, and is returned.
+        reads_posterior: the form takes weights or sites against the posterior of the statistics the batch is added to, that of `src`.
+        In place that is this model.  Functional without a decay it is this model too, whose statistics the clone still equals and
+        whose posterior is usually already solved; after a decay it is the sibling, which therefore gets its warm start before the
+        absorb instead of after it."""
         if inplace:
-            self._absorb(self._kernel_cache, X, Y, noise, init=False)
-            self.num_data = self.num_data + q
+            if gamma is not None:
+                self.forget_(gamma)
+            grown = absorb(self, self._kernel_cache, self)
+            if grown is not None:
+                self.num_data = self.num_data + grown
             self._dump_caches()
-            self._seed_rank_updated_cache(self, old_pc, X, noise, Y)
             return None
         new_cache = self._clone_cache(self._kernel_cache)
-        new_gp = self._sibling(new_cache, self.num_data + q)
+        new_gp = self._sibling(new_cache, self.num_data)
         if gamma is not None:
             new_gp._decay(gamma, self.num_data)          # the clone's buffers: the parent keeps its statistics bit for bit
-        new_gp._absorb(new_cache, X, Y, noise, init=False)
-        self._sibling_mean_state(new_gp)
-        self._seed_rank_updated_cache(new_gp, old_pc, X, noise, Y)
+        warm_first = reads_posterior and gamma is not None
+        if warm_first:
+            self._sibling_mean_state(new_gp)             # (warm start of the solve the weights / sites need)
+        grown = absorb(new_gp, new_cache, new_gp if warm_first else self)
+        if grown is not None:
+            new_gp.num_data = self.num_data + grown
+        new_gp._dump_caches()                            # (a prediction cache the weights / sites were read from predates the batch)
+        if not warm_first:
+            self._sibling_mean_state(new_gp)
         return new_gp
 
     def _sibling(self, new_cache, num_data):
@@ -1335,87 +1431,38 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         q = n * (d + 1 if Y is not None else d) if grad_mask is None else int(present.sum())     # scalar observations
         if self.grow_grid:
             self.grow_to_cover_(X)
-        gamma = self.forgetting_factor if _decay else None
-        if gamma == 1.0:
-            gamma = None
-        if inplace:
-            if gamma is not None:
-                self.forget_(gamma)
-            self._absorb_grad(self._kernel_cache, X, Yc, Nc, present)
-            self.num_data = self.num_data + q
-            self._dump_caches()
-            return None
-        new_cache = self._clone_cache(self._kernel_cache)
-        new_gp = self._sibling(new_cache, self.num_data + q)
-        if gamma is not None:
-            new_gp._decay(gamma, self.num_data)
-        new_gp._absorb_grad(new_cache, X, Yc, Nc, present)
-        self._sibling_mean_state(new_gp)
-        return new_gp
+
+        def absorb(model, cache, src):
+            model._absorb_grad(cache, X, Yc, Nc, present)
+            return q
+
+        return self._condition(absorb, inplace, self._gamma(_decay))
 
     def _absorb_grad(self, cache, X, Yc, Nc, present, half_delta=None):
         """_absorb for [n, d + 1] channel tensors (values Yc, noises Nc, bool present), one launch (wiski_scatter_stats_grad).  The
         carried residual follows when the mean state is current.  What a derivative row cannot be followed through is given up
         rather than updated: the spectral factor is marked stale (it rebuilds from the stencil, exactly), the two-level block is
         lost, a carried root pair is dropped, and no rank update is prepared."""
-        if half_delta is not None:
-            raise NotImplementedError("derivative observations do not follow the data-parallel statistics exchange (half_delta)")
-        if self.num_outputs > 1 or "path_probes" in cache:
-            raise NotImplementedError("derivative observations: single output, no path probes")
-        op = _wtw_ops(cache["WtW"])[0]
-        if not grid_ops.is_half_stencil(self._grid, op.stencil) or "_cnt" not in cache:
-            raise NotImplementedError("derivative observations need the native half-stencil cache (a full stencil was handed over)")
-        self._finish_pending()
-        mine = cache is self._kernel_cache
-        if mine:
-            self.leave_stencil_shard()
+        op = self._native_half_op(cache, "derivative observations", half_delta)
+        if "path_probes" in cache:
+            raise NotImplementedError("derivative observations: no path probes (they follow value rows only)")
+        mine = self._before_launch(cache)
         zero, one = torch.zeros((), dtype=self._dtype, device=self._device), torch.ones((), dtype=self._dtype, device=self._device)
         wb = torch.where(present, 1.0 / Nc, zero)
         wa = torch.where(present, self._weight_a(Nc, False), zero)
         no = torch.where(present, Nc, one)               # an absent channel: wa = wb = 0, noise = 1 -- nothing anywhere
         Yc = torch.where(present, Yc, zero)
-        ms = self._mean_state
-        carry = mine and ms is not None and ms.get("R_ok", False) and settings.residual_carry_over.on()
-        if mine and ms is not None and not carry:
-            ms["R_ok"] = False
+        ms = self._carried(mine)
         grid_ops.scatter_stats_grad(self._grid, X, Yc, wa, wb, no, cache["interpolation_cache"][0, :, 0], op.stencil, cache["_cnt"][0],
-                                    cache["_stats"][0], self._err, u=ms["U"][0] if carry else None, res=ms["R"][0] if carry else None)
-        op.root = op.inv_root = None                     # L L^T described the matrix without these rows
+                                    cache["_stats"][0], self._err, u=ms["U"][0] if ms else None, res=ms["R"][0] if ms else None)
+        self._give_up(cache)                             # L L^T described the matrix without these rows
         if mine:
-            self._two_level_lose()
-            for fac in self.__dict__.get("_spectral", {}).values():
-                fac.stale = True
             # the noise-weight sum (preconditioner shift only) is the mass of cnt, to which a derivative channel adds its diagonal
             self._wsum_dev = cache["_cnt"].sum(dim=1, dtype=torch.float64)
             self._wsum_host = [0.0] * self.num_outputs
             self._wsum_dirty = True
 
     # ------------------------------------------------- outlier-robust absorb --
-    def _condition_robust(self, X, Y, noise, inplace, gamma, q):
-        """condition_on_observations of a model with robust_c, once the grid has grown: decay, weigh, absorb.  The
-        weights are taken against the posterior of the statistics the batch is added to -- the decayed ones under forgetting."""
-        if inplace:
-            if gamma is not None:
-                self.forget_(gamma)
-            self._absorb_robust(self._kernel_cache, X, Y, noise, self)
-            self.num_data = self.num_data + q
-            self._dump_caches()
-            return None
-        new_cache = self._clone_cache(self._kernel_cache)
-        new_gp = self._sibling(new_cache, self.num_data + q)
-        src = self                                   # without a decay the clone's posterior is this model's, usually already solved
-        if gamma is not None:
-            new_gp._decay(gamma, self.num_data)          # the clone's buffers: the parent keeps its statistics bit for bit
-            self._sibling_mean_state(new_gp)             # (warm start of the solve the weights need)
-            src = new_gp
-        new_gp._absorb_robust(new_cache, X, Y, noise, src)
-        new_gp._dump_caches()                            # (the prediction cache the weights were read from predates the batch)
-        if src is self:
-            self._sibling_mean_state(new_gp)
-        elif not self.training:
-            new_gp.eval()
-        return new_gp
-
     def _robust_inputs(self, X, noise):
         """(u [m], inv_scale [n]) of a batch under THIS model's current posterior: the grid mean from the prediction cache (every
         regime keeps one), and 1 / sqrt(sigma2 noise_i) ("noise") or 1 / sqrt(var_i + sigma2 noise_i) ("predictive", var_i the
@@ -1436,37 +1483,19 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         wb omega: a carried root pair, the spectral factor, the path probes, the noise-weight sum.  The two-level block is given up
         (a model with robust_c never takes the fused streaming step that feeds it) and the dense rank-update seed is skipped: the
         next posterior is factored afresh."""
-        if self.num_outputs > 1:
-            raise NotImplementedError("robust_c is implemented for a single output")
-        op = _wtw_ops(cache["WtW"])[0]
-        if not grid_ops.is_half_stencil(self._grid, op.stencil) or "_cnt" not in cache:
-            raise NotImplementedError("robust_c needs the native half-stencil cache (a full stencil was handed over)")
-        X = X.reshape(-1, self._grid.d).to(self._device, self._dtype).contiguous()
-        y = Y.to(self._device, self._dtype).reshape(-1).contiguous()
+        op = self._native_half_op(cache, "robust_c")
+        X, y, no, wa, wb = self._canon_batch(X, Y, noise)
         n = X.shape[0]
-        unit = noise is None
-        no, wa, wb = self._batch_weights(None if unit else noise.to(self._device, self._dtype).reshape(-1).contiguous(), False, n)
         u, inv_scale = src._robust_inputs(X, no)             # (finishes whatever is pending, leaves a stencil shard)
-        self._finish_pending()
-        self.leave_stencil_shard()
-        ms = self._mean_state if src is self else None
-        carry = ms is not None and ms.get("R_ok", False) and settings.residual_carry_over.on() and ms["U"][0].data_ptr() == u.data_ptr()
-        if self._mean_state is not None and not carry:
-            self._mean_state["R_ok"] = False
+        ms = self._carried(self._before_launch(cache), u=u)
         omega = grid_ops.scatter_stats_robust(self._grid, X, y, wa, wb, no, inv_scale, self.robust_c, cache["interpolation_cache"][0, :, 0],
-                                              op.stencil, cache["_cnt"][0], cache["_stats"][0], self._err, u, res=ms["R"][0] if carry else None)
+                                              op.stencil, cache["_cnt"][0], cache["_stats"][0], self._err, u, res=ms["R"][0] if ms else None)
         self.last_robust_weights = omega
         if n == 0:
-            return
-        wa_eff, wb_eff = wa * omega, wb * omega              # a point outside the grid: omega = 0, nothing anywhere
+            return 0
         self._two_level_lose()                               # (its block is rebuilt from the stencil where one is wanted again)
-        if getattr(op, "root", None) is not None:
-            Wd = grid_ops.wt_columns(self._grid, X, self._err)
-            op.update_roots_((Wd * wa_eff.sqrt()[:, None]).t().contiguous())
-        self._spectral_absorb(0, X, wa_eff, y * wb_eff)
-        self._wsum_add(0, n, wa_eff)
-        if "path_probes" in cache:
-            self._absorb_probes(cache, X, wa_eff)
+        self._follow(cache, 0, X, wa * omega, y * (wb * omega))      # a point outside the grid: omega = 0, nothing anywhere
+        return n
 
     # ------------------------------------------------ interval observations --
     def _condition_interval(self, X, Y, noise, lower, upper, inplace, _decay):
@@ -1497,30 +1526,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
                 raise ValueError(f"noise must hold one value per point ([{n}]), got {tuple(noise.shape)}")
         if self.grow_grid:
             self.grow_to_cover_(X)
-        gamma = self.forgetting_factor if _decay else None
-        if gamma == 1.0:
-            gamma = None
-        if inplace:
-            if gamma is not None:
-                self.forget_(gamma)
-            entered = self._absorb_interval(self._kernel_cache, X, lo, hi, noise, self)
-            self.num_data = self.num_data + entered
-            self._dump_caches()
-            return None
-        new_cache = self._clone_cache(self._kernel_cache)
-        new_gp = self._sibling(new_cache, self.num_data)
-        src = self                                   # without a decay the clone's posterior is this model's, usually already solved
-        if gamma is not None:
-            new_gp._decay(gamma, self.num_data)          # the clone's buffers: the parent keeps its statistics bit for bit
-            self._sibling_mean_state(new_gp)             # (warm start of the solve the sites need)
-            src = new_gp
-        new_gp.num_data = self.num_data + new_gp._absorb_interval(new_cache, X, lo, hi, noise, src)
-        new_gp._dump_caches()                            # (the prediction cache the sites were read from predates the batch)
-        if src is self:
-            self._sibling_mean_state(new_gp)
-        elif not self.training:
-            new_gp.eval()
-        return new_gp
+        return self._condition(lambda model, cache, src: model._absorb_interval(cache, X, lo, hi, noise, src), inplace, self._gamma(_decay),
+                               reads_posterior=True)
 
     def _absorb_interval(self, cache, X, lo, hi, noise, src, half_delta=None):
         """_absorb of one batch of interval observations, one launch (wiski_scatter_stats_interval).  `src`: the model whose posterior
@@ -1530,41 +1537,23 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         and the pseudo-targets: a carried root pair, the spectral factor, the path probes, the noise-weight sum.  The two-level block
         is given up and the dense rank-update seed is skipped, as in _absorb_robust.  Returns the number of points num_data grows by:
         those that entered, and those outside the grid (which _raise_out_of_bounds takes off again when the flag is read)."""
-        if half_delta is not None:
-            raise NotImplementedError("interval observations do not follow the data-parallel statistics exchange (half_delta): the sites of "
-                                      "a shard would be matched on one rank and the other ranks' followers never see them")
-        op = _wtw_ops(cache["WtW"])[0]
-        if not grid_ops.is_half_stencil(self._grid, op.stencil) or "_cnt" not in cache:
-            raise NotImplementedError("interval observations need the native half-stencil cache (a full stencil was handed over)")
-        X = X.reshape(-1, self._grid.d).to(self._device, self._dtype).contiguous()
+        op = self._native_half_op(cache, "interval observations", half_delta)
+        X, _, no, wa, wb = self._canon_batch(X, None, noise)
         n = X.shape[0]
-        no, wa, wb = self._batch_weights(None if noise is None else noise.contiguous(), False, n)
         u = src.prediction_cache["pred_mean"][0, :, 0]       # (finishes whatever is pending, leaves a stencil shard)
         with torch.no_grad(), settings.skip_posterior_variances(False):
             pvar = src._eval_forward(X).variance.reshape(-1).to(self._dtype).contiguous()
-        self._finish_pending()
-        self.leave_stencil_shard()
-        ms = self._mean_state if src is self else None
-        carry = ms is not None and ms.get("R_ok", False) and settings.residual_carry_over.on() and ms["U"][0].data_ptr() == u.data_ptr()
-        if self._mean_state is not None and not carry:
-            self._mean_state["R_ok"] = False
+        ms = self._carried(self._before_launch(cache), u=u)
         flag0 = self._err.clone()
         sites = grid_ops.scatter_stats_interval(self._grid, X, lo.contiguous(), hi.contiguous(), pvar, self._sigma2(0), wa, wb, no,
                                                 cache["interpolation_cache"][0, :, 0], op.stencil, cache["_cnt"][0], cache["_stats"][0], self._err, u,
-                                                res=ms["R"][0] if carry else None)
+                                                res=ms["R"][0] if ms else None)
         self.last_interval_sites = sites
         if n == 0:
             return 0
         yt, omega, _ = sites
-        wa_eff, wb_eff = wa * omega, wb * omega              # a skipped point, a point outside the grid: omega = 0, nothing anywhere
         self._two_level_lose()                               # (its block is rebuilt from the stencil where one is wanted again)
-        if getattr(op, "root", None) is not None:
-            Wd = grid_ops.wt_columns(self._grid, X, self._err)
-            op.update_roots_((Wd * wa_eff.sqrt()[:, None]).t().contiguous())
-        self._spectral_absorb(0, X, wa_eff, yt * wb_eff)
-        self._wsum_add(0, n, wa_eff)
-        if "path_probes" in cache:
-            self._absorb_probes(cache, X, wa_eff)
+        self._follow(cache, 0, X, wa * omega, yt * (wb * omega))     # a skipped point, a point outside the grid: omega = 0, nothing anywhere
         entered, dropped = torch.stack([(omega > 0).sum(), (self._err - flag0).reshape(-1)[0] >> 1]).tolist()
         return int(entered) + int(dropped)
 
@@ -1594,23 +1583,6 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         return lb + torch.log1p(-torch.exp(la - lb))
 
     # ------------------------------------------------------- sliding window --
-    def _condition_window(self, X, Y, noise, inplace):
-        """condition_on_observations of a model with window, once the grid has grown: the batch enters the statistics
-        and the ring, what the ring's slots held leaves.  The grid may grow under a window (grow_grid, a growing regrid_): the ring
-        holds coordinates, not node indices, so a stored point finds its nodes on the grown grid when it leaves -- which is also why
-        no node may be removed.  The functional form clones the ring with the cache."""
-        if inplace:
-            self._absorb_window(self._kernel_cache, X, Y, noise)
-            self._dump_caches()
-            self._window_rebuild_due()
-            return None
-        new_cache = self._clone_cache(self._kernel_cache)
-        new_gp = self._sibling(new_cache, self.num_data)
-        new_gp._absorb_window(new_cache, X, Y, noise)
-        self._sibling_mean_state(new_gp)
-        new_gp._window_rebuild_due()
-        return new_gp
-
     def _window_rebuild_due(self):
         self._win_updates += 1
         if self.window_rebuild_every is not None and self._win_updates % self.window_rebuild_every == 0:
@@ -1635,26 +1607,14 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         pair is dropped, the spectral factor marked stale (it rebuilds from the stencil, exactly), the two-level block lost, no rank
         update prepared.  The noise-weight sum loses what left: on the host for the slots written at unit noise; for the others the
         device part moves by the ring's wa over the launch's slots, after minus before -- O(batch) work, queued, no host read or copy."""
-        if self.num_outputs > 1:
-            raise NotImplementedError("window is implemented for a single output")
-        op = _wtw_ops(cache["WtW"])[0]
-        if not grid_ops.is_half_stencil(self._grid, op.stencil) or "_cnt" not in cache:
-            raise NotImplementedError("window needs the native half-stencil cache (a full stencil was handed over)")
+        op = self._native_half_op(cache, "window")
         ring = cache["_ring"]
-        self._finish_pending()
-        mine = cache is self._kernel_cache
-        if mine:
-            self.leave_stencil_shard()
-        X = X.reshape(-1, self._grid.d).to(self._device, self._dtype).contiguous()
-        y = Y.to(self._device, self._dtype).reshape(-1).contiguous()
-        n = X.shape[0]
+        mine = self._before_launch(cache)
         unit = noise is None
-        no, wa, wb = self._batch_weights(None if unit else noise.to(self._device, self._dtype).reshape(-1).contiguous(), init, n)
-        ms = self._mean_state if mine else None
-        carry = not init and ms is not None and ms.get("R_ok", False) and settings.residual_carry_over.on()
-        if mine and self._mean_state is not None and not carry:
-            self._mean_state["R_ok"] = False
-        if carry:
+        X, y, no, wa, wb = self._canon_batch(X, Y, noise, init)
+        n = X.shape[0]
+        ms = self._carried(mine, init)
+        if ms is not None:
             u = ms["U"][0]
         else:                                            # (the kernel takes both sweeps against some u; without res it goes nowhere)
             u = self.__dict__.get("_win_zero_u")
@@ -1672,7 +1632,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             self._wsum_host[0] += (float(hi - lo) if unit else 0.0) - float(left_unit)
             ring.mark(spans, unit)
             grid_ops.scatter_stats_window(self._grid, X[lo:hi], y[lo:hi], wa[lo:hi], wb[lo:hi], no[lo:hi], ring, cache["interpolation_cache"][0, :, 0],
-                                          op.stencil, cache["_cnt"][0], cache["_stats"][0], self._err, u, res=ms["R"][0] if carry else None)
+                                          op.stencil, cache["_cnt"][0], cache["_stats"][0], self._err, u, res=ms["R"][0] if ms else None)
             if left_dev is not None or not unit:
                 delta = 0.0 if left_dev is None else -left_dev
                 if not unit:                             # what entered, as the ring now holds it (a point dropped at entry: 0)
@@ -1680,13 +1640,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
                 self._wsum_dev[0] += delta
                 self._wsum_dirty = True
         self.num_data = ring.fill - self._win_voids
-        if n == 0:
-            return
-        op.root = op.inv_root = None                     # L L^T described the matrix with the points that left
-        if mine:
-            self._two_level_lose()
-            for fac in self.__dict__.get("_spectral", {}).values():
-                fac.stale = True
+        if n > 0:
+            self._give_up(cache)                         # L L^T described the matrix with the points that left
 
     def window_points(self):
         """(X [k, d], Y [k], noise [k]) of the points the model is the GP of, oldest first; slots whose point was dropped at entry
@@ -1713,7 +1668,6 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         op = _wtw_ops(cache["WtW"])[0]
         for t in (cache["interpolation_cache"], cache["_stats"], cache["_cnt"], op.stencil):
             t.zero_()
-        op.root = op.inv_root = None
         # an empty or void slot holds no weight and noise 1: absorbed at any point inside the grid it adds nothing anywhere
         dead = (ring.wa == 0) & (ring.wb == 0)
         centre = torch.tensor([g0 + 0.5 * h * (g - 1) for g0, h, g in zip(self._grid.g0, self._grid.h, self._grid.g)], dtype=self._dtype, device=self._device)
@@ -1722,9 +1676,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
                                    cache["_cnt"][0], cache["_stats"][0], self._err)
         if self._mean_state is not None:
             self._mean_state["R_ok"] = False
-        self._two_level_lose()
-        for fac in self.__dict__.get("_spectral", {}).values():
-            fac.stale = True
+        self._give_up(cache)
         self._dump_caches()
         return self
 
@@ -1738,11 +1690,9 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         the statistics decay between the evaluation and the absorb (one more launch, ``wiski_decay_stats``)."""
         if self.grow_grid:
             self.grow_to_cover_(X)
-        gamma = self.forgetting_factor
-        if gamma is not None and gamma != 1.0:
+        gamma = self._gamma()
+        if gamma is not None:
             self._finish_pending()                   # the solve in flight belongs to the undecayed statistics
-        else:
-            gamma = None
         st = self._stream_fast_state(X, Y)
         if st is None:
             self._finish_pending()
@@ -2362,21 +2312,14 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             regions.append((cache["path_probes"], math.sqrt(gamma)))          # cov(P_s) = A stays exact
         # R = b - Z - A U of the mean state: Z = Kt^-1 U does not depend on the data, so gamma R - (1 - gamma) Z is the residual of the
         # same (U, Z) in the decayed system -- the next refresh starts warm and without an A U product
-        ms = self._mean_state
-        carry = ms is not None and ms.get("R_ok", False) and settings.residual_carry_over.on()
-        if ms is not None and not carry:
-            ms["R_ok"] = False
+        ms = self._carried(True)
         # (one launch for up to 8 outputs; beyond, one per 8 -- of stats rows and of the device parts of the noise-weight sums alike)
         grid_ops.decay_stats(gamma, regions, stats=cache["_stats"], counts=[float(count)] * self.num_outputs,
-                             R=ms["R"] if carry else None, Z=ms["Z"] if carry else None, side=self._wsum_dev)
+                             R=ms["R"] if ms else None, Z=ms["Z"] if ms else None, side=self._wsum_dev)
         self._wsum_host = [gamma * w for w in self._wsum_host]
         self._wsum_dev_host = [gamma * w for w in self._wsum_dev_host]
         # derived from A (set_train_data's recipe, except that what is invariant under a scaling stays):
-        for op in ops:
-            op.root = op.inv_root = None            # L L^T described the undecayed matrix
-        for fac in self.__dict__.get("_spectral", {}).values():
-            fac.stale = True                         # rebuilt from the stencil when next asked
-        self._two_level_lose()                       # (its Gram matrix belongs to the undecayed statistics)
+        self._give_up(cache)                         # (root pair, Gram matrix and factors belong to the undecayed statistics)
         # the preconditioner (_memo["precond"]) stays: its eigenbasis depends on the NORMALISED density profile of cnt, which a scaling
         # leaves alone, and its shift is wsum / norm at every use.  The mass the profile was taken at stays as well, so that "the data
         # volume has doubled / halved since" keeps looking at the profile of a stream whose old points fade
