@@ -876,6 +876,36 @@ typedef struct wiski_regrid_plan {
 int wiski_regrid_stats_f32(const wiski_grid* grid, const int32_t* below, const int32_t* above, const int32_t* g_new, const wiski_regrid_plan* plan, double* d_record, void* stream);
 int wiski_regrid_stats_f64(const wiski_grid* grid, const int32_t* below, const int32_t* above, const int32_t* g_new, const wiski_regrid_plan* plan, double* d_record, void* stream);
 
+/* ---- polynomial trend with marginalised coefficients (trend.hip) ----
+ * y_i = h(x_i)^T beta + w(x_i)^T u + eps_i with beta ~ N(0, tau^2 I): h(x) holds the p monomials of total degree <= deg (0, 1 or 2) in the
+ * normalised coordinates t_k = (x_k - center[k]) / scale[k], graded lexicographic -- 1, t_1 .. t_d, t_1^2, t_1 t_2, .., t_1 t_d, t_2^2, ..
+ * -- so p = 1, d + 1 or (d + 1)(d + 2) / 2 (at most 15).  d_center and d_scale are DEVICE arrays of d doubles for both entry points.
+ *
+ * wiski_scatter_trend: the trend's statistics, additive over points and batches, in ONE launch:
+ *     d_C [m][p] (working precision, trend-minor)   += sum_i wa_i w(x_i) h(x_i)^T        one atomic add per non-zero tap and basis function
+ *     d_G [p][p] (fp64; the UPPER triangle only)    += sum_i wa_i h_i h_i^T              the caller mirrors it
+ *     d_g [p]    (fp64)                             += sum_i wby_i h_i
+ * d_wa NULL: unit weights; d_wby [n] is wb_i y_i, as the absorb's followers receive it.  A point enters C, G and g exactly when it enters
+ * W^T D^-1 W: inside / outside is decided as wiski_scatter_stats decides it, in the working precision (wiski_scatter_probes has the
+ * details, including the fp64 choice of the one-hot boundary cells); a point outside sets bit 0 of *d_err and contributes nothing.
+ * Everything is evaluated in IEEE fp64 for both entry points, one rounding per operation (no fused multiply-adds): the coordinates are
+ * read in the working precision and widened, the weights follow wiski_interp's rule as written for wiski_scatter_probes,
+ * w = ((w_0 w_1) w_2) w_3 over the dims, t_k as above, the products t_a t_b, and the increment (wa w) h_j, which is rounded once to the
+ * working precision before its atomic add (the order of the adds, hence the last bits of C, is not fixed).  G and g are summed per
+ * workgroup in fp64 -- products (wa h_a) h_b and wby h_a -- and added with one fp64 atomic per entry and workgroup.
+ * n = 0 is a no-op (d_x and d_wby may then be NULL).  WISKI_E_BADARG: deg outside {0, 1, 2}, n < 0, a NULL pointer other than d_wa.
+ *
+ * wiski_trend_rows: the query rows of the trend, one fused gather:
+ *     d_R [n][p] = h(x*) - sum_t w_t(x*) S[idx_t][:]       with d_S [m][p] trend-minor (S = M C, the caller's solve)
+ *     d_H [n][p] = h(x*)                                   where d_H is not NULL
+ * d_S NULL writes R = H.  Weights, basis and the sum are taken in fp64 as above (the sum over the taps in tap order, dim 0 slowest), the
+ * results rounded once.  A point outside the grid sets bit 0 of *d_err and its row is h(x*).  n = 0 is a no-op (d_x and d_R may then be NULL);
+ * WISKI_E_BADARG as above (d_S and d_H may be NULL). */
+int wiski_scatter_trend_f32(const wiski_grid* grid, const float* d_x, const float* d_wa, const float* d_wby, int64_t n, int32_t deg, const double* d_center, const double* d_scale, float* d_C, double* d_G, double* d_g, int32_t* d_err, void* stream);
+int wiski_scatter_trend_f64(const wiski_grid* grid, const double* d_x, const double* d_wa, const double* d_wby, int64_t n, int32_t deg, const double* d_center, const double* d_scale, double* d_C, double* d_G, double* d_g, int32_t* d_err, void* stream);
+int wiski_trend_rows_f32(const wiski_grid* grid, const float* d_x, int64_t n, int32_t deg, const double* d_center, const double* d_scale, const float* d_S, float* d_R, float* d_H, int32_t* d_err, void* stream);
+int wiski_trend_rows_f64(const wiski_grid* grid, const double* d_x, int64_t n, int32_t deg, const double* d_center, const double* d_scale, const double* d_S, double* d_R, double* d_H, int32_t* d_err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -197,6 +197,9 @@ class ShardedStatsUpdater:
         if getattr(model, "window", None) is not None:
             # what leaves the window must leave every replica, and a replica's ring would hold its own shard only: single-GPU for now
             raise NotImplementedError("ShardedStatsUpdater does not carry a sliding window: build the model with window=None")
+        if getattr(model, "_trend_deg", None) is not None:
+            # C, G, g are additive over shards and would all-reduce like b, but no exchange here carries them: the deltas hold A, b, cnt
+            raise NotImplementedError("ShardedStatsUpdater does not carry trend statistics: build the model with trend=None")
         self.model = model
         self.group = group
         self.exchange = exchange

@@ -607,6 +607,79 @@ def scatter_probes(grid, x, wa, first_index, seed, P, err):
     _hip.check(rc, "wiski_scatter_probes")
 
 
+TREND_DEGREES = {"constant": 0, "linear": 1, "quadratic": 2}
+
+
+def trend_size(d, deg):
+    """p: the number of monomials of total degree <= deg in d coordinates (deg 0, 1, 2)."""
+    if deg not in (0, 1, 2):
+        raise ValueError(f"the trend's degree must be 0, 1 or 2, got {deg!r}")
+    return 1 if deg == 0 else (d + 1 if deg == 1 else (d + 1) * (d + 2) // 2)
+
+
+def _trend_frame(grid, deg, center, scale, what):
+    p = trend_size(grid.d, int(deg))
+    for t in (center, scale):
+        if t.dtype != torch.float64 or t.shape != (grid.d,) or not t.is_contiguous():
+            raise ValueError(f"{what} needs the basis centre and scale as contiguous fp64 tensors [{grid.d}]")
+    return p
+
+
+def _same_device(what, x, **tensors):
+    for name, t in tensors.items():
+        if t is not None and t.device != x.device:
+            raise ValueError(f"{what}: {name} lives on {t.device}, the points on {x.device}")
+
+
+def scatter_trend(grid, x, wa, wby, deg, center, scale, C, G, g, err):
+    """The trend's statistics of the points x [n, d] (``wiski_scatter_trend``), in one launch: C [m, p] +=
+    sum_i wa_i w(x_i) h(x_i)^T (the points' dtype, trend-minor), G [p, p] += sum_i wa_i h_i h_i^T (fp64; the kernel adds to the UPPER
+    triangle only: ``trend_mirror`` completes it), g [p] += sum_i wby_i h_i (fp64).  wa [n] or None = unit weights; wby [n] = wb * y.
+    center / scale: fp64 [d], the normalisation of the basis.  A no-op for n = 0."""
+    x = _x2d(x, grid)
+    n = x.shape[0]
+    p = _trend_frame(grid, deg, center, scale, "scatter_trend")
+    if C.shape != (grid.m, p) or C.dtype != x.dtype or not C.is_contiguous():
+        raise ValueError(f"scatter_trend needs contiguous C [m = {grid.m}, p = {p}] in the points' dtype, got {tuple(C.shape)} ({C.dtype})")
+    if (G.shape != (p, p) or g.shape != (p,) or G.dtype != torch.float64 or g.dtype != torch.float64 or not G.is_contiguous()
+            or not g.is_contiguous()):
+        raise ValueError(f"scatter_trend needs contiguous fp64 G [{p}, {p}] and g [{p}], got {tuple(G.shape)} ({G.dtype}) and {tuple(g.shape)} ({g.dtype})")
+    for name, w in (("wby", wby), ("wa", wa)):
+        if w is not None and (w.shape != (n,) or w.dtype != x.dtype):
+            raise ValueError(f"scatter_trend needs {name} [{n}] in the points' dtype, got {tuple(w.shape)} ({w.dtype})")
+    _same_device("scatter_trend", x, wa=wa, wby=wby, center=center, scale=scale, C=C, G=G, g=g, err=err)
+    wby = wby.contiguous()
+    wa = None if wa is None else wa.contiguous()
+    rc = _hip.fn("wiski_scatter_trend", x.dtype)(grid.ref, _hip.dptr(x), _hip.dptr(wa), _hip.dptr(wby), ctypes.c_int64(n), ctypes.c_int32(int(deg)),
+                                                 _hip.dptr(center), _hip.dptr(scale), _hip.dptr(C), _hip.dptr(G), _hip.dptr(g), _hip.dptr(err),
+                                                 _hip.stream_ptr(x.device))
+    _hip.check(rc, "wiski_scatter_trend")
+
+
+def trend_mirror(G):
+    """The symmetric G of the upper triangle ``scatter_trend`` accumulates (a new tensor)."""
+    U = torch.triu(G)
+    return U + torch.triu(G, 1).t()
+
+
+def trend_rows(grid, x, deg, center, scale, S, err, want_basis=False):
+    """R* [n, p] = h(x*) - W* S of the points x [n, d] in one fused gather (``wiski_trend_rows``), S [m, p] trend-minor in the points'
+    dtype; S None: R* = H*, the basis rows.  want_basis: returns (R*, H*).  Points outside the grid are flagged in err; their rows
+    are h(x*)."""
+    x = _x2d(x, grid)
+    n = x.shape[0]
+    p = _trend_frame(grid, deg, center, scale, "trend_rows")
+    if S is not None and (S.shape != (grid.m, p) or S.dtype != x.dtype or not S.is_contiguous()):
+        raise ValueError(f"trend_rows needs contiguous S [m = {grid.m}, p = {p}] in the points' dtype, got {tuple(S.shape)} ({S.dtype})")
+    _same_device("trend_rows", x, center=center, scale=scale, S=S, err=err)
+    R = torch.empty((n, p), dtype=x.dtype, device=x.device)
+    H = torch.empty((n, p), dtype=x.dtype, device=x.device) if want_basis else None
+    rc = _hip.fn("wiski_trend_rows", x.dtype)(grid.ref, _hip.dptr(x), ctypes.c_int64(n), ctypes.c_int32(int(deg)), _hip.dptr(center), _hip.dptr(scale),
+                                              _hip.dptr(S), _hip.dptr(R), _hip.dptr(H), _hip.dptr(err), _hip.stream_ptr(x.device))
+    _hip.check(rc, "wiski_trend_rows")
+    return (R, H) if want_basis else R
+
+
 def decay_stats(gamma, regions, stats=None, counts=None, R=None, Z=None, side=None):
     """Exponential forgetting in ONE launch (``wiski_decay_stats``): every ``(tensor, factor)`` of `regions` is scaled in
     place, ``x <- x * factor`` with the factor rounded once to the tensors' dtype (the stencil pack, b, cnt: gamma; the path probes:

@@ -264,6 +264,10 @@ class BatchedWoodburyMarginalLogLikelihood(torch.nn.Module):
 
     def forward(self, distro=None, targets=None, *args):
         model = self.model
+        if getattr(model, "_trend_deg", None) is not None:
+            raise NotImplementedError("the marginal likelihood of a model with a trend is not implemented (its gradient needs the terms Z^T dKt Z "
+                                      "of the trend's solve columns): model.trend_evidence() gives the trend's share of the evidence at fixed "
+                                      "hyper-parameters")
         # graph context (models/_streaming_wrapper.py): the call is being recorded into a captured graph -- the factor state comes
         # from static staging buffers, the data count from a device scalar, and nothing here may touch the host-device boundary
         gctx = model.__dict__.get("_graph_ctx")

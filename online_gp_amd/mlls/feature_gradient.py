@@ -29,6 +29,9 @@ from .. import grid_ops, settings
 def mll_feature_surrogate(model, features, targets, noise=None, chunk=4096, probes=None, probe_weight=None):
     """features [n, d] (requires grad), targets [n, out], noise [n, out] or None (= ones).  The model's statistics must
     have been built from ``features.detach()`` (``set_train_data``).  probes [P, m] / probe_weight: matrix-free regime only."""
+    if getattr(model, "_trend_deg", None) is not None:
+        raise NotImplementedError("mll_feature_surrogate is not implemented for a model with a trend: the gradient written out here is that of "
+                                  "the zero-mean MLL (hyper-parameter and stem learning under a trend are out of scope, DESIGN.md 3.22)")
     dense = model._use_dense()
     grid = model._grid
     dev, dt = model._device, model._dtype

@@ -18,6 +18,9 @@ from .. import grid_ops, settings
 
 
 def sm_partial_mll(ski_gp, new_x, new_y, num_seen):
+    if getattr(ski_gp, "_trend_deg", None) is not None:
+        raise NotImplementedError("sm_partial_mll is not implemented for a model with a trend: its increment is that of the zero-mean model "
+                                  "(hyper-parameter and stem learning under a trend are out of scope, DESIGN.md 3.22)")
     grid = ski_gp._grid
     dev, dt = ski_gp._device, ski_gp._dtype
     x = new_x.reshape(-1, grid.d).to(dev, dt)

@@ -107,6 +107,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         robust_scale="noise",
         window=None,
         window_rebuild_every=None,
+        trend=None,
+        trend_prior_var=None,
     ):
         super().__init__()
         assert train_inputs is not None or kernel_cache is not None
@@ -189,6 +191,40 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         if num_path_probes > 0 and num_outputs > 1:
             raise NotImplementedError("path probes (num_path_probes > 0) are implemented for a single output")
         self._path_probes_init = (num_path_probes, int(path_seed))
+        # polynomial trend with marginalised coefficients: y = h(x)^T beta + f(x) + eps, beta ~ N(0, trend_prior_var I)
+        # (None: the flat prior).  Its statistics C, G, g live in the kernel cache beside b and follow it through every hand-over; the
+        # degree is fixed when the first model of a chain is built.  None: every path is what it is without the feature
+        if trend is not None and trend not in grid_ops.TREND_DEGREES:
+            raise ValueError(f"trend must be None, 'constant', 'linear' or 'quadratic', got {trend!r}")
+        if trend_prior_var is not None:
+            trend_prior_var = float(trend_prior_var)
+            if not (trend_prior_var > 0.0 and math.isfinite(trend_prior_var)):
+                raise ValueError(f"trend_prior_var must be a finite positive number or None (the flat prior), got {trend_prior_var}")
+        deg = None if trend is None else grid_ops.TREND_DEGREES[trend]
+        if kernel_cache is not None and "trend_C" in kernel_cache:
+            if deg is not None and deg != kernel_cache["trend_deg"]:
+                raise ValueError(f"trend={trend!r}, but the kernel cache handed over carries the statistics of a trend of degree "
+                                 f"{kernel_cache['trend_deg']} (the degree is fixed when the first model of the chain is built; trend=None takes the cache's)")
+            deg = kernel_cache["trend_deg"]
+        elif kernel_cache is not None and deg is not None:
+            raise ValueError(f"trend={trend!r}, but the kernel cache handed over carries no trend statistics: they can only be accumulated "
+                             "while the points stream by (build the first model of the chain from data with trend)")
+        if deg is None and trend_prior_var is not None:
+            raise ValueError("trend_prior_var needs trend")
+        if deg is not None:
+            if num_outputs > 1:
+                raise NotImplementedError("trend is implemented for a single output (one coefficient vector, one set of p solve columns)")
+            if robust_c is not None:
+                raise NotImplementedError("trend does not combine with robust_c: the Huber weights are taken against the grid mean alone, "
+                                          "which under a trend is not the predictive mean")
+            if window is not None:
+                raise NotImplementedError("trend does not combine with window: the ring's kernel takes a point out of A and b only, "
+                                          "and the trend statistics would keep it")
+            if num_path_probes > 0 or (kernel_cache is not None and "path_probes" in kernel_cache):
+                raise NotImplementedError("trend does not combine with path probes (num_path_probes > 0): a sample path would need a "
+                                          "joint draw of the coefficients, which sample_paths does not make")
+        self._trend_deg = deg
+        self.trend_prior_var = trend_prior_var
 
         if covar_module is None:
             if grid_bounds is None:
@@ -278,7 +314,29 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         if S > 0:
             # P [m, S], probe-minor; path_count: global index of the next point (the generator is keyed on (seed, index, s))
             cache.update(path_probes=torch.zeros((m, S), dtype=self._dtype, device=self._device), path_seed=seed, path_count=0)
+        if self._trend_deg is not None:
+            # C [m, p] trend-minor in the model's dtype (the layout of P), G [p, p] and g [p] in fp64 (as _stats); the basis is
+            # normalised by the centre and half-extent of THIS grid, for good: a property of the basis, which regrid_ leaves alone
+            g = self._grid
+            p = grid_ops.trend_size(g.d, self._trend_deg)
+            half = [0.5 * hq * (gq - 1) for hq, gq in zip(g.h, g.g)]
+            f64 = dict(dtype=torch.float64, device=self._device)
+            cache.update(trend_C=torch.zeros((m, p), dtype=self._dtype, device=self._device), trend_G=torch.zeros((p, p), **f64),
+                         trend_g=torch.zeros(p, **f64), trend_deg=self._trend_deg,
+                         trend_center=torch.tensor([g0 + hf for g0, hf in zip(g.g0, half)], **f64), trend_scale=torch.tensor(half, **f64))
         return cache
+
+    _TREND_KEYS = ("trend_C", "trend_G", "trend_g", "trend_deg", "trend_center", "trend_scale")
+
+    @classmethod
+    def _trend_entries(cls, cache, move=None, **replace):
+        """The trend's entries of `cache` for a cache that takes its place ({} without a trend): each tensor through `move` (clone,
+        to(device); None: as it is), `replace` naming those that come new."""
+        if "trend_C" not in cache:
+            return {}
+        ent = {k: (move(cache[k]) if move is not None and torch.is_tensor(cache[k]) else cache[k]) for k in cls._TREND_KEYS}
+        ent.update(replace)
+        return ent
 
     def _pack_cache(self, b, stats, ops, cnt=None):
         out = b.shape[0]
@@ -309,6 +367,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             new.update(path_probes=cache["path_probes"].clone(), path_seed=cache["path_seed"], path_count=cache["path_count"])
         if cache.get("_ring") is not None:              # the window's points follow the statistics they are the points of
             new["_ring"] = cache["_ring"].clone()
+        new.update(self._trend_entries(cache, move=torch.clone))    # a child's increments never reach the parent's statistics
         facs = cache.get("_spectral")
         if facs:
             new["_spectral"] = {o: fac.clone() for o, fac in facs.items() if fac.ref is not None and not fac.stale}
@@ -355,6 +414,10 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         if self.window is not None and half_delta is not None:
             raise NotImplementedError("window does not follow the data-parallel statistics exchange (half_delta): the ring of a replica "
                                       "would hold its own shard only, and what leaves must leave every replica")
+        if self._trend_deg is not None and half_delta is not None:
+            # (keyed on the model, as robust_c and window are: the updater absorbs into a delta dict of its own, which carries no trend entries)
+            raise NotImplementedError("trend does not follow the data-parallel statistics exchange (half_delta): the deltas that are "
+                                      "all-reduced carry A, b and cnt only, and C, G, g of the other ranks' points would never arrive")
         mine = self._before_launch(cache)            # the generic absorb writes every group
         X = X.reshape(-1, self._grid.d).to(self._device, self._dtype).contiguous()
         Y = Y.to(self._device, self._dtype)
@@ -475,6 +538,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             self._wsum_add(o, n, wa)
         if "path_probes" in cache:                   # (single output)
             self._absorb_probes(cache, X, wa, init)
+        if "trend_C" in cache:                       # (single output)
+            self._absorb_trend(cache, X, wa, wby)
 
     def _give_up(self, cache):
         """Follower policy "give up": the launch changed A by something that cannot be followed point by point (a derivative row, a
@@ -499,6 +564,13 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         if n:
             grid_ops.scatter_probes(self._grid, X, wa, cache["path_count"], cache["path_seed"], P, self._err)
             cache["path_count"] += n
+
+    def _absorb_trend(self, cache, X, wa, wby):
+        """Every point that enters A with the weight wa (None: unit) and b with wby enters the trend statistics C, G, g with the same
+        (one launch, wiski_scatter_trend).  A restart finds them zero: a fresh cache, or set_train_data, which zeroes them with b."""
+        if X.shape[0]:
+            grid_ops.scatter_trend(self._grid, X, wa, wby, cache["trend_deg"], cache["trend_center"], cache["trend_scale"], cache["trend_C"],
+                                   cache["trend_G"], cache["trend_g"], self._err)
 
     def _absorb_all_outputs(self, cache, X, Y, noise, init, ops, ms):
         """Several outputs, native packed half stencils, no root pairs to carry: ONE scatter launch for all of them
@@ -653,7 +725,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         """May a request go to the spectral factor (lazy/spectral_woodbury.py)?  Beyond the dense regime always; inside it only for
         the reference's per-batch loop, whose owner (a streaming wrapper) has said so -- direct users of the model, BO posteriors
         and fantasies keep the nodal dense factor with its cached M and rank-q updates."""
-        if settings.spectral_factor.off():
+        if settings.spectral_factor.off() or self._trend_deg is not None:    # (a trend's moments always come through the prediction cache)
             return False
         if not self._use_dense():
             return True
@@ -770,6 +842,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         the LDS-window kernel restricted to the replica's group range."""
         if self.window is not None:
             raise NotImplementedError("window does not combine with enter_stencil_shard: the window absorb writes every stencil group")
+        self._refuse_trend("enter_stencil_shard", "the trend's solve columns S = M C need the whole stencil at every refresh")
         op = _wtw_ops(self._kernel_cache["WtW"])[0]
         if (world <= 1 and not comm) or self.num_outputs != 1 or self._use_dense() or not op.is_half or self._grid.m % 4 or op.root is not None:
             return False
@@ -917,7 +990,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         self._apply_pending_rank_update()
         pc = self._memo.get("prediction_cache")
         if pc is not None:
-            return pc
+            return self._with_trend(pc)
         if self._use_dense() or self._wsum_dirty:
             self.check_bounds()          # dense path has no solver poll to ride on; a dirty weight sum needs the read anyway
         out, m = self.num_outputs, self._grid.m
@@ -989,7 +1062,115 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         self._poll_hint = 0 if ms is not None else 2      # after a cold solve: see _first_poll
         pc = {"pred_mean": U[..., None], "pred_cov": posts[0] if out == 1 else BatchOperator(posts), "cg_iters": iters, "ver": ver}
         self._memo["prediction_cache"] = pc
+        return self._with_trend(pc)
+
+    # ---------------------------------------------------------------- trend --
+    def _with_trend(self, pc):
+        """On a trend model the prediction cache additionally holds ``trend = {S, Lchol, beta, ...}``: S = M C by p more
+        columns of the solve the cache already makes (dense and PCG through the same call), then p x p algebra in fp64:
+        Lambda0 = G - C^T S, Lambda = Lambda0 + (sigma2 / tau2) I = L L^T, v = g - S^T b, beta = Lambda^-1 v; where the solve hands its
+        Z = Kt^-1 S over (PCG), Lambda0 and v are corrected by the solve's own residual, which leaves them second-order accurate in it."""
+        cache = self._kernel_cache
+        if "trend_C" not in cache or "trend" in pc:
+            return pc
+        post = pc["pred_cov"]
+        C = cache["trend_C"]
+        p = C.shape[1]
+        Ct = C.t().contiguous()                                    # solve_columns takes [k, m]
+        St = torch.empty_like(Ct)
+        resid = None
+        chunk = max(1, int(settings.variance_chunk.value()))
+        for s in range(0, p, chunk):
+            e = min(s + chunk, p)
+            U, Z = post.solve_columns(Ct[s:e].contiguous())
+            St[s:e] = U
+            if getattr(post, "last_err", 0):
+                self._raise_out_of_bounds(post.last_err)
+            if Z is not None:
+                # the solve's own residual C - Q S (Z = Kt^-1 S comes with the solve): corrects Lambda0 to second order in it
+                if resid is None:
+                    resid = torch.empty((p, self._grid.m), dtype=torch.float64, device=self._device)
+                resid[s:e] = Ct[s:e].double() - Z.double() - grid_ops.stencil_spmv(self._grid, post.wtw.stencil, U).double()
+        S64, C64 = St.double(), Ct.double()
+        b64 = cache["interpolation_cache"][0, :, 0].double()
+        G = grid_ops.trend_mirror(cache["trend_G"])
+        lam0 = G - C64 @ S64.t()
+        if resid is not None:
+            lam0 = lam0 - S64 @ resid.t()                          # G - C^T S - S^T (C - Q S)
+        lam0 = 0.5 * (lam0 + lam0.t())
+        s2 = self._sigma2(0)
+        tau2 = self.trend_prior_var
+        lam = lam0.clone()
+        if tau2 is not None:
+            lam.diagonal().add_(s2 / tau2)
+        # factored with the basis functions scaled to unit weighted norm (G~ = D G D with unit diagonal, D = diag(G)^-1/2), so that a
+        # monomial that is small over the data -- data confined to a part of the first grid -- is judged by its own size.  An entry of
+        # Lambda0~ is known to about eps of the dtype C is kept in (eps |G~| with |G~| <= 1), so under the flat prior a squared pivot at
+        # or below 8 eps is not distinguishable from zero: the coefficients are not determined to that precision, and the model says so
+        dsc = G.diagonal().clamp_min(torch.finfo(torch.float64).tiny).rsqrt()
+        Ls, info = torch.linalg.cholesky_ex(lam * dsc[:, None] * dsc[None, :])
+        L = Ls / dsc[:, None]                                      # Lambda = L L^T, lower triangular
+        floor = 8.0 * torch.finfo(self._dtype).eps
+        if int(info) != 0 or not bool(torch.isfinite(L).all()) or (tau2 is None and float(Ls.diagonal().min()) ** 2 <= floor):
+            if tau2 is None:
+                raise RuntimeError(f"trend: under the flat prior (trend_prior_var=None) the {p} coefficients are not determined by the data "
+                                   f"absorbed so far -- Lambda0 = H^T Sigma^-1 H is singular to the precision of the statistics (fewer than {p} "
+                                   f"informative points, or basis functions that the data cannot tell apart in {self._dtype}: a squared pivot of "
+                                   "Lambda0, in the basis scaled to unit diag G, at or below 8 eps); absorb more points or give trend_prior_var")
+            raise RuntimeError("trend: Lambda = Lambda0 + (sigma2 / tau2) I is not positive definite")
+        v = cache["trend_g"] - S64 @ b64
+        if resid is not None:
+            v = v - resid @ pc["pred_mean"][0, :, 0].double()      # C^T M b = S^T b + (C - Q S)^T mu0: the same correction for v
+        beta = torch.cholesky_solve(v[:, None], L)[:, 0]
+        pc["trend"] = {"S": St.t().contiguous(), "Lchol": L, "beta": beta, "v": v, "Lambda0": lam0, "ver": pc.get("ver")}
         return pc
+
+    def _trend_state(self):
+        if self._trend_deg is None:
+            raise RuntimeError("the model was built without trend")
+        with torch.no_grad():
+            return self.prediction_cache["trend"]
+
+    def trend_coefficients(self):
+        """(beta_hat [p], cov [p, p]) of the trend's coefficients given the data, in the normalised basis of ``trend_basis`` (fp64):
+        beta_hat = Lambda^-1 v and cov = sigma2 Lambda^-1."""
+        tr = self._trend_state()
+        p = tr["beta"].shape[0]
+        eye = torch.eye(p, dtype=torch.float64, device=self._device)
+        return tr["beta"].clone(), self._sigma2(0) * torch.cholesky_solve(eye, tr["Lchol"])
+
+    def trend_basis(self, X):
+        """H [n, p]: the monomials of total degree <= the trend's in t_k = (x_k - c_k) / s_k at X [n, d], graded lexicographic
+        (1, t_1 .. t_d, t_1^2, t_1 t_2, ...); c and s are the centre and half-extent of the grid the first model of the chain was built
+        on.  Defined outside the grid as well (no bounds error is raised for such points)."""
+        if self._trend_deg is None:
+            raise RuntimeError("the model was built without trend")
+        cache = self._kernel_cache
+        Xf = X.detach().reshape(-1, self._grid.d).to(self._device, self._dtype).contiguous()
+        scratch = grid_ops.new_err_flag(self._device)            # (the basis has no bounds: the model's flag stays as it is)
+        return grid_ops.trend_rows(self._grid, Xf, cache["trend_deg"], cache["trend_center"], cache["trend_scale"], None, scratch)
+
+    def trend_evidence(self):
+        """log p_trend(y) - log p_0(y) (fp64 scalar): what the marginal likelihood of the data gains by the trend, at the current
+        hyper-parameters -- -1/2 log|I + (tau2 / sigma2) Lambda0| + 1/2 v^T Lambda^-1 v / sigma2.  A proper prior only: under the flat
+        prior the evidence is defined up to a constant, and a ValueError says so."""
+        if self._trend_deg is None:
+            raise RuntimeError("the model was built without trend")
+        tau2 = self.trend_prior_var
+        if tau2 is None:
+            raise ValueError("trend_evidence needs a proper prior (trend_prior_var): under the flat prior the evidence is defined up to "
+                             "an infinite constant only")
+        tr = self._trend_state()
+        s2 = self._sigma2(0)
+        L, v = tr["Lchol"], tr["v"]
+        p = v.shape[0]
+        logdet = 2.0 * torch.log(L.diagonal()).sum() + p * math.log(tau2 / s2)      # log|Lambda| + p log(tau2 / sigma2)
+        quad = v @ torch.cholesky_solve(v[:, None], L)[:, 0]
+        return -0.5 * logdet + 0.5 * quad / s2
+
+    def _refuse_trend(self, what, why):
+        if self._trend_deg is not None:
+            raise NotImplementedError(f"{what} is not implemented for a model with a trend: {why}")
 
     def _make_predictive_covar(self, *args, **kwargs):
         return self.prediction_cache["pred_cov"]
@@ -1082,6 +1263,11 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
     def _eval_forward(self, X):
         grid, out = self._grid, self.num_outputs
         X = X.to(self._device, self._dtype)
+        if self._trend_deg is not None:
+            if X.dim() > 2:
+                self._refuse_trend("a batched posterior (X [..., n, d])", "the trend's rank-p term is formed for one set of query points")
+            if torch.is_grad_enabled() and X.requires_grad:
+                self._refuse_trend("a posterior differentiable in X", "the trend rows R* = H* - W* S have no backward")
         block = None
         lead = X.shape[:-1]
         if X.dim() > 2:
@@ -1143,6 +1329,12 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
                 mean = grid_ops.gather(grid, Xf, pc["pred_mean"][..., 0], self._err)  # [n, out]   left_interp, :206-210
             else:
                 mean = grid_ops.Gather.apply(grid, Xg, pc["pred_mean"][..., 0], self._err)    # (the same launch, differentiable)
+        trend_rows = None
+        if self._trend_deg is not None:
+            # mean = W* mu0 + R* beta with R* = H* - W* S (one fused gather); the covariance gains sigma2 R* Lambda^-1 R*^T below
+            tr, kc = pc["trend"], self._kernel_cache
+            trend_rows = grid_ops.trend_rows(grid, Xf, kc["trend_deg"], kc["trend_center"], kc["trend_scale"], tr["S"], self._err)
+            mean = mean + (trend_rows.double() @ tr["beta"]).to(self._dtype)[:, None]
         if settings.deferred_bounds_check.off():
             flag = grid_ops.read_flag(self._err)       # gpytorch raises inside this call for queries outside the grid
             if flag:
@@ -1161,6 +1353,10 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         if covs is not None and settings.fast_pred_samples.on():
             # BFN:229-243: hand out a root form of the covariance where a factor provides one (else the exact covariance, as always)
             covs = [(c.root_decomposition() or c) for c in covs]
+        if covs is not None and trend_rows is not None:
+            from ..lazy.trend import TrendCovariance
+
+            covs = [TrendCovariance(covs[0], trend_rows, pc["trend"]["Lchol"], self._hyper()[0][1] if self.has_learnable_noise else 1.0)]
         # output shapes follow :248-252
         if out == 1:
             mean_o = mean[:, 0].reshape(lead)
@@ -1185,6 +1381,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         C^1 only, so a derivative of the jet with respect to X jumps at the cell faces.  One output, unbatched X."""
         from ..lazy.jet import JetCovariance, JetPosterior
 
+        self._refuse_trend("posterior_jet", "the jet rows of the basis (h and its gradient) are not built")
         if self.num_outputs > 1:
             raise NotImplementedError("posterior_jet is implemented for a single output")
         if X.dim() > 2:
@@ -1219,6 +1416,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         is refused with ``ValueError`` rather than silently evaluated instead of integrated."""
         from ..lazy.quadrature import BoxCovariance, IntegralPosterior, check_bounds_host, scale_by_volume
 
+        self._refuse_trend("posterior_integral", "the box integrals of the basis are not built")
         if self.num_outputs > 1:
             raise NotImplementedError("posterior_integral is implemented for a single output")
         grid = self._grid
@@ -1274,6 +1472,14 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         holds ``(ytilde, omega, log_z)``.  This is parallel assumed-density filtering: an approximation of the non-Gaussian
         posterior, whose MLL is the Gaussian MLL of the pseudo-data; ``log_z.sum()`` is the prequential evidence of the batch.  A
         point with nothing to say (omega = 0) enters nothing and does not count in ``num_data``.  Single output, unbatched X."""
+        if self._trend_deg is not None:
+            if lower is not None or upper is not None:
+                self._refuse_trend("interval observations (lower / upper)", "a site is matched against the grid mean alone, which under a trend "
+                                   "is not the predictive mean")
+            if grad_Y is not None:
+                self._refuse_trend("derivative observations (grad_Y)", "the trend statistics take value rows only (no gradient of the basis)")
+            if X.dim() > 2 or (Y is not None and Y.dim() > 2):
+                self._refuse_trend("batched conditioning (fantasies)", "a fantasy batch carries A and b only, not the trend statistics")
         if lower is not None or upper is not None:
             if grad_Y is not None or grad_noise is not None or grad_mask is not None:
                 raise NotImplementedError("interval observations bound values only: lower / upper take no grad_Y")
@@ -1377,6 +1583,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             robust_scale=self.robust_scale,
             window=self.window,
             window_rebuild_every=self.window_rebuild_every,
+            trend_prior_var=self.trend_prior_var,        # (the degree travels with the cache)
         )
         new_gp._win_voids, new_gp._win_updates = self._win_voids, self._win_updates
         new_gp._wsum_dev = self._wsum_dev.clone()
@@ -1912,7 +2119,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
 
     def _stream_fast_state(self, X, Y):
         """(prepared StreamStep, mean state, preconditioner state) when the one-call streaming step applies, else None."""
-        if (self.robust_c is not None or self.window is not None or self.num_outputs != 1 or self._use_dense() or settings.spectral_preconditioner.off() or settings.residual_carry_over.off()
+        if (self.robust_c is not None or self.window is not None or self._trend_deg is not None or self.num_outputs != 1 or self._use_dense() or settings.spectral_preconditioner.off() or settings.residual_carry_over.off()
                 or X.dim() != 2 or not X.is_cuda or X.dtype != self._dtype or not X.is_contiguous() or Y.dtype != self._dtype):
             return None
         ms = self._mean_state
@@ -2064,6 +2271,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         randomness) and are therefore correlated: draw all the paths an acquisition needs in one call."""
         from ..sample_paths import GridSamplePaths
 
+        self._refuse_trend("sample_paths", "a path would need a joint draw of the coefficients and the inducing values")
         if self.num_outputs != 1:
             raise NotImplementedError("sample_paths is implemented for a single output")
         num_paths = int(num_paths)
@@ -2148,6 +2356,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         if not plain:
             from .fantasy import BatchedFantasyModel
 
+            self._refuse_trend("batched conditioning (fantasies)", "a fantasy batch carries A and b only, not the trend statistics")
             return BatchedFantasyModel(self, inputs, targets, noise_term)
         if targets.dim() == 1:
             targets = targets[:, None]
@@ -2212,6 +2421,11 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             P = cache["path_probes"]
             new_P = mk(m2, P.shape[1])
             regions.append((P.contiguous(), new_P, 1, P.shape[1]))
+        new_C = None
+        if "trend_C" in cache:                       # probe-shaped; G, g and the basis' centre and scale do not depend on the grid
+            tC = cache["trend_C"]
+            new_C = mk(m2, tC.shape[1])
+            regions.append((tC.contiguous(), new_C, 1, tC.shape[1]))
         rows, mass = grid_ops.regrid_stats(old, new, a, regions)
         if sum(rows) > 0 and drop == "zero":
             dims = [q for q in range(old.d) if a[q] < 0 or bb[q] < 0]
@@ -2226,6 +2440,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             fresh.update(path_probes=new_P, path_seed=cache["path_seed"], path_count=cache["path_count"])
         if cache.get("_ring") is not None:
             fresh["_ring"] = cache["_ring"]              # coordinates, not node indices: the ring is the same on the grown grid
+        if new_C is not None:
+            fresh.update(self._trend_entries(cache, trend_C=new_C))
         self._drop_spectral()
         cache.clear()
         cache.update(fresh)
@@ -2274,7 +2490,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
     # ------------------------------------------------------------ forgetting --
     def forget_(self, gamma):
         """Exponential forgetting, in place: every streamed statistic is scaled by gamma in (0, 1] -- A, b, c, cnt by
-        gamma, the path probes by sqrt(gamma), log|D| moved by -n log gamma -- in ONE launch (``wiski_decay_stats``).  The model is then
+        gamma, the path probes by sqrt(gamma), log|D| moved by -n log gamma -- in ONE launch (``wiski_decay_stats``; a trend model's C rides on it,
+        its p x p G and p-vector g are scaled by two small launches beside it).  The model is then
         exactly the GP in which every point absorbed so far has its noise d_i replaced by d_i / gamma (k calls: d_i gamma^-k): posterior,
         marginal likelihood and sample paths follow.  ``num_data`` counts points and stays.  The warm-start state of the mean solve is
         kept (its carried residual follows in closed form in the same launch); everything else derived from A is rebuilt on next use.
@@ -2310,6 +2527,10 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             regions.append((cache["_cnt"], gamma))
         if "path_probes" in cache:
             regions.append((cache["path_probes"], math.sqrt(gamma)))          # cov(P_s) = A stays exact
+        if "trend_C" in cache:                       # C, G, g are sums of wa- and wb-weighted terms, like A and b
+            regions.append((cache["trend_C"], gamma))    # (rides on the launch below; G and g, <= 240 fp64 scalars, take two small ones of their own)
+            cache["trend_G"].mul_(gamma)
+            cache["trend_g"].mul_(gamma)
         # R = b - Z - A U of the mean state: Z = Kt^-1 U does not depend on the data, so gamma R - (1 - gamma) Z is the residual of the
         # same (U, Z) in the decayed system -- the next refresh starts warm and without an A U product
         ms = self._carried(True)
@@ -2342,6 +2563,9 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         cache["_stats"].zero_()
         if "_cnt" in cache:
             cache["_cnt"].zero_()
+        for k in ("trend_C", "trend_G", "trend_g"):
+            if k in cache:
+                cache[k].zero_()
         for op in _wtw_ops(cache["WtW"]):
             op.stencil.zero_()
             op.root = op.inv_root = None            # L L^T described the old matrix
@@ -2384,6 +2608,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
                 self._kernel_cache.update(path_probes=c["path_probes"].to(device), path_seed=c["path_seed"], path_count=c["path_count"])
             if c.get("_ring") is not None:
                 self._kernel_cache["_ring"] = c["_ring"].to(device)
+            self._kernel_cache.update(self._trend_entries(c, move=lambda t: t.to(device)))
             self._device = torch.device(device)
             self._err = grid_ops.new_err_flag(device)
             self._mean_state = None
