@@ -314,7 +314,11 @@ typedef struct wiski_twolevel {
  * (first_check), queue the poll, return WISKI_PENDING without waiting -- the host gets its time back while the GPU iterates;
  * 2 = RESUME with the same arguments: wait for that poll (normally long over), finish with synchronous polls if it had not
  * converged, fill h_iters / h_relres / h_err, return 0 / WISKI_E_NOTCONV.  Between START and RESUME nothing else may touch
- * (d_U, d_Z, d_R, d_work) or the system (d_A, d_RHS); the handle owns its own poll buffer. */
+ * (d_U, d_Z, d_R, d_work) or the system (d_A, d_RHS); the handle owns its own poll buffer.
+ * first_check = -1 (needs a handle; every other negative value, and -1 without a handle, is WISKI_E_BADARG): the first poll goes
+ * to max(1, handle->first_ok), where the solve this handle finished last first met the tolerance -- solves of one stream are
+ * alike, so that poll neither fails (as one placed earlier would, at the price of a host round trip with the GPU idle) nor runs
+ * iterations the solve does not need.  Without such history (first_ok_valid == 0) as first_check = 0. */
 typedef struct wiski_pcg_async {
   int32_t state;   /* 0 idle, 1 a started solve is waiting to be resumed */
   int32_t it;      /* iterations queued so far */
@@ -326,6 +330,13 @@ typedef struct wiski_pcg_async {
                         kernel guarded by that poll (wiski_pcg_async_guard) has run */
   double shift;      /* wiski_stream_step: the preconditioner shift the pending solve was STARTed with -- its RESUME continues
                         with it even if the caller has meanwhile set the next step's shift in the argument struct */
+  int32_t first_ok;        /* hindsight of the last solve this handle finished (RESUME, or mode 0 with a handle): the first iteration
+                              at which every column had met the tolerance -- the largest over the columns of each column's first such
+                              iteration, 0 when the start was already converged, <= h_iters -- or -1 when some column never did.
+                              The poll publishes it beside the norms (the device keeps ||r_j||^2 of every iteration j; the scan
+                              looks back at most 32 iterations), so a poll placed later than needed still tells where it was needed */
+  int32_t first_ok_valid;  /* 1 when first_ok >= 0 describes a finished solve: what first_check = -1 places the next first poll by.
+                              Set with first_ok, cleared by wiski_pcg_async_free (and in a zero-initialised handle) */
 } wiski_pcg_async;
 int wiski_pcg_async_f32(const wiski_grid* grid, const float* d_A_st, const float* d_tcol, float kscale, const float* d_evec, const float* d_evec2, const float* d_eval, float shift, const float* d_RHS, int32_t k, float* d_U, float* d_Z, int32_t warm, double tol, int32_t max_iter, int32_t check_every, int32_t first_check, void* d_work, int64_t work_bytes, int32_t* h_iters, double* h_relres, const int32_t* d_err, int32_t* h_err, int32_t a_sym, float* d_R, void* stream, wiski_pcg_async* handle, int32_t mode);
 int wiski_pcg_async_f64(const wiski_grid* grid, const double* d_A_st, const double* d_tcol, double kscale, const double* d_evec, const double* d_evec2, const double* d_eval, double shift, const double* d_RHS, int32_t k, double* d_U, double* d_Z, int32_t warm, double tol, int32_t max_iter, int32_t check_every, int32_t first_check, void* d_work, int64_t work_bytes, int32_t* h_iters, double* h_relres, const int32_t* d_err, int32_t* h_err, int32_t a_sym, double* d_R, void* stream, wiski_pcg_async* handle, int32_t mode);
@@ -372,7 +383,10 @@ int wiski_gather_zero_f64(const wiski_grid* grid, const double* d_x, int64_t n, 
  * defer = 0 just finishes a pending solve.  So the host-language work between two steps overlaps the GPU's CG iterations.
  * (With a mean requested the absorb is in fact queued BEFORE the RESUME, guarded on the device by the verdict of the pending
  * poll -- wiski_pcg_async_guard -- and queued again unguarded only if that verdict was "not converged" or "error flag set";
- * the results are those of the order described above.) */
+ * the results are those of the order described above.)
+ * first_check = -1 with a handle: the step places the first poll of its solve itself, at max(1, handle->first_ok) -- in a call
+ * that RESUMEs a pending solve that is the hindsight this very RESUME produced, never one step old -- and as first_check = 0
+ * while the handle has no history.  -1 without a handle and every other negative value: WISKI_E_BADARG, nothing queued. */
 typedef struct wiski_stream_args_f32 {
   float* d_A_half; float* d_b; float* d_cnt; double* d_stats; int32_t* d_err;     /* statistics + out-of-grid flag      */
   float* d_U; float* d_Z; float* d_R;                                              /* posterior-mean state (in place)    */

@@ -32,7 +32,8 @@ struct PcgArgs {
   double tol = 0;                 // every column: ||r|| / ||rhs|| < tol
   int max_iter = 0;
   int check_every = 0;            // iterations between two convergence polls; < 1: 10
-  int first_check = 0;            // iterations before the first poll; < 1: check_every
+  int first_check = 0;            // iterations before the first poll; 0: check_every; -1 (needs a handle): where the handle's previous
+                                  // solve first met the tolerance (first_ok), check_every without such history
   // workspace
   void* work = nullptr;           // PcgLayout<real>::bytes(m, k, max_iter) bytes of device scratch
   int64_t work_bytes = 0;
@@ -41,6 +42,8 @@ struct PcgArgs {
   double* h_relres = nullptr;     // [k] final relative residuals
   const int32_t* d_err = nullptr; // device: the out-of-grid flag of the absorb / gather entry points
   int32_t* h_err = nullptr;       // its raw value as the last poll saw it
+  int32_t* h_first_ok = nullptr;  // hindsight of the last poll: the first iteration slot at which every column had met the tolerance
+                                  // (the largest over the columns of each column's first such slot; <= h_iters), -1: some column never did
   // deferred poll: 0 = run to convergence; 1 = START: queue the iterations up to the first poll, queue the poll, return
   // WISKI_PENDING without waiting for it; 2 = RESUME a started solve (same arguments): wait for that poll, finish with
   // synchronous polls if it had not converged.  Nothing but the resume call may use (U, Z, R, work) in between

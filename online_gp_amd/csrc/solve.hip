@@ -1580,7 +1580,8 @@ static int spectral_mm_impl(const wiski_grid* grid, const real* d_evec, const re
 // coherent buffer and then releases a sequence number; the host spins on it.  A poll costs a few
 // microseconds instead of the ~80 us of hipMemcpyAsync + hipStreamSynchronize + relaunch bubble.
 struct WiskiPoll {
-  double* h = nullptr;       // host view:   [0] = sequence (as int64), [1..k] = rn0, [k+1..2k] = rn, [2k+1] = err flag, [2k+2] = guard
+  double* h = nullptr;       // host view:   [0] = sequence (as int64), [1..k] = rn0, [k+1..2k] = rn, [2k+1] = err flag, [2k+2] = guard,
+                             // [2k+3] = first_ok: the first slot at which every column had met the tolerance, -1: none (pcg_first_ok)
   double* d = nullptr;       // device view of the same pinned allocation
   long long* g = nullptr;    // device memory: +seq when the poll `seq` found every column converged and no error flag, else -seq --
                              // the guard of a speculatively queued absorb (wiski_scatter_stats_step); mirrored in h[2k+2]
@@ -1596,7 +1597,7 @@ static int poll_reserve(WiskiPoll& P, int k) {
   if (P.cap >= k) return WISKI_OK;
   if (P.h) (void)hipHostFree(P.h);
   const int cap = k < 64 ? 64 : k;
-  if (hipHostMalloc((void**)&P.h, (size_t)(2 * cap + 3) * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent | hipHostMallocPortable) !=
+  if (hipHostMalloc((void**)&P.h, (size_t)(2 * cap + 4) * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent | hipHostMallocPortable) !=
       hipSuccess)
     return WISKI_E_LAUNCH;
   if (hipHostGetDevicePointer((void**)&P.d, P.h, 0) != hipSuccess) return WISKI_E_LAUNCH;
@@ -1669,15 +1670,34 @@ extern "C" int wiski_read_flag(const int32_t* d_flag, int32_t* h_value, void* st
   return WISKI_OK;
 }
 
+// Hindsight of a poll at iteration slot `slot`: the first slot j <= slot at which column c had met the tolerance -- where pcg_active
+// froze it -- or PCG_NEVER_OK.  A poll after iteration `slot` tells the host whether `slot` iterations sufficed; this tells it whether
+// fewer would have, so the next solve of the stream can place its first poll there (PcgArgs::first_check = -1).  The norms of all
+// slots stay in the scalar block; they are read around L2 as the publishers read rn(slot), at most 32 slots back (independent loads).
+constexpr int PCG_NEVER_OK = 0x7fffffff;
+constexpr int PCG_HINDSIGHT_SLOTS = 32;
+__device__ __forceinline__ int pcg_first_ok(const PcgScal& S, int slot, int c, double r0, double tol2) {
+  if (!(r0 > 0)) return 0;
+  const double lim = tol2 * r0;
+  int first = PCG_NEVER_OK;
+  for (int j = slot, lo = slot > PCG_HINDSIGHT_SLOTS ? slot - PCG_HINDSIGHT_SLOTS : 0; j >= lo; --j)
+    if (__hip_atomic_load(S.rn(j) + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= lim) first = j;
+  return first;
+}
+
 __global__ void k_pcg_publish(PcgScal S, int slot, double* __restrict__ poll, const int32_t* __restrict__ err, long long seq, double tol2,
                               long long* __restrict__ guard) {
+  __shared__ int s_first;
   const int k = S.k;
   int ok = 1;
+  if (threadIdx.x == 0) s_first = 0;
+  __syncthreads();
   for (int c = threadIdx.x; c < k; c += blockDim.x) {
     const double r0 = S.rn0()[c], r1 = S.rn(slot)[c];
     poll[1 + c] = r0;
     poll[1 + k + c] = r1;
     if (r0 > 0 && r1 > tol2 * r0) ok = 0;        // the host's convergence test, on the same doubles
+    atomicMax(&s_first, pcg_first_ok(S, slot, c, r0, tol2));
   }
   ok = __syncthreads_and(ok);
   if (threadIdx.x == 0) {
@@ -1685,6 +1705,7 @@ __global__ void k_pcg_publish(PcgScal S, int slot, double* __restrict__ poll, co
     const long long gv = (ok && e == 0.0) ? seq : -seq;
     poll[1 + 2 * k] = e;
     poll[2 + 2 * k] = (double)gv;
+    poll[3 + 2 * k] = s_first == PCG_NEVER_OK ? -1.0 : (double)s_first;
     if (guard) *guard = gv;
   }
   __threadfence_system();
@@ -1881,13 +1902,14 @@ __global__ __launch_bounds__(256) void k_pcg_update_x(int m, int it, double tol2
     // block's ||r||^2 contribution has been performed at the memory side and publishes what k_pcg_publish would, reading the
     // norms around L2.  The contribution is a RETURNING atomic and the ticket is issued only once its result is back -- a
     // release fence here would write back the L2 lines of u, z, r the block has just dirtied (k = 64: 34 -> 113 us).
-    __shared__ int s_last;
+    __shared__ int s_last, s_first;
     if (threadIdx.x == 0) {
       const double prev = atomicAdd(S.rn(it + 1) + c, acc);
       unsigned one = 1u;
       asm volatile("" : "+v"(one) : "v"(prev));            // orders the ticket after the arrival of `prev`
       const unsigned t = atomicAdd(S.ticket(), one);
       s_last = t == gridDim.x * gridDim.y - 1;
+      s_first = 0;
     }
     __syncthreads();
     if (s_last) {
@@ -1899,6 +1921,7 @@ __global__ __launch_bounds__(256) void k_pcg_update_x(int m, int it, double tol2
         poll[1 + c2] = r0;
         poll[1 + k + c2] = r1;
         if (r0 > 0 && r1 > tol2 * r0) ok = 0;    // the host's convergence test, on the same doubles
+        atomicMax(&s_first, pcg_first_ok(S, it + 1, c2, r0, tol2));
       }
       ok = __syncthreads_and(ok);                // s_last is block-uniform: every thread of the block is here
       if (threadIdx.x == 0) {
@@ -1908,6 +1931,7 @@ __global__ __launch_bounds__(256) void k_pcg_update_x(int m, int it, double tol2
         const long long gv = (ok && e == 0.0) ? seq : -seq;
         poll[1 + 2 * k] = e;
         poll[2 + 2 * k] = (double)gv;
+        poll[3 + 2 * k] = s_first == PCG_NEVER_OK ? -1.0 : (double)s_first;
         if (guard) *guard = gv;
         __hip_atomic_store(S.ticket(), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);    // ready for the next poll of this solve
       }
@@ -1957,6 +1981,7 @@ template <typename real>
 static int pcg_validate(const GridDev<real>& G, const PcgArgs<real>& a, const PcgPath& path) {
   if (!a.A || !a.RHS || !a.U || !a.Z || !a.work || a.k < 1 || a.max_iter < 1) return WISKI_E_BADARG;
   if (a.mode != 0 && !a.handle) return WISKI_E_BADARG;                       // START / RESUME live in a handle
+  if (a.first_check < -1 || (a.first_check == -1 && !a.handle)) return WISKI_E_BADARG;   // auto placement reads the handle's history
   if (a.mode == 2 && a.handle->state != 1) return WISKI_E_BADARG;            // nothing was started on this one
   if (!path.spectral && !a.tcol) return WISKI_E_BADARG;                      // no preconditioner at all
   if (a.work_bytes < PcgLayout<real>::bytes(G.m, a.k, a.max_iter)) return WISKI_E_WORKSPACE;
@@ -2133,6 +2158,7 @@ static int pcg_iterate(const PcgPlan<real>& plan) {
 
   std::vector<double> h_rn0(k), h_rn(k);
   double err_seen = 0;
+  int first_ok_seen = -1;     // hindsight of the last poll collected (pcg_first_ok)
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return WISKI_E_LAUNCH;
   // a deferred solve owns a poll buffer of its own (nobody else may publish into it between start and resume)
@@ -2153,6 +2179,7 @@ static int pcg_iterate(const PcgPlan<real>& plan) {
       h_rn[c] = P.h[1 + k + c];
     }
     err_seen = P.h[1 + 2 * k];
+    first_ok_seen = (int)P.h[3 + 2 * k];
   };
   bool deferred = false;      // START mode: the first poll has been queued but not waited for
   // after_publish: the poll with sequence number `seq` (iteration slot `slot`) has been queued
@@ -2193,6 +2220,9 @@ static int pcg_iterate(const PcgPlan<real>& plan) {
     first_check = it;          // from here on: a poll after every check_every-th further iteration
     mode = 0;
   }
+  // auto: where the handle's previous solve first met the tolerance -- no earlier (that poll would fail if the stream is as it
+  // was), no later (an iteration the solve does not need); without such history as first_check = 0
+  if (first_check == -1) first_check = as->first_ok_valid ? (as->first_ok > 1 ? as->first_ok : 1) : 0;
   if (first_check < 1) first_check = check_every;
   if (first_check > max_iter) first_check = max_iter;
   // host convergence polls: after `first_check` iterations, then every `check_every`
@@ -2266,7 +2296,12 @@ static int pcg_iterate(const PcgPlan<real>& plan) {
     if (rc) return rc;
   }
   if (a.h_iters) *a.h_iters = it;
-  if (a.h_err) *a.h_err = (int32_t)err_seen;   // raw flag word: bit 0 = any point outside the grid, bits 1.. = count of such training points
+  if (a.h_first_ok) *a.h_first_ok = first_ok_seen;
+  if (as) {
+    as->first_ok = first_ok_seen;
+    as->first_ok_valid = first_ok_seen >= 0 ? 1 : 0;
+  }
+  if (a.h_err) *a.h_err = (int32_t)err_seen;  // raw flag word: bit 0 = any point outside the grid, bits 1.. = count of such training points
   if (a.h_relres)
     for (int c = 0; c < k; ++c) a.h_relres[c] = h_rn0[c] > 0 ? sqrt(h_rn[c] / h_rn0[c]) : 0.0;
   return done ? WISKI_OK : WISKI_E_NOTCONV;
@@ -2480,6 +2515,8 @@ int wiski_pcg_async_free(wiski_pcg_async* as) {
     as->poll = nullptr;
   }
   as->state = 0;
+  as->first_ok = 0;
+  as->first_ok_valid = 0;
   return WISKI_OK;
 }
 int wiski_pcg_async_guard(const wiski_pcg_async* as, const void** d_guard, int64_t* expect) { return pcg_guard(as, d_guard, expect); }

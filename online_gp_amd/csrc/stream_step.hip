@@ -62,6 +62,10 @@ static int stream_step_impl(const wiski_grid* grid, const typename StreamArgs<re
   if (!grid || !a || q < 0 || !a->d_A_half || !a->d_b || !a->d_U || !a->d_Z || !a->d_R) return WISKI_E_BADARG;
   if (q > 0 && (!d_x || !d_y || !d_wa || !d_wb || !d_noise)) return WISKI_E_BADARG;
   if (wiski_shard_active(a->shard) && q > 0 && !d_mean_out) return WISKI_E_BADARG;   // the sharded absorb is the mean-emitting kernel
+  // first_check = -1: pcg() places the first poll where the handle's last finished solve first met the tolerance (first_ok).  The
+  // solve below is queued after the RESUME of the pending one, so that is the hindsight of the solve just resumed.  Refused here
+  // as pcg_validate would, before the absorb is queued
+  if (first_check < -1 || (first_check == -1 && !as)) return WISKI_E_BADARG;
   int rc = WISKI_OK;
   if (h_resumed) *h_resumed = 0;
   PcgArgs<real> solve = solve_args<real>(a, carry, first_check);   // this stream's solve, reporting into the caller's outputs

@@ -5,6 +5,7 @@ the HIP kernels under csrc/.
 """
 import ctypes
 import math
+import time
 import warnings
 
 import numpy as np
@@ -1049,12 +1050,15 @@ class _StreamArgs64(ctypes.Structure):
 
 class _PcgAsync(ctypes.Structure):
     _fields_ = [("state", ctypes.c_int32), ("it", ctypes.c_int32), ("seq", ctypes.c_int64), ("poll", ctypes.c_void_p),
-                ("prezeroed", ctypes.c_int32), ("guard_ok", ctypes.c_int32), ("shift", ctypes.c_double)]
+                ("prezeroed", ctypes.c_int32), ("guard_ok", ctypes.c_int32), ("shift", ctypes.c_double),
+                ("first_ok", ctypes.c_int32), ("first_ok_valid", ctypes.c_int32)]
 
 
 class StreamStep:
     """Prepared call of ``wiski_stream_step`` (include/wiski.h): the model-resident pointers are marshalled once, a step only
     passes the batch.  Returns (iterations, relative residual, raw out-of-grid flag, converged)."""
+
+    step_log = None
 
     def __init__(self, grid, dtype, device, A_half, b, cnt, stats, err, U, Z, R, tcol, workspace, max_iter):
         self.grid, self.dtype, self.device = grid, dtype, device
@@ -1072,6 +1076,10 @@ class StreamStep:
         self.eig_keep = None
         self.handle = _PcgAsync()              # deferred-poll state (include/wiski.h: wiski_pcg_async)
         self.resumed = ctypes.c_int32(0)
+        # diagnostic, off by default: a file name here (or in StreamStep.step_log before the step is built) appends one line per call --
+        # host time, the first_check passed, where the new solve's first poll was placed, what the resumed solve reported, whether the
+        # speculative absorb ran (profiles/r09_poll_hindsight.txt was taken with it)
+        self.step_log = StreamStep.step_log
 
     @property
     def pending(self):
@@ -1154,6 +1162,12 @@ class StreamStep:
         elif rc != 1:
             _hip.check(rc, "wiski_stream_step")
         res = (int(self.it.value), float(self.rr.value), int(self.herr.value), rc != -4)
+        if self.step_log:
+            h = self.handle
+            with open(self.step_log, "a") as f:
+                f.write("t_us=%.1f q=%d first_check=%d placed=%d rc=%d resumed=%d iters=%d relres=%.3e guard_ok=%d first_ok=%d/%d\n" % (
+                    time.perf_counter() * 1e6, q, int(first_check), h.it if use_handle else -1, rc, self.resumed.value, res[0], res[1],
+                    h.guard_ok, h.first_ok, h.first_ok_valid))
         if not use_handle:
             return res
         # resumed == 2: a pending solve was finished AND this step's solve ran synchronously -- `res` describes the latter

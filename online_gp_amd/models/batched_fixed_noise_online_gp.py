@@ -1925,7 +1925,13 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         self._refresh_count = getattr(self, "_refresh_count", 0) + 1
         self._two_level_step(step, pst, X, q)            # (may set the poll hint: before _first_poll)
         last = (getattr(self, "_last_iters", None) or [0])[0]
-        fc, probe = self._first_poll(last)
+        # with a deferred-poll handle the library places the first poll itself, by the hindsight of the solve this call resumes
+        # (stencil-sharded replicas keep the host's placement: their ranks must poll in lock step -- and so does a single GPU under
+        # settings.two_level_lockstep, which exists to give it the replicas' iteration counts: a poll placed by hindsight reports the
+        # masked iteration it costs when the stream gets easier, the host's early polls after a block switch do not)
+        auto = (settings.poll_hindsight.on() and (settings.deferred_refresh.on() or step.pending)
+                and self.__dict__.get("_stencil_shard") is None and settings.two_level_lockstep.off())
+        fc, probe = self._first_poll(last, step.pending if auto else None)
         carry = ms.get("R_ok", False) and self._refresh_count % 16 != 0
         step.args.shift = float(self._wsum[0]) / pst["norm"]
         step.set_keep(self._keep_for_step(step, pst))
@@ -2035,7 +2041,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         if getattr(step, "_two_level", None) is not tl:
             step.set_two_level(tl)
 
-    def _first_poll(self, last):
+    def _first_poll(self, last, auto=None):
         """Where a warm refresh polls convergence first: (iteration count, is this a probe?).  Streaming steps are alike (at
         50^3 the uniform bench stream needs 3 iterations for its first ~40 steps and 2 ever after; the clustered one 6, now and
         then 5), so the first poll goes where the previous refresh converged.  A *probe* polls one iteration earlier to notice
@@ -2044,9 +2050,17 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         every 4th refresh while the last converged residual says one iteration less might do (it is below tol / 10; the
         contraction per iteration is ~0.08 here: the residual after 3 iterations falls from 8e-5 to 7e-6 before 2 suffice),
         otherwise after 8, 16, 32 refreshes.  (Probing every other refresh, as before: 50 % failed polls, 0.221 ms per step
-        against 0.216 with this placement, tools/policy_probe.py.)"""
+        against 0.216 with this placement, tools/policy_probe.py.)
+        `auto` (not None: the step carries a deferred-poll handle and ``settings.poll_hindsight`` is on; its value says whether a
+        solve is pending): -1, "place it by the hindsight of the previous solve" (include/wiski.h, first_check = -1) wherever the
+        rules above would have answered from the history -- every poll reports where its solve first met the tolerance, so there is
+        nothing to probe for.  Only the explicit hint of the first step after a cold solve stays."""
         if not last:
             return 0, False
+        if auto is not None:
+            self._poll_hint_sticky = self._probe_pending = 0
+            hint = getattr(self, "_poll_hint", 0)
+            return (min(last, hint) if hint and not auto else -1), False
         sticky = getattr(self, "_poll_hint_sticky", 0)
         if sticky:
             # a new block of the two-level preconditioner went in: for this step and the next (whose `last` still predates the
@@ -2093,7 +2107,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
     def _note_solve(self, ms, res, fc, probe=False):
         """Host bookkeeping after a refresh: iteration history for the poll placement, residual validity, out-of-grid error."""
         it, rel, flag, conv = res
-        if fc:
+        if fc > 0:                                   # (-1: the library placed the poll, nothing to learn here)
             self._note_poll(it, fc, probe)
         self._last_iters = [it]
         self._last_rel = rel

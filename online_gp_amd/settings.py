@@ -287,6 +287,16 @@ class two_level_lockstep(_feature_flag):
     _state = False
 
 
+class poll_hindsight(_feature_flag):
+    """One-call streaming steps with a deferred-poll handle let the library place the first convergence poll of their solve
+    (``first_check = -1``, include/wiski.h): where the previous solve of the stream first met the tolerance, which every poll
+    reports beside the residual norms -- no probes one iteration early and no early polls after a new two-level block went in.
+    Off: the host-side placement of ``_first_poll`` (stencil-sharded steps always use it, and so do steps under
+    ``two_level_lockstep``, whose iteration counts are meant to equal the replicas')."""
+
+    _state = True
+
+
 class two_level_growth(_value_context):
     """A refresh of the two-level block is started when the absorbed weight has grown by this factor since the last one
     (50^3 road-like stream: 1.1 -> 22 refreshes per 3droad-sized pass, 2.57 iterations per step; 1.2 -> 13 and 2.62)."""
