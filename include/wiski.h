@@ -523,6 +523,33 @@ int wiski_scatter_stats_interval_f64(const wiski_grid* grid, const double* d_x, 
 int wiski_absorb_interval_f32(const wiski_grid* grid, const wiski_absorb_args* args, const float* d_lo, const float* d_hi, const float* d_pvar, double sigma2, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, void* stream);
 int wiski_absorb_interval_f64(const wiski_grid* grid, const wiski_absorb_args* args, const double* d_lo, const double* d_hi, const double* d_pvar, double sigma2, double* d_ytilde_out, double* d_omega_out, double* d_logz_out, void* stream);
 
+/* Count observations: point p carries a count d_y_p and a second number d_t_p.  `family`:
+ *   WISKI_COUNT_POISSON   y ~ Poisson(t exp f(x)), t > 0 the exposure, y >= 0 (non-integers allowed: the constant is lgamma);
+ *   WISKI_COUNT_BINOMIAL  y successes of t trials at success probability 1 / (1 + exp(-f(x))), 0 <= y <= t.
+ * Every point is moment-matched against the posterior BEFORE the batch, inside the launch that absorbs it, as an interval
+ * observation is.  With mu = w_p . u, v = max(d_pvar_p, 0) and l the likelihood,
+ *   Z = int l(f) N(f; mu, v) df,   alpha = d log Z / d mu,   beta = -d^2 log Z / d mu^2,
+ *   tau = beta / (1 - v beta),   ytilde = mu + alpha / beta,   omega = sigma2 noise_p tau,
+ * evaluated in double in both precisions by a quadrature whose nodes are the 64 lanes of the point's wave (sectioning to the mode,
+ * a bracket where the log integrand has fallen by 40, 64 Gauss-Legendre nodes on either side of the mode), and the point enters as
+ * the target ytilde at noise noise_p / omega_p -- the effective noise variance 1 / tau.  omega is NOT capped at 1: a count has no
+ * Gaussian noise of its own, callers pass noise = wa = wb = 1.  v = 0 gives the Laplace site at mu.  A point is SKIPPED -- it enters
+ * nothing and is not flagged in d_err -- when omega < 1e-12 (WISKI_COUNT_OMEGA_MIN), when beta is not positive and finite, or when
+ * the datum is invalid (y < 0, t <= 0, y > t for the binomial, a NaN: log Z = NaN).  Outputs and every other argument as
+ * wiski_scatter_stats_interval; d_logz_out is the log predictive probability of the count.  wiski_absorb_count takes the record
+ * (its d_y is ignored) plus the count arguments, so that every refused combination (a guard, zero regions, a shard, an owner
+ * workspace, nout > 1, channels, a full stencil) can be reached and tested; wiski_absorb_args has NOT grown.
+ * wiski_count_sites evaluates the sites alone, one wave per site and no scatter, from given means d_mu and variances d_pvar [n]:
+ * d_omega_out receives tau (sigma2 noise = 1). */
+#define WISKI_COUNT_POISSON 0
+#define WISKI_COUNT_BINOMIAL 1
+int wiski_scatter_stats_count_f32(const wiski_grid* grid, const float* d_x, const float* d_y, const float* d_t, int family, const float* d_pvar, double sigma2, const float* d_wa, const float* d_wb, const float* d_noise, int64_t n, float* d_b, float* d_A_half, float* d_cnt, const float* d_u, float* d_res, float* d_mean_out, double* d_stats, int32_t* d_err, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, void* stream);
+int wiski_scatter_stats_count_f64(const wiski_grid* grid, const double* d_x, const double* d_y, const double* d_t, int family, const double* d_pvar, double sigma2, const double* d_wa, const double* d_wb, const double* d_noise, int64_t n, double* d_b, double* d_A_half, double* d_cnt, const double* d_u, double* d_res, double* d_mean_out, double* d_stats, int32_t* d_err, double* d_ytilde_out, double* d_omega_out, double* d_logz_out, void* stream);
+int wiski_absorb_count_f32(const wiski_grid* grid, const wiski_absorb_args* args, const float* d_y, const float* d_t, int family, const float* d_pvar, double sigma2, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, void* stream);
+int wiski_absorb_count_f64(const wiski_grid* grid, const wiski_absorb_args* args, const double* d_y, const double* d_t, int family, const double* d_pvar, double sigma2, double* d_ytilde_out, double* d_omega_out, double* d_logz_out, void* stream);
+int wiski_count_sites_f32(const float* d_mu, const float* d_pvar, const float* d_y, const float* d_t, int family, int64_t n, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, void* stream);
+int wiski_count_sites_f64(const double* d_mu, const double* d_pvar, const double* d_y, const double* d_t, int family, int64_t n, double* d_ytilde_out, double* d_omega_out, double* d_logz_out, void* stream);
+
 /* The two halves of a stencil-sharded step on their own (wiski_stream_step uses them when args->shard is set): the absorb
  * restricted to the stencil groups [g_lo, g_hi) (same arguments as wiski_scatter_stats_step; always the atomic form), and
  * wiski_pcg_async with every A . v product summed over the ranks of `shard`. */

@@ -3,10 +3,11 @@
 // may be asked to do, as ONE named record.  Every member defaults to "off"; the extern "C" entry points of scatter_stats.hip
 // and the streaming step (stream_step.hip) fill the fields they expose and call absorb().  Which combinations are refused is
 // absorb_validate() in scatter_stats.hip; whoever writes another form of the absorb has to honour every group below.
-// Five kernels stand behind it: the atomic form (k_scatter_stats[_sym]; the owner form where its workspace is given and applies),
+// Six kernels stand behind it: the atomic form (k_scatter_stats[_sym]; the owner form where its workspace is given and applies),
 // the derivative-observation form (`channels`, scatter_grad.h), the outlier-robust form (`inv_scale`, scatter_robust.h), the
-// sliding-window form (`ring_*`, scatter_window.h) and the interval form (`lo`, scatter_interval.h).  The last four implement the
-// plain single-output half-stencil absorb with cnt and the carry and refuse every other group.  What the five half-stencil kernels do per point -- the tap tables, the per-tap
+// sliding-window form (`ring_*`, scatter_window.h), the interval form (`lo`, scatter_interval.h) and the count form (`count_y`,
+// scatter_count.h).  The last five implement the plain single-output half-stencil absorb with cnt and the carry and refuse every
+// other group.  What the six half-stencil kernels do per point -- the tap tables, the per-tap
 // atomics, the pair loop that encodes the row-interleaved layout, the two scalars -- is stated once, in scatter_half.h.
 #pragma once
 #include "wiski_common.h"
@@ -93,10 +94,21 @@ struct AbsorbArgs {
   double sigma2 = 0;                // the noise scale: the point's noise variance is sigma2 noise
   real* ytilde_out = nullptr;       // [n] the pseudo-target each point entered with; the predictive mean for a skipped point
   double* logz_out = nullptr;       // [n] log P(lo <= y <= hi) under the posterior before the batch  (omega_out: the robust group's field)
+  // count: count_y != NULL makes every point a count observation (scatter_count.h): count_y successes / events at count_t trials /
+  // exposure under the family's link, moment-matched against the posterior before the batch by a quadrature over the lanes of the
+  // point's wave, and entered as the target ytilde at noise / omega, omega = sigma2 noise tau (not capped); y is ignored.  An
+  // invalid datum (y < 0, t <= 0, y > t for the binomial, a NaN) and a site with omega < WISKI_COUNT_OMEGA_MIN are skipped, as in the
+  // interval form, whose pvar / sigma2 / ytilde_out / omega_out / logz_out it shares and needs, with u, A and cnt.  Single-output
+  // half-stencil atomic form only: no channels, inv_scale, ring, interval bounds, guard, zero regions, shard or owner workspace
+  const real* count_y = nullptr;    // [n] counts (non-integers allowed)
+  const real* count_t = nullptr;    // [n] exposure (Poisson) / trials (binomial)
+  int count_family = 0;             // WISKI_COUNT_POISSON, WISKI_COUNT_BINOMIAL
 
   bool sharded() const { return g_lo > 0 || g_hi < (1 << 30); }
   bool windowed() const { return ring_x || ring_y || ring_wa || ring_wb || ring_noise || ring_cap || ring_head || void_left; }
-  bool interval() const { return lo || hi || pvar || sigma2 != 0 || ytilde_out || logz_out; }
+  bool counted() const { return count_y || count_t || count_family != 0; }
+  // (the fields the two moment-matched forms share belong to the interval group unless the count group is given)
+  bool interval() const { return lo || hi || (!counted() && (pvar || sigma2 != 0 || ytilde_out || logz_out)); }
 };
 
 // Validates, then queues the absorb on `stream`: WISKI_OK, WISKI_E_BADARG (nothing was launched) or WISKI_E_LAUNCH.

@@ -177,6 +177,7 @@ __global__ __launch_bounds__(256) void k_scatter_stats_sym(GridDev<real> G, cons
 #include "scatter_robust.h"
 #include "scatter_window.h"
 #include "scatter_interval.h"
+#include "scatter_count.h"
 
 // Unpacks the row-interleaved half stencil into a full offset-major stencil full[o][i] = A[i, i + off(o)]
 // (diagnostics, tests, and models handed a full-stencil cache):
@@ -244,7 +245,20 @@ static int64_t owner_min_points() {
 template <typename real>
 static int absorb_validate(const AbsorbArgs<real>& a, int d) {
   if (a.n == 0) return WISKI_OK;                       // nothing to absorb: not even the pointers are looked at
-  if (!a.x || (!a.y && !a.lo) || !a.wa || !a.wb || !a.noise || !a.b || !a.stats || !a.err) return WISKI_E_BADARG;   // what every form reads and writes (the interval form has no y)
+  if (!a.x || (!a.y && !a.lo && !a.count_y) || !a.wa || !a.wb || !a.noise || !a.b || !a.stats || !a.err) return WISKI_E_BADARG;   // what every form reads and writes (the interval and count forms have no y)
+  if (a.counted()) {
+    // count (scatter_count.h): the whole group and the fields it shares with the interval form, but not its bounds; the sites need u;
+    // A, cnt and the three outputs are written unconditionally; the plain single-output half-stencil atomic form only, and neither
+    // the robust nor the window one.  res and mean_out are optional
+    if (a.lo || a.hi) return WISKI_E_BADARG;
+    if (!a.count_y || !a.count_t || (a.count_family != WISKI_COUNT_POISSON && a.count_family != WISKI_COUNT_BINOMIAL)) return WISKI_E_BADARG;
+    if (!a.pvar || !a.ytilde_out || !a.omega_out || !a.logz_out) return WISKI_E_BADARG;
+    if (!(a.sigma2 > 0) || !std::isfinite(a.sigma2)) return WISKI_E_BADARG;
+    if (!a.u || !a.half || !a.A || !a.cnt || a.nout != 1 || a.channels) return WISKI_E_BADARG;
+    if (a.inv_scale || a.huber_c != (real)0 || a.windowed()) return WISKI_E_BADARG;
+    if (a.guard || a.n1_bytes || a.n2_bytes || a.z1 || a.z2 || a.sharded() || a.bin || a.bin_bytes) return WISKI_E_BADARG;
+    return WISKI_OK;
+  }
   if (a.interval()) {
     // interval (scatter_interval.h): the whole group; the sites need u; A, cnt and the three outputs are written unconditionally;
     // the plain single-output half-stencil atomic form only, and neither the robust nor the window one.  res and mean_out are optional
@@ -368,6 +382,7 @@ int absorb(const wiski_grid* grid, const AbsorbArgs<real>& a, void* stream) {
   int rc = make_grid_dev<real>(grid, &G);
   if (rc == WISKI_OK) rc = absorb_validate(a, G.d);
   if (rc != WISKI_OK || a.n == 0) return rc;
+  if (a.counted()) return launch_count(G, a, (hipStream_t)stream);
   if (a.interval()) return launch_interval(G, a, (hipStream_t)stream);
   if (a.windowed()) return launch_window(G, a, (hipStream_t)stream);
   if (a.inv_scale) return launch_robust(G, a, (hipStream_t)stream);
@@ -469,6 +484,22 @@ static int entry_absorb_interval(const wiski_grid* g, const wiski_absorb_args* p
   return p ? entry_interval(g, absorb_args<real>(*p), lo, hi, pvar, sigma2, ytilde_out, omega_out, logz_out, s) : WISKI_E_BADARG;
 }
 template <typename real>
+static int entry_count(const wiski_grid* g, AbsorbArgs<real> a, const real* cy, const real* ct, int family, const real* pvar, double sigma2, real* ytilde_out, real* omega_out, double* logz_out, void* s) {
+  a.y = nullptr;                                       // ignored by the form
+  a.count_y = cy; a.count_t = ct; a.count_family = family; a.pvar = pvar; a.sigma2 = sigma2; a.ytilde_out = ytilde_out; a.omega_out = omega_out; a.logz_out = logz_out;
+  return cy ? absorb(g, a, s) : WISKI_E_BADARG;
+}
+template <typename real>
+static int entry_scatter_count(const wiski_grid* g, const real* x, const real* cy, const real* ct, int family, const real* pvar, double sigma2, const real* wa, const real* wb, const real* noise, int64_t n, real* b, real* A_half, real* cnt, const real* u, real* res, real* mean_out, double* stats, int32_t* err, real* ytilde_out, real* omega_out, double* logz_out, void* s) {
+  AbsorbArgs<real> a = absorb_args(x, (const real*)nullptr, wa, wb, noise, n, b, A_half, true, stats, err);
+  absorb_carry(a, cnt, u, res, mean_out);
+  return entry_count(g, a, cy, ct, family, pvar, sigma2, ytilde_out, omega_out, logz_out, s);
+}
+template <typename real>
+static int entry_absorb_count(const wiski_grid* g, const wiski_absorb_args* p, const real* cy, const real* ct, int family, const real* pvar, double sigma2, real* ytilde_out, real* omega_out, double* logz_out, void* s) {
+  return p ? entry_count(g, absorb_args<real>(*p), cy, ct, family, pvar, sigma2, ytilde_out, omega_out, logz_out, s) : WISKI_E_BADARG;
+}
+template <typename real>
 static int entry_plain(const wiski_grid* g, const real* x, const real* y, const real* wa, const real* wb, const real* noise, int64_t n, real* b, real* A, bool half, double* stats, int32_t* err, void* s) {
   return absorb(g, absorb_args(x, y, wa, wb, noise, n, b, A, half, stats, err), s);
 }
@@ -514,6 +545,12 @@ int wiski_scatter_stats_interval_f32(const wiski_grid* g, const float* x, const 
 int wiski_scatter_stats_interval_f64(const wiski_grid* g, const double* x, const double* lo, const double* hi, const double* pvar, double sigma2, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return entry_scatter_interval(g, x, lo, hi, pvar, sigma2, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, ytilde_out, omega_out, logz_out, s); }
 int wiski_absorb_interval_f32(const wiski_grid* g, const wiski_absorb_args* p, const float* lo, const float* hi, const float* pvar, double sigma2, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return entry_absorb_interval(g, p, lo, hi, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
 int wiski_absorb_interval_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* lo, const double* hi, const double* pvar, double sigma2, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return entry_absorb_interval(g, p, lo, hi, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
+int wiski_scatter_stats_count_f32(const wiski_grid* g, const float* x, const float* y, const float* t, int family, const float* pvar, double sigma2, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return entry_scatter_count(g, x, y, t, family, pvar, sigma2, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, ytilde_out, omega_out, logz_out, s); }
+int wiski_scatter_stats_count_f64(const wiski_grid* g, const double* x, const double* y, const double* t, int family, const double* pvar, double sigma2, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return entry_scatter_count(g, x, y, t, family, pvar, sigma2, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, ytilde_out, omega_out, logz_out, s); }
+int wiski_absorb_count_f32(const wiski_grid* g, const wiski_absorb_args* p, const float* y, const float* t, int family, const float* pvar, double sigma2, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return entry_absorb_count(g, p, y, t, family, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
+int wiski_absorb_count_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* y, const double* t, int family, const double* pvar, double sigma2, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return entry_absorb_count(g, p, y, t, family, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
+int wiski_count_sites_f32(const float* mu, const float* pvar, const float* y, const float* t, int family, int64_t n, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return count_sites_impl(mu, pvar, y, t, family, n, ytilde_out, omega_out, logz_out, s); }
+int wiski_count_sites_f64(const double* mu, const double* pvar, const double* y, const double* t, int family, int64_t n, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return count_sites_impl(mu, pvar, y, t, family, n, ytilde_out, omega_out, logz_out, s); }
 int wiski_scatter_stats_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A, double* stats, int32_t* err, void* s) { return entry_plain(g, x, y, wa, wb, noise, n, b, A, false, stats, err, s); }
 int wiski_scatter_stats_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A, double* stats, int32_t* err, void* s) { return entry_plain(g, x, y, wa, wb, noise, n, b, A, false, stats, err, s); }
 int wiski_scatter_stats_sym_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, double* stats, int32_t* err, void* s) { return entry_plain(g, x, y, wa, wb, noise, n, b, A_half, true, stats, err, s); }

@@ -381,9 +381,11 @@ class ShardedStatsUpdater:
                 self._delta["_cnt"].zero_()
         return self._delta
 
-    def update(self, X, Y, noise=None, *, lower=None, upper=None):
+    def update(self, X, Y, noise=None, *, lower=None, upper=None, counts=None, exposure=None, trials=None):
         from . import grid_ops
 
+        if counts is not None or exposure is not None or trials is not None:
+            raise NotImplementedError("ShardedStatsUpdater does not carry count observations (counts): condition the model itself")
         if lower is not None or upper is not None:
             # the sites of a shard would be matched on one rank, and the other ranks' followers never see them: single-GPU for now
             raise NotImplementedError("ShardedStatsUpdater does not carry interval observations (lower / upper): condition the model itself")

@@ -488,6 +488,63 @@ def scatter_stats_interval(grid, x, lower, upper, pvar, sigma2, wa, wb, noise, b
     return ytilde, omega, log_z
 
 
+COUNT_FAMILIES = {"poisson": 0, "binomial": 1}      # WISKI_COUNT_POISSON, WISKI_COUNT_BINOMIAL
+
+
+def scatter_stats_count(grid, x, counts, t, family, pvar, sigma2, wa, wb, noise, b, A_half, cnt, stats, err, u, res=None, mean_out=None):
+    """The count-observation absorb in ONE launch (``wiski_scatter_stats_count``): point i carries the count
+    ``counts_i`` at exposure (``family`` "poisson": y ~ Poisson(t exp f)) or out of trials (``"binomial"``, logit link) ``t_i``.  It is
+    moment-matched against the posterior before the batch -- the grid mean ``u`` [m], the posterior variance ``pvar`` [n] of f at x --
+    by a quadrature over the lanes of its wave and enters (b, A_half, cnt, stats) -- and the carried residual ``res``, if given -- as
+    the target ytilde_i at noise_i / omega_i, omega = sigma2 noise tau (effective noise variance 1 / tau; not capped).  Returns
+    (ytilde [n], omega [n], log_z [n] float64); a skipped point (omega below 1e-12, an invalid datum) has omega = 0 and ytilde = w . u,
+    a point outside the grid (0, 0, 0).  ``mean_out`` [n] receives w . u."""
+    x = _x2d(x, grid)
+    n = x.shape[0]
+    if family not in COUNT_FAMILIES:
+        raise ValueError(f"scatter_stats_count: family must be one of {sorted(COUNT_FAMILIES)}, got {family!r}")
+    for name, v in (("counts", counts), ("t", t), ("pvar", pvar), ("wa", wa), ("wb", wb), ("noise", noise), ("mean_out", mean_out)):
+        if v is not None and (tuple(v.shape) != (n,) or v.dtype != x.dtype):
+            raise ValueError(f"scatter_stats_count: {name} must be [{n}] {x.dtype}, got {tuple(v.shape)} {v.dtype}")
+    if u is None or tuple(u.shape) != (grid.m,) or u.dtype != x.dtype:
+        raise ValueError(f"scatter_stats_count: u must be the grid mean [{grid.m}] {x.dtype}")
+    ytilde = torch.empty(n, dtype=x.dtype, device=x.device)
+    omega = torch.empty(n, dtype=x.dtype, device=x.device)
+    log_z = torch.empty(n, dtype=torch.float64, device=x.device)
+    if n == 0:
+        return ytilde, omega, log_z
+    rc = _hip.fn("wiski_scatter_stats_count", x.dtype)(grid.ref, _hip.dptr(x), _hip.dptr(counts.contiguous()), _hip.dptr(t.contiguous()),
+                                                       ctypes.c_int(COUNT_FAMILIES[family]), _hip.dptr(pvar.contiguous()), ctypes.c_double(float(sigma2)),
+                                                       _hip.dptr(wa.contiguous()), _hip.dptr(wb.contiguous()), _hip.dptr(noise.contiguous()), ctypes.c_int64(n),
+                                                       _hip.dptr(b), _hip.dptr(A_half), _hip.dptr(cnt), _hip.dptr(u), _hip.dptr(res), _hip.dptr(mean_out),
+                                                       _hip.dptr(stats), _hip.dptr(err), _hip.dptr(ytilde), _hip.dptr(omega), _hip.dptr(log_z),
+                                                       _hip.stream_ptr(x.device))
+    _hip.check(rc, "wiski_scatter_stats_count")
+    return ytilde, omega, log_z
+
+
+def count_sites(mean, pvar, counts, t, family):
+    """The sites of count observations alone (``wiski_count_sites``: the device function of ``scatter_stats_count``, one wave per
+    site, no scatter) against given means and variances [n]: (ytilde [n], tau [n], log_z [n] float64), tau the site precision (the
+    omega of ``scatter_stats_count`` at sigma2 noise = 1)."""
+    if family not in COUNT_FAMILIES:
+        raise ValueError(f"count_sites: family must be one of {sorted(COUNT_FAMILIES)}, got {family!r}")
+    n = mean.shape[0]
+    for name, v in (("mean", mean), ("pvar", pvar), ("counts", counts), ("t", t)):
+        if tuple(v.shape) != (n,) or v.dtype != mean.dtype:
+            raise ValueError(f"count_sites: {name} must be [{n}] {mean.dtype}, got {tuple(v.shape)} {v.dtype}")
+    ytilde = torch.empty(n, dtype=mean.dtype, device=mean.device)
+    tau = torch.empty(n, dtype=mean.dtype, device=mean.device)
+    log_z = torch.empty(n, dtype=torch.float64, device=mean.device)
+    if n == 0:
+        return ytilde, tau, log_z
+    rc = _hip.fn("wiski_count_sites", mean.dtype)(_hip.dptr(mean.contiguous()), _hip.dptr(pvar.contiguous()), _hip.dptr(counts.contiguous()),
+                                                  _hip.dptr(t.contiguous()), ctypes.c_int(COUNT_FAMILIES[family]), ctypes.c_int64(n), _hip.dptr(ytilde),
+                                                  _hip.dptr(tau), _hip.dptr(log_z), _hip.stream_ptr(mean.device))
+    _hip.check(rc, "wiski_count_sites")
+    return ytilde, tau, log_z
+
+
 class WindowRing:
     """The device-resident ring of a sliding window (``wiski_window_ring``): x [cap, d], y / wa / wb / noise [cap]
     in the working precision, and on the host ``head`` -- the slot the next entering point takes -- and ``fill``, the number of

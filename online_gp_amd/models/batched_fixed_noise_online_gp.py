@@ -134,6 +134,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         self.last_robust_weights = None              # omega [q] of the last robustly absorbed batch, on the device
         # interval observations (_absorb_interval): (ytilde, omega, log_z) [q] of the last batch given as bounds
         self.last_interval_sites = None
+        # count observations (_absorb_count): (ytilde, omega, log_z) [q] of the last batch given as counts
+        self.last_count_sites = None
         # sliding window (_absorb_window): the model is the GP of exactly the last `window` points; every update absorbs
         # its batch, stores it in a device-resident ring and takes out what the ring's slots held, in one launch
         if window is not None:
@@ -1442,7 +1444,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
 
     # -------------------------------------------------------------- updates --
     def condition_on_observations(self, X, Y, noise=None, inplace=False, _decay=True, *, grad_Y=None, grad_noise=None, grad_mask=None,
-                                  lower=None, upper=None):
+                                  lower=None, upper=None, counts=None, exposure=None, trials=None):
         """a7, :258-285.  inplace: the statistics buffers are updated where they
         live (O(4^{2d}) atomics per point); otherwise they are cloned first and a
         sibling model sharing covar_module / likelihood is returned.  With a ``forgetting_factor`` the statistics -- of the clone,
@@ -1471,7 +1473,20 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         ``noise_i / omega_i`` in the same launch; ``last_interval_sites`` -- of the returned model, in the functional form -- then
         holds ``(ytilde, omega, log_z)``.  This is parallel assumed-density filtering: an approximation of the non-Gaussian
         posterior, whose MLL is the Gaussian MLL of the pseudo-data; ``log_z.sum()`` is the prequential evidence of the batch.  A
-        point with nothing to say (omega = 0) enters nothing and does not count in ``num_data``.  Single output, unbatched X."""
+        point with nothing to say (omega = 0) enters nothing and does not count in ``num_data``.  Single output, unbatched X.
+
+        ``counts`` [n] with ``Y=None``: count observations (``_condition_count``) -- ``counts_i ~ Poisson(exposure_i
+        exp f(x_i))`` (``exposure`` None: 1), or with ``trials`` given ``counts_i`` successes of ``trials_i`` at success probability
+        sigmoid(f(x_i)).  Moment-matched and absorbed like bounds, at the effective noise variance ``1 / tau_i``;
+        ``last_count_sites`` holds ``(ytilde, omega, log_z)`` with ``omega = sigma2 tau``.  Single output, unbatched X."""
+        if counts is not None or exposure is not None or trials is not None:
+            if self._trend_deg is not None:
+                self._refuse_trend("count observations (counts)", "a site is matched against the grid mean alone, which under a trend "
+                                   "is not the predictive mean")
+            if Y is not None or noise is not None or grad_Y is not None or grad_noise is not None or grad_mask is not None or lower is not None or upper is not None:
+                raise NotImplementedError("a batch of counts is given as counts with exposure or trials alone: no Y, noise, grad_* or lower / upper "
+                                          "(a count has no Gaussian noise of its own)")
+            return self._condition_count(X, counts, exposure, trials, inplace, _decay)
         if self._trend_deg is not None:
             if lower is not None or upper is not None:
                 self._refuse_trend("interval observations (lower / upper)", "a site is matched against the grid mean alone, which under a trend "
@@ -1763,6 +1778,103 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         self._follow(cache, 0, X, wa * omega, yt * (wb * omega))     # a skipped point, a point outside the grid: omega = 0, nothing anywhere
         entered, dropped = torch.stack([(omega > 0).sum(), (self._err - flag0).reshape(-1)[0] >> 1]).tolist()
         return int(entered) + int(dropped)
+
+    # --------------------------------------------------- count observations --
+    def _count_batch(self, n, counts, exposure, trials):
+        """(counts [n], t [n], family) on the model's device in its dtype: ``trials`` given means binomial, otherwise Poisson at
+        ``exposure`` (None: 1)."""
+        if counts is None:
+            raise ValueError("exposure / trials describe counts, which were not given")
+        if exposure is not None and trials is not None:
+            raise ValueError("counts are Poisson at an exposure or binomial out of trials, not both")
+        t = trials if trials is not None else exposure
+        y = counts.to(self._device, self._dtype).reshape(-1).contiguous()
+        t = torch.ones(n, dtype=self._dtype, device=self._device) if t is None else t.to(self._device, self._dtype).reshape(-1).contiguous()
+        if y.shape[0] != n or t.shape[0] != n:
+            raise ValueError(f"counts and exposure / trials must hold one value per point ([{n}]), got {tuple(y.shape)} and {tuple(t.shape)}")
+        return y, t, "binomial" if trials is not None else "poisson"
+
+    def _condition_count(self, X, counts, exposure, trials, inplace, _decay):
+        """condition_on_observations with counts: grow, decay, moment-match, absorb -- _condition_interval with the
+        count launch.  The sites are taken against the posterior of the statistics the batch is added to."""
+        if self.num_outputs > 1:
+            raise NotImplementedError("count observations are implemented for a single output")
+        if self.robust_c is not None:
+            raise NotImplementedError("count observations do not combine with robust_c: a site is a weight already, and no kernel applies both")
+        if self.window is not None:
+            raise NotImplementedError("count observations do not combine with window: the ring stores targets, and a site depends on the "
+                                      "posterior it was matched against")
+        if X.dim() > 2:
+            raise NotImplementedError("batched conditioning (fantasies) takes targets, not counts")
+        X = X.reshape(-1, self._grid.d)
+        y, t, family = self._count_batch(X.shape[0], counts, exposure, trials)
+        if self.grow_grid:
+            self.grow_to_cover_(X)
+        return self._condition(lambda model, cache, src: model._absorb_count(cache, X, y, t, family, src), inplace, self._gamma(_decay),
+                               reads_posterior=True)
+
+    def _absorb_count(self, cache, X, y, t, family, src, half_delta=None):
+        """_absorb of one batch of counts, one launch (wiski_scatter_stats_count): _absorb_interval with the count sites, at
+        noise = wa = wb = 1 -- the effective noise variance of a point is sigma2 / omega = 1 / tau."""
+        op = self._native_half_op(cache, "count observations", half_delta)
+        X, _, no, wa, wb = self._canon_batch(X, None, None)
+        n = X.shape[0]
+        u = src.prediction_cache["pred_mean"][0, :, 0]       # (finishes whatever is pending, leaves a stencil shard)
+        with torch.no_grad(), settings.skip_posterior_variances(False):
+            pvar = src._eval_forward(X).variance.reshape(-1).to(self._dtype).contiguous()
+        ms = self._carried(self._before_launch(cache), u=u)
+        flag0 = self._err.clone()
+        sites = grid_ops.scatter_stats_count(self._grid, X, y, t, family, pvar, self._sigma2(0), wa, wb, no,
+                                             cache["interpolation_cache"][0, :, 0], op.stencil, cache["_cnt"][0], cache["_stats"][0], self._err, u,
+                                             res=ms["R"][0] if ms else None)
+        self.last_count_sites = sites
+        if n == 0:
+            return 0
+        yt, omega, _ = sites
+        self._two_level_lose()                               # (its block is rebuilt from the stencil where one is wanted again)
+        self._follow(cache, 0, X, wa * omega, yt * (wb * omega))     # a skipped point, a point outside the grid: omega = 0, nothing anywhere
+        entered, dropped = torch.stack([(omega > 0).sum(), (self._err - flag0).reshape(-1)[0] >> 1]).tolist()
+        return int(entered) + int(dropped)
+
+    def _latent_moments(self, X):
+        """(mean, variance) [n] of f at X under the current posterior, in the model's dtype."""
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad(), settings.skip_posterior_variances(False):
+                mvn = self(X.to(self._device, self._dtype))
+                return mvn.mean.reshape(-1).contiguous(), mvn.variance.reshape(-1).clamp_min(0.0).contiguous()
+        finally:
+            if was_training:
+                self.train()
+
+    def count_log_probability(self, X, counts, exposure=None, trials=None):
+        """log P(counts_i | x_i) [n] (float64) under the current posterior -- the log Z of the sites a batch of these counts would be
+        absorbed with (``wiski_count_sites``: the device function of the absorb, no scatter)."""
+        mean, var = self._latent_moments(X)
+        y, t, family = self._count_batch(mean.shape[0], counts, exposure, trials)
+        return grid_ops.count_sites(mean, var, y, t, family)[2]
+
+    def predict_counts(self, X, exposure=None, trials=None):
+        """(mean, variance) [n] (float64) of a future count at X.  Poisson: closed form from the log-normal rate, E = t exp(mu + v / 2),
+        Var = E + E^2 (exp v - 1).  Binomial: with p = sigmoid(f), E = t E p and Var = t E[p (1 - p)] + t^2 Var p, the moments of p by
+        a 64-point Gauss-Hermite rule in torch fp64."""
+        if exposure is not None and trials is not None:
+            raise ValueError("counts are Poisson at an exposure or binomial out of trials, not both")
+        mean, var = (a.double() for a in self._latent_moments(X))
+        t = trials if trials is not None else exposure
+        t = torch.ones_like(mean) if t is None else t.to(mean.device, torch.float64).reshape(-1)
+        if trials is None:
+            e = t * torch.exp(mean + 0.5 * var)
+            return e, e + e * e * torch.expm1(var)
+        import numpy as np
+
+        z, w = np.polynomial.hermite_e.hermegauss(64)
+        z = torch.as_tensor(z, dtype=torch.float64, device=mean.device)
+        w = torch.as_tensor(w / w.sum(), dtype=torch.float64, device=mean.device)
+        p = torch.sigmoid(mean[:, None] + var.sqrt()[:, None] * z)
+        ep, ep2 = p @ w, (p * p) @ w
+        return t * ep, t * (ep - ep2) + t * t * (ep2 - ep * ep)
 
     def interval_probability(self, X, lower, upper, noise=None):
         """log P(lower_i <= f(x_i) + eps_i <= upper_i) [n] under the current posterior, eps_i ~ N(0, sigma2 noise_i) (``noise`` None:

@@ -82,6 +82,16 @@ class OnlineSKIBotorchModel(FixedNoiseOnlineSKIGP):
         self.eval()
         return super().posterior_integral(lower, upper, joint=joint, average=average)      # (cast there, after the checks in the caller's precision)
 
+    def count_log_probability(self, X, counts, exposure=None, trials=None):
+        """log P(counts_i | x_i) under the current posterior (``FixedNoiseOnlineSKIGP.count_log_probability``)."""
+        self.eval()
+        return super().count_log_probability(X.to(self._dtype), counts, exposure=exposure, trials=trials)
+
+    def predict_counts(self, X, exposure=None, trials=None):
+        """Mean and variance of a future count at X (``FixedNoiseOnlineSKIGP.predict_counts``)."""
+        self.eval()
+        return super().predict_counts(X.to(self._dtype), exposure=exposure, trials=trials)
+
     def posterior(self, X, observation_noise=False, **kwargs):
         self.eval()
         X = X.to(self._dtype)

@@ -86,6 +86,25 @@ class OnlineSKIRegression(StreamingSKIWrapper):
         self._ensure_eval()
         return self.gp.posterior_integral(lower, upper, joint=joint, average=average)
 
+    def predict_counts(self, inputs, exposure=None, trials=None):
+        """(mean, variance) of a future count at the inputs when the latent function is a log rate (``exposure``) or a logit
+        (``trials``): the GP's ``predict_counts``.  Only with the ``Identity`` stem, as the GP's count observations are."""
+        from .stems import Identity
+
+        if not isinstance(self.stem, Identity):
+            raise NotImplementedError("predict_counts needs the Identity stem (the GP's count observations are taken at its own inputs)")
+        self._ensure_eval()
+        return self.gp.predict_counts(self._as_rows(inputs), exposure=exposure, trials=trials)
+
+    def count_log_probability(self, inputs, counts, exposure=None, trials=None):
+        """log P(counts_i | x_i) under the current posterior: the GP's ``count_log_probability``.  Only with the ``Identity`` stem."""
+        from .stems import Identity
+
+        if not isinstance(self.stem, Identity):
+            raise NotImplementedError("count_log_probability needs the Identity stem (the GP's count observations are taken at its own inputs)")
+        self._ensure_eval()
+        return self.gp.count_log_probability(self._as_rows(inputs), counts, exposure=exposure, trials=trials)
+
     def evaluate(self, inputs, targets):
         """(rmse, nll): means over batches of 1024 of the per-batch RMSE and mean Gaussian NLL; one host sync."""
         inputs = self._as_rows(inputs)
