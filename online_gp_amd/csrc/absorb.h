@@ -3,12 +3,14 @@
 // may be asked to do, as ONE named record.  Every member defaults to "off"; the extern "C" entry points of scatter_stats.hip
 // and the streaming step (stream_step.hip) fill the fields they expose and call absorb().  Which combinations are refused is
 // absorb_validate() in scatter_stats.hip; whoever writes another form of the absorb has to honour every group below.
-// Six kernels stand behind it: the atomic form (k_scatter_stats[_sym]; the owner form where its workspace is given and applies),
-// the derivative-observation form (`channels`, scatter_grad.h), the outlier-robust form (`inv_scale`, scatter_robust.h), the
-// sliding-window form (`ring_*`, scatter_window.h), the interval form (`lo`, scatter_interval.h) and the count form (`count_y`,
-// scatter_count.h).  The last five implement the plain single-output half-stencil absorb with cnt and the carry and refuse every
-// other group.  What the six half-stencil kernels do per point -- the tap tables, the per-tap
-// atomics, the pair loop that encodes the row-interleaved layout, the two scalars -- is stated once, in scatter_half.h.
+// Four half-stencil kernels stand behind it, besides the full-stencil k_scatter_stats and the owner form (where its workspace is
+// given and applies): the atomic form (k_scatter_stats_sym), the derivative-observation form (`channels`, scatter_grad.h), the
+// sliding-window form (`ring_*`, scatter_window.h) and the site-weighted form (k_scatter_stats_site, scatter_site.h), which is the
+// outlier-robust (`inv_scale`, scatter_robust.h), the interval (`lo`, scatter_interval.h) or the count absorb (`count_y`,
+// scatter_count.h) by the site it is given.  What they do per point -- the tap tables, the per-tap atomics, the pair loop that
+// encodes the row-interleaved layout, the two scalars -- is stated once, in scatter_half.h.
+// Every group from `channels` on is the single-output half-stencil atomic form only, with cnt and the carry (res and mean_out stay
+// optional): it excludes each of the others, the guard, the zero regions, the shard and the owner workspace.
 #pragma once
 #include "wiski_common.h"
 
@@ -58,14 +60,12 @@ struct AbsorbArgs {
   int nout = 1;
   ScatterBatch bt;
   // channels: 0, or d + 1 scalar observations per point -- its value and its d partial derivatives, each with its own y / wa / wb /
-  // noise (an absent one: wa = wb = 0, noise = 1) -- summed on chip into one atomic per tap pair (scatter_grad.h).  Single-output
-  // half-stencil atomic form only, with cnt and the carry; no guard, zero regions, shard or owner form
+  // noise (an absent one: wa = wb = 0, noise = 1) -- summed on chip into one atomic per tap pair (scatter_grad.h)
   int channels = 0;
   // robust: inv_scale != NULL Huber-weights every point against the posterior before the batch (scatter_robust.h):
   //   z = (y - w_p . u) inv_scale,  omega = min(1, huber_c / |z|);  wa, wb enter as omega wa, omega wb, log noise as log(noise / omega)
   // -- the absorb of the point at noise / omega.  inv_scale_p = 0 exempts a point (omega = 1).  Needs u, A, cnt, omega_out and a
-  // finite huber_c > 0; res and mean_out stay optional.  Single-output half-stencil atomic form only: no channels, guard, zero
-  // regions, shard or owner workspace
+  // finite huber_c > 0
   const real* inv_scale = nullptr;  // [n] 1 / scale of each point's innovation
   real huber_c = 0;
   real* omega_out = nullptr;        // [n] the weight each point entered with; 0 for a point outside the grid
@@ -73,8 +73,7 @@ struct AbsorbArgs {
   // (ring_head + j) mod ring_cap, and the point that slot held is taken out again with its weights negated, all in one launch.
   // An empty slot holds wa = wb = 0, noise = 1; a point outside the grid is stored void (wa = wb = 0, noise = 1, y = 0, x = NaN) and
   // void_left counts the void slots that were overwritten.  Needs all five arrays, ring_cap >= 1, 0 <= ring_head < ring_cap,
-  // n <= ring_cap (the slots of a launch are distinct), u, A, cnt and void_left; res and mean_out stay optional.  Single-output
-  // half-stencil atomic form only: no channels, inv_scale, guard, zero regions, shard or owner workspace
+  // n <= ring_cap (the slots of a launch are distinct), u, A, cnt and void_left
   real* ring_x = nullptr;           // [ring_cap, d]
   real* ring_y = nullptr;           // [ring_cap]
   real* ring_wa = nullptr;          // [ring_cap]
@@ -86,8 +85,7 @@ struct AbsorbArgs {
   // before the batch (scatter_interval.h): with mu = w_p . u, v = pvar, dn = sigma2 noise the site (ytilde, omega) follows from the
   // Gaussian mass of [lo, hi] under N(mu, v + dn), and the point enters as the target ytilde at noise / omega; y is ignored.  A
   // site with omega < WISKI_INTERVAL_OMEGA_MIN, lo > hi or a NaN bound is skipped: nothing anywhere, omega_out = 0, no flag in err.
-  // Needs hi, pvar, u, A, cnt, the three outputs and a finite sigma2 > 0; res and mean_out stay optional.  Single-output
-  // half-stencil atomic form only: no channels, inv_scale, ring, guard, zero regions, shard or owner workspace
+  // Needs hi, pvar, u, A, cnt, the three outputs and a finite sigma2 > 0
   const real* lo = nullptr;         // [n] lower ends (-inf: none)
   const real* hi = nullptr;         // [n] upper ends (+inf: none); lo == hi: an exact value
   const real* pvar = nullptr;       // [n] posterior variance of f at the point before the batch, in the units of y^2 (negative: 0)
@@ -98,8 +96,7 @@ struct AbsorbArgs {
   // exposure under the family's link, moment-matched against the posterior before the batch by a quadrature over the lanes of the
   // point's wave, and entered as the target ytilde at noise / omega, omega = sigma2 noise tau (not capped); y is ignored.  An
   // invalid datum (y < 0, t <= 0, y > t for the binomial, a NaN) and a site with omega < WISKI_COUNT_OMEGA_MIN are skipped, as in the
-  // interval form, whose pvar / sigma2 / ytilde_out / omega_out / logz_out it shares and needs, with u, A and cnt.  Single-output
-  // half-stencil atomic form only: no channels, inv_scale, ring, interval bounds, guard, zero regions, shard or owner workspace
+  // interval form, whose pvar / sigma2 / ytilde_out / omega_out / logz_out it shares and needs, with u, A and cnt
   const real* count_y = nullptr;    // [n] counts (non-integers allowed)
   const real* count_t = nullptr;    // [n] exposure (Poisson) / trials (binomial)
   int count_family = 0;             // WISKI_COUNT_POISSON, WISKI_COUNT_BINOMIAL
@@ -109,6 +106,7 @@ struct AbsorbArgs {
   bool counted() const { return count_y || count_t || count_family != 0; }
   // (the fields the two moment-matched forms share belong to the interval group unless the count group is given)
   bool interval() const { return lo || hi || (!counted() && (pvar || sigma2 != 0 || ytilde_out || logz_out)); }
+  bool site_form() const { return inv_scale || interval() || counted(); }   // the forms of k_scatter_stats_site (scatter_site.h)
 };
 
 // Validates, then queues the absorb on `stream`: WISKI_OK, WISKI_E_BADARG (nothing was launched) or WISKI_E_LAUNCH.

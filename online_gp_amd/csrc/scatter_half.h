@@ -1,5 +1,5 @@
 // The half-stencil point sweep: what the three atomic forms of the absorb that keep the symmetric half of W^T D^-1 W
-// (k_scatter_stats_sym in scatter_stats.hip, k_scatter_stats_grad in scatter_grad.h, k_scatter_stats_robust in scatter_robust.h)
+// (k_scatter_stats_sym in scatter_stats.hip, k_scatter_stats_grad in scatter_grad.h, k_scatter_stats_site in scatter_site.h)
 // do per point, stated once.  One wave per point, four points per block: each lane fills its taps of the point's LDS tables,
 // the wave reduces v . u, every lane issues the atomics of its own taps on b / cnt / res, and then the wave walks the prefix-pair
 // list with lane = (a2, b2, pair slot).  C is the number of observation channels a point carries: 1 for a value, d + 1 for a

@@ -174,6 +174,7 @@ __global__ __launch_bounds__(256) void k_scatter_stats_sym(GridDev<real> G, cons
 
 #include "scatter_owner.h"
 #include "scatter_grad.h"
+#include "scatter_site.h"
 #include "scatter_robust.h"
 #include "scatter_window.h"
 #include "scatter_interval.h"
@@ -246,46 +247,31 @@ template <typename real>
 static int absorb_validate(const AbsorbArgs<real>& a, int d) {
   if (a.n == 0) return WISKI_OK;                       // nothing to absorb: not even the pointers are looked at
   if (!a.x || (!a.y && !a.lo && !a.count_y) || !a.wa || !a.wb || !a.noise || !a.b || !a.stats || !a.err) return WISKI_E_BADARG;   // what every form reads and writes (the interval and count forms have no y)
-  if (a.counted()) {
-    // count (scatter_count.h): the whole group and the fields it shares with the interval form, but not its bounds; the sites need u;
-    // A, cnt and the three outputs are written unconditionally; the plain single-output half-stencil atomic form only, and neither
-    // the robust nor the window one.  res and mean_out are optional
-    if (a.lo || a.hi) return WISKI_E_BADARG;
-    if (!a.count_y || !a.count_t || (a.count_family != WISKI_COUNT_POISSON && a.count_family != WISKI_COUNT_BINOMIAL)) return WISKI_E_BADARG;
-    if (!a.pvar || !a.ytilde_out || !a.omega_out || !a.logz_out) return WISKI_E_BADARG;
-    if (!(a.sigma2 > 0) || !std::isfinite(a.sigma2)) return WISKI_E_BADARG;
+  if (a.site_form() || a.windowed()) {
+    // The site-weighted forms (scatter_site.h) and the window form (scatter_window.h) are the plain single-output half-stencil
+    // atomic absorb with cnt: their sites and sweeps need u; A and cnt are written unconditionally; no channels.  None of them
+    // has a guard, zero regions, a shard or the owner workspace.  res and mean_out are optional: u alone is a complete request
     if (!a.u || !a.half || !a.A || !a.cnt || a.nout != 1 || a.channels) return WISKI_E_BADARG;
-    if (a.inv_scale || a.huber_c != (real)0 || a.windowed()) return WISKI_E_BADARG;
     if (a.guard || a.n1_bytes || a.n2_bytes || a.z1 || a.z2 || a.sharded() || a.bin || a.bin_bytes) return WISKI_E_BADARG;
-    return WISKI_OK;
-  }
-  if (a.interval()) {
-    // interval (scatter_interval.h): the whole group; the sites need u; A, cnt and the three outputs are written unconditionally;
-    // the plain single-output half-stencil atomic form only, and neither the robust nor the window one.  res and mean_out are optional
-    if (!a.lo || !a.hi || !a.pvar || !a.ytilde_out || !a.omega_out || !a.logz_out) return WISKI_E_BADARG;
-    if (!(a.sigma2 > 0) || !std::isfinite(a.sigma2)) return WISKI_E_BADARG;
-    if (!a.u || !a.half || !a.A || !a.cnt || a.nout != 1 || a.channels) return WISKI_E_BADARG;
-    if (a.inv_scale || a.huber_c != (real)0 || a.windowed()) return WISKI_E_BADARG;
-    if (a.guard || a.n1_bytes || a.n2_bytes || a.z1 || a.z2 || a.sharded() || a.bin || a.bin_bytes) return WISKI_E_BADARG;
-    return WISKI_OK;
-  }
-  if (a.windowed()) {
-    // window (scatter_window.h): a whole ring with head inside it and no more entering points than slots, so that the slots of
-    // the launch are distinct; u, A, cnt and void_left are used unconditionally; the plain single-output half-stencil atomic
-    // form only, and not the robust one either.  res and mean_out are optional
-    if (!a.ring_x || !a.ring_y || !a.ring_wa || !a.ring_wb || !a.ring_noise || !a.void_left) return WISKI_E_BADARG;
-    if (a.ring_cap < 1 || a.ring_head < 0 || a.ring_head >= a.ring_cap || a.n > a.ring_cap) return WISKI_E_BADARG;
-    if (!a.u || !a.half || !a.A || !a.cnt || a.nout != 1 || a.channels) return WISKI_E_BADARG;
-    if (a.inv_scale || a.omega_out || a.huber_c != (real)0) return WISKI_E_BADARG;
-    if (a.guard || a.n1_bytes || a.n2_bytes || a.z1 || a.z2 || a.sharded() || a.bin || a.bin_bytes) return WISKI_E_BADARG;
-    return WISKI_OK;
-  }
-  if (a.inv_scale) {
-    // robust (scatter_robust.h): the weights need u; A, cnt and omega_out are written unconditionally; the plain single-output
-    // half-stencil atomic form only.  res and mean_out are optional here: u alone is a complete request
-    if (!a.u || !a.half || !a.A || !a.cnt || !a.omega_out || a.nout != 1 || a.channels) return WISKI_E_BADARG;
-    if (a.guard || a.n1_bytes || a.n2_bytes || a.z1 || a.z2 || a.sharded() || a.bin || a.bin_bytes) return WISKI_E_BADARG;
-    if (!(a.huber_c > (real)0) || !std::isfinite(a.huber_c)) return WISKI_E_BADARG;
+    if (a.counted() || a.interval()) {
+      // the moment-matched forms: the posterior variance, a noise scale, the three outputs; neither robust nor windowed
+      if (!a.pvar || !a.ytilde_out || !a.omega_out || !a.logz_out) return WISKI_E_BADARG;
+      if (!(a.sigma2 > 0) || !std::isfinite(a.sigma2)) return WISKI_E_BADARG;
+      if (a.inv_scale || a.huber_c != (real)0 || a.windowed()) return WISKI_E_BADARG;
+      // count (scatter_count.h): the whole group, and not the interval form's bounds; interval (scatter_interval.h): both bounds
+      if (a.counted()) {
+        if (a.lo || a.hi) return WISKI_E_BADARG;
+        if (!a.count_y || !a.count_t || (a.count_family != WISKI_COUNT_POISSON && a.count_family != WISKI_COUNT_BINOMIAL)) return WISKI_E_BADARG;
+      } else if (!a.lo || !a.hi) return WISKI_E_BADARG;
+    } else if (a.windowed()) {
+      // window: a whole ring with head inside it and no more entering points than slots, so that the slots of the launch are
+      // distinct; void_left is used unconditionally; not the robust form either
+      if (!a.ring_x || !a.ring_y || !a.ring_wa || !a.ring_wb || !a.ring_noise || !a.void_left) return WISKI_E_BADARG;
+      if (a.ring_cap < 1 || a.ring_head < 0 || a.ring_head >= a.ring_cap || a.n > a.ring_cap) return WISKI_E_BADARG;
+      if (a.inv_scale || a.omega_out || a.huber_c != (real)0) return WISKI_E_BADARG;
+    } else if (!a.omega_out || !(a.huber_c > (real)0) || !std::isfinite(a.huber_c)) {
+      return WISKI_E_BADARG;                             // robust (scatter_robust.h): omega_out is written unconditionally, a finite threshold
+    }
     return WISKI_OK;
   }
   if (a.omega_out || a.huber_c != (real)0) return WISKI_E_BADARG;                                        // the robust group without inv_scale
@@ -382,10 +368,10 @@ int absorb(const wiski_grid* grid, const AbsorbArgs<real>& a, void* stream) {
   int rc = make_grid_dev<real>(grid, &G);
   if (rc == WISKI_OK) rc = absorb_validate(a, G.d);
   if (rc != WISKI_OK || a.n == 0) return rc;
-  if (a.counted()) return launch_count(G, a, (hipStream_t)stream);
-  if (a.interval()) return launch_interval(G, a, (hipStream_t)stream);
+  if (a.counted()) return launch_site(G, a, SiteCount<real>::of(a), (hipStream_t)stream);
+  if (a.interval()) return launch_site(G, a, SiteInterval<real>::of(a), (hipStream_t)stream);
   if (a.windowed()) return launch_window(G, a, (hipStream_t)stream);
-  if (a.inv_scale) return launch_robust(G, a, (hipStream_t)stream);
+  if (a.inv_scale) return launch_site(G, a, SiteRobust<real>::of(a), (hipStream_t)stream);
   if (a.channels) return launch_grad(G, a, (hipStream_t)stream);
   return owner_applies(G, a) ? launch_owner(G, a, (hipStream_t)stream) : launch_atomic(G, a, (hipStream_t)stream);
 }

@@ -435,18 +435,28 @@ def scatter_stats_grad(grid, x, Y, wa, wb, noise, b, A_half, cnt, stats, err, u=
     _hip.check(rc, "wiski_scatter_stats_grad")
 
 
+def _absorb_points(op, grid, x, u, per_point, u_is="the grid mean", sites=False):
+    """What the absorbs taken against ``u`` check alike: x as [n, d], every given ``per_point`` tensor [n] in x's dtype, u [m].
+    Returns (x, n) and, with ``sites``, the outputs of a moment-matched form as well: (ytilde [n], omega [n], log_z [n] float64)."""
+    x = _x2d(x, grid)
+    n = x.shape[0]
+    for name, t in per_point.items():
+        if t is not None and (tuple(t.shape) != (n,) or t.dtype != x.dtype):
+            raise ValueError(f"{op}: {name} must be [{n}] {x.dtype}, got {tuple(t.shape)} {t.dtype}")
+    if u is None or tuple(u.shape) != (grid.m,) or u.dtype != x.dtype:
+        raise ValueError(f"{op}: u must be {u_is} [{grid.m}] {x.dtype}")
+    if not sites:
+        return x, n
+    return x, n, (torch.empty(n, dtype=x.dtype, device=x.device), torch.empty(n, dtype=x.dtype, device=x.device),
+                  torch.empty(n, dtype=torch.float64, device=x.device))
+
+
 def scatter_stats_robust(grid, x, y, wa, wb, noise, inv_scale, c, b, A_half, cnt, stats, err, u, res=None, mean_out=None):
     """The outlier-robust absorb in ONE launch (``wiski_scatter_stats_robust``): every point is Huber-weighted
     against the posterior mean ``u`` [m] before the batch, z = (y - w . u) inv_scale, omega = min(1, c / |z|), and enters
     (b, A_half, cnt, stats) -- and the carried residual ``res``, if given -- as the same point at noise / omega.  ``inv_scale``
     [n] (0 exempts a point).  Returns omega [n] (0 for a point outside the grid); ``mean_out`` [n] receives w . u."""
-    x = _x2d(x, grid)
-    n = x.shape[0]
-    for name, t in (("y", y), ("wa", wa), ("wb", wb), ("noise", noise), ("inv_scale", inv_scale), ("mean_out", mean_out)):
-        if t is not None and (tuple(t.shape) != (n,) or t.dtype != x.dtype):
-            raise ValueError(f"scatter_stats_robust: {name} must be [{n}] {x.dtype}, got {tuple(t.shape)} {t.dtype}")
-    if u is None or tuple(u.shape) != (grid.m,) or u.dtype != x.dtype:
-        raise ValueError(f"scatter_stats_robust: u must be the grid mean [{grid.m}] {x.dtype}")
+    x, n = _absorb_points("scatter_stats_robust", grid, x, u, dict(y=y, wa=wa, wb=wb, noise=noise, inv_scale=inv_scale, mean_out=mean_out))
     omega = torch.empty(n, dtype=x.dtype, device=x.device)
     if n == 0:
         return omega
@@ -466,16 +476,8 @@ def scatter_stats_interval(grid, x, lower, upper, pvar, sigma2, wa, wb, noise, b
     ``sigma2 * noise`` -- and enters (b, A_half, cnt, stats) -- and the carried residual ``res``, if given -- as the target ytilde_i
     at noise_i / omega_i.  Returns (ytilde [n], omega [n], log_z [n] float64); a skipped point (nothing to say: omega below 1e-12,
     lower > upper, a NaN bound) has omega = 0 and ytilde = w . u, a point outside the grid (0, 0, 0).  ``mean_out`` [n] receives w . u."""
-    x = _x2d(x, grid)
-    n = x.shape[0]
-    for name, t in (("lower", lower), ("upper", upper), ("pvar", pvar), ("wa", wa), ("wb", wb), ("noise", noise), ("mean_out", mean_out)):
-        if t is not None and (tuple(t.shape) != (n,) or t.dtype != x.dtype):
-            raise ValueError(f"scatter_stats_interval: {name} must be [{n}] {x.dtype}, got {tuple(t.shape)} {t.dtype}")
-    if u is None or tuple(u.shape) != (grid.m,) or u.dtype != x.dtype:
-        raise ValueError(f"scatter_stats_interval: u must be the grid mean [{grid.m}] {x.dtype}")
-    ytilde = torch.empty(n, dtype=x.dtype, device=x.device)
-    omega = torch.empty(n, dtype=x.dtype, device=x.device)
-    log_z = torch.empty(n, dtype=torch.float64, device=x.device)
+    x, n, (ytilde, omega, log_z) = _absorb_points("scatter_stats_interval", grid, x, u, sites=True,
+                                                  per_point=dict(lower=lower, upper=upper, pvar=pvar, wa=wa, wb=wb, noise=noise, mean_out=mean_out))
     if n == 0:
         return ytilde, omega, log_z
     rc = _hip.fn("wiski_scatter_stats_interval", x.dtype)(grid.ref, _hip.dptr(x), _hip.dptr(lower.contiguous()), _hip.dptr(upper.contiguous()),
@@ -499,18 +501,10 @@ def scatter_stats_count(grid, x, counts, t, family, pvar, sigma2, wa, wb, noise,
     the target ytilde_i at noise_i / omega_i, omega = sigma2 noise tau (effective noise variance 1 / tau; not capped).  Returns
     (ytilde [n], omega [n], log_z [n] float64); a skipped point (omega below 1e-12, an invalid datum) has omega = 0 and ytilde = w . u,
     a point outside the grid (0, 0, 0).  ``mean_out`` [n] receives w . u."""
-    x = _x2d(x, grid)
-    n = x.shape[0]
     if family not in COUNT_FAMILIES:
         raise ValueError(f"scatter_stats_count: family must be one of {sorted(COUNT_FAMILIES)}, got {family!r}")
-    for name, v in (("counts", counts), ("t", t), ("pvar", pvar), ("wa", wa), ("wb", wb), ("noise", noise), ("mean_out", mean_out)):
-        if v is not None and (tuple(v.shape) != (n,) or v.dtype != x.dtype):
-            raise ValueError(f"scatter_stats_count: {name} must be [{n}] {x.dtype}, got {tuple(v.shape)} {v.dtype}")
-    if u is None or tuple(u.shape) != (grid.m,) or u.dtype != x.dtype:
-        raise ValueError(f"scatter_stats_count: u must be the grid mean [{grid.m}] {x.dtype}")
-    ytilde = torch.empty(n, dtype=x.dtype, device=x.device)
-    omega = torch.empty(n, dtype=x.dtype, device=x.device)
-    log_z = torch.empty(n, dtype=torch.float64, device=x.device)
+    x, n, (ytilde, omega, log_z) = _absorb_points("scatter_stats_count", grid, x, u, sites=True,
+                                                  per_point=dict(counts=counts, t=t, pvar=pvar, wa=wa, wb=wb, noise=noise, mean_out=mean_out))
     if n == 0:
         return ytilde, omega, log_z
     rc = _hip.fn("wiski_scatter_stats_count", x.dtype)(grid.ref, _hip.dptr(x), _hip.dptr(counts.contiguous()), _hip.dptr(t.contiguous()),
@@ -628,13 +622,7 @@ def scatter_stats_window(grid, x, y, wa, wb, noise, ring, b, A_half, cnt, stats,
     of ``ring``; what those slots held leaves the statistics again, with its weights negated.  ``u`` [m]: the posterior mean on the
     grid both sweeps are taken against (any vector when neither ``res`` nor ``mean_out`` is asked for); ``mean_out`` [n] receives
     w . u of the entering points.  Advances ``ring.head`` and ``ring.fill``."""
-    x = _x2d(x, grid)
-    n = x.shape[0]
-    for name, t in (("y", y), ("wa", wa), ("wb", wb), ("noise", noise), ("mean_out", mean_out)):
-        if t is not None and (tuple(t.shape) != (n,) or t.dtype != x.dtype):
-            raise ValueError(f"scatter_stats_window: {name} must be [{n}] {x.dtype}, got {tuple(t.shape)} {t.dtype}")
-    if u is None or tuple(u.shape) != (grid.m,) or u.dtype != x.dtype:
-        raise ValueError(f"scatter_stats_window: u must be a grid vector [{grid.m}] {x.dtype}")
+    x, n = _absorb_points("scatter_stats_window", grid, x, u, dict(y=y, wa=wa, wb=wb, noise=noise, mean_out=mean_out), u_is="a grid vector")
     if ring.d != grid.d or ring.x.dtype != x.dtype or ring.x.device != x.device:
         raise ValueError(f"scatter_stats_window: the ring holds {ring.d}-d {ring.x.dtype} points on {ring.x.device}")
     if n == 0:

@@ -1707,33 +1707,46 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         next posterior is factored afresh."""
         op = self._native_half_op(cache, "robust_c")
         X, y, no, wa, wb = self._canon_batch(X, Y, noise)
-        n = X.shape[0]
         u, inv_scale = src._robust_inputs(X, no)             # (finishes whatever is pending, leaves a stencil shard)
-        ms = self._carried(self._before_launch(cache), u=u)
-        omega = grid_ops.scatter_stats_robust(self._grid, X, y, wa, wb, no, inv_scale, self.robust_c, cache["interpolation_cache"][0, :, 0],
-                                              op.stencil, cache["_cnt"][0], cache["_stats"][0], self._err, u, res=ms["R"][0] if ms else None)
+        targets, res = self._site_targets(cache, op, u)
+        omega = grid_ops.scatter_stats_robust(self._grid, X, y, wa, wb, no, inv_scale, self.robust_c, *targets, res=res)
         self.last_robust_weights = omega
-        if n == 0:
-            return 0
-        self._two_level_lose()                               # (its block is rebuilt from the stencil where one is wanted again)
-        self._follow(cache, 0, X, wa * omega, y * (wb * omega))      # a point outside the grid: omega = 0, nothing anywhere
+        return self._follow_sites(cache, X, wa, wb, y, omega)
+
+    def _site_targets(self, cache, op, u):
+        """What a site-weighted absorb (grid_ops.scatter_stats_robust / _interval / _count) writes, as the tail of its argument
+        list: (b, A_half, cnt, stats, err, u) and res, the carried residual where one is kept."""
+        ms = self._carried(self._before_launch(cache), u=u)
+        return (cache["interpolation_cache"][0, :, 0], op.stencil, cache["_cnt"][0], cache["_stats"][0], self._err, u), ms["R"][0] if ms else None
+
+    def _follow_sites(self, cache, X, wa, wb, ytilde, omega):
+        """After a site-weighted absorb: everything that follows the stream point by point receives the targets ytilde at the
+        effective weights wa omega, wb omega.  Returns the number of points of the batch."""
+        n = X.shape[0]
+        if n:
+            self._two_level_lose()                           # (its block is rebuilt from the stencil where one is wanted again)
+            self._follow(cache, 0, X, wa * omega, ytilde * (wb * omega))     # a skipped point, a point outside the grid: omega = 0, nothing anywhere
         return n
 
     # ------------------------------------------------ interval observations --
+    def _refuse_for_sites(self, X, form, given):
+        """What a moment-matched form (`form` observations, given as `given`) does not combine with."""
+        if self.num_outputs > 1:
+            raise NotImplementedError(f"{form} observations are implemented for a single output")
+        if self.robust_c is not None:
+            raise NotImplementedError(f"{form} observations do not combine with robust_c: a site is a weight already, and no kernel applies both")
+        if self.window is not None:
+            raise NotImplementedError(f"{form} observations do not combine with window: the ring stores targets, and a site depends on the "
+                                      "posterior it was matched against")
+        if X.dim() > 2:
+            raise NotImplementedError(f"batched conditioning (fantasies) takes targets, not {given}")
+
     def _condition_interval(self, X, Y, noise, lower, upper, inplace, _decay):
         """condition_on_observations with lower / upper: grow, decay, moment-match, absorb.  The sites are taken
         against the posterior of the statistics the batch is added to -- the decayed ones under forgetting."""
         if Y is not None:
             raise NotImplementedError("a batch is given as targets Y or as bounds lower / upper, not both (an exact value is lower == upper)")
-        if self.num_outputs > 1:
-            raise NotImplementedError("interval observations are implemented for a single output")
-        if self.robust_c is not None:
-            raise NotImplementedError("interval observations do not combine with robust_c: a site is a weight already, and no kernel applies both")
-        if self.window is not None:
-            raise NotImplementedError("interval observations do not combine with window: the ring stores targets, and a site depends on the "
-                                      "posterior it was matched against")
-        if X.dim() > 2:
-            raise NotImplementedError("batched conditioning (fantasies) takes targets, not bounds")
+        self._refuse_for_sites(X, "interval", "bounds")
         d = self._grid.d
         X = X.reshape(-1, d)
         n = X.shape[0]
@@ -1751,33 +1764,35 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         return self._condition(lambda model, cache, src: model._absorb_interval(cache, X, lo, hi, noise, src), inplace, self._gamma(_decay),
                                reads_posterior=True)
 
-    def _absorb_interval(self, cache, X, lo, hi, noise, src, half_delta=None):
-        """_absorb of one batch of interval observations, one launch (wiski_scatter_stats_interval).  `src`: the model whose posterior
-        the sites are matched against -- this one, or in the functional form without a decay the parent, whose statistics the clone
-        still equals: its grid mean from the prediction cache and its posterior variance at X (one more solve on the paths every
-        posterior call takes).  Everything that follows the stream point by point receives the effective weights wa omega, wb omega
-        and the pseudo-targets: a carried root pair, the spectral factor, the path probes, the noise-weight sum.  The two-level block
-        is given up and the dense rank-update seed is skipped, as in _absorb_robust.  Returns the number of points num_data grows by:
-        those that entered, and those outside the grid (which _raise_out_of_bounds takes off again when the flag is read)."""
-        op = self._native_half_op(cache, "interval observations", half_delta)
+    def _absorb_matched(self, cache, X, noise, src, form, launch, half_delta=None):
+        """_absorb of one batch of moment-matched observations (`form`: what _native_half_op calls them), one launch:
+        ``launch(X, pvar, sigma2, wa, wb, noise, b, A_half, cnt, stats, err, u, res=)`` is grid_ops.scatter_stats_interval or
+        _count with its data bound.  `src`: the model whose posterior the sites are matched against -- this one, or in the
+        functional form without a decay the parent, whose statistics the clone still equals: its grid mean from the prediction
+        cache and its posterior variance at X (one more solve on the paths every posterior call takes).  Everything that follows
+        the stream point by point receives the effective weights wa omega, wb omega and the pseudo-targets: a carried root pair,
+        the spectral factor, the path probes, the noise-weight sum.  The two-level block is given up and the dense rank-update
+        seed is skipped, as in _absorb_robust.  Returns the sites and the number of points num_data grows by: those that entered,
+        and those outside the grid (which _raise_out_of_bounds takes off again when the flag is read)."""
+        op = self._native_half_op(cache, form, half_delta)
         X, _, no, wa, wb = self._canon_batch(X, None, noise)
-        n = X.shape[0]
         u = src.prediction_cache["pred_mean"][0, :, 0]       # (finishes whatever is pending, leaves a stencil shard)
         with torch.no_grad(), settings.skip_posterior_variances(False):
             pvar = src._eval_forward(X).variance.reshape(-1).to(self._dtype).contiguous()
-        ms = self._carried(self._before_launch(cache), u=u)
+        targets, res = self._site_targets(cache, op, u)
         flag0 = self._err.clone()
-        sites = grid_ops.scatter_stats_interval(self._grid, X, lo.contiguous(), hi.contiguous(), pvar, self._sigma2(0), wa, wb, no,
-                                                cache["interpolation_cache"][0, :, 0], op.stencil, cache["_cnt"][0], cache["_stats"][0], self._err, u,
-                                                res=ms["R"][0] if ms else None)
-        self.last_interval_sites = sites
-        if n == 0:
-            return 0
-        yt, omega, _ = sites
-        self._two_level_lose()                               # (its block is rebuilt from the stencil where one is wanted again)
-        self._follow(cache, 0, X, wa * omega, yt * (wb * omega))     # a skipped point, a point outside the grid: omega = 0, nothing anywhere
-        entered, dropped = torch.stack([(omega > 0).sum(), (self._err - flag0).reshape(-1)[0] >> 1]).tolist()
-        return int(entered) + int(dropped)
+        sites = launch(X, pvar, self._sigma2(0), wa, wb, no, *targets, res=res)
+        if not self._follow_sites(cache, X, wa, wb, *sites[:2]):
+            return sites, 0
+        entered, dropped = torch.stack([(sites[1] > 0).sum(), (self._err - flag0).reshape(-1)[0] >> 1]).tolist()
+        return sites, int(entered) + int(dropped)
+
+    def _absorb_interval(self, cache, X, lo, hi, noise, src, half_delta=None):
+        """_absorb_matched with the interval launch (wiski_scatter_stats_interval)."""
+        self.last_interval_sites, grown = self._absorb_matched(
+            cache, X, noise, src, "interval observations", half_delta=half_delta,
+            launch=lambda X, *rest, **kw: grid_ops.scatter_stats_interval(self._grid, X, lo.contiguous(), hi.contiguous(), *rest, **kw))
+        return grown
 
     # --------------------------------------------------- count observations --
     def _count_batch(self, n, counts, exposure, trials):
@@ -1797,15 +1812,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
     def _condition_count(self, X, counts, exposure, trials, inplace, _decay):
         """condition_on_observations with counts: grow, decay, moment-match, absorb -- _condition_interval with the
         count launch.  The sites are taken against the posterior of the statistics the batch is added to."""
-        if self.num_outputs > 1:
-            raise NotImplementedError("count observations are implemented for a single output")
-        if self.robust_c is not None:
-            raise NotImplementedError("count observations do not combine with robust_c: a site is a weight already, and no kernel applies both")
-        if self.window is not None:
-            raise NotImplementedError("count observations do not combine with window: the ring stores targets, and a site depends on the "
-                                      "posterior it was matched against")
-        if X.dim() > 2:
-            raise NotImplementedError("batched conditioning (fantasies) takes targets, not counts")
+        self._refuse_for_sites(X, "count", "counts")
         X = X.reshape(-1, self._grid.d)
         y, t, family = self._count_batch(X.shape[0], counts, exposure, trials)
         if self.grow_grid:
@@ -1814,27 +1821,12 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
                                reads_posterior=True)
 
     def _absorb_count(self, cache, X, y, t, family, src, half_delta=None):
-        """_absorb of one batch of counts, one launch (wiski_scatter_stats_count): _absorb_interval with the count sites, at
-        noise = wa = wb = 1 -- the effective noise variance of a point is sigma2 / omega = 1 / tau."""
-        op = self._native_half_op(cache, "count observations", half_delta)
-        X, _, no, wa, wb = self._canon_batch(X, None, None)
-        n = X.shape[0]
-        u = src.prediction_cache["pred_mean"][0, :, 0]       # (finishes whatever is pending, leaves a stencil shard)
-        with torch.no_grad(), settings.skip_posterior_variances(False):
-            pvar = src._eval_forward(X).variance.reshape(-1).to(self._dtype).contiguous()
-        ms = self._carried(self._before_launch(cache), u=u)
-        flag0 = self._err.clone()
-        sites = grid_ops.scatter_stats_count(self._grid, X, y, t, family, pvar, self._sigma2(0), wa, wb, no,
-                                             cache["interpolation_cache"][0, :, 0], op.stencil, cache["_cnt"][0], cache["_stats"][0], self._err, u,
-                                             res=ms["R"][0] if ms else None)
-        self.last_count_sites = sites
-        if n == 0:
-            return 0
-        yt, omega, _ = sites
-        self._two_level_lose()                               # (its block is rebuilt from the stencil where one is wanted again)
-        self._follow(cache, 0, X, wa * omega, yt * (wb * omega))     # a skipped point, a point outside the grid: omega = 0, nothing anywhere
-        entered, dropped = torch.stack([(omega > 0).sum(), (self._err - flag0).reshape(-1)[0] >> 1]).tolist()
-        return int(entered) + int(dropped)
+        """_absorb_matched with the count launch (wiski_scatter_stats_count), at noise = wa = wb = 1 -- the effective noise
+        variance of a point is sigma2 / omega = 1 / tau."""
+        self.last_count_sites, grown = self._absorb_matched(
+            cache, X, None, src, "count observations", half_delta=half_delta,
+            launch=lambda X, *rest, **kw: grid_ops.scatter_stats_count(self._grid, X, y, t, family, *rest, **kw))
+        return grown
 
     def _latent_moments(self, X):
         """(mean, variance) [n] of f at X under the current posterior, in the model's dtype."""

@@ -216,6 +216,32 @@ def test_kernel_matches_the_dense_reference(name, fam, tdt, tol):
                for a, b in zip(sites, sites2))
 
 
+@pytest.mark.parametrize("tdt", [torch.float64, torch.float32])
+@pytest.mark.parametrize("fam", list(FAMILIES))
+def test_absorb_and_count_sites_run_the_same_site(fam, tdt):
+    """The absorb and wiski_count_sites evaluate one device function.  At sigma2 = noise = wa = wb = 1 the absorb's omega is tau, and
+    its mean_out is the mean its site was taken at: count_sites at (mean_out, pvar) returns the same (ytilde, omega, log Z), bit for
+    bit, at every point inside the grid (the three invalid data included: ytilde = mu, omega = 0, log Z = NaN)."""
+    from online_gp_amd import grid_ops
+
+    c = _kernel_case("d1", fam)
+    grid = c["grid"]
+    mk = lambda a: torch.as_tensor(a, device=DEV, dtype=tdt)
+    X, y, t, pvar, u = (mk(c[k]) for k in ("X", "y", "t", "pvar", "u"))
+    one = torch.ones(N, device=DEV, dtype=tdt)
+    got, err = _buffers(grid, tdt), grid_ops.new_err_flag(DEV)
+    mean = torch.full((N,), float("nan"), device=DEV, dtype=tdt)
+    absorbed = grid_ops.scatter_stats_count(grid, X, y, t, fam, pvar, 1.0, one, one, one, got["b"], got["A"], got["cnt"], got["stats"], err, u,
+                                            res=got["res"], mean_out=mean)
+    alone = grid_ops.count_sites(mean, pvar, y, t, fam)
+    ok = torch.as_tensor(c["ok"], device=DEV)
+    assert int(ok.sum()) == N - 1 and int((absorbed[1][ok] > 0).sum()) == N - 1 - len(INVALID)
+    for k, a, b in zip(("ytilde", "omega", "log_z"), absorbed, alone):
+        a, b = a[ok], b[ok]
+        print(f"{fam} {tdt} {k}: largest difference {float(torch.nan_to_num(a.double() - b.double(), nan=0.0).abs().max()):.3e}")
+        assert torch.equal(torch.isnan(a), torch.isnan(b)) and torch.equal(torch.nan_to_num(a, nan=-7.0), torch.nan_to_num(b, nan=-7.0)), k
+
+
 @pytest.mark.parametrize("tdt", [torch.float32, torch.float64])
 def test_absorb_refuses_the_count_group_with_what_the_kernel_does_not_do(tdt):
     """Through the full argument record plus the count group (wiski_absorb_count): every combination the contract refuses is

@@ -471,8 +471,10 @@ def test_absorb_shards_tile_the_half_stencil(d, tdt, ndt, tol):
 @pytest.mark.parametrize("tdt,ndt,tol", DTYPES)
 def test_three_absorb_forms_agree_where_they_overlap(d, tdt, ndt, tol):
     """The same points, weights and u through the plain form, the robust form with inv_scale = 0 (every omega = 1) and the derivative
-    form with only channel 0 present (the others wa = wb = 0, noise = 1): the same A, b, cnt, res, statistics and mean_out.  Point 5
-    lies outside the grid: err = 3 in each, omega_out = 0, mean_out = 0, and the sums are those of the batch without it."""
+    form with only channel 0 present (the others wa = wb = 0, noise = 1) and, as a fourth, the interval form with lower = upper = y at
+    sigma2 = 1 (an exact value: ytilde = y and omega = 1 exactly, whatever pvar): the same A, b, cnt, res, statistics and mean_out.
+    Point 5 lies outside the grid: err = 3 in each, omega_out = 0 (the interval form: ytilde, omega, log Z all 0), mean_out = 0, and
+    the sums are those of the batch without it."""
     from online_gp_amd import grid_ops
 
     grid, X, y, w, noise, u = _sweep_case(d, tdt, outside=True)
@@ -489,6 +491,15 @@ def test_three_absorb_forms_agree_where_they_overlap(d, tdt, ndt, tol):
     expect[5] = 0
     assert torch.equal(omega, expect)
 
+    interval = _sweep_buffers(grid, tdt)
+    err = grid_ops.new_err_flag("cuda")
+    pvar = torch.linspace(0.0, 2.0, n, device="cuda", dtype=tdt)
+    ytilde, omega_i, logz = grid_ops.scatter_stats_interval(grid, X, y, y.clone(), pvar, 1.0, w, w, noise, interval["b"], interval["A"], interval["cnt"],
+                                                            interval["stats"], err, u, res=interval["res"], mean_out=interval["mean"])
+    assert int(err.item()) == 3
+    assert torch.equal(omega_i, expect)
+    assert float(ytilde[5]) == 0.0 and float(logz[5]) == 0.0
+
     grad = _sweep_buffers(grid, tdt)
     col0 = lambda v, fill: torch.cat([v[:, None], torch.full((n, d), fill, device="cuda", dtype=tdt)], dim=1).contiguous()
     mean_c = torch.full((n, C), float("nan"), device="cuda", dtype=tdt)
@@ -502,11 +513,12 @@ def test_three_absorb_forms_agree_where_they_overlap(d, tdt, ndt, tol):
     keep = torch.arange(n, device="cuda") != 5
     without = _sweep_buffers(grid, tdt, n - 1)
     assert _plain_absorb(grid, X[keep].contiguous(), y[keep].contiguous(), w[keep].contiguous(), noise[keep].contiguous(), u, without, tdt) == 0
-    assert float(plain["mean"][5]) == 0.0 and float(robust["mean"][5]) == 0.0
+    assert float(plain["mean"][5]) == 0.0 and float(robust["mean"][5]) == 0.0 and float(interval["mean"][5]) == 0.0
+    assert torch.equal(ytilde[keep], y[keep])
     for key in ("A", "b", "cnt", "res", "stats"):
         assert _close(without[key], plain[key], tol), key
     assert _close(without["mean"], plain["mean"][keep], tol)
-    for name, form in (("robust", robust), ("grad", grad)):
+    for name, form in (("robust", robust), ("grad", grad), ("interval", interval)):
         for key in ("A", "b", "cnt", "res", "stats", "mean"):
             assert _close(form[key], plain[key], tol), (name, key)
 
