@@ -550,6 +550,24 @@ int wiski_absorb_count_f64(const wiski_grid* grid, const wiski_absorb_args* args
 int wiski_count_sites_f32(const float* d_mu, const float* d_pvar, const float* d_y, const float* d_t, int family, int64_t n, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, void* stream);
 int wiski_count_sites_f64(const double* d_mu, const double* d_pvar, const double* d_y, const double* d_t, int family, int64_t n, double* d_ytilde_out, double* d_omega_out, double* d_logz_out, void* stream);
 
+/* Noisy-input observations: point p was taken at x_p + e_p, e_p ~ N(0, diag(d_xvar_p)), d_xvar [n, d] in the grid's units squared
+ * (DESIGN.md 3.24).  To first order the location error is extra output noise grad f^T diag(xvar) grad f, with the slope taken under
+ * the posterior BEFORE the batch, inside the launch that absorbs it.  With mu = w_p . u, g_k = (d w_p / d x_k) . u (zero in a
+ * one-hot boundary cell of dim k, as in wiski_gather_grad), v = max(d_pvar_p, 0), gamma_k = max(d_gvar_p,k, 0) the posterior variance
+ * of d f / d x_k (d_gvar [n, d]; NULL: 0, the rule of the posterior mean's slope alone) and dn = sigma2 noise_p,
+ *   s_in = sum_k xvar_k (g_k^2 + gamma_k),   omega = dn / (dn + s_in),   log Z = log N(y; mu, v + dn + s_in),
+ * evaluated in double in both precisions, and the point enters as its own target d_y_p at noise noise_p / omega_p.  xvar = 0 gives
+ * omega = 1 exactly: the plain absorb.  A point is SKIPPED -- it enters nothing, reports omega = 0 and is not flagged in d_err --
+ * when an xvar_k is negative or NaN or s_in is not finite (log Z = NaN), or when omega < 1e-12 (WISKI_INPUT_NOISE_OMEGA_MIN).
+ * d_omega_out [n], d_logz_out [n] (double) and, optionally, d_grad_out [n, d] (the slopes g as reduced by the kernel) are written
+ * for every point; a point outside the grid reports zeros.  Every other argument as wiski_scatter_stats_interval.
+ * wiski_absorb_input_noise takes the record plus the group, so that every refused combination (a guard, zero regions, a shard, an
+ * owner workspace, nout > 1, channels, a full stencil, no d_y) can be reached and tested; wiski_absorb_args has NOT grown. */
+int wiski_scatter_stats_input_noise_f32(const wiski_grid* grid, const float* d_x, const float* d_y, const float* d_xvar, const float* d_gvar, const float* d_pvar, double sigma2, const float* d_wa, const float* d_wb, const float* d_noise, int64_t n, float* d_b, float* d_A_half, float* d_cnt, const float* d_u, float* d_res, float* d_mean_out, double* d_stats, int32_t* d_err, float* d_omega_out, double* d_logz_out, float* d_grad_out, void* stream);
+int wiski_scatter_stats_input_noise_f64(const wiski_grid* grid, const double* d_x, const double* d_y, const double* d_xvar, const double* d_gvar, const double* d_pvar, double sigma2, const double* d_wa, const double* d_wb, const double* d_noise, int64_t n, double* d_b, double* d_A_half, double* d_cnt, const double* d_u, double* d_res, double* d_mean_out, double* d_stats, int32_t* d_err, double* d_omega_out, double* d_logz_out, double* d_grad_out, void* stream);
+int wiski_absorb_input_noise_f32(const wiski_grid* grid, const wiski_absorb_args* args, const float* d_xvar, const float* d_gvar, const float* d_pvar, double sigma2, float* d_omega_out, double* d_logz_out, float* d_grad_out, void* stream);
+int wiski_absorb_input_noise_f64(const wiski_grid* grid, const wiski_absorb_args* args, const double* d_xvar, const double* d_gvar, const double* d_pvar, double sigma2, double* d_omega_out, double* d_logz_out, double* d_grad_out, void* stream);
+
 /* The two halves of a stencil-sharded step on their own (wiski_stream_step uses them when args->shard is set): the absorb
  * restricted to the stencil groups [g_lo, g_hi) (same arguments as wiski_scatter_stats_step; always the atomic form), and
  * wiski_pcg_async with every A . v product summed over the ranks of `shard`. */

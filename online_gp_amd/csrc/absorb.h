@@ -6,8 +6,8 @@
 // Four half-stencil kernels stand behind it, besides the full-stencil k_scatter_stats and the owner form (where its workspace is
 // given and applies): the atomic form (k_scatter_stats_sym), the derivative-observation form (`channels`, scatter_grad.h), the
 // sliding-window form (`ring_*`, scatter_window.h) and the site-weighted form (k_scatter_stats_site, scatter_site.h), which is the
-// outlier-robust (`inv_scale`, scatter_robust.h), the interval (`lo`, scatter_interval.h) or the count absorb (`count_y`,
-// scatter_count.h) by the site it is given.  What they do per point -- the tap tables, the per-tap atomics, the pair loop that
+// outlier-robust (`inv_scale`, scatter_robust.h), the interval (`lo`, scatter_interval.h), the count (`count_y`, scatter_count.h) or
+// the noisy-input absorb (`xvar`, scatter_input_noise.h) by the site it is given.  What they do per point -- the tap tables, the per-tap atomics, the pair loop that
 // encodes the row-interleaved layout, the two scalars -- is stated once, in scatter_half.h.
 // Every group from `channels` on is the single-output half-stencil atomic form only, with cnt and the carry (res and mean_out stay
 // optional): it excludes each of the others, the guard, the zero regions, the shard and the owner workspace.
@@ -100,13 +100,22 @@ struct AbsorbArgs {
   const real* count_y = nullptr;    // [n] counts (non-integers allowed)
   const real* count_t = nullptr;    // [n] exposure (Poisson) / trials (binomial)
   int count_family = 0;             // WISKI_COUNT_POISSON, WISKI_COUNT_BINOMIAL
+  // input noise: xvar != NULL makes every point an observation at an uncertain location, x_p + e_p with e_p ~ N(0, diag(xvar_p))
+  // (scatter_input_noise.h): with g_k = (d w_p / d x_k) . u the slope of the predictive mean before the batch, the point enters as
+  // its own target y at noise / omega, omega = dn / (dn + sum_k xvar_k (g_k^2 + max(gvar_k, 0))), dn = sigma2 noise.  A negative or
+  // NaN xvar_k, a non-finite sum and an omega < WISKI_INPUT_NOISE_OMEGA_MIN are skipped, as in the interval form, whose pvar /
+  // sigma2 / omega_out / logz_out it shares and needs, with y, u, A and cnt; ytilde_out is not used (ytilde = y)
+  const real* xvar = nullptr;       // [n, d] variance of the location error per dim, in the grid's units squared
+  const real* gvar = nullptr;       // [n, d] posterior variance of d f / d x_k before the batch, in y^2 per grid unit squared; NULL: 0
+  real* grad_out = nullptr;         // [n, d] the slopes g as the wave reduced them (0 for a point outside the grid); optional
 
   bool sharded() const { return g_lo > 0 || g_hi < (1 << 30); }
   bool windowed() const { return ring_x || ring_y || ring_wa || ring_wb || ring_noise || ring_cap || ring_head || void_left; }
   bool counted() const { return count_y || count_t || count_family != 0; }
-  // (the fields the two moment-matched forms share belong to the interval group unless the count group is given)
-  bool interval() const { return lo || hi || (!counted() && (pvar || sigma2 != 0 || ytilde_out || logz_out)); }
-  bool site_form() const { return inv_scale || interval() || counted(); }   // the forms of k_scatter_stats_site (scatter_site.h)
+  bool input_noise() const { return xvar || gvar || grad_out; }
+  // (the fields the matched forms share belong to whichever of the count and input-noise groups is given, else to the interval group)
+  bool interval() const { return lo || hi || (!counted() && !input_noise() && (pvar || sigma2 != 0 || ytilde_out || logz_out)); }
+  bool site_form() const { return inv_scale || interval() || counted() || input_noise(); }   // the forms of k_scatter_stats_site (scatter_site.h)
 };
 
 // Validates, then queues the absorb on `stream`: WISKI_OK, WISKI_E_BADARG (nothing was launched) or WISKI_E_LAUNCH.

@@ -206,6 +206,7 @@ struct SiteCount : SiteOutputs<real> {
   const real* noise;
   int family;
   double sigma2;
+  static constexpr bool kGrad = false;
   struct Datum {
     double y = -1.0, t = 0, v = 0, noise = 1;
   };

@@ -194,6 +194,53 @@ __device__ __forceinline__ void half_tap_table(const GridDev<real>& G, const int
   }
 }
 
+// The gradient of the point's predictive mean beside a single-channel tap table: gu[q] = (d w_p / d x_q) . u, from the lane's own
+// taps (flat_t, as half_tap_table left them) and reduced over the wave, in every lane.  The derivative row of dim q is the product of
+// the w digits with dim q's replaced by dw (point_stencil_grad: zero in a one-hot boundary cell of the dim), so a site that needs
+// the slope (scatter_input_noise.h) costs d products and one more read of u per tap and d wave reductions per point, and the LDS
+// table, the atomics and the pair loop stay those of C = 1.  u is read where ANY derivative weight is non-zero: at a node the value
+// weight of a neighbour vanishes and its derivative weight does not.
+template <typename real>
+__device__ __forceinline__ real half_pick4(const real v[4], int c) { return c == 0 ? v[0] : (c == 1 ? v[1] : (c == 2 ? v[2] : v[3])); }
+
+template <typename real, int D>
+__device__ __forceinline__ void half_tap_grad(const real w[D][4], const real (*dw)[4], int lane, const real* __restrict__ u,
+                                              const int flat_t[HalfTaps<D>::TPL], real gu[D]) {
+#pragma unroll
+  for (int q = 0; q < D; ++q) gu[q] = (real)0;
+#pragma unroll
+  for (int t = 0; t < HalfTaps<D>::TPL; ++t) {
+    const int a = lane + t * 64;
+    if (a < HalfTaps<D>::T) {
+      // the tap's digits: w by index, as half_tap_table reads it, dw by selects.  Both by index cost the d = 1 instantiations 36 B
+      // of scratch per lane, both by selects the d >= 2 ones 48-144 B (the compiler's resource remarks); this way none has any
+      real wd[D], dwd[D], v[D];
+      bool touched = false;
+#pragma unroll
+      for (int q = 0; q < D; ++q) {
+        const int c = tap_digit<D>(a, q);
+        wd[q] = w[q][c];
+        dwd[q] = half_pick4<real>(dw[q], c);
+      }
+#pragma unroll
+      for (int q = 0; q < D; ++q) {
+        real vq = (real)1;
+#pragma unroll
+        for (int o = 0; o < D; ++o) vq *= o == q ? dwd[o] : wd[o];
+        v[q] = vq;
+        touched |= vq != (real)0;
+      }
+      if (touched) {
+        const real ug = u[flat_t[t]];
+#pragma unroll
+        for (int q = 0; q < D; ++q) gu[q] += v[q] * ug;
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < D; ++q) gu[q] = wave_reduce_sum<real>(gu[q]);
+}
+
 // The carry (optional), per channel: v_c . u is the predictive mean (c = 0) / gradient (c = 1 + q) of the point under the
 // posterior BEFORE this update (u = the current posterior mean on the grid) -- mean_out, [n][C], makes the separate gather launch
 // of a streaming step unnecessary -- and innov_c = wb_c y_c - wa_c (v_c . u): res += sum_c v_c innov_c keeps res = b - z - A u

@@ -81,6 +81,7 @@ struct SiteInterval : SiteOutputs<real> {
   const real* pvar;
   const real* noise;
   double sigma2;
+  static constexpr bool kGrad = false;
   struct Datum {
     double lo = 0, hi = 0, v = 0, noise = 1;
   };

@@ -15,6 +15,7 @@ struct SiteRobust {
   const real* inv_scale;
   real huber_c;
   real* omega_out;
+  static constexpr bool kGrad = false;
   struct Datum {
     real y = 0, is = 0;
   };

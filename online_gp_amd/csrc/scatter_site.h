@@ -1,6 +1,7 @@
-// The site-weighted absorb: what the outlier-robust, interval and count forms (scatter_robust.h, scatter_interval.h,
-// scatter_count.h) do alike, stated once.  Each of them turns a point's datum and its predictive mean
-// mu = w_p . u under the posterior BEFORE the batch into a pseudo-target and a weight (ytilde, omega), and the point enters as
+// The site-weighted absorb: what the outlier-robust, interval, count and noisy-input forms (scatter_robust.h, scatter_interval.h,
+// scatter_count.h, scatter_input_noise.h) do alike, stated once.  Each of them turns a point's
+// datum and its predictive mean mu = w_p . u (the last one also the mean's slope) under the posterior BEFORE the batch into a
+// pseudo-target and a weight (ytilde, omega), and the point enters as
 // ytilde at noise noise_p / omega: A, cnt and the carried residual with omega wa, b and sum wb y^2 with omega wb and ytilde for y,
 // log|D| with log(noise / omega).  mu is what the sweep already reduces over the wave, so a site costs its loads and stores and no
 // second pass over the stencil.  All sites of a launch are taken against the same u: they depend neither on the order of the
@@ -16,6 +17,13 @@
 //   store(p, ytilde, omega, logz)
 //                   what the form reports per point, by lane 0: the rounded values the point entered with; all zero for a point
 //                   outside the grid, which has zero rows
+//   kGrad           compile-time: false for a site of mu alone.  true (scatter_input_noise.h): the site is also a function of the
+//                   slope of the predictive mean, g_q = (d w_p / d x_q) . u.  The sweep then sets the point up with derivative
+//                   weights (half_point_setup<real, D, true>), reduces the d slopes over the wave beside mu (half_tap_grad,
+//                   scatter_half.h: from the lane's own taps -- the LDS tap table stays single-channel) and hands them on:
+//                   eval(datum, mu, g, lane) and store(p, ytilde, omega, logz, g), g a real[D], zero for a point outside the grid.
+//                   Between the set-up and the tap table the site may re-evaluate the weights of a point inside the grid in more
+//                   than the working precision, refine<D>(G, x, p, inside, w, dw): the cell stays the one the set-up chose
 // and a static of(AbsorbArgs) that fills it.  A new observation form supplies that struct and one entry in absorb_validate(),
 // AbsorbArgs::site_form() and absorb().
 #pragma once
@@ -67,7 +75,12 @@ __global__ __launch_bounds__(256) void k_scatter_stats_site(GridDev<real> G, con
     const bool valid = p < n;
     int j0[D], flat_t[H::TPL];
     real w[D][4], val_t[H::TPL][1], yw[1], wac[1], wu[1], innov[1];
-    const bool inside = half_point_setup<real, D>(G, x, p, n, lane == 0, err, bad, j0, w);
+    [[maybe_unused]] real dw[Site::kGrad ? D : 1][4], gu[D];
+    bool inside;
+    if constexpr (Site::kGrad) {
+      inside = half_point_setup<real, D, true>(G, x, p, n, lane == 0, err, bad, j0, w, dw);
+      S.template refine<D>(G, x, p, inside, w, dw);
+    } else inside = half_point_setup<real, D>(G, x, p, n, lane == 0, err, bad, j0, w);
     typename Site::Datum dat{};
     real wap = 0, wbp = 0;
     if (valid) {
@@ -76,16 +89,21 @@ __global__ __launch_bounds__(256) void k_scatter_stats_site(GridDev<real> G, con
       wbp = wb[p];
     }
     half_tap_table<real, D, 1>(G, j0, w, nullptr, lane, u, s_val[loc], s_idx[loc], flat_t, val_t, wu);   // wu: the predictive mean of the point before the batch
+    if constexpr (Site::kGrad) half_tap_grad<real, D>(w, dw, lane, u, flat_t, gu);   // zero for a point outside the grid and past the batch
     const double n_p = valid ? (double)noise[p] : 1.0;
     SiteValue st{0.0, 0.0, 0.0, false};
-    if (inside) st = S.eval(dat, wu[0], lane);
+    if (inside) {
+      if constexpr (Site::kGrad) st = S.eval(dat, wu[0], gu, lane);
+      else st = S.eval(dat, wu[0], lane);
+    }
     const real omega = (real)st.omega, yt = (real)st.ytilde;
     wbp *= omega;
     wac[0] = wap * omega;
     yw[0] = yt * wbp;
     half_carry<real, 1>(u, yw, wac, wu, mean_out, p, lane == 0 && valid, innov);   // with the weights the point enters with
     if (lane == 0 && valid) {
-      S.store(p, yt, omega, st.logz);
+      if constexpr (Site::kGrad) S.store(p, yt, omega, st.logz, gu);
+      else S.store(p, yt, omega, st.logz);
       if (st.enters) {
         c_acc += st.ytilde * st.ytilde * (double)wbp;
         ld_acc += log(n_p / st.omega);

@@ -179,6 +179,7 @@ __global__ __launch_bounds__(256) void k_scatter_stats_sym(GridDev<real> G, cons
 #include "scatter_window.h"
 #include "scatter_interval.h"
 #include "scatter_count.h"
+#include "scatter_input_noise.h"
 
 // Unpacks the row-interleaved half stencil into a full offset-major stencil full[o][i] = A[i, i + off(o)]
 // (diagnostics, tests, and models handed a full-stencil cache):
@@ -253,13 +254,17 @@ static int absorb_validate(const AbsorbArgs<real>& a, int d) {
     // has a guard, zero regions, a shard or the owner workspace.  res and mean_out are optional: u alone is a complete request
     if (!a.u || !a.half || !a.A || !a.cnt || a.nout != 1 || a.channels) return WISKI_E_BADARG;
     if (a.guard || a.n1_bytes || a.n2_bytes || a.z1 || a.z2 || a.sharded() || a.bin || a.bin_bytes) return WISKI_E_BADARG;
-    if (a.counted() || a.interval()) {
-      // the moment-matched forms: the posterior variance, a noise scale, the three outputs; neither robust nor windowed
-      if (!a.pvar || !a.ytilde_out || !a.omega_out || !a.logz_out) return WISKI_E_BADARG;
+    if (a.counted() || a.interval() || a.input_noise()) {
+      // the matched forms: the posterior variance, a noise scale, their outputs (the noisy-input form's pseudo-target is y itself: it
+      // has no ytilde_out); neither robust nor windowed
+      if (!a.pvar || !a.omega_out || !a.logz_out || (a.ytilde_out == nullptr) != a.input_noise()) return WISKI_E_BADARG;
       if (!(a.sigma2 > 0) || !std::isfinite(a.sigma2)) return WISKI_E_BADARG;
       if (a.inv_scale || a.huber_c != (real)0 || a.windowed()) return WISKI_E_BADARG;
-      // count (scatter_count.h): the whole group, and not the interval form's bounds; interval (scatter_interval.h): both bounds
-      if (a.counted()) {
+      // input noise (scatter_input_noise.h): its variances and the targets, and neither of the other two groups; count
+      // (scatter_count.h): the whole group, and not the interval form's bounds; interval (scatter_interval.h): both bounds
+      if (a.input_noise()) {
+        if (!a.xvar || !a.y || a.counted() || a.lo || a.hi) return WISKI_E_BADARG;
+      } else if (a.counted()) {
         if (a.lo || a.hi) return WISKI_E_BADARG;
         if (!a.count_y || !a.count_t || (a.count_family != WISKI_COUNT_POISSON && a.count_family != WISKI_COUNT_BINOMIAL)) return WISKI_E_BADARG;
       } else if (!a.lo || !a.hi) return WISKI_E_BADARG;
@@ -368,6 +373,7 @@ int absorb(const wiski_grid* grid, const AbsorbArgs<real>& a, void* stream) {
   int rc = make_grid_dev<real>(grid, &G);
   if (rc == WISKI_OK) rc = absorb_validate(a, G.d);
   if (rc != WISKI_OK || a.n == 0) return rc;
+  if (a.input_noise()) return launch_site(G, a, SiteInputNoise<real>::of(a, *grid), (hipStream_t)stream);
   if (a.counted()) return launch_site(G, a, SiteCount<real>::of(a), (hipStream_t)stream);
   if (a.interval()) return launch_site(G, a, SiteInterval<real>::of(a), (hipStream_t)stream);
   if (a.windowed()) return launch_window(G, a, (hipStream_t)stream);
@@ -486,6 +492,21 @@ static int entry_absorb_count(const wiski_grid* g, const wiski_absorb_args* p, c
   return p ? entry_count(g, absorb_args<real>(*p), cy, ct, family, pvar, sigma2, ytilde_out, omega_out, logz_out, s) : WISKI_E_BADARG;
 }
 template <typename real>
+static int entry_input_noise(const wiski_grid* g, AbsorbArgs<real> a, const real* xvar, const real* gvar, const real* pvar, double sigma2, real* omega_out, double* logz_out, real* grad_out, void* s) {
+  a.xvar = xvar; a.gvar = gvar; a.grad_out = grad_out; a.pvar = pvar; a.sigma2 = sigma2; a.omega_out = omega_out; a.logz_out = logz_out;
+  return xvar ? absorb(g, a, s) : WISKI_E_BADARG;
+}
+template <typename real>
+static int entry_scatter_input_noise(const wiski_grid* g, const real* x, const real* y, const real* xvar, const real* gvar, const real* pvar, double sigma2, const real* wa, const real* wb, const real* noise, int64_t n, real* b, real* A_half, real* cnt, const real* u, real* res, real* mean_out, double* stats, int32_t* err, real* omega_out, double* logz_out, real* grad_out, void* s) {
+  AbsorbArgs<real> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
+  absorb_carry(a, cnt, u, res, mean_out);
+  return entry_input_noise(g, a, xvar, gvar, pvar, sigma2, omega_out, logz_out, grad_out, s);
+}
+template <typename real>
+static int entry_absorb_input_noise(const wiski_grid* g, const wiski_absorb_args* p, const real* xvar, const real* gvar, const real* pvar, double sigma2, real* omega_out, double* logz_out, real* grad_out, void* s) {
+  return p ? entry_input_noise(g, absorb_args<real>(*p), xvar, gvar, pvar, sigma2, omega_out, logz_out, grad_out, s) : WISKI_E_BADARG;
+}
+template <typename real>
 static int entry_plain(const wiski_grid* g, const real* x, const real* y, const real* wa, const real* wb, const real* noise, int64_t n, real* b, real* A, bool half, double* stats, int32_t* err, void* s) {
   return absorb(g, absorb_args(x, y, wa, wb, noise, n, b, A, half, stats, err), s);
 }
@@ -537,6 +558,10 @@ int wiski_absorb_count_f32(const wiski_grid* g, const wiski_absorb_args* p, cons
 int wiski_absorb_count_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* y, const double* t, int family, const double* pvar, double sigma2, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return entry_absorb_count(g, p, y, t, family, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
 int wiski_count_sites_f32(const float* mu, const float* pvar, const float* y, const float* t, int family, int64_t n, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return count_sites_impl(mu, pvar, y, t, family, n, ytilde_out, omega_out, logz_out, s); }
 int wiski_count_sites_f64(const double* mu, const double* pvar, const double* y, const double* t, int family, int64_t n, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return count_sites_impl(mu, pvar, y, t, family, n, ytilde_out, omega_out, logz_out, s); }
+int wiski_scatter_stats_input_noise_f32(const wiski_grid* g, const float* x, const float* y, const float* xvar, const float* gvar, const float* pvar, double sigma2, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, float* omega_out, double* logz_out, float* grad_out, void* s) { return entry_scatter_input_noise(g, x, y, xvar, gvar, pvar, sigma2, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, omega_out, logz_out, grad_out, s); }
+int wiski_scatter_stats_input_noise_f64(const wiski_grid* g, const double* x, const double* y, const double* xvar, const double* gvar, const double* pvar, double sigma2, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, double* omega_out, double* logz_out, double* grad_out, void* s) { return entry_scatter_input_noise(g, x, y, xvar, gvar, pvar, sigma2, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, omega_out, logz_out, grad_out, s); }
+int wiski_absorb_input_noise_f32(const wiski_grid* g, const wiski_absorb_args* p, const float* xvar, const float* gvar, const float* pvar, double sigma2, float* omega_out, double* logz_out, float* grad_out, void* s) { return entry_absorb_input_noise(g, p, xvar, gvar, pvar, sigma2, omega_out, logz_out, grad_out, s); }
+int wiski_absorb_input_noise_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* xvar, const double* gvar, const double* pvar, double sigma2, double* omega_out, double* logz_out, double* grad_out, void* s) { return entry_absorb_input_noise(g, p, xvar, gvar, pvar, sigma2, omega_out, logz_out, grad_out, s); }
 int wiski_scatter_stats_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A, double* stats, int32_t* err, void* s) { return entry_plain(g, x, y, wa, wb, noise, n, b, A, false, stats, err, s); }
 int wiski_scatter_stats_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A, double* stats, int32_t* err, void* s) { return entry_plain(g, x, y, wa, wb, noise, n, b, A, false, stats, err, s); }
 int wiski_scatter_stats_sym_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, double* stats, int32_t* err, void* s) { return entry_plain(g, x, y, wa, wb, noise, n, b, A_half, true, stats, err, s); }

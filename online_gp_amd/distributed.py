@@ -381,9 +381,12 @@ class ShardedStatsUpdater:
                 self._delta["_cnt"].zero_()
         return self._delta
 
-    def update(self, X, Y, noise=None, *, lower=None, upper=None, counts=None, exposure=None, trials=None):
+    def update(self, X, Y, noise=None, *, lower=None, upper=None, counts=None, exposure=None, trials=None, input_var=None):
         from . import grid_ops
 
+        if input_var is not None or getattr(self.model, "input_var", None) is not None:
+            # the slope moments of a shard would be taken on one rank, and the other ranks' followers never see its weights
+            raise NotImplementedError("ShardedStatsUpdater does not carry noisy-input observations (input_var): condition the model itself")
         if counts is not None or exposure is not None or trials is not None:
             raise NotImplementedError("ShardedStatsUpdater does not carry count observations (counts): condition the model itself")
         if lower is not None or upper is not None:

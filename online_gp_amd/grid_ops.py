@@ -517,6 +517,36 @@ def scatter_stats_count(grid, x, counts, t, family, pvar, sigma2, wa, wb, noise,
     return ytilde, omega, log_z
 
 
+def scatter_stats_input_noise(grid, x, y, xvar, gvar, pvar, sigma2, wa, wb, noise, b, A_half, cnt, stats, err, u, res=None, mean_out=None,
+                              want_grad=False):
+    """The noisy-input absorb in ONE launch (``wiski_scatter_stats_input_noise``): point i was taken at x_i + e_i,
+    e_i ~ N(0, diag(xvar_i)) (``xvar`` [n, d], in the grid's units squared).  Against the posterior before the batch -- the grid mean
+    ``u`` [m] with its slope g_i at x_i, the posterior variances ``pvar`` [n] of f and ``gvar`` [n, d] of its partial derivatives
+    (None: 0, the slope of the mean alone) -- the location error is the extra output noise s_in = sum_k xvar_k (g_k^2 + gvar_k), and the
+    point enters (b, A_half, cnt, stats) -- and the carried residual ``res``, if given -- as y_i at noise_i / omega_i, omega = dn /
+    (dn + s_in), dn = sigma2 noise_i.  Returns (omega [n], log_z [n] float64) and, with ``want_grad``, the slopes g [n, d] as the
+    kernel reduced them; a skipped point (omega below 1e-12, a negative or NaN xvar) has omega = 0, a point outside the grid zeros.
+    ``mean_out`` [n] receives w . u."""
+    op = "scatter_stats_input_noise"
+    x, n = _absorb_points(op, grid, x, u, dict(y=y, pvar=pvar, wa=wa, wb=wb, noise=noise, mean_out=mean_out))
+    for name, t in (("xvar", xvar), ("gvar", gvar)):
+        if (t is None and name == "xvar") or (t is not None and (tuple(t.shape) != (n, grid.d) or t.dtype != x.dtype)):
+            raise ValueError(f"{op}: {name} must be [{n}, {grid.d}] {x.dtype}, got {None if t is None else (tuple(t.shape), t.dtype)}")
+    omega = torch.empty(n, dtype=x.dtype, device=x.device)
+    log_z = torch.empty(n, dtype=torch.float64, device=x.device)
+    grad = torch.empty((n, grid.d), dtype=x.dtype, device=x.device) if want_grad else None
+    if n:
+        rc = _hip.fn("wiski_scatter_stats_input_noise", x.dtype)(grid.ref, _hip.dptr(x), _hip.dptr(y.contiguous()), _hip.dptr(xvar.contiguous()),
+                                                                 _hip.dptr(None if gvar is None else gvar.contiguous()), _hip.dptr(pvar.contiguous()),
+                                                                 ctypes.c_double(float(sigma2)), _hip.dptr(wa.contiguous()), _hip.dptr(wb.contiguous()),
+                                                                 _hip.dptr(noise.contiguous()), ctypes.c_int64(n), _hip.dptr(b), _hip.dptr(A_half),
+                                                                 _hip.dptr(cnt), _hip.dptr(u), _hip.dptr(res), _hip.dptr(mean_out), _hip.dptr(stats),
+                                                                 _hip.dptr(err), _hip.dptr(omega), _hip.dptr(log_z), _hip.dptr(grad),
+                                                                 _hip.stream_ptr(x.device))
+        _hip.check(rc, "wiski_scatter_stats_input_noise")
+    return (omega, log_z, grad) if want_grad else (omega, log_z)
+
+
 def count_sites(mean, pvar, counts, t, family):
     """The sites of count observations alone (``wiski_count_sites``: the device function of ``scatter_stats_count``, one wave per
     site, no scatter) against given means and variances [n]: (ytilde [n], tau [n], log_z [n] float64), tau the site precision (the

@@ -109,6 +109,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         window_rebuild_every=None,
         trend=None,
         trend_prior_var=None,
+        input_var=None,
+        input_noise_slope="posterior",
     ):
         super().__init__()
         assert train_inputs is not None or kernel_cache is not None
@@ -136,6 +138,21 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         self.last_interval_sites = None
         # count observations (_absorb_count): (ytilde, omega, log_z) [q] of the last batch given as counts
         self.last_count_sites = None
+        # noisy-input observations (_absorb_input_noise): the variance of the error of the recorded locations -- a scalar
+        # or [d] -- that every unbatched update not given its own `input_var` is absorbed with; None: every path is what it is without
+        # the feature.  input_noise_slope: the noise of a point is inflated by input_var E[(d f)^2] under the posterior before its batch
+        # ("posterior": squared mean slope plus slope variance) or by the squared slope of the posterior mean alone ("mean", the textbook
+        # rule, which lets the first batches of a stream in at almost no extra noise)
+        if input_noise_slope not in ("posterior", "mean"):
+            raise ValueError(f"input_noise_slope must be 'posterior' or 'mean', got {input_noise_slope!r}")
+        if input_var is not None:
+            input_var = torch.as_tensor(input_var, dtype=torch.float64).detach().cpu()
+            if input_var.dim() > 1 or not bool((input_var >= 0).all()) or not bool(torch.isfinite(input_var).all()):
+                raise ValueError("input_var of a model must be a finite non-negative scalar or one value per input dimension [d] "
+                                 "(a batch passes its own [n] or [n, d] to condition_on_observations)")
+        self.input_var = input_var
+        self.input_noise_slope = input_noise_slope
+        self.last_input_noise_sites = None           # (omega, log_z, grad_mean) of the last batch absorbed with an input variance
         # sliding window (_absorb_window): the model is the GP of exactly the last `window` points; every update absorbs
         # its batch, stores it in a device-resident ring and takes out what the ring's slots held, in one launch
         if window is not None:
@@ -240,6 +257,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         self.train_targets = None
         self.covar_module = covar_module.to(device)
         self._grid = self.covar_module.grid_spec
+        if self.input_var is not None and self.input_var.dim() == 1 and self.input_var.shape[0] != self._grid.d:
+            raise ValueError(f"input_var of a model must be a scalar or one value per input dimension [{self._grid.d}], got {tuple(self.input_var.shape)}")
         self._dtype = dtype
         self._device = device
         if num_dims is not None and num_dims != self._grid.d:
@@ -1444,7 +1463,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
 
     # -------------------------------------------------------------- updates --
     def condition_on_observations(self, X, Y, noise=None, inplace=False, _decay=True, *, grad_Y=None, grad_noise=None, grad_mask=None,
-                                  lower=None, upper=None, counts=None, exposure=None, trials=None):
+                                  lower=None, upper=None, counts=None, exposure=None, trials=None, input_var=None):
         """a7, :258-285.  inplace: the statistics buffers are updated where they
         live (O(4^{2d}) atomics per point); otherwise they are cloned first and a
         sibling model sharing covar_module / likelihood is returned.  With a ``forgetting_factor`` the statistics -- of the clone,
@@ -1478,7 +1497,19 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         ``counts`` [n] with ``Y=None``: count observations (``_condition_count``) -- ``counts_i ~ Poisson(exposure_i
         exp f(x_i))`` (``exposure`` None: 1), or with ``trials`` given ``counts_i`` successes of ``trials_i`` at success probability
         sigmoid(f(x_i)).  Moment-matched and absorbed like bounds, at the effective noise variance ``1 / tau_i``;
-        ``last_count_sites`` holds ``(ytilde, omega, log_z)`` with ``omega = sigma2 tau``.  Single output, unbatched X."""
+        ``last_count_sites`` holds ``(ytilde, omega, log_z)`` with ``omega = sigma2 tau``.  Single output, unbatched X.
+
+        ``input_var`` -- a scalar, [d], [n] or [n, d] -- with targets ``Y``: the recorded locations X are off by an error of that
+        variance per dimension, in the units of X squared (``_condition_input_noise``).  To first order the error is
+        extra output noise ``sum_k input_var_k E[(d_k f)^2]`` under the posterior before the batch (after growing and decaying;
+        ``input_noise_slope="mean"``: the squared slope of the posterior mean alone), and the point enters as ``Y_i`` at noise
+        ``noise_i / omega_i`` in the same launch; ``last_input_noise_sites`` then holds ``(omega, log_z, grad_mean)``.  A model built
+        with ``input_var`` applies it to every unbatched update that passes none.  Single output, unbatched X."""
+        if input_var is None and self.input_var is not None and X.dim() <= 2 and (Y is None or Y.dim() <= 2):
+            input_var = self.input_var
+        if input_var is not None:
+            given = dict(grad_Y=grad_Y, grad_noise=grad_noise, grad_mask=grad_mask, lower=lower, upper=upper, counts=counts, exposure=exposure, trials=trials)
+            return self._condition_input_noise(X, Y, noise, input_var, inplace, _decay, [k for k, v in given.items() if v is not None])
         if counts is not None or exposure is not None or trials is not None:
             if self._trend_deg is not None:
                 self._refuse_trend("count observations (counts)", "a site is matched against the grid mean alone, which under a trend "
@@ -1599,6 +1630,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             window=self.window,
             window_rebuild_every=self.window_rebuild_every,
             trend_prior_var=self.trend_prior_var,        # (the degree travels with the cache)
+            input_var=self.input_var,
+            input_noise_slope=self.input_noise_slope,
         )
         new_gp._win_voids, new_gp._win_updates = self._win_voids, self._win_updates
         new_gp._wsum_dev = self._wsum_dev.clone()
@@ -1764,7 +1797,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         return self._condition(lambda model, cache, src: model._absorb_interval(cache, X, lo, hi, noise, src), inplace, self._gamma(_decay),
                                reads_posterior=True)
 
-    def _absorb_matched(self, cache, X, noise, src, form, launch, half_delta=None):
+    def _absorb_matched(self, cache, X, noise, src, form, launch, half_delta=None, pvar_of=None):
         """_absorb of one batch of moment-matched observations (`form`: what _native_half_op calls them), one launch:
         ``launch(X, pvar, sigma2, wa, wb, noise, b, A_half, cnt, stats, err, u, res=)`` is grid_ops.scatter_stats_interval or
         _count with its data bound.  `src`: the model whose posterior the sites are matched against -- this one, or in the
@@ -1777,8 +1810,11 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         op = self._native_half_op(cache, form, half_delta)
         X, _, no, wa, wb = self._canon_batch(X, None, noise)
         u = src.prediction_cache["pred_mean"][0, :, 0]       # (finishes whatever is pending, leaves a stencil shard)
-        with torch.no_grad(), settings.skip_posterior_variances(False):
-            pvar = src._eval_forward(X).variance.reshape(-1).to(self._dtype).contiguous()
+        if pvar_of is not None:                              # (a form that takes more than the variance of f from that posterior)
+            pvar = pvar_of(src, X)
+        else:
+            with torch.no_grad(), settings.skip_posterior_variances(False):
+                pvar = src._eval_forward(X).variance.reshape(-1).to(self._dtype).contiguous()
         targets, res = self._site_targets(cache, op, u)
         flag0 = self._err.clone()
         sites = launch(X, pvar, self._sigma2(0), wa, wb, no, *targets, res=res)
@@ -1827,6 +1863,76 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             cache, X, None, src, "count observations", half_delta=half_delta,
             launch=lambda X, *rest, **kw: grid_ops.scatter_stats_count(self._grid, X, y, t, family, *rest, **kw))
         return grown
+
+    # --------------------------------------------------- noisy-input observations --
+    def _canon_input_var(self, input_var, n):
+        """input_var -- a scalar, [d], [n] or [n, d] (a vector of length n == d counts as [d]) -- as [n, d] on the model's device."""
+        d = self._grid.d
+        v = torch.as_tensor(input_var).detach().to(self._device, self._dtype)
+        if v.dim() == 1 and v.shape[0] != d and v.shape[0] == n:
+            v = v[:, None]
+        if tuple(v.shape) not in ((), (d,), (n, 1), (n, d)):
+            raise ValueError(f"input_var must be a scalar, [{d}], [{n}] or [{n}, {d}], got {tuple(v.shape)}")
+        return v.expand(n, d).contiguous()
+
+    def _condition_input_noise(self, X, Y, noise, input_var, inplace, _decay, others):
+        """condition_on_observations with input_var: grow, decay, take the slope moments, absorb -- _condition_interval
+        with the noisy-input launch.  The sites are taken against the posterior of the statistics the batch is added to."""
+        if others:
+            raise NotImplementedError(f"noisy-input observations inflate the noise of targets Y: input_var takes no {' / '.join(others)} "
+                                      "(no kernel applies two sites)")
+        self._refuse_trend("noisy-input observations (input_var)", "a site is matched against the grid mean alone, which under a trend "
+                           "is not the predictive mean")
+        self._refuse_for_sites(X, "noisy-input", "input_var")
+        if Y is None:
+            raise ValueError("input_var describes the locations of targets Y, which were not given")
+        if Y.dim() > 2:
+            raise NotImplementedError("batched conditioning (fantasies) takes targets, not input_var")
+        X = X.reshape(-1, self._grid.d)
+        n = X.shape[0]
+        y = Y.to(self._device, self._dtype).reshape(-1)
+        if y.shape[0] != n:
+            raise ValueError(f"Y must hold one target per point ([{n}]), got {tuple(Y.shape)}")
+        xvar = self._canon_input_var(input_var, n)
+        if noise is not None:
+            noise = noise.to(self._device, self._dtype).reshape(-1)
+            if noise.shape[0] != n:
+                raise ValueError(f"noise must hold one value per point ([{n}]), got {tuple(noise.shape)}")
+        if self.grow_grid:
+            self.grow_to_cover_(X)
+        return self._condition(lambda model, cache, src: model._absorb_input_noise(cache, X, y, xvar, noise, src), inplace, self._gamma(_decay),
+                               reads_posterior=True)
+
+    def _absorb_input_noise(self, cache, X, y, xvar, noise, src, half_delta=None):
+        """_absorb_matched with the noisy-input launch (wiski_scatter_stats_input_noise).  "posterior": the variances of f and of its
+        partial derivatives at X are the diagonal of ONE posterior_jet covariance of `src`; "mean": the variance of f as for intervals,
+        no slope variance.  The pseudo-target is y itself."""
+        gvar = []
+
+        def jet_variances(src, X):
+            diag = torch.diagonal(src.posterior_jet(X).covariance, dim1=-2, dim2=-1).to(self._dtype)
+            gvar.append(diag[:, 1:].contiguous())
+            return diag[:, 0].contiguous()
+
+        def launch(X, *rest, **kw):
+            omega, log_z, grad = grid_ops.scatter_stats_input_noise(self._grid, X, y.contiguous(), xvar, gvar[0] if gvar else None, *rest, want_grad=True, **kw)
+            return y, omega, log_z, grad
+
+        sites, grown = self._absorb_matched(cache, X, noise, src, "noisy-input observations", launch, half_delta=half_delta,
+                                            pvar_of=jet_variances if self.input_noise_slope == "posterior" else None)
+        self.last_input_noise_sites = sites[1:]
+        return grown
+
+    def posterior_noisy_input(self, X, input_var):
+        """(mean [n], variance [n]) of f at queries whose locations are uncertain, X [n, d] with error variance ``input_var`` (a scalar,
+        [d], [n] or [n, d]) per dimension: to first order the mean is that of ``posterior(X)`` and the variance gains
+        ``sum_k input_var_k (E[g_k]^2 + Var g_k)`` with g the gradient under ``posterior_jet(X)``.  Plain torch on
+        the jet; outputs are detached.  One output, unbatched X."""
+        jet = self.posterior_jet(X)
+        xvar = self._canon_input_var(input_var, jet.n).to(jet.mean.dtype)
+        diag = torch.diagonal(jet.covariance, dim1=-2, dim2=-1)
+        g = jet.mean[:, 1:]
+        return jet.mean[:, 0], diag[:, 0] + (xvar * (g * g + diag[:, 1:].clamp_min(0.0))).sum(-1)
 
     def _latent_moments(self, X):
         """(mean, variance) [n] of f at X under the current posterior, in the model's dtype."""
@@ -2237,7 +2343,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
 
     def _stream_fast_state(self, X, Y):
         """(prepared StreamStep, mean state, preconditioner state) when the one-call streaming step applies, else None."""
-        if (self.robust_c is not None or self.window is not None or self._trend_deg is not None or self.num_outputs != 1 or self._use_dense() or settings.spectral_preconditioner.off() or settings.residual_carry_over.off()
+        if (self.robust_c is not None or self.window is not None or self._trend_deg is not None or self.input_var is not None or self.num_outputs != 1 or self._use_dense() or settings.spectral_preconditioner.off() or settings.residual_carry_over.off()
                 or X.dim() != 2 or not X.is_cuda or X.dtype != self._dtype or not X.is_contiguous() or Y.dtype != self._dtype):
             return None
         ms = self._mean_state

@@ -3,7 +3,7 @@
 
     OnlineSKIRegression(stem, init_x, init_y, lr, grid_size, grid_bound, covar_module=None, **kw)
         (**kw: num_path_probes, path_seed, forgetting_factor, grow_grid, max_grid_size, robust_c, robust_scale, window,
-        window_rebuild_every -- passed to the GP)
+        window_rebuild_every, input_var, input_noise_slope -- passed to the GP; input_var needs the Identity stem)
     .fit(x, y, num_epochs, test_dataset=None) -> list of per-epoch dicts
     .update(x, y, update_stem=True, update_gp=True) -> (stem_loss, gp_loss)
     .evaluate(x, y) -> (rmse, nll)        .predict(x) -> (mean [n, out], var [n, out])
@@ -31,6 +31,12 @@ class OnlineSKIRegression(StreamingSKIWrapper):
         self.target_dim = init_y.shape[-1]
         self._target_batch_shape = torch.Size([]) if self.target_dim == 1 else torch.Size([self.target_dim])
         stem = stem.to(init_x.device)
+        if kwargs.get("input_var") is not None:
+            from .stems import Identity
+
+            if not isinstance(stem, Identity):
+                raise NotImplementedError("input_var needs the Identity stem (the variance is that of the GP's own inputs, not of what a "
+                                          "learned stem maps them to)")
         feats = stem(init_x).detach()
         half_width = grid_bound + _GRID_MARGIN
         gp = FixedNoiseOnlineSKIGP(
@@ -44,6 +50,7 @@ class OnlineSKIRegression(StreamingSKIWrapper):
             grow_grid=kwargs.get("grow_grid", False), max_grid_size=kwargs.get("max_grid_size"),
             robust_c=kwargs.get("robust_c"), robust_scale=kwargs.get("robust_scale", "noise"),
             window=kwargs.get("window"), window_rebuild_every=kwargs.get("window_rebuild_every"),
+            input_var=kwargs.get("input_var"), input_noise_slope=kwargs.get("input_noise_slope", "posterior"),
         )
         self._setup(stem, gp, lr, init_x)
 

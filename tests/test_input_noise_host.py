@@ -1,0 +1,161 @@
+"""No GPU: the site of a noisy-input observation, its reference, and the choice of the default rule, in numpy fp64.
+
+The reference's slope is checked against central differences of its own predictive mean; with zero input variance its absorb is the
+plain one (tests/robust_reference.py at weight one) to 1e-14; the skip rules are pinned case by case; and the toy problem of the design
+-- tanh(12 (x - 1/2)) recorded at locations that are off by sigma_x = 0.03, streamed in 8 batches of 16 from a cold start -- runs
+through the dense reference model alone for seeds 0 .. 9: inflating by the posterior's E[(d f)^2] must beat the plain model by half
+a nat of NLPD on every seed and stay below -1.5, which pins the default (``input_noise_slope="posterior"``) independently of any kernel.
+"""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+
+import input_noise_reference as nref
+import robust_reference as rref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _grid(d):
+    g = {1: [9], 2: [8, 7], 3: [6, 7, 5]}[d]
+    return nref.Grid.from_bounds([[-1.0, 1.0 + 0.25 * q] for q in range(d)], g)
+
+
+def _interior_points(grid, n, rng):
+    """Points in cells away from the boundary cells of every dim and away from the cell faces (the cubic is C^1 only)."""
+    cell = np.stack([rng.integers(1, gq - 2, n) for gq in grid.g], 1)
+    return np.array(grid.g0) + np.array(grid.h) * (cell + rng.uniform(0.1, 0.9, (n, grid.d)))
+
+
+@pytest.mark.parametrize("d", [1, 2, 3])
+def test_reference_slope_is_the_central_difference_of_its_own_mean(d):
+    """g_k = (d w / d x_k) . u against (mu(x + e_k t) - mu(x - e_k t)) / 2t with t = 1e-6 h: the interpolant is a cubic in the cell, so
+    the truncation is t^2 mu''' / 6 ~ 1e-12 of |u| / h and the rounding 1e-16 |u| / t ~ 1e-10 |u| / h: asserted at 1e-8 |u|_max / h."""
+    grid, rng = _grid(d), np.random.default_rng(10 + d)
+    X, u = _interior_points(grid, 20, rng), rng.standard_normal(_grid(d).m)
+    r = nref.dense_absorb(grid, X, np.zeros(20), np.zeros((20, d)), None, np.ones(20), np.ones(20), np.ones(20), np.ones(20), 1.0, u)
+    for k in range(d):
+        t = 1e-6 * grid.h[k]
+        e = np.zeros(d)
+        e[k] = t
+        mp, mm = (nref.rows(grid, X + s * e)[0] @ u for s in (1.0, -1.0))
+        err = np.abs((mp - mm) / (2 * t) - r["grad"][:, k]).max()
+        print(f"d = {d}, dim {k}: max |g - central difference| = {err:.3e}  (max |g| {np.abs(r['grad'][:, k]).max():.3f})")
+        assert err <= 1e-8 * np.abs(u).max() / grid.h[k] and np.abs(r["grad"][:, k]).max() > 0.1
+
+
+def test_slope_is_zero_in_a_boundary_cell_of_its_dim_only():
+    grid, rng = _grid(2), np.random.default_rng(3)
+    u = rng.standard_normal(grid.m)
+    X = np.array([[grid.g0[0] + 0.4 * grid.h[0], 0.1], [0.05, grid.g0[1] + (grid.g[1] - 1.5) * grid.h[1]]])
+    g = nref.dense_absorb(grid, X, np.zeros(2), np.zeros((2, 2)), None, np.ones(2), np.ones(2), np.ones(2), np.ones(2), 1.0, u)["grad"]
+    assert g[0, 0] == 0.0 and g[0, 1] != 0.0 and g[1, 1] == 0.0 and g[1, 0] != 0.0
+
+
+@pytest.mark.parametrize("d", [1, 2, 3])
+def test_zero_input_variance_is_the_plain_absorb(d):
+    grid, rng = _grid(d), np.random.default_rng(20 + d)
+    n = 25
+    X = _interior_points(grid, n, rng)
+    X[3] = np.array(grid.g0) - 1.0                                       # one point outside
+    y, noise, pvar, u = rng.standard_normal(n), rng.uniform(0.5, 2.0, n), rng.uniform(0.0, 2.0, n), rng.standard_normal(grid.m)
+    gvar = rng.uniform(0.0, 2.0, (n, d))
+    r = nref.dense_absorb(grid, X, y, np.zeros((n, d)), gvar, 1.0 / noise, 1.0 / noise, noise, pvar, 0.7, u)
+    p = rref.dense_absorb(grid, X, y, 1.0 / noise, 1.0 / noise, noise, np.zeros(n), 1.0, u)      # inv_scale = 0: omega = 1
+    ok = nref.inside(grid, X)
+    assert np.array_equal(r["omega"], ok.astype(np.float64)) and r["err"] == p["err"] == 3
+    for k in ("A", "A_half", "b", "cnt", "res", "stats", "mean_out"):
+        assert np.abs(r[k] - p[k]).max() <= 1e-14 * max(1.0, np.abs(p[k]).max()), k
+    z = y - r["mean_out"]
+    s2 = pvar + 0.7 * noise
+    assert np.allclose(r["log_z"][ok], (-0.5 * z * z / s2 - 0.5 * np.log(2 * np.pi * s2))[ok], rtol=1e-14, atol=0)
+
+
+def test_site_values_and_the_textbook_rule():
+    st = nref.sites([1.0], [0.4], [[2.0, -1.0]], [0.3], [[0.5, 0.25]], [0.2], [[0.01, 0.04]])
+    s_in = 0.01 * (4.0 + 0.5) + 0.04 * (1.0 + 0.25)
+    assert np.isclose(st["s_in"][0], s_in, rtol=1e-15) and np.isclose(st["omega"][0], 0.2 / (0.2 + s_in), rtol=1e-15)
+    S = 0.3 + 0.2 + s_in
+    assert np.isclose(st["log_z"][0], -0.5 * 0.36 / S - 0.5 * np.log(2 * np.pi * S), rtol=1e-15)
+    mean_only = nref.sites([1.0], [0.4], [[2.0, -1.0]], [0.3], None, [0.2], [[0.01, 0.04]])
+    assert np.isclose(mean_only["s_in"][0], 0.01 * 4.0 + 0.04 * 1.0, rtol=1e-15) and mean_only["omega"][0] > st["omega"][0]
+    neg = nref.sites([1.0], [0.4], [[2.0, -1.0]], [-0.3], [[-0.5, 0.25]], [0.2], [[0.01, 0.04]])     # negative variances count as zero
+    assert np.isclose(neg["s_in"][0], 0.01 * 4.0 + 0.04 * 1.25, rtol=1e-15)
+    assert np.isclose(neg["log_z"][0], -0.5 * 0.36 / (0.2 + neg["s_in"][0]) - 0.5 * np.log(2 * np.pi * (0.2 + neg["s_in"][0])), rtol=1e-15)
+
+
+def test_the_skip_rule():
+    g = [[3.0, 1.0]] * 6
+    xvar = np.array([[0.0, 0.0], [np.nan, 0.1], [0.1, -1e-3], [np.inf, 0.1], [1e12, 0.0], [1e9, 0.0]])
+    st = nref.sites(np.full(6, 0.5), np.full(6, 0.2), g, np.full(6, 0.3), None, np.full(6, 0.1), xvar)
+    assert st["omega"][0] == 1.0 and not st["skipped"][0]
+    assert st["skipped"][1:5].all() and (st["omega"][1:5] == 0.0).all()
+    assert np.isnan(st["log_z"][1:4]).all() and np.isfinite(st["log_z"][4])           # omega below the threshold: log Z stays the density
+    assert not st["skipped"][5] and 1e-12 < st["omega"][5] < 1e-10                    # 0.1 / 9e9: small, and informative still
+    assert nref.OMEGA_MIN == 1e-12
+    src = open(os.path.join(ROOT, "online_gp_amd", "csrc", "scatter_input_noise.h")).read()
+    assert "#define WISKI_INPUT_NOISE_OMEGA_MIN 1e-12" in src
+
+
+def test_a_point_outside_the_grid_is_dropped_and_counted():
+    grid = _grid(2)
+    X = np.array([[0.1, 0.2], [5.0, 0.0], [-0.3, 0.4]])
+    r = nref.dense_absorb(grid, X, [0.3, 0.1, 0.2], np.full((3, 2), 0.01), None, np.ones(3), np.ones(3), np.ones(3), np.full(3, 0.2), 0.5,
+                          np.linspace(-1, 1, grid.m))
+    assert r["err"] == 3 and r["omega"][1] == 0.0 and r["log_z"][1] == 0.0 and (r["grad"][1] == 0.0).all() and not r["skipped"][1]
+    assert 0 < r["omega"][0] < 1 and 0 < r["omega"][2] < 1
+
+
+@pytest.mark.parametrize("name", list(nref.KGRIDS))
+def test_reference_split_of_the_kernel_case(name):
+    """What the batch of the GPU kernel tests (input_noise_reference.kernel_case) is meant to contain, on the reference alone."""
+    c = nref.kernel_case(name)
+    r, ok, d = c["ref"], c["ok"], c["d"]
+    assert list(np.nonzero(~ok)[0]) == [nref.OUTSIDE] and r["err"] == 3
+    assert list(np.nonzero(r["skipped"])[0]) == [nref.NANXI, nref.HUGE] and list(np.nonzero(c["ref_mean"]["skipped"])[0]) == [nref.NANXI, nref.HUGE]
+    assert (r["omega"][list(nref.ZERO)] == 1.0).all() and np.isnan(r["log_z"][nref.NANXI]) and np.isfinite(r["log_z"][nref.HUGE])
+    assert c["pvar"][nref.PVAR0] == 0.0 and c["pvar"][nref.PVARNEG] < 0.0 and (c["gvar"][nref.PVARNEG] < 0.0).all()
+    for q in range(d):                                                # the slope is zero in a boundary cell of its own dim, and only there
+        assert r["grad"][4 + q, q] == 0.0 and r["grad"][20 + q, q] == 0.0
+    assert int((r["grad"] == 0.0).sum()) == 2 * d + d                 # (and for the point outside)
+    ent = ok & ~r["skipped"] & (r["omega"] < 1.0)
+    ratio = r["s_in"][ent] / c["dn"][ent]
+    print(f"{name}: s_in / dn of the inflated sites {ratio.min():.2e} .. {ratio.max():.2e}; omega {r['omega'][ent].min():.2e} .. {r['omega'][ent].max():.4f}")
+    assert ratio.min() <= 1.01e-3 and ratio.max() >= 0.99e3 and int(ent.sum()) == nref.N - 6
+    assert (r["omega"][ent] >= 1e4 * nref.OMEGA_MIN).all()
+
+
+def test_kernel_is_declared_and_listed_for_the_build():
+    from online_gp_amd import _hip, grid_ops
+
+    hdr = open(os.path.join(ROOT, "include", "wiski.h")).read()
+    for name in ("wiski_scatter_stats_input_noise_f32", "wiski_scatter_stats_input_noise_f64", "wiski_absorb_input_noise_f32", "wiski_absorb_input_noise_f64"):
+        assert name in hdr
+    assert "scatter_input_noise.h" in _hip._HEADERS and os.path.exists(os.path.join(ROOT, "online_gp_amd", "csrc", "scatter_input_noise.h"))
+    assert '#include "scatter_input_noise.h"' in open(os.path.join(ROOT, "online_gp_amd", "csrc", "scatter_stats.hip")).read()
+    assert callable(grid_ops.scatter_stats_input_noise)
+    # the public argument record has not grown: callers built against the previous header keep working
+    assert ctypes.sizeof(_hip.wiski_absorb_args) == 224
+
+
+_toy = {}
+
+
+def _toy_nlpd(seed, slope):
+    if (seed, slope) not in _toy:
+        _toy[(seed, slope)] = nref.toy_run(seed, slope)[:2]
+    return _toy[(seed, slope)]
+
+
+@pytest.mark.parametrize("seed", range(10))
+def test_toy_stream_the_posterior_slope_rule_pays_on_every_seed(seed):
+    """NLPD of the noise-free truth at 200 clean test points after the stream.  The simulation behind the design measured, over these
+    ten seeds, the plain model at -1.23 .. +4.87, the rule of the mean's slope at -2.32 .. +2.39, this rule at -2.06 .. -1.74 (smallest
+    gap to the plain model 0.8); asserted: at least 0.5 better than the plain model, and at most -1.5."""
+    plain, rule, mean_only = (_toy_nlpd(seed, s) for s in (None, "posterior", "mean"))
+    print(f"seed {seed}: NLPD / RMSE  plain {plain[0]:+.3f} / {plain[1]:.4f}   mean's slope {mean_only[0]:+.3f} / {mean_only[1]:.4f}   "
+          f"posterior {rule[0]:+.3f} / {rule[1]:.4f}")
+    assert rule[0] <= plain[0] - 0.5
+    assert rule[0] <= -1.5
