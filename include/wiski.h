@@ -220,7 +220,12 @@ int wiski_kron_toeplitz_grad_f64(const wiski_grid* grid, const double* d_tcol, c
 /* Spectral functions of Kt = kscale*Kuu in its Kronecker eigenbasis (d_evec/d_eval
  * as for wiski_pcg): d_out[c] = V diag(lam^pw / (1 + shift*lam)^rw) V^T d_V[c].
  * pw = 0.5, rw = 0 gives the symmetric root Kt^(1/2) (logdet(Q) by stochastic
- * Lanczos quadrature, BWM:27 inv_quad_logdet).  d_tmp: k*m reals. */
+ * Lanczos quadrature, BWM:27 inv_quad_logdet).  d_tmp: k*m reals.
+ * The factors need not be orthogonal: d_evec holds d row-major g[q] x g[q] tables F_q (column = mode) and the
+ * product is (kron F_q) diag(f) (kron F_q)^T d_V[c]; f is 0 where pw != 0 and lam <= 0.  Supported: 4 <= g[q] <= 128
+ * in both precisions (a factor is held in g[q]^2 reals of LDS, 128 KB in fp64 at g = 128, requested per launch;
+ * WISKI_E_LAUNCH if the device refuses it), k >= 1, d_out distinct from d_V; anything else returns WISKI_E_BADARG
+ * before any launch.  wiski_kron_toeplitz_mm takes 4 <= g[q] <= 256. */
 int wiski_kron_spectral_mm_f32(const wiski_grid* grid, const float* d_evec, const float* d_eval, float kscale, float shift, float pw, float rw, const float* d_V, int32_t k, float* d_tmp, float* d_out, void* stream);
 int wiski_kron_spectral_mm_f64(const wiski_grid* grid, const double* d_evec, const double* d_eval, double kscale, double shift, double pw, double rw, const double* d_V, int32_t k, double* d_tmp, double* d_out, void* stream);
 

@@ -1323,6 +1323,19 @@ __global__ __launch_bounds__(256) void k_dense_mode(GridDev<real> G, int q, cons
   }
 }
 
+// k_dense_mode keeps its g x g factor in dynamic LDS: g * g reals, 128 KB in fp64 at the g = 128 its launchers admit (plus 128 B static,
+// within the CU's 160 KB).  More than 48 KB of dynamic LDS needs an opt-in per instantiation; a launcher calls this before each launch.
+template <typename real, int MODE>
+static int dense_mode_lds(size_t sh) {
+  static size_t lds_set = 0;
+  if (sh > 48 * 1024 && sh > lds_set) {
+    if (hipFuncSetAttribute((const void*)k_dense_mode<real, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess)
+      return WISKI_E_LAUNCH;
+    lds_set = sh;
+  }
+  return WISKI_OK;
+}
+
 // Spectral preconditioner apply:  t = (I + a Kt)^-1 r,  y = Kt t = (Kt^-1 + a I)^-1 r
 // via Kt = V diag(lam) V^T.  ty = [t (k cols) | y (k cols)]; sa/sb: 2k-column scratch.
 // Also accumulates rho[c] += r[c] . y[c].
@@ -1345,6 +1358,7 @@ static int launch_spectral_precond(const GridDev<real>& G, const real* evec, con
   for (int q = 0; q < d; ++q) {
     real* dst = (cur == sa) ? sb : sa;
     const size_t sh = (size_t)G.g[q] * G.g[q] * sizeof(real);
+    if (int rc = q < d - 1 ? dense_mode_lds<real, 0>(sh) : dense_mode_lds<real, 1>(sh)) return rc;
     if (q < d - 1)
       hipLaunchKernelGGL((k_dense_mode<real, 0>), dim3(gx, (unsigned)k), dim3(256), sh, s, G, q, evec + eoff[q], (const real*)nullptr, 0, 1, cur, dst, (int64_t)0, evals,
                          kscale, shift, (const real*)nullptr, 0, (double*)nullptr);
@@ -1358,6 +1372,7 @@ static int launch_spectral_precond(const GridDev<real>& G, const real* evec, con
     const bool last = q == d - 1;
     real* dst = last ? ty : ((cur == sa) ? sb : sa);
     const size_t sh = (size_t)G.g[q] * G.g[q] * sizeof(real);
+    if (int rc = !last ? dense_mode_lds<real, 0>(sh) : dense_mode_lds<real, 2>(sh)) return rc;
     if (!last)
       hipLaunchKernelGGL((k_dense_mode<real, 0>), dim3(gx, (unsigned)(2 * k)), dim3(256), sh, s, G, q, evec + eoff[q], evec2 ? evec2 + eoff[q] : (const real*)nullptr, k, 0, cur, dst, (int64_t)0,
                          evals, kscale, shift, (const real*)nullptr, 0, (double*)nullptr);
@@ -1564,6 +1579,7 @@ static int spectral_mm_impl(const wiski_grid* grid, const real* d_evec, const re
     const int transposed = step < d ? 1 : 0;
     real* dst = ((2 * d - 1 - step) % 2 == 0) ? d_out : d_tmp;
     const size_t sh = (size_t)G.g[q] * G.g[q] * sizeof(real);
+    if ((rc = dense_mode_lds<real, 0>(sh))) return rc;
     hipLaunchKernelGGL((k_dense_mode<real, 0>), grd, dim3(256), sh, s, G, q, d_evec + eoff[q], (const real*)nullptr, 0, transposed, cur, dst, (int64_t)0, d_eval, kscale,
                        shift, (const real*)nullptr, 0, (double*)nullptr);
     cur = dst;
