@@ -194,7 +194,13 @@ int wiski_gather_box_f32(const wiski_grid* grid, const float* d_tab, const int32
 int wiski_gather_box_f64(const wiski_grid* grid, const double* d_tab, const int32_t* d_range, int64_t B, const double* d_V, int32_t k, int32_t rows_per_box, int32_t nsplit, double* d_part, double* d_out, void* stream);
 
 /* replaces WtW._matmul (URLT:47-48) on the stencil form:
- * d_out[c] = beta * d_add[c] + A_st . d_V[c]   (d_add may be NULL). */
+ * d_out[c] = beta * d_add[c] + A_st . d_V[c]   (d_add may be NULL).
+ * d_A_st is offset-major [7^d][m]: offset o has the base-7 digits (dimension 0 slowest) digit - 3 = shift per dimension, entry
+ * (o, i) is A[i, i + off(o)].  CONTRACT of both forms: an entry whose neighbour i + shift leaves the grid in any dimension must be
+ * an exact zero, and every stored entry and every element of d_V (and d_add) finite -- the kernels clamp or wrap the neighbour
+ * index of such entries instead of branching, so they multiply a zero with some other element of d_V.
+ * Refused with WISKI_E_BADARG before anything is launched or written: a NULL d_A_st / d_A_half, d_V or d_out, k < 1, d_out == d_V
+ * (both forms), a grid make_grid would refuse (d outside 1..4, a g[q] < 4, 2^31 nodes or more). */
 int wiski_stencil_spmv_f32(const wiski_grid* grid, const float* d_A_st, const float* d_V, int32_t k, const float* d_add, float beta, float* d_out, void* stream);
 int wiski_stencil_spmv_f64(const wiski_grid* grid, const double* d_A_st, const double* d_V, int32_t k, const double* d_add, double beta, double* d_out, void* stream);
 /* Same product on the symmetric half stencil d_A_half (layout: wiski_scatter_stats_sym); every
@@ -202,6 +208,18 @@ int wiski_stencil_spmv_f64(const wiski_grid* grid, const double* d_A_st, const d
  * form.  d_out must not alias d_V. */
 int wiski_stencil_spmv_sym_f32(const wiski_grid* grid, const float* d_A_half, const float* d_V, int32_t k, const float* d_add, float beta, float* d_out, void* stream);
 int wiski_stencil_spmv_sym_f64(const wiski_grid* grid, const double* d_A_half, const double* d_V, int32_t k, const double* d_add, double beta, double* d_out, void* stream);
+/* Which kernel the two products above take for k columns of elem_bytes (4 or 8) wide reals on the full (half == 0) or the half
+ * stencil; launches nothing, reads the same once-per-process switches (WISKI_SYM_DMA, WISKI_SPMM_BCAST) as the launchers.
+ *   0 k_stencil_spmv            full, m % 4 != 0                 *kc = 1, 2 or 4 columns per pass
+ *   1 k_stencil_spmv4 (+ k_spmv_reduce)  full, m % 4 == 0        *kc = 1, 2, 4, 8; d = 2, 3 and k >= 8: k_stencil_spmm, *kc = 8 or 16
+ *   2 k_stencil_spmv_sym        half, m % 4 != 0                 *kc = 1, 2 or 4
+ *   3 k_stencil_spmv4_sym       half, m % 4 == 0, none of 4..7   *kc = 1, 2 or 4
+ *   4 k_spmv_sym_dma            fp32, d = 3, k = 1, LDS <= 64 KB *kc = 1
+ *   5 k_spmv_sym_dma_mc         fp32, d = 3, 2 <= k < 16, g[2] >= 4, LDS <= 64 KB   *kc = 2 (k < 4) or 4
+ *   6 k_spmm_sym_bcast          k >= 16 (fp32) / 24 (fp64)       *kc = 64 (columns per slice)
+ *   7 k_spmm_sym_cols           WISKI_SPMM_BCAST=0 and k >= 32   *kc = k rounded up to a multiple of 16
+ * kc may be NULL.  WISKI_E_BADARG: k < 1, elem_bytes other than 4 or 8, a grid the products refuse. */
+int wiski_stencil_spmv_path(const wiski_grid* grid, int32_t k, int32_t elem_bytes, int32_t half, int32_t* kc);
 
 /* a8/a9/a11 -- replaces Kuu @ V (BFN:334-348,363-366) with
  * Kuu = kron_i SymToeplitz(tcol_i): d_out[c] = scale * Kuu d_V[c].

@@ -216,10 +216,21 @@ __global__ __launch_bounds__(256) void k_stencil_spmv(GridDev<real> G, const rea
   }
 }
 
+// Columns per pass of the kernels that take 1, 2 or 4 (k_stencil_spmv, k_stencil_spmv_sym, k_stencil_spmv4_sym).
+static inline int spmv_kc(int k) { return k >= 4 ? 4 : (k >= 2 ? 2 : 1); }
+// Columns per pass of the wide full-stencil product (m % 4 == 0), and whether the LDS-staged k_stencil_spmm takes it (many right-hand
+// sides, d = 2 or 3: 16 columns per pass in fp32 from k = 16, else 8) rather than k_stencil_spmv4 (1, 2, 4 or 8).
+template <typename real>
+static inline int spmv4_kc(const GridDev<real>& G, int k, bool* spmm) {
+  *spmm = k >= 8 && (G.d == 2 || G.d == 3);
+  if (*spmm) return sizeof(real) == 4 && k >= 16 ? 16 : 8;
+  return k >= 8 ? 8 : spmv_kc(k);
+}
+
 template <typename real>
 static int launch_spmv(const GridDev<real>& G, const real* A_st, const real* V, int k, const real* add, real beta, real* out, double* dots,
                        hipStream_t s) {
-  const int kc = k >= 4 ? 4 : (k >= 2 ? 2 : 1);
+  const int kc = spmv_kc(k);
   dim3 grd((unsigned)((G.m + 255) / 256), (unsigned)((k + kc - 1) / kc));
   size_t sh = (size_t)G.R * sizeof(int);
   if (sh < 16 * sizeof(double)) sh = 16 * sizeof(double);
@@ -522,14 +533,16 @@ static int launch_spmv4(const GridDev<real>& G, const real* A_st, const real* V,
   int nmid = 1;
   for (int q = 1; q < G.d - 1; ++q) nmid *= 7;
   const bool prof = g_prof.on && g_prof.used + 2 <= g_prof.ev.size();
-  if (k >= 8 && (G.d == 2 || G.d == 3) && nmid <= 64 && !prof) {
+  bool spmm = false;
+  int kc = spmv4_kc<real>(G, k, &spmm);
+  if (spmm && !prof) {
     // many right-hand sides: LDS-staged SpMM (fp32: 16 columns per pass, fp64: 8)
     if constexpr (sizeof(real) == 4) {
-      if (k >= 16) return launch_spmm_kc<real, 16>(G, A_st, V, k, nmid, part, add, beta, dots, s);
+      if (kc == 16) return launch_spmm_kc<real, 16>(G, A_st, V, k, nmid, part, add, beta, dots, s);
     }
     return launch_spmm_kc<real, 8>(G, A_st, V, k, nmid, part, add, beta, dots, s);
   }
-  const int kc = k >= 8 ? 8 : (k >= 4 ? 4 : (k >= 2 ? 2 : 1));
+  if (spmm) kc = 8;   // a profiled launch keeps the event-bracketed k_stencil_spmv4
   dim3 grd((unsigned)((G.m / 4 + 255) / 256), (unsigned)nch, (unsigned)((k + kc - 1) / kc));
   if (prof) (void)hipEventRecord(g_prof.ev[g_prof.used++], s);
 #define SPMV4(KC)                                                                                                              \
@@ -625,7 +638,7 @@ __global__ __launch_bounds__(256) void k_stencil_spmv_sym(GridDev<real> G, const
 template <typename real>
 static int launch_spmv_sym(const GridDev<real>& G, const real* A_h, const real* V, int k, const real* add, real beta, real* out, double* dots,
                            hipStream_t s) {
-  const int kc = k >= 4 ? 4 : (k >= 2 ? 2 : 1);
+  const int kc = spmv_kc(k);
   dim3 grd((unsigned)((G.m + 255) / 256), (unsigned)((k + kc - 1) / kc));
   const size_t sh = (size_t)((G.R + 1) / 2) * (sizeof(int64_t) + 2 * sizeof(int));
 #define SPMV(KC)                                                                                                                 \
@@ -975,6 +988,28 @@ static inline int sym_partials(const GridDev<real>& G, int k, int* zl) {
   return sym_nch<real>(G, k) + 1;
 }
 
+// Which kernel serves a stencil product of k columns, and with how many columns per pass: the one choice behind spmv_impl,
+// spmv_sym_impl and launch_spmv4_sym (codes as documented at wiski_stencil_spmv_path, include/wiski.h).
+//   full stencil   0 k_stencil_spmv (m % 4 != 0)        1 k_stencil_spmv4 / k_stencil_spmm + k_spmv_reduce
+//   half stencil   2 k_stencil_spmv_sym (m % 4 != 0)    3 k_stencil_spmv4_sym    4 k_spmv_sym_dma    5 k_spmv_sym_dma_mc
+//                  6 k_spmm_sym_bcast (kc = 64: the slice width)    7 k_spmm_sym_cols (kc = the padded column count)
+enum { SPMV_GENERIC = 0, SPMV_WIDE = 1, SPMV_SYM_GENERIC = 2, SPMV_SYM_LDS = 3, SPMV_SYM_DMA = 4, SPMV_SYM_DMA_MC = 5, SPMV_SYM_BCAST = 6,
+       SPMV_SYM_COLS = 7 };
+struct SpmvPath { int code, kc; };
+template <typename real>
+static inline SpmvPath spmv_path(const GridDev<real>& G, int k, bool half) {
+  if (!half) {
+    if (G.m % 4 != 0) return {SPMV_GENERIC, spmv_kc(k)};
+    bool spmm = false;
+    return {SPMV_WIDE, spmv4_kc<real>(G, k, &spmm)};
+  }
+  if (G.m % 4 != 0) return {SPMV_SYM_GENERIC, spmv_kc(k)};
+  if (sym_use_cols(k, sizeof(real))) return sym_use_bcast() ? SpmvPath{SPMV_SYM_BCAST, 64} : SpmvPath{SPMV_SYM_COLS, spmmc_kp(k)};
+  if (sym_use_dma<real>(G, k)) return {SPMV_SYM_DMA, 1};
+  if (sym_use_dma_mc<real>(G, k)) return {SPMV_SYM_DMA_MC, k >= 4 ? 4 : 2};
+  return {SPMV_SYM_LDS, spmv_kc(k)};
+}
+
 // One launch with optional per-dispatch timing: in profiling mode the start/stop events are attached to the
 // kernel's own dispatch packet (hipExtLaunchKernelGGL), so their difference is the kernel's execution time --
 // a hipEventRecord bracket adds ~3 us of marker-packet latency to a 20 us kernel.
@@ -1018,13 +1053,16 @@ static int launch_spmv4_sym(const GridDev<real>& G, const real* A_h, const real*
   if (shard_tab && !(sizeof(real) == 4 && sym_use_dma<real>(G, k))) return WISKI_E_BADARG;
   const bool ranged = g_hi >= 0;
   if (ranged && (shard_tab || k != 1 || g_lo < 0 || g_hi < g_lo || g_hi > sym_groups(G.d))) return WISKI_E_BADARG;
-  if (sym_use_cols(k, sizeof(real)) && !ranged) {
+  // a ranged launch (the groups of one shard, k = 1) is always the LDS-window kernel's
+  const SpmvPath path = ranged ? SpmvPath{SPMV_SYM_LDS, 1} : spmv_path<real>(G, k, true);
+  if (path.code == SPMV_SYM_GENERIC) return WISKI_E_BADARG;   // m % 4 != 0 is launch_spmv_sym's
+  if (path.code == SPMV_SYM_BCAST || path.code == SPMV_SYM_COLS) {
     // part[0] <- A V (column-major, written by the product itself); the row-major copy of V lives behind it
     const int m = G.m, kp = spmmc_kp(k);
     const int64_t km = (int64_t)k * m;
     real* Vt = part + km;
     real* Ot = part;
-    if (sym_use_bcast()) {   // coefficients on the vector path, DPP row broadcast (spmm_sym_bcast.h); operands in 64-column slices
+    if (path.code == SPMV_SYM_BCAST) {   // coefficients on the vector path, DPP row broadcast (spmm_sym_bcast.h); operands in 64-column slices
       const int ns = (k + 63) / 64;
       dim3 tg((unsigned)(8 * (((m + 63) / 64 + 7) / 8)), (unsigned)ns);            // (padded: XCD-contiguous row tiles, see the kernel)
       if (dots && add) hipLaunchKernelGGL((k_transpose_cm_rm<real, true, true>), tg, dim3(256), 0, s, m, k, 64 * ns, V, Vt, add, beta, dots);
@@ -1067,7 +1105,7 @@ static int launch_spmv4_sym(const GridDev<real>& G, const real* A_h, const real*
     return hipGetLastError() == hipSuccess ? WISKI_OK : WISKI_E_LAUNCH;
   }
   if constexpr (sizeof(real) == 4) {
-    if (sym_use_dma<real>(G, k) && !ranged) {
+    if (path.code == SPMV_SYM_DMA) {
       const int W4 = symdma_w4(G.g[2]), WP = symdma_wp(G.g[2]);
       const size_t sh = symdma_lds_bytes(G.g[2], g_sym_dma_nst);
       SymDmaParts tab{};
@@ -1098,8 +1136,8 @@ static int launch_spmv4_sym(const GridDev<real>& G, const real* A_h, const real*
     }
   }
   if constexpr (sizeof(real) == 4) {
-    if (sym_use_dma_mc<real>(G, k) && !ranged) {
-      const int kc = k >= 4 ? 4 : 2;
+    if (path.code == SPMV_SYM_DMA_MC) {
+      const int kc = path.kc;
       const int W4 = symdma_w4(G.g[2]), WP = symdma_wp(G.g[2]);
       const size_t sh = symdma_mc_lds_bytes(G.g[2], kc);
       const int nrb = (G.m + 255) / 256;
@@ -1125,7 +1163,7 @@ static int launch_spmv4_sym(const GridDev<real>& G, const real* A_h, const real*
   if (ng - (int)((int64_t)(nch - 1) * ng / nch) > 176 || ng > 176 * nch) return WISKI_E_BADARG;
   // columns per pass over A_h (8 per pass, with the v / transposed windows of 4 live at a time, was measured:
   // 344 / 488 VGPRs leave one wave per SIMD, 1.3x / 2.2x slower)
-  const int kc = k >= 4 ? 4 : (k >= 2 ? 2 : 1);
+  const int kc = path.kc;
   // window span: one full cycle of the second-to-last stencil digit, shrunk to fit 48 KB of LDS
   int span = G.d >= 2 ? 6 * G.stride[G.d - 2] : 0;
   const int bs = sym_block(), nw = bs / 64;
@@ -2345,9 +2383,9 @@ static int spmv_impl(const wiski_grid* grid, const real* d_A, const real* d_V, i
   GridDev<real> G;
   int rc = make_grid_dev<real>(grid, &G);
   if (rc) return rc;
-  if (!d_A || !d_V || !d_out || k < 1) return WISKI_E_BADARG;
+  if (!d_A || !d_V || !d_out || k < 1 || d_out == d_V) return WISKI_E_BADARG;   // (the generic kernel gathers V while other rows are stored)
   hipStream_t s = (hipStream_t)stream;
-  if (G.m % 4 != 0) return launch_spmv<real>(G, d_A, d_V, k, d_add, beta, d_out, nullptr, s);
+  if (spmv_path<real>(G, k, false).code == SPMV_GENERIC) return launch_spmv<real>(G, d_A, d_V, k, d_add, beta, d_out, nullptr, s);
   const int nch = spmv_nch(G.d);
   const int64_t km = (int64_t)k * G.m;
   real* part = nullptr;
@@ -2371,7 +2409,7 @@ static int spmv_sym_impl(const wiski_grid* grid, const real* d_A, const real* d_
   if (rc) return rc;
   if (!d_A || !d_V || !d_out || k < 1 || d_out == d_V) return WISKI_E_BADARG;
   hipStream_t s = (hipStream_t)stream;
-  if (G.m % 4 != 0) return launch_spmv_sym<real>(G, d_A, d_V, k, d_add, beta, d_out, nullptr, s);
+  if (spmv_path<real>(G, k, true).code == SPMV_SYM_GENERIC) return launch_spmv_sym<real>(G, d_A, d_V, k, d_add, beta, d_out, nullptr, s);
   int zl = 0;
   const int nch = sym_partials<real>(G, k, &zl);
   const int64_t km = (int64_t)k * G.m;
@@ -2463,6 +2501,21 @@ int wiski_stencil_spmv_f32(const wiski_grid* g, const float* A, const float* V, 
 int wiski_stencil_spmv_f64(const wiski_grid* g, const double* A, const double* V, int32_t k, const double* add, double beta, double* out, void* s) { return spmv_impl<double>(g, A, V, k, add, beta, out, s); }
 int wiski_stencil_spmv_sym_f32(const wiski_grid* g, const float* A, const float* V, int32_t k, const float* add, float beta, float* out, void* s) { return spmv_sym_impl<float>(g, A, V, k, add, beta, out, s); }
 int wiski_stencil_spmv_sym_f64(const wiski_grid* g, const double* A, const double* V, int32_t k, const double* add, double beta, double* out, void* s) { return spmv_sym_impl<double>(g, A, V, k, add, beta, out, s); }
+int wiski_stencil_spmv_path(const wiski_grid* g, int32_t k, int32_t elem_bytes, int32_t half, int32_t* kc) {
+  if (k < 1 || (elem_bytes != 4 && elem_bytes != 8)) return WISKI_E_BADARG;
+  SpmvPath p;
+  if (elem_bytes == 4) {
+    GridDev<float> G;
+    if (int rc = make_grid_dev<float>(g, &G)) return rc;
+    p = spmv_path<float>(G, k, half != 0);
+  } else {
+    GridDev<double> G;
+    if (int rc = make_grid_dev<double>(g, &G)) return rc;
+    p = spmv_path<double>(G, k, half != 0);
+  }
+  if (kc) *kc = p.kc;
+  return p.code;
+}
 int wiski_kron_toeplitz_mm_f32(const wiski_grid* g, const float* tcol, const float* V, int32_t k, float scale, float* tmp, float* out, void* s) { return kron_impl<float>(g, tcol, V, k, scale, tmp, out, s); }
 int wiski_kron_toeplitz_mm_f64(const wiski_grid* g, const double* tcol, const double* V, int32_t k, double scale, double* tmp, double* out, void* s) { return kron_impl<double>(g, tcol, V, k, scale, tmp, out, s); }
 int wiski_kron_toeplitz_grad_f32(const wiski_grid* g, const float* tcol, const float* X, const float* Y, int32_t k, float* tmp, double* grad, void* s) { return kron_grad_impl<float>(g, tcol, X, Y, k, tmp, grad, s); }
