@@ -162,7 +162,7 @@ class GraphedHyperStep:
         gp = self.w.gp
         ready = False
         if (self._prepared is not None and self.graph is not None and self.disabled is None and settings.graphed_hyper_step.on()
-                and settings.spectral_factor.on() and not gp._wsum_dirty and gp.__dict__.get("_pending_step") is None):
+                and settings.spectral_factor.on() and not gp._wsum_dirty and gp._pending_step is None):
             sps = self._prepared_sps
             ready = (all(sp[0].cur is sp[1] for sp in sps) and self._token(sps) == self._prepared
                      and gp.__dict__.get("_bounds_clean_at") == (gp.num_data, sps[0][0].data_version))

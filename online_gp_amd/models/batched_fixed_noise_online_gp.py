@@ -26,6 +26,7 @@ from ..kernels import GridInterpolationKernel, RBFKernel, ScaleKernel
 from ..lazy.operators import (InducingPosterior, InterpolatedKernel, KroneckerToeplitz, PredictiveCovariance, StencilWtW, with_input_grad)
 from ..lazy.dense_woodbury import DenseInducingPosterior
 from ..likelihoods import FNMGLikelihood
+from .step_pacing import PollPacing, basis_kept, basis_slow, density_profiles, profiles_moved
 
 
 class BatchOperator(LazyCovariance):
@@ -285,6 +286,13 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         self._pcg_ws = grid_ops.PCGWorkspace()
         self._memo = {}
         self._mean_state = None  # warm-start state of the posterior-mean solve
+        # the streaming step's own state, None while idle
+        self._last_iters = None                      # CG iterations of the last mean solve, per output
+        self._pending_step = None                    # the StreamStep whose deferred refresh is in flight (_finish_pending)
+        self._stream_step_cache = None               # (key, prepared StreamStep) of _stream_fast_state
+        self._profile_look = None                    # the density-profile look in flight (_density_profile_still_fits)
+        self._profile_look_host = None               # its pinned host buffer, allocated once
+        self._pacing = PollPacing(1e-7 if dtype == torch.float32 else 1e-11)     # where the mean solve polls first, refresh count
 
         if kernel_cache is None:
             self._kernel_cache = self._fresh_cache()
@@ -685,7 +693,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         describe exactly the points that were absorbed -- a caller may catch the error and carry on."""
         dropped = flag >> 1
         self._err.zero_()
-        self.__dict__.pop("_stream_step_cache", None)
+        self._stream_step_cache = None
         self._drop_spectral()          # rows of out-of-grid points were zero for the factor too, but a prepared state may be half-updated
         if dropped and self.window is not None:
             ring = self._kernel_cache["_ring"]
@@ -771,31 +779,14 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         st = self._memo.setdefault("precond", {}).get(o)
         wsum = float(self._wsum[o])
         stale = st is None or st["ver"] != ver
-        its = (getattr(self, "_last_iters", None) or [0] * (o + 1))[o]
-        if not stale:
-            if st.get("it0") is None and its > 0:
-                st["it0"] = its                          # iteration level of this basis when it was fresh
-            slow = st.get("it0") is not None and its >= st["it0"] + 2 and wsum > 1.1 * st["wsum"]
+        slow = not stale and basis_slow(st, (self._last_iters or [0] * (o + 1))[o], wsum)
         if stale or wsum > 2.0 * st["wsum"] or wsum < 0.5 * st["wsum"] or slow:
             profiles, norm = None, float(self._grid.m)
-            cnt = self._kernel_cache.get("_cnt") if settings.density_profile_preconditioner.on() else None
-            if cnt is not None and wsum > 0:
-                c3 = cnt[o].reshape(self._grid.g).double()
-                margs = [c3.sum(dim=[r for r in range(self._grid.d) if r != q]) if self._grid.d > 1 else c3 for q in range(self._grid.d)]
-                # (cnt of a cell whose points have all left a sliding window is zero up to rounding only: no negative density)
-                margs = torch.stack([torch.nn.functional.pad(mg, (0, max(self._grid.g) - mg.numel())) for mg in margs]).clamp_min(0).cpu().numpy()
-                if margs.max() > 0:
-                    profiles, norm = [], 1.0
-                    for q, gq in enumerate(self._grid.g):
-                        t = margs[q, :gq] / margs[q, :gq].max()
-                        t = t.clip(1e-2, None)
-                        profiles.append(t)
-                        norm *= float(t.sum())
+            if settings.density_profile_preconditioner.on() and self._kernel_cache.get("_cnt") is not None and wsum > 0:
+                profiles, norm = density_profiles(self._cnt_marginals(o).cpu().numpy(), self._grid.g, self._grid.m)
             old = None if stale else st.get("profiles")
-            if (old is not None and profiles is not None and
-                    max(float(abs(a - b).max()) for a, b in zip(profiles, old)) <= settings.precond_profile_drift.value()):
-                st["wsum"] = wsum                      # same density shape: keep the eigenbasis, only the scale moves
-                st["it0"] = None
+            if old is not None and profiles is not None and not profiles_moved(profiles, old):
+                basis_kept(st, wsum)
             else:
                 host = {}
                 # where the truncated preconditioner can engage (_keep_for_step: one output, d = 3, fp32) decompose the fp64 columns:
@@ -809,6 +800,14 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
                 st = {"ver": ver, "wsum": wsum, "eig": eig, "norm": norm, "profiles": profiles, "it0": None, "eig_host": host}
                 self._memo["precond"][o] = st
         return st["eig"], wsum / st["norm"]
+
+    def _cnt_marginals(self, o):
+        """Per-dim marginals of the row sums of W^T D^-1 W of output o, [d, max g] in fp64 on the device (rows padded with zeros)."""
+        g, d = self._grid.g, self._grid.d
+        c3 = self._kernel_cache["_cnt"][o].reshape(g).double()
+        margs = [c3.sum(dim=[r for r in range(d) if r != q]) if d > 1 else c3 for q in range(d)]
+        # (cnt of a cell whose points have all left a sliding window is zero up to rounding only: no negative density)
+        return torch.stack([torch.nn.functional.pad(mg, (0, max(g) - mg.numel())) for mg in margs]).clamp_min(0)
 
     def _posterior_op(self, o):
         self.leave_stencil_shard()                   # solves outside the sharded streaming step need the whole stencil
@@ -845,7 +844,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             tl = tr.rebuild(self._grid, self._device, pst, post.kscale, post.wtw.stencil, float(self._wsum[0]), self._err)
             if tl is not None:
                 tr.block.ensure_cols(k)
-                self._poll_hint_sticky = 2                   # a new block: the next warm steps poll after 2 iterations (as _two_level_step)
+                self._pacing.new_block()
         return tl
 
     # ------------------------------------------------------- stencil shard --
@@ -879,7 +878,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             flat[a:b].zero_()
         self.__dict__["_stencil_shard"] = {"rank": rank, "world": world, "allreduce": allreduce, "allreduce_full": allreduce_full or (lambda t: allreduce(t, None)),
                                            "comm": comm}
-        self.__dict__.pop("_stream_step_cache", None)
+        self._stream_step_cache = None
         self._drop_spectral()
         return True
 
@@ -891,7 +890,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             return
         self._finish_pending()
         self.__dict__["_stencil_shard"] = None
-        self.__dict__.pop("_stream_step_cache", None)
+        self._stream_step_cache = None
         sh["allreduce_full"](_wtw_ops(self._kernel_cache["WtW"])[0].stencil)
 
     # ------------------------------------------------------ spectral factor --
@@ -1052,24 +1051,22 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             pst = self._memo.get("precond", {}).get(o) if tr is not None else None
             if pst is not None and "eig_host" in pst and pst.get("eig") is post.eigen:
                 tl = tr.for_step(self._grid, self._device, pst, post.kscale, float(self._wsum[0]), self._err,
-                                 lockstep=settings.two_level_lockstep.on(), last_iters=(getattr(self, "_last_iters", None) or [0])[0])
+                                 lockstep=settings.two_level_lockstep.on(), last_iters=(self._last_iters or [0])[0])
                 if tr.switched:
-                    self._poll_hint_sticky = 2               # a new block: poll after 2 iterations, then after every one (as _two_level_step)
+                    self._pacing.new_block()
             # warm refreshes poll convergence first where the previous one converged (streaming steps are
             # alike), every 8th one an iteration earlier, and then after every iteration
             fc, probe = 0, False
-            if warm and getattr(self, "_last_iters", None):
-                self._refresh_count = getattr(self, "_refresh_count", 0) + 1
-                fc, probe = self._first_poll(self._last_iters[o])
+            if warm and self._last_iters:
+                self._pacing.count()
+                fc, probe = self._pacing.place(self._last_iters[o])
                 post.check_every = 1
             # warm = 2: R was kept equal to b - Z - A U by the scatter launches since the last solve (recomputed
             # from scratch every 16th refresh so that fp rounding of the recursion cannot accumulate)
-            if carried and getattr(self, "_refresh_count", 0) % 16 == 0:
+            if carried and self._pacing.recompute_due():
                 carried = False
             post.solve_columns(b[o, :, 0][None], U=Uo, Z=Zo, warm=2 if carried else warm, first_check=fc, inplace=True, R=Ro, two_level=tl)
-            if fc:
-                self._note_poll(post.last_iters, fc, probe)
-            self._last_rel = None                    # this path does not keep the converged residual: timer-paced probes only
+            self._pacing.solved(post.last_iters, None, fc, probe)    # this path does not keep the converged residual: timer-paced probes only
             iters.append(post.last_iters)
             posts.append(post)
             if post.last_err:            # out-of-grid flag delivered with the convergence poll (no extra sync)
@@ -1080,7 +1077,10 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         # do not carry it into the next refresh as if it were
         self._mean_state = None if self._use_dense() else {"U": U, "Z": Z, "R": R, "R_ok": converged, "ver": ver}
         self._last_iters = list(iters)
-        self._poll_hint = 0 if ms is not None else 2      # after a cold solve: see _first_poll
+        if ms is not None:
+            self._pacing.warm()
+        else:
+            self._pacing.cold()
         pc = {"pred_mean": U[..., None], "pred_cov": posts[0] if out == 1 else BatchOperator(posts), "cg_iters": iters, "ver": ver}
         self._memo["prediction_cache"] = pc
         return self._with_trend(pc)
@@ -2132,17 +2132,18 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         # bookkeeping of _absorb / prediction_cache
         self._wsum_add(0, q, None)
         self.num_data = self.num_data + q
-        self._refresh_count = getattr(self, "_refresh_count", 0) + 1
-        self._two_level_step(step, pst, X, q)            # (may set the poll hint: before _first_poll)
-        last = (getattr(self, "_last_iters", None) or [0])[0]
+        pacing = self._pacing
+        pacing.count()
+        self._two_level_step(step, pst, X, q)            # (may announce a new block: before the placement)
+        last = (self._last_iters or [0])[0]
         # with a deferred-poll handle the library places the first poll itself, by the hindsight of the solve this call resumes
         # (stencil-sharded replicas keep the host's placement: their ranks must poll in lock step -- and so does a single GPU under
         # settings.two_level_lockstep, which exists to give it the replicas' iteration counts: a poll placed by hindsight reports the
         # masked iteration it costs when the stream gets easier, the host's early polls after a block switch do not)
         auto = (settings.poll_hindsight.on() and (settings.deferred_refresh.on() or step.pending)
                 and self.__dict__.get("_stencil_shard") is None and settings.two_level_lockstep.off())
-        fc, probe = self._first_poll(last, step.pending if auto else None)
-        carry = ms.get("R_ok", False) and self._refresh_count % 16 != 0
+        fc, probe = pacing.place(last, step.pending if auto else None)
+        carry = ms.get("R_ok", False) and not pacing.recompute_due()
         step.args.shift = float(self._wsum[0]) / pst["norm"]
         step.set_keep(self._keep_for_step(step, pst))
         y1 = Y.reshape(-1)
@@ -2158,9 +2159,9 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
                 if prev[2]:                              # the PREVIOUS batch held out-of-grid points: this one was not queued at all
                     self._wsum_host[0] -= float(q)
                     self.num_data = self.num_data - q
-                    self._refresh_count -= 1
-                self._note_solve(ms, prev, *getattr(self, "_pending_fc", (0, False)))
-            self._pending_fc = (fc, probe)
+                    pacing.uncount()
+                self._note_solve(ms, prev, *pacing.queued)
+            pacing.queue(fc, probe)
             if not pending:                              # deferral switched off meanwhile: this call ran to convergence
                 self._note_solve(ms, (step.it.value, step.rr.value, step.herr.value, True), fc, probe)
             return mean
@@ -2243,85 +2244,18 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             sub = max(settings.two_level_subsample.value(), sh["world"]) if sh is not None and sh["world"] > 1 else None
             tl = tr.for_step(self._grid, self._device, pst, 1.0 / s2, float(self._wsum[0]), self._err,
                              lockstep=sh is not None or settings.two_level_lockstep.on(),
-                             last_iters=(getattr(self, "_last_iters", None) or [0])[0], subsample=sub)
+                             last_iters=(self._last_iters or [0])[0], subsample=sub)
             if tr.switched:
-                # a new block: the iteration count of the previous solves says little about the next one -- poll after 2 iterations,
-                # then after every one (the poll placement would otherwise walk down one iteration per probe)
-                self._poll_hint_sticky = 2
+                self._pacing.new_block()
         if getattr(step, "_two_level", None) is not tl:
             step.set_two_level(tl)
-
-    def _first_poll(self, last, auto=None):
-        """Where a warm refresh polls convergence first: (iteration count, is this a probe?).  Streaming steps are alike (at
-        50^3 the uniform bench stream needs 3 iterations for its first ~40 steps and 2 ever after; the clustered one 6, now and
-        then 5), so the first poll goes where the previous refresh converged.  A *probe* polls one iteration earlier to notice
-        that the stream got easier; one that fails costs a stand-alone vector update + poll and a host round trip (~14 us of a
-        ~215 us step), one that is not made when it would have succeeded costs an iteration (41 us) per step.  So: probe
-        every 4th refresh while the last converged residual says one iteration less might do (it is below tol / 10; the
-        contraction per iteration is ~0.08 here: the residual after 3 iterations falls from 8e-5 to 7e-6 before 2 suffice),
-        otherwise after 8, 16, 32 refreshes.  (Probing every other refresh, as before: 50 % failed polls, 0.221 ms per step
-        against 0.216 with this placement, tools/policy_probe.py.)
-        `auto` (not None: the step carries a deferred-poll handle and ``settings.poll_hindsight`` is on; its value says whether a
-        solve is pending): -1, "place it by the hindsight of the previous solve" (include/wiski.h, first_check = -1) wherever the
-        rules above would have answered from the history -- every poll reports where its solve first met the tolerance, so there is
-        nothing to probe for.  Only the explicit hint of the first step after a cold solve stays."""
-        if not last:
-            return 0, False
-        if auto is not None:
-            self._poll_hint_sticky = self._probe_pending = 0
-            hint = getattr(self, "_poll_hint", 0)
-            return (min(last, hint) if hint and not auto else -1), False
-        sticky = getattr(self, "_poll_hint_sticky", 0)
-        if sticky:
-            # a new block of the two-level preconditioner went in: for this step and the next (whose `last` still predates the
-            # switch: deferred refreshes report one step late) poll after 2 iterations, then after every one
-            self._poll_hint_sticky = sticky - 1
-            return min(last, 2), False
-        hint = getattr(self, "_poll_hint", 0)
-        if hint:
-            # the previous solve was a cold one: its count (8 at 50^3) says nothing about a warm, residual-carrying refresh
-            # (3 there).  Poll early and then after every iteration -- a few extra polls instead of walking down from the
-            # cold count one wasted iteration per refresh.
-            return min(last, hint), False
-        pend = getattr(self, "_probe_pending", 0)
-        if pend:
-            # deferred refreshes: the verdict of the probe queued by the previous step is not in yet (and `last` is older
-            # still).  Poll where the probe did: if it fails this costs one more cheap poll, if it succeeds an iteration less.
-            self._probe_pending = 0
-            return pend, False
-        wait = getattr(self, "_probe_wait", 0)
-        rel = getattr(self, "_last_rel", None)
-        tol = settings.cg_tolerance.value() or (1e-7 if self._dtype == torch.float32 else 1e-11)
-        informed = rel is not None and rel < 0.1 * tol
-        if informed:
-            wait = min(wait, 4)
-        probe = wait <= 0 and last > 1
-        self._probe_informed = informed
-        self._probe_wait = wait - 1
-        fc = max(1, last - (1 if probe else 0))
-        if probe:
-            self._probe_pending = fc
-        return fc, probe
-
-    def _note_poll(self, it, fc, probe):
-        if probe:
-            self._probe_pending = 0
-            if it <= fc:
-                self._probe_gap, self._probe_wait = 0, 8        # cut to 4 by _first_poll if the new residual invites it
-            elif getattr(self, "_probe_informed", False):
-                self._probe_wait = 4
-            else:
-                self._probe_gap = min(32, max(8, 2 * getattr(self, "_probe_gap", 0)))
-                self._probe_wait = self._probe_gap
 
     def _note_solve(self, ms, res, fc, probe=False):
         """Host bookkeeping after a refresh: iteration history for the poll placement, residual validity, out-of-grid error."""
         it, rel, flag, conv = res
-        if fc > 0:                                   # (-1: the library placed the poll, nothing to learn here)
-            self._note_poll(it, fc, probe)
+        self._pacing.solved(it, rel, fc, probe)
+        self._pacing.warm()
         self._last_iters = [it]
-        self._last_rel = rel
-        self._poll_hint = 0
         ms["R_ok"] = bool(conv)
         pc = self._memo.get("prediction_cache")
         if pc is not None:
@@ -2332,14 +2266,14 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
 
     def _finish_pending(self):
         """A deferred refresh (settings.deferred_refresh) is still in flight: wait for its poll, finish the solve if needed."""
-        step = self.__dict__.get("_pending_step")
+        step = self._pending_step
         if step is None:
             return
         self._pending_step = None
         if step.pending:
             prev, _ = step(None, None, None, None, None, None, 0, 0, defer=False)
             if prev is not None and self._mean_state is not None:
-                self._note_solve(self._mean_state, prev, *getattr(self, "_pending_fc", (0, False)))
+                self._note_solve(self._mean_state, prev, *self._pacing.queued)
 
     def _stream_fast_state(self, X, Y):
         """(prepared StreamStep, mean state, preconditioner state) when the one-call streaming step applies, else None."""
@@ -2360,10 +2294,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             return None
         if wsum_new > 2.0 * pst["wsum"] and not self._density_profile_still_fits(pst):
             return None                                   # the density profile has moved: generic path (new eigenbasis) this step
-        its = (getattr(self, "_last_iters", None) or [0])[0]
-        if pst.get("it0") is None and its > 0:
-            pst["it0"] = its
-        if pst.get("it0") is not None and its >= pst["it0"] + 2 and wsum_new > 1.1 * pst["wsum"]:
+        if basis_slow(pst, (self._last_iters or [0])[0], wsum_new):
             return None
         tol = _default_tol(self._dtype)
         c = self._kernel_cache
@@ -2372,7 +2303,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         key = (None if sh is None else (sh["rank"], sh["world"]), ver, ms["U"].data_ptr(), ms["Z"].data_ptr(), ms["R"].data_ptr(), op.stencil.data_ptr(), c["interpolation_cache"].data_ptr(),
                c["_cnt"].data_ptr(), c["_stats"].data_ptr(), self._err.data_ptr(), pst["eig"][0].data_ptr(), str(self._device), tol,
                settings.cg_check_every.value(), settings.max_cg_iterations.value())
-        cached = self.__dict__.get("_stream_step_cache")
+        cached = self._stream_step_cache
         if cached is None or cached[0] != key:
             tcol, s2, _ = self._hyper()[0]
             step = grid_ops.StreamStep(self._grid, self._dtype, self._device, op.stencil, c["interpolation_cache"][0, :, 0], c["_cnt"][0],
@@ -2381,8 +2312,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             step.set_solver(1.0 / s2, pst["eig"], 0.0, tol, 1)
             if sh is not None:
                 step.set_shard(sh["rank"], sh["world"], comm=sh.get("comm"), allreduce=sh["allreduce"])
-            cached = (key, step)
-            self.__dict__["_stream_step_cache"] = cached
+            cached = self._stream_step_cache = (key, step)
         return cached[1], ms, pst
 
     def _density_profile_still_fits(self, pst):
@@ -2394,39 +2324,29 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         (settings.precond_profile_drift): the eigenbasis stays, only the scale follows.  False: the profile moved (or there is
         none) -- the caller falls back to the generic path and `_precond` re-solves the eigenbasis."""
         old = pst.get("profiles")
-        cnt = self._kernel_cache.get("_cnt") if settings.density_profile_preconditioner.on() else None
-        if old is None or cnt is None:
+        if old is None or settings.density_profile_preconditioner.off() or self._kernel_cache.get("_cnt") is None:
             return False
-        g = self._grid.g
-        look = self.__dict__.get("_profile_look")
+        look = self._profile_look
         if look is None:
-            c3 = cnt[0].reshape(g).double()
-            margs = [c3.sum(dim=[r for r in range(self._grid.d) if r != q]) if self._grid.d > 1 else c3 for q in range(self._grid.d)]
-            margs = torch.stack([torch.nn.functional.pad(mg, (0, max(g) - mg.numel())) for mg in margs]).clamp_min(0)
-            host = self.__dict__.get("_profile_look_host")            # pinned once (a pinned allocation costs ~0.3 ms)
+            margs = self._cnt_marginals(0)
+            host = self._profile_look_host                            # pinned once (a pinned allocation costs ~0.3 ms)
             if host is None or host.shape != margs.shape:
-                host = torch.empty(margs.shape, dtype=margs.dtype, pin_memory=True)
-                self.__dict__["_profile_look_host"] = host
+                host = self._profile_look_host = torch.empty(margs.shape, dtype=margs.dtype, pin_memory=True)
             host.copy_(margs, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
-            self.__dict__["_profile_look"] = (host, ev, float(self._wsum[0]), margs)
+            self._profile_look = (host, ev, float(self._wsum[0]), margs)
             return True
         host, ev, wsum_then, _ = look
         if self.__dict__.get("_stencil_shard") is not None:
             ev.synchronize()                              # sharded replicas must all read the verdict at the SAME step (control flow
         elif not ev.query():                              # that depends on copy timing would let the ranks' collectives diverge)
             return True                                   # still in flight
-        self.__dict__["_profile_look"] = None
-        margs = host.numpy()
-        if not margs.max() > 0:
+        self._profile_look = None
+        profiles, _ = density_profiles(host.numpy(), self._grid.g, self._grid.m)
+        if profiles is None or profiles_moved(profiles, old):
             return False
-        for q, gq in enumerate(g):
-            t = (margs[q, :gq] / margs[q, :gq].max()).clip(1e-2, None)
-            if float(abs(t - old[q]).max()) > settings.precond_profile_drift.value():
-                return False
-        pst["wsum"] = wsum_then                           # same density shape: keep the eigenbasis, only the scale moves
-        pst["it0"] = None
+        basis_kept(pst, wsum_then)
         return True
 
     def _rank_update_source(self, q):
@@ -2672,8 +2592,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         self.covar_module.set_grid_spec(new)
         self._grid = new
         self._memo = {}                                # Toeplitz columns, preconditioner, prediction cache, root space, ...
-        for name in ("_stream_step_cache", "_two_level", "_profile_look", "_profile_look_host"):
-            self.__dict__.pop(name, None)
+        self._stream_step_cache = self._profile_look = self._profile_look_host = None
+        self.__dict__.pop("_two_level", None)
         self._half_delta = None
         self._pcg_ws = grid_ops.PCGWorkspace()
         self._mean_state = None                        # (Z = Kt^-1 U does not embed: the next solve starts cold)
@@ -2781,7 +2701,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             train_targets = train_targets[:, None]
         noise = self._canon_noise(train_noise_term, train_targets)
         self._finish_pending()                      # a deferred solve must not be resumed on zeroed statistics
-        self.__dict__.pop("_stream_step_cache", None)
+        self._stream_step_cache = None
         cache = self._kernel_cache
         cache["interpolation_cache"].zero_()
         cache["_stats"].zero_()
@@ -2837,7 +2757,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             self._err = grid_ops.new_err_flag(device)
             self._mean_state = None
             self._memo = {}
-            self.__dict__.pop("_stream_step_cache", None)
+            self._stream_step_cache = None
             self._drop_spectral()
         return res
 

@@ -291,7 +291,7 @@ class poll_hindsight(_feature_flag):
     """One-call streaming steps with a deferred-poll handle let the library place the first convergence poll of their solve
     (``first_check = -1``, include/wiski.h): where the previous solve of the stream first met the tolerance, which every poll
     reports beside the residual norms -- no probes one iteration early and no early polls after a new two-level block went in.
-    Off: the host-side placement of ``_first_poll`` (stencil-sharded steps always use it, and so do steps under
+    Off: the host-side placement of ``PollPacing.place`` (stencil-sharded steps always use it, and so do steps under
     ``two_level_lockstep``, whose iteration counts are meant to equal the replicas')."""
 
     _state = True
