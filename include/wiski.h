@@ -546,6 +546,25 @@ int wiski_scatter_stats_interval_f64(const wiski_grid* grid, const double* d_x, 
 int wiski_absorb_interval_f32(const wiski_grid* grid, const wiski_absorb_args* args, const float* d_lo, const float* d_hi, const float* d_pvar, double sigma2, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, void* stream);
 int wiski_absorb_interval_f64(const wiski_grid* grid, const wiski_absorb_args* args, const double* d_lo, const double* d_hi, const double* d_pvar, double sigma2, double* d_ytilde_out, double* d_omega_out, double* d_logz_out, void* stream);
 
+/* Interval observations of the value AND the partial derivatives of a point: the C = d + 1 channels of
+ * wiski_scatter_stats_grad (0: f(x_p), 1 + q: df/dx_q (x_p)), each present one (d_wa[p][c] != 0) an interval
+ *   d_lo[p][c] <= (row_c . u) + eps <= d_hi[p][c]   at noise sigma2 d_noise[p][c]
+ * -- "f increases in x_q" is d_lo = 0 on channel 1 + q, a slope bound is [-L, L].  Every channel is moment-matched as in
+ * wiski_scatter_stats_interval, against its own predictive mean row_c . u and its posterior variance d_pvar[p][c] before the
+ * batch (the channels of a point independently of each other), and all of them enter in the one launch of the derivative
+ * form: one atomic per tap pair.  The skip rules are those of the interval form, per channel; lo == hi is an exact value and
+ * enters with omega = 1 exactly.  All per-point arrays, the three outputs and d_mean_out are [n][d + 1].  A skipped channel
+ * reports (row_c . u, 0, log Z), an absent one and every channel of a point outside the grid (0, 0, 0); such a point is flagged
+ * and counted once.  A derivative channel in a boundary cell of its dim has a zero row: its site is evaluated at mean 0 and
+ * enters the two scalars only.  Required: d_hi, d_pvar, d_u, d_A_half, d_cnt, the three outputs and a finite sigma2 > 0; d_res
+ * and d_mean_out are optional.  Symmetric half stencil, atomic form, one output, d = 1..4; anything else is WISKI_E_BADARG
+ * before a launch.  wiski_absorb_args has NOT grown: wiski_absorb_grad_interval takes the record (its d_y is ignored, its
+ * channels must be d + 1) plus the form's arguments, so that every refused combination can be reached and tested. */
+int wiski_scatter_stats_grad_interval_f32(const wiski_grid* grid, const float* d_x, const float* d_lo, const float* d_hi, const float* d_pvar, double sigma2, const float* d_wa, const float* d_wb, const float* d_noise, int64_t n, float* d_b, float* d_A_half, float* d_cnt, const float* d_u, float* d_res, float* d_mean_out, double* d_stats, int32_t* d_err, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, void* stream);
+int wiski_scatter_stats_grad_interval_f64(const wiski_grid* grid, const double* d_x, const double* d_lo, const double* d_hi, const double* d_pvar, double sigma2, const double* d_wa, const double* d_wb, const double* d_noise, int64_t n, double* d_b, double* d_A_half, double* d_cnt, const double* d_u, double* d_res, double* d_mean_out, double* d_stats, int32_t* d_err, double* d_ytilde_out, double* d_omega_out, double* d_logz_out, void* stream);
+int wiski_absorb_grad_interval_f32(const wiski_grid* grid, const wiski_absorb_args* args, const float* d_lo, const float* d_hi, const float* d_pvar, double sigma2, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, void* stream);
+int wiski_absorb_grad_interval_f64(const wiski_grid* grid, const wiski_absorb_args* args, const double* d_lo, const double* d_hi, const double* d_pvar, double sigma2, double* d_ytilde_out, double* d_omega_out, double* d_logz_out, void* stream);
+
 /* Count observations: point p carries a count d_y_p and a second number d_t_p.  `family`:
  *   WISKI_COUNT_POISSON   y ~ Poisson(t exp f(x)), t > 0 the exposure, y >= 0 (non-integers allowed: the constant is lgamma);
  *   WISKI_COUNT_BINOMIAL  y successes of t trials at success probability 1 / (1 + exp(-f(x))), 0 <= y <= t.

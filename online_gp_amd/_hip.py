@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 _SO = os.path.join(_CSRC, "libwiski_hip.so")
 _SOURCES = ["interp_gather.hip", "scatter_stats.hip", "solve.hip", "spectral.hip", "dense.hip", "collective.hip", "stream_step.hip", "spectral_basis.hip", "hyper_columns.hip", "two_level.hip", "hyper_step.hip", "lookahead.hip", "sample_paths.hip", "decay_stats.hip", "regrid_stats.hip", "trend.hip"]
-_HEADERS = ["wiski_common.h", "spmv_sym_dma.h", "spmv_sym_dma_mc.h", "spmm_sym_cols.h", "spmm_sym_bcast.h", "scatter_half.h", "scatter_owner.h", "scatter_grad.h", "scatter_site.h", "scatter_robust.h", "scatter_window.h", "scatter_interval.h", "scatter_count.h", "scatter_input_noise.h", "absorb.h", "dense_small.h", "dense_coop.h",
+_HEADERS = ["wiski_common.h", "spmv_sym_dma.h", "spmv_sym_dma_mc.h", "spmm_sym_cols.h", "spmm_sym_bcast.h", "scatter_half.h", "scatter_owner.h", "scatter_grad.h", "scatter_site.h", "scatter_robust.h", "scatter_window.h", "scatter_interval.h", "scatter_count.h", "scatter_input_noise.h", "scatter_grad_interval.h", "absorb.h", "dense_small.h", "dense_coop.h",
             os.path.join("..", "..", "include", "wiski.h")]
 MAX_DIM = 4
 
@@ -93,6 +93,18 @@ class wiski_absorb_args(ctypes.Structure):
 class wiski_window_ring(ctypes.Structure):
     """The device-resident ring of a sliding-window absorb (include/wiski.h): five arrays of `cap` slots and the host-kept head."""
     _fields_ = [(k, ctypes.c_void_p) for k in ("d_x", "d_y", "d_wa", "d_wb", "d_noise")] + [("cap", ctypes.c_int64), ("head", ctypes.c_int64)]
+
+
+def _grad_interval_signatures():
+    """argtypes of the four entries of the channel-interval absorb (include/wiski.h), by name: pointers as
+    c_void_p, in the order of the prototypes.  lib() sets them, so that a call with a wrong argument count fails in ctypes."""
+    p, f64, i64 = ctypes.c_void_p, ctypes.c_double, ctypes.c_int64
+    flat = [ctypes.POINTER(wiski_grid)] + [p] * 4 + [f64] + [p] * 3 + [i64] + [p] * 11 + [p]
+    record = [ctypes.POINTER(wiski_grid), ctypes.POINTER(wiski_absorb_args)] + [p] * 3 + [f64] + [p] * 3 + [p]
+    return {name + suf: sig for name, sig in (("wiski_scatter_stats_grad_interval", flat), ("wiski_absorb_grad_interval", record)) for suf in ("_f32", "_f64")}
+
+
+SIGNATURES = _grad_interval_signatures()
 
 
 def sources():
@@ -202,6 +214,9 @@ def lib():
         _lib = ctypes.CDLL(_SO)
         _lib.wiski_pcg_workspace_bytes.restype = ctypes.c_int64
         _lib.wiski_twolevel_refresh_workspace_bytes.restype = ctypes.c_int64
+        for name, sig in SIGNATURES.items():
+            f = getattr(_lib, name)
+            f.argtypes, f.restype = sig, ctypes.c_int
     if hasattr(_lib, "wiski_root_update_workspace_elems"):
         _lib.wiski_root_update_workspace_elems.restype = ctypes.c_int64
     return _lib

@@ -3,9 +3,9 @@
 // may be asked to do, as ONE named record.  Every member defaults to "off"; the extern "C" entry points of scatter_stats.hip
 // and the streaming step (stream_step.hip) fill the fields they expose and call absorb().  Which combinations are refused is
 // absorb_validate() in scatter_stats.hip; whoever writes another form of the absorb has to honour every group below.
-// Four half-stencil kernels stand behind it, besides the full-stencil k_scatter_stats and the owner form (where its workspace is
-// given and applies): the atomic form (k_scatter_stats_sym), the derivative-observation form (`channels`, scatter_grad.h), the
-// sliding-window form (`ring_*`, scatter_window.h) and the site-weighted form (k_scatter_stats_site, scatter_site.h), which is the
+// Five half-stencil kernels stand behind it, besides the full-stencil k_scatter_stats and the owner form (where its workspace is
+// given and applies): the atomic form (k_scatter_stats_sym), the derivative-observation form (`channels`, scatter_grad.h), its
+// interval-site form (`clo`, scatter_grad_interval.h), the sliding-window form (`ring_*`, scatter_window.h) and the site-weighted form (k_scatter_stats_site, scatter_site.h), which is the
 // outlier-robust (`inv_scale`, scatter_robust.h), the interval (`lo`, scatter_interval.h), the count (`count_y`, scatter_count.h) or
 // the noisy-input absorb (`xvar`, scatter_input_noise.h) by the site it is given.  What they do per point -- the tap tables, the per-tap atomics, the pair loop that
 // encodes the row-interleaved layout, the two scalars -- is stated once, in scatter_half.h.
@@ -108,13 +108,23 @@ struct AbsorbArgs {
   const real* xvar = nullptr;       // [n, d] variance of the location error per dim, in the grid's units squared
   const real* gvar = nullptr;       // [n, d] posterior variance of d f / d x_k before the batch, in y^2 per grid unit squared; NULL: 0
   real* grad_out = nullptr;         // [n, d] the slopes g as the wave reduced them (0 for a point outside the grid); optional
+  // channel intervals: clo != NULL, with channels = d + 1, makes every present channel (wa != 0) of every point an interval
+  // observation clo <= v_c . u + eps <= chi at noise sigma2 noise -- bounds on f and on its partial derivatives -- each moment-matched
+  // as in the interval form against mu_c = v_c . u and cpvar, and entered as ytilde_c at noise / omega_c in the one launch of the
+  // derivative form (scatter_grad_interval.h).  A group of its own, not the interval group's fields: besides its three arrays it
+  // uses sigma2 and the outputs ytilde_out / omega_out / logz_out, which are [n][channels] here.  y is ignored.  Needs chi, cpvar, u,
+  // A, cnt, the three outputs and a finite sigma2 > 0; excludes lo / hi / pvar and every other group
+  const real* clo = nullptr;        // [n][channels] lower ends (-inf: none)
+  const real* chi = nullptr;        // [n][channels] upper ends (+inf: none); clo == chi: an exact value
+  const real* cpvar = nullptr;      // [n][channels] posterior variance of each channel before the batch (negative: 0)
 
   bool sharded() const { return g_lo > 0 || g_hi < (1 << 30); }
   bool windowed() const { return ring_x || ring_y || ring_wa || ring_wb || ring_noise || ring_cap || ring_head || void_left; }
   bool counted() const { return count_y || count_t || count_family != 0; }
   bool input_noise() const { return xvar || gvar || grad_out; }
-  // (the fields the matched forms share belong to whichever of the count and input-noise groups is given, else to the interval group)
-  bool interval() const { return lo || hi || (!counted() && !input_noise() && (pvar || sigma2 != 0 || ytilde_out || logz_out)); }
+  // (the fields the matched forms share belong to whichever of the count, input-noise and channel-interval groups is given, else to the interval group)
+  bool grad_interval() const { return clo || chi || cpvar; }
+  bool interval() const { return lo || hi || (!counted() && !input_noise() && !grad_interval() && (pvar || sigma2 != 0 || ytilde_out || logz_out)); }
   bool site_form() const { return inv_scale || interval() || counted() || input_noise(); }   // the forms of k_scatter_stats_site (scatter_site.h)
 };
 

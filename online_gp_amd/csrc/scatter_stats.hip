@@ -180,6 +180,7 @@ __global__ __launch_bounds__(256) void k_scatter_stats_sym(GridDev<real> G, cons
 #include "scatter_interval.h"
 #include "scatter_count.h"
 #include "scatter_input_noise.h"
+#include "scatter_grad_interval.h"
 
 // Unpacks the row-interleaved half stencil into a full offset-major stencil full[o][i] = A[i, i + off(o)]
 // (diagnostics, tests, and models handed a full-stencil cache):
@@ -247,7 +248,16 @@ static int64_t owner_min_points() {
 template <typename real>
 static int absorb_validate(const AbsorbArgs<real>& a, int d) {
   if (a.n == 0) return WISKI_OK;                       // nothing to absorb: not even the pointers are looked at
-  if (!a.x || (!a.y && !a.lo && !a.count_y) || !a.wa || !a.wb || !a.noise || !a.b || !a.stats || !a.err) return WISKI_E_BADARG;   // what every form reads and writes (the interval and count forms have no y)
+  if (!a.x || (!a.y && !a.lo && !a.count_y && !a.clo) || !a.wa || !a.wb || !a.noise || !a.b || !a.stats || !a.err) return WISKI_E_BADARG;   // what every form reads and writes (the interval, count and channel-interval forms have no y)
+  if (a.grad_interval()) {
+    // channel intervals (scatter_grad_interval.h): the derivative form's single-output half-stencil atomic absorb with u, A and cnt, the
+    // whole group, a noise scale and the three outputs -- and nothing of any other group
+    if (a.channels != d + 1 || !a.half || !a.u || !a.A || !a.cnt || !a.clo || !a.chi || !a.cpvar) return WISKI_E_BADARG;
+    if (!a.ytilde_out || !a.omega_out || !a.logz_out || !(a.sigma2 > 0) || !std::isfinite(a.sigma2) || a.nout != 1) return WISKI_E_BADARG;
+    if (a.lo || a.hi || a.pvar || a.counted() || a.input_noise() || a.inv_scale || a.huber_c != (real)0 || a.windowed()) return WISKI_E_BADARG;
+    if (a.guard || a.n1_bytes || a.n2_bytes || a.z1 || a.z2 || a.sharded() || a.bin || a.bin_bytes) return WISKI_E_BADARG;
+    return WISKI_OK;
+  }
   if (a.site_form() || a.windowed()) {
     // The site-weighted forms (scatter_site.h) and the window form (scatter_window.h) are the plain single-output half-stencil
     // atomic absorb with cnt: their sites and sweeps need u; A and cnt are written unconditionally; no channels.  None of them
@@ -373,6 +383,7 @@ int absorb(const wiski_grid* grid, const AbsorbArgs<real>& a, void* stream) {
   int rc = make_grid_dev<real>(grid, &G);
   if (rc == WISKI_OK) rc = absorb_validate(a, G.d);
   if (rc != WISKI_OK || a.n == 0) return rc;
+  if (a.grad_interval()) return launch_grad_site(G, a, (hipStream_t)stream);
   if (a.input_noise()) return launch_site(G, a, SiteInputNoise<real>::of(a, *grid), (hipStream_t)stream);
   if (a.counted()) return launch_site(G, a, SiteCount<real>::of(a), (hipStream_t)stream);
   if (a.interval()) return launch_site(G, a, SiteInterval<real>::of(a), (hipStream_t)stream);
@@ -507,6 +518,23 @@ static int entry_absorb_input_noise(const wiski_grid* g, const wiski_absorb_args
   return p ? entry_input_noise(g, absorb_args<real>(*p), xvar, gvar, pvar, sigma2, omega_out, logz_out, grad_out, s) : WISKI_E_BADARG;
 }
 template <typename real>
+static int entry_grad_interval(const wiski_grid* g, AbsorbArgs<real> a, const real* lo, const real* hi, const real* pvar, double sigma2, real* ytilde_out, real* omega_out, double* logz_out, void* s) {
+  a.y = nullptr;                                       // ignored by the form
+  a.clo = lo; a.chi = hi; a.cpvar = pvar; a.sigma2 = sigma2; a.ytilde_out = ytilde_out; a.omega_out = omega_out; a.logz_out = logz_out;
+  return lo ? absorb(g, a, s) : WISKI_E_BADARG;
+}
+template <typename real>
+static int entry_scatter_grad_interval(const wiski_grid* g, const real* x, const real* lo, const real* hi, const real* pvar, double sigma2, const real* wa, const real* wb, const real* noise, int64_t n, real* b, real* A_half, real* cnt, const real* u, real* res, real* mean_out, double* stats, int32_t* err, real* ytilde_out, real* omega_out, double* logz_out, void* s) {
+  AbsorbArgs<real> a = absorb_args(x, (const real*)nullptr, wa, wb, noise, n, b, A_half, true, stats, err);
+  absorb_carry(a, cnt, u, res, mean_out);
+  a.channels = g ? g->d + 1 : 0;
+  return entry_grad_interval(g, a, lo, hi, pvar, sigma2, ytilde_out, omega_out, logz_out, s);
+}
+template <typename real>
+static int entry_absorb_grad_interval(const wiski_grid* g, const wiski_absorb_args* p, const real* lo, const real* hi, const real* pvar, double sigma2, real* ytilde_out, real* omega_out, double* logz_out, void* s) {
+  return p ? entry_grad_interval(g, absorb_args<real>(*p), lo, hi, pvar, sigma2, ytilde_out, omega_out, logz_out, s) : WISKI_E_BADARG;
+}
+template <typename real>
 static int entry_plain(const wiski_grid* g, const real* x, const real* y, const real* wa, const real* wb, const real* noise, int64_t n, real* b, real* A, bool half, double* stats, int32_t* err, void* s) {
   return absorb(g, absorb_args(x, y, wa, wb, noise, n, b, A, half, stats, err), s);
 }
@@ -562,6 +590,10 @@ int wiski_scatter_stats_input_noise_f32(const wiski_grid* g, const float* x, con
 int wiski_scatter_stats_input_noise_f64(const wiski_grid* g, const double* x, const double* y, const double* xvar, const double* gvar, const double* pvar, double sigma2, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, double* omega_out, double* logz_out, double* grad_out, void* s) { return entry_scatter_input_noise(g, x, y, xvar, gvar, pvar, sigma2, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, omega_out, logz_out, grad_out, s); }
 int wiski_absorb_input_noise_f32(const wiski_grid* g, const wiski_absorb_args* p, const float* xvar, const float* gvar, const float* pvar, double sigma2, float* omega_out, double* logz_out, float* grad_out, void* s) { return entry_absorb_input_noise(g, p, xvar, gvar, pvar, sigma2, omega_out, logz_out, grad_out, s); }
 int wiski_absorb_input_noise_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* xvar, const double* gvar, const double* pvar, double sigma2, double* omega_out, double* logz_out, double* grad_out, void* s) { return entry_absorb_input_noise(g, p, xvar, gvar, pvar, sigma2, omega_out, logz_out, grad_out, s); }
+int wiski_scatter_stats_grad_interval_f32(const wiski_grid* g, const float* x, const float* lo, const float* hi, const float* pvar, double sigma2, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return entry_scatter_grad_interval(g, x, lo, hi, pvar, sigma2, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, ytilde_out, omega_out, logz_out, s); }
+int wiski_scatter_stats_grad_interval_f64(const wiski_grid* g, const double* x, const double* lo, const double* hi, const double* pvar, double sigma2, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return entry_scatter_grad_interval(g, x, lo, hi, pvar, sigma2, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, ytilde_out, omega_out, logz_out, s); }
+int wiski_absorb_grad_interval_f32(const wiski_grid* g, const wiski_absorb_args* p, const float* lo, const float* hi, const float* pvar, double sigma2, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return entry_absorb_grad_interval(g, p, lo, hi, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
+int wiski_absorb_grad_interval_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* lo, const double* hi, const double* pvar, double sigma2, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return entry_absorb_grad_interval(g, p, lo, hi, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
 int wiski_scatter_stats_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A, double* stats, int32_t* err, void* s) { return entry_plain(g, x, y, wa, wb, noise, n, b, A, false, stats, err, s); }
 int wiski_scatter_stats_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A, double* stats, int32_t* err, void* s) { return entry_plain(g, x, y, wa, wb, noise, n, b, A, false, stats, err, s); }
 int wiski_scatter_stats_sym_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, double* stats, int32_t* err, void* s) { return entry_plain(g, x, y, wa, wb, noise, n, b, A_half, true, stats, err, s); }

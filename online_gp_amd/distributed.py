@@ -381,9 +381,14 @@ class ShardedStatsUpdater:
                 self._delta["_cnt"].zero_()
         return self._delta
 
-    def update(self, X, Y, noise=None, *, lower=None, upper=None, counts=None, exposure=None, trials=None, input_var=None):
+    def update(self, X, Y, noise=None, *, lower=None, upper=None, counts=None, exposure=None, trials=None, input_var=None,
+               grad_lower=None, grad_upper=None):
         from . import grid_ops
 
+        if grad_lower is not None or grad_upper is not None:
+            # as for value bounds: the sites of a shard would be matched on one rank, and the other ranks' followers never see them
+            raise NotImplementedError("ShardedStatsUpdater does not carry interval observations of gradients (grad_lower / grad_upper): "
+                                      "condition the model itself")
         if input_var is not None or getattr(self.model, "input_var", None) is not None:
             # the slope moments of a shard would be taken on one rank, and the other ranks' followers never see its weights
             raise NotImplementedError("ShardedStatsUpdater does not carry noisy-input observations (input_var): condition the model itself")

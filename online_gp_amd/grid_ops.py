@@ -490,6 +490,37 @@ def scatter_stats_interval(grid, x, lower, upper, pvar, sigma2, wa, wb, noise, b
     return ytilde, omega, log_z
 
 
+def scatter_stats_grad_interval(grid, x, lower, upper, pvar, sigma2, wa, wb, noise, b, A_half, cnt, stats, err, u, res=None, mean_out=None):
+    """Interval sites on values AND partial derivatives in ONE absorb launch (``wiski_scatter_stats_grad_interval``).
+    lower / upper / pvar / wa / wb / noise (and mean_out) are [n, d + 1] -- column 0 the channel of f, column 1 + q that of df/dx_q;
+    an absent channel has wa = wb = 0, noise = 1.  Every present channel says lower <= (its row . f) + eps <= upper (either end may be
+    infinite; equal ends are an exact value) and is moment-matched, independently of the point's other channels, against the
+    posterior before the batch -- the grid mean ``u`` [m], the posterior variance ``pvar`` of the channel, the noise ``sigma2 *
+    noise`` -- and enters (b, A_half, cnt, stats) -- and the carried residual ``res``, if given -- as the target ytilde at noise /
+    omega.  Returns (ytilde, omega, log_z float64), [n, d + 1] each: a skipped channel has omega = 0 and ytilde = its predictive mean,
+    an absent channel and every channel of a point outside the grid (0, 0, 0).  ``mean_out`` receives the predictive mean and gradient."""
+    op = "scatter_stats_grad_interval"
+    x = _x2d(x, grid)
+    n, C = x.shape[0], grid.d + 1
+    for name, t in (("lower", lower), ("upper", upper), ("pvar", pvar), ("wa", wa), ("wb", wb), ("noise", noise), ("mean_out", mean_out)):
+        if (t is None and name != "mean_out") or (t is not None and (tuple(t.shape) != (n, C) or t.dtype != x.dtype)):
+            raise ValueError(f"{op}: {name} must be [{n}, {C}] {x.dtype}, got {None if t is None else (tuple(t.shape), t.dtype)}")
+    if u is None or tuple(u.shape) != (grid.m,) or u.dtype != x.dtype:
+        raise ValueError(f"{op}: u must be the grid mean [{grid.m}] {x.dtype}")
+    ytilde, omega = torch.empty((n, C), dtype=x.dtype, device=x.device), torch.empty((n, C), dtype=x.dtype, device=x.device)
+    log_z = torch.empty((n, C), dtype=torch.float64, device=x.device)
+    if n == 0:
+        return ytilde, omega, log_z
+    rc = _hip.fn("wiski_scatter_stats_grad_interval", x.dtype)(grid.ref, _hip.dptr(x), _hip.dptr(lower.contiguous()), _hip.dptr(upper.contiguous()),
+                                                               _hip.dptr(pvar.contiguous()), ctypes.c_double(float(sigma2)), _hip.dptr(wa.contiguous()),
+                                                               _hip.dptr(wb.contiguous()), _hip.dptr(noise.contiguous()), ctypes.c_int64(n), _hip.dptr(b),
+                                                               _hip.dptr(A_half), _hip.dptr(cnt), _hip.dptr(u), _hip.dptr(res), _hip.dptr(mean_out),
+                                                               _hip.dptr(stats), _hip.dptr(err), _hip.dptr(ytilde), _hip.dptr(omega), _hip.dptr(log_z),
+                                                               _hip.stream_ptr(x.device))
+    _hip.check(rc, "wiski_scatter_stats_grad_interval")
+    return ytilde, omega, log_z
+
+
 COUNT_FAMILIES = {"poisson": 0, "binomial": 1}      # WISKI_COUNT_POISSON, WISKI_COUNT_BINOMIAL
 
 

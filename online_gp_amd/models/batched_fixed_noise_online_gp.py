@@ -86,6 +86,21 @@ def interval_from_labels(labels):
     return torch.where(pos, zero, zero - float("inf")), torch.where(pos, zero + float("inf"), zero)
 
 
+def monotone_bounds(n, d, dims, sign=+1):
+    """(grad_lower, grad_upper [n, d] float64, grad_mask bool [n, d]) of "f increases (``sign`` < 0: decreases) in the dims ``dims``"
+    (an int or a sequence), for ``condition_on_observations(..., grad_lower=, grad_upper=, grad_mask=)``: the partials of those dims
+    are bounded by 0 from below (above), the other dims are not observed."""
+    dims = [int(dims)] if isinstance(dims, int) else [int(q) for q in dims]
+    if sign == 0 or any(not 0 <= q < d for q in dims):
+        raise ValueError(f"monotone_bounds: dims must lie in 0..{d - 1} and sign must not be 0, got {dims}, {sign}")
+    inf = float("inf")
+    lo, hi = torch.full((n, d), -inf, dtype=torch.float64), torch.full((n, d), inf, dtype=torch.float64)
+    mask = torch.zeros((n, d), dtype=torch.bool)
+    mask[:, dims] = True
+    (lo if sign > 0 else hi)[:, dims] = 0.0
+    return lo, hi, mask
+
+
 class FixedNoiseOnlineSKIGP(torch.nn.Module):
     def __init__(
         self,
@@ -137,6 +152,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         self.last_robust_weights = None              # omega [q] of the last robustly absorbed batch, on the device
         # interval observations (_absorb_interval): (ytilde, omega, log_z) [q] of the last batch given as bounds
         self.last_interval_sites = None
+        # interval observations of gradients (_absorb_grad_interval): (ytilde, omega, log_z) [q, d + 1] of the last such batch
+        self.last_grad_interval_sites = None
         # count observations (_absorb_count): (ytilde, omega, log_z) [q] of the last batch given as counts
         self.last_count_sites = None
         # noisy-input observations (_absorb_input_noise): the variance of the error of the recorded locations -- a scalar
@@ -1463,7 +1480,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
 
     # -------------------------------------------------------------- updates --
     def condition_on_observations(self, X, Y, noise=None, inplace=False, _decay=True, *, grad_Y=None, grad_noise=None, grad_mask=None,
-                                  lower=None, upper=None, counts=None, exposure=None, trials=None, input_var=None):
+                                  lower=None, upper=None, counts=None, exposure=None, trials=None, input_var=None, grad_lower=None, grad_upper=None):
         """a7, :258-285.  inplace: the statistics buffers are updated where they
         live (O(4^{2d}) atomics per point); otherwise they are cloned first and a
         sibling model sharing covar_module / likelihood is returned.  With a ``forgetting_factor`` the statistics -- of the clone,
@@ -1504,20 +1521,33 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         extra output noise ``sum_k input_var_k E[(d_k f)^2]`` under the posterior before the batch (after growing and decaying;
         ``input_noise_slope="mean"``: the squared slope of the posterior mean alone), and the point enters as ``Y_i`` at noise
         ``noise_i / omega_i`` in the same launch; ``last_input_noise_sites`` then holds ``(omega, log_z, grad_mean)``.  A model built
-        with ``input_var`` applies it to every unbatched update that passes none.  Single output, unbatched X."""
+        with ``input_var`` applies it to every unbatched update that passes none.  Single output, unbatched X.
+
+        ``grad_lower`` / ``grad_upper`` -- a scalar, [d] or [n, d]; a missing side is -inf / +inf -- bound the partial derivatives:
+        grad_lower_iq <= d_q f(x_i) + eps_iq <= grad_upper_iq (``_condition_grad_interval``; "increasing in dim q" is
+        ``monotone_bounds``).  ``grad_noise`` and ``grad_mask`` as for ``grad_Y`` (for a sign constraint pass a small ``grad_noise``).
+        The value of a point may be given as ``Y`` (exact), as ``lower`` / ``upper`` (an interval) or not at all.  Every present
+        channel is moment-matched like a bound on a value, against its own mean and variance under ``posterior_jet`` before the
+        batch, and all of them are absorbed in one launch; ``last_grad_interval_sites`` holds ``(ytilde, omega, log_z)``, [n, d + 1]
+        each.  ``num_data`` grows by the channels that entered.  No ``grad_Y`` beside them (an exact partial is equal bounds).  Single
+        output, unbatched X."""
         if input_var is None and self.input_var is not None and X.dim() <= 2 and (Y is None or Y.dim() <= 2):
             input_var = self.input_var
         if input_var is not None:
-            given = dict(grad_Y=grad_Y, grad_noise=grad_noise, grad_mask=grad_mask, lower=lower, upper=upper, counts=counts, exposure=exposure, trials=trials)
+            given = dict(grad_Y=grad_Y, grad_noise=grad_noise, grad_mask=grad_mask, lower=lower, upper=upper, counts=counts, exposure=exposure, trials=trials,
+                         grad_lower=grad_lower, grad_upper=grad_upper)
             return self._condition_input_noise(X, Y, noise, input_var, inplace, _decay, [k for k, v in given.items() if v is not None])
         if counts is not None or exposure is not None or trials is not None:
             if self._trend_deg is not None:
                 self._refuse_trend("count observations (counts)", "a site is matched against the grid mean alone, which under a trend "
                                    "is not the predictive mean")
-            if Y is not None or noise is not None or grad_Y is not None or grad_noise is not None or grad_mask is not None or lower is not None or upper is not None:
+            if (Y is not None or noise is not None or grad_Y is not None or grad_noise is not None or grad_mask is not None or lower is not None
+                    or upper is not None or grad_lower is not None or grad_upper is not None):
                 raise NotImplementedError("a batch of counts is given as counts with exposure or trials alone: no Y, noise, grad_* or lower / upper "
                                           "(a count has no Gaussian noise of its own)")
             return self._condition_count(X, counts, exposure, trials, inplace, _decay)
+        if grad_lower is not None or grad_upper is not None:
+            return self._condition_grad_interval(X, Y, noise, lower, upper, grad_Y, grad_lower, grad_upper, grad_noise, grad_mask, inplace, _decay)
         if self._trend_deg is not None:
             if lower is not None or upper is not None:
                 self._refuse_trend("interval observations (lower / upper)", "a site is matched against the grid mean alone, which under a trend "
@@ -1992,6 +2022,137 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         lo = torch.full((n,), -inf, dtype=torch.float64, device=mean.device) if lower is None else lower.to(mean.device, torch.float64).reshape(-1)
         hi = torch.full((n,), inf, dtype=torch.float64, device=mean.device) if upper is None else upper.to(mean.device, torch.float64).reshape(-1)
         dn = self._sigma2(0) * (1.0 if noise is None else noise.to(mean.device, torch.float64).reshape(-1))
+        s = (var.clamp_min(0.0) + dn).sqrt()
+        a, b = (lo - mean) / s, (hi - mean) / s
+        flip = a + b > 0
+        a, b = torch.where(flip, -b, a), torch.where(flip, -a, b)
+        la, lb = torch.special.log_ndtr(a), torch.special.log_ndtr(b)
+        return lb + torch.log1p(-torch.exp(la - lb))
+
+    # ------------------------------------- interval observations of gradients --
+    def _condition_grad_interval(self, X, Y, noise, lower, upper, grad_Y, grad_lower, grad_upper, grad_noise, grad_mask, inplace, _decay):
+        """condition_on_observations with grad_lower / grad_upper: the batch becomes [n, d + 1] channel tensors of
+        bounds -- column 0 the value (Y: equal bounds; lower / upper; or absent), column 1 + q the partial in dim q -- each with its
+        noise and a presence flag; then grow, decay, moment-match, absorb, as _condition_interval."""
+        if grad_Y is not None:
+            raise NotImplementedError("a partial derivative is given as grad_Y or as bounds grad_lower / grad_upper, not both "
+                                      "(an exact partial is grad_lower == grad_upper)")
+        self._refuse_trend("interval observations of gradients (grad_lower / grad_upper)", "a site is matched against the grid mean alone, "
+                           "which under a trend is not the predictive mean")
+        self._refuse_for_sites(X, "gradient-interval", "grad_lower / grad_upper")
+        if Y is not None and Y.dim() > 2:
+            raise NotImplementedError("batched conditioning (fantasies) takes targets, not grad_lower / grad_upper")
+        if Y is not None and (lower is not None or upper is not None):
+            raise NotImplementedError("a batch is given as targets Y or as bounds lower / upper, not both (an exact value is lower == upper)")
+        if "path_probes" in self._kernel_cache:
+            raise NotImplementedError("a model with path probes cannot absorb derivative observations (its probes follow value rows only)")
+        d, dev, dt = self._grid.d, self._device, self._dtype
+        X = X.reshape(-1, d).to(dev, dt).contiguous()
+        n = X.shape[0]
+        inf = float("inf")
+
+        def per_point(t, name, fill):
+            if t is None:
+                return torch.full((n,), fill, dtype=dt, device=dev)
+            t = torch.as_tensor(t).detach().to(dev, dt).reshape(-1)
+            if t.shape[0] != n:
+                raise ValueError(f"{name} must hold one value per point ([{n}]), got {tuple(t.shape)}")
+            return t
+
+        def per_partial(t, name, fill):
+            if t is None:
+                return torch.full((n, d), fill, dtype=dt, device=dev)
+            t = torch.as_tensor(t).detach().to(dev, dt)
+            if tuple(t.shape) not in ((), (d,), (n, d)):
+                raise ValueError(f"{name} must be a scalar, [{d}] or [{n}, {d}], got {tuple(t.shape)}")
+            return t.expand(n, d)
+
+        lo = torch.empty((n, d + 1), dtype=dt, device=dev)
+        hi = torch.empty((n, d + 1), dtype=dt, device=dev)
+        Nc = torch.ones((n, d + 1), dtype=dt, device=dev)
+        present = torch.ones((n, d + 1), dtype=torch.bool, device=dev)
+        lo[:, 1:], hi[:, 1:] = per_partial(grad_lower, "grad_lower", -inf), per_partial(grad_upper, "grad_upper", inf)
+        if Y is not None:
+            lo[:, 0] = hi[:, 0] = per_point(Y, "Y", 0.0)
+        elif lower is not None or upper is not None:
+            lo[:, 0], hi[:, 0] = per_point(lower, "lower", -inf), per_point(upper, "upper", inf)
+        else:
+            lo[:, 0], hi[:, 0] = -inf, inf
+            present[:, 0] = False
+        if noise is not None:
+            Nc[:, 0] = per_point(noise, "noise", 1.0)
+        if grad_noise is None:
+            Nc[:, 1:] = Nc[:, :1]                        # the value observation's noise (unit noise without one)
+        else:
+            gn = torch.as_tensor(grad_noise).detach().to(dev, dt)
+            if tuple(gn.shape) not in ((), (n,), (n, d)):
+                raise ValueError(f"grad_noise must be a scalar, [{n}] or [{n}, {d}], got {tuple(gn.shape)}")
+            Nc[:, 1:] = gn[:, None] if gn.dim() == 1 else gn
+        if grad_mask is not None:
+            if tuple(grad_mask.shape) != (n, d):
+                raise ValueError(f"grad_mask must be [{n}, {d}], got {tuple(grad_mask.shape)}")
+            present[:, 1:] = grad_mask.to(dev, torch.bool)
+        if self.grow_grid:
+            self.grow_to_cover_(X)
+        return self._condition(lambda model, cache, src: model._absorb_grad_interval(cache, X, lo, hi, Nc, present, src), inplace, self._gamma(_decay),
+                               reads_posterior=True)
+
+    def _absorb_grad_interval(self, cache, X, lo, hi, noise, present, src):
+        """_absorb for [n, d + 1] channel tensors of bounds (lo, hi, noises, bool present), one launch
+        (wiski_scatter_stats_grad_interval).  `src`: the model whose posterior the sites are matched against, as in _absorb_matched:
+        its grid mean from the prediction cache, and the variances of f and of its partial derivatives at X from the diagonal of ONE
+        posterior_jet covariance.  The followers are those of _absorb_grad: what a derivative row cannot be followed through is
+        given up.  Returns what num_data grows by: the channels that entered, and the present channels of points outside the grid
+        (which _raise_out_of_bounds takes off again when the flag is read)."""
+        op = self._native_half_op(cache, "interval observations of gradients")
+        if "path_probes" in cache:
+            raise NotImplementedError("interval observations of gradients: no path probes (they follow value rows only)")
+        u = src.prediction_cache["pred_mean"][0, :, 0]       # (finishes whatever is pending, leaves a stencil shard)
+        pvar = torch.diagonal(src.posterior_jet(X).covariance, dim1=-2, dim2=-1).to(self._dtype).contiguous()
+        mine = self._before_launch(cache)
+        zero, one = torch.zeros((), dtype=self._dtype, device=self._device), torch.ones((), dtype=self._dtype, device=self._device)
+        wb = torch.where(present, 1.0 / noise, zero)
+        wa = torch.where(present, self._weight_a(noise, False), zero)
+        no = torch.where(present, noise, one)            # an absent channel: wa = wb = 0, noise = 1 -- nothing anywhere
+        ms = self._carried(mine, u=u)
+        sites = grid_ops.scatter_stats_grad_interval(self._grid, X, torch.where(present, lo, zero), torch.where(present, hi, zero), pvar, self._sigma2(0),
+                                                     wa, wb, no, cache["interpolation_cache"][0, :, 0], op.stencil, cache["_cnt"][0], cache["_stats"][0],
+                                                     self._err, u, res=ms["R"][0] if ms else None)
+        self.last_grad_interval_sites = sites
+        if X.shape[0] == 0:
+            return 0
+        self._give_up(cache)                             # L L^T described the matrix without these rows
+        if mine:
+            # the noise-weight sum (preconditioner shift only) is the mass of cnt, to which a derivative channel adds its diagonal
+            self._wsum_dev = cache["_cnt"].sum(dim=1, dtype=torch.float64)
+            self._wsum_host = [0.0] * self.num_outputs
+            self._wsum_dirty = True
+        # a point is outside the grid where the kernel says so: x < g0 or x > g0 + h (g - 1), in the working precision
+        g = self._grid
+        g0 = torch.tensor(g.g0, dtype=self._dtype)
+        top = (g0 + torch.tensor(g.h, dtype=self._dtype) * torch.tensor([gi - 1 for gi in g.g], dtype=self._dtype)).to(self._device)
+        outside = ~((X >= g0.to(self._device)) & (X <= top)).all(1)
+        return int(((sites[1] > 0).sum() + (present & outside[:, None]).sum()).item())
+
+    def gradient_interval_probability(self, X, lower, upper, noise=None):
+        """log P(lower_iq <= d_q f(x_i) + eps_iq <= upper_iq) [n, d] (float64) under the current posterior, eps_iq ~ N(0, sigma2
+        noise_iq) (``noise`` None: unit noise; a scalar, [n] or [n, d]); either bound may be None, a scalar, [d] or [n, d], or
+        infinite.  Plain torch on the gradient moments of ``posterior_jet``: the Gaussian mass of the interval through
+        ``torch.special.log_ndtr``, mirrored so that the difference is taken in the lower tail, as in ``interval_probability``."""
+        jet = self.posterior_jet(X)
+        mean = jet.mean[:, 1:].double()
+        var = torch.diagonal(jet.covariance, dim1=-2, dim2=-1)[:, 1:].double()
+        n, d = mean.shape
+        inf = float("inf")
+
+        def bound(t, fill):
+            t = torch.full((), fill, dtype=torch.float64) if t is None else torch.as_tensor(t).detach()
+            return t.to(mean.device, torch.float64).expand(n, d)
+
+        lo, hi = bound(lower, -inf), bound(upper, inf)
+        nz = torch.ones((), dtype=torch.float64) if noise is None else torch.as_tensor(noise).detach()
+        nz = nz.to(mean.device, torch.float64)
+        dn = self._sigma2(0) * (nz[:, None] if nz.dim() == 1 else nz)
         s = (var.clamp_min(0.0) + dn).sqrt()
         a, b = (lo - mean) / s, (hi - mean) / s
         flip = a + b > 0
