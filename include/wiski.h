@@ -592,6 +592,40 @@ int wiski_absorb_count_f64(const wiski_grid* grid, const wiski_absorb_args* args
 int wiski_count_sites_f32(const float* d_mu, const float* d_pvar, const float* d_y, const float* d_t, int family, int64_t n, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, void* stream);
 int wiski_count_sites_f64(const double* d_mu, const double* d_pvar, const double* d_y, const double* d_t, int family, int64_t n, double* d_ytilde_out, double* d_omega_out, double* d_logz_out, void* stream);
 
+/* Categorical observations: point p carries a label d_labels_p in {0 .. C - 1}, C = nout outputs.  The likelihood is
+ * the multinomial probit, y = argmax_c (f_c(x) + eps_c), eps_c ~ N(0, s_c), s_c = sigma2[c] noise_c,p.  Every point is moment-matched
+ * against the posterior BEFORE the batch, inside the launch that absorbs it: with mu_c = w_p . u_c (u is [C][m]), v_c = max(d_pvar[c][p], 0),
+ * a_c = v_c + s_c, z_c(t) = (t - mu_c) / sqrt a_c, r = phi / Phi and E[.] the expectation under the normalised integrand of
+ *   Z = P(y) = int N(t; mu_y, a_y) prod_{c != y} Phi(z_c(t)) dt,
+ *   c = y:   alpha = (E t - mu_y) / a_y,          beta = 1 / a_y - Var t / a_y^2,
+ *   c != y:  alpha = -E r(z_c) / sqrt a_c,        beta = (E[r (r + z_c)] - Var r) / a_c,
+ *   tau_c = beta_c / (1 - v_c beta_c),   ytilde_c = mu_c + alpha_c / beta_c,   omega_c = s_c tau_c,
+ * evaluated in double in both precisions by the quadrature of the count form (its nodes are the 64 lanes of the point's wave), and
+ * output c takes the point as the target ytilde_c at noise noise_c,p / omega_c.  This is the one form that couples outputs: a kernel
+ * of its own, one wave per point, which builds the point's stencil once, reduces the C means, and runs the atomics of every output
+ * whose site enters into d_b / d_cnt / d_res at + c m, d_A_half + c A_stride, d_stats + 2 c; d_wa / d_wb / d_noise of output c are at
+ * + c w_stride (0: shared by all outputs).  A site is SKIPPED for its output only when beta_c is not positive and finite or
+ * omega_c < 1e-12 (WISKI_COUNT_OMEGA_MIN: a class far below the label's says nothing).  A label that is not an integer in [0, C),
+ * or NaN, skips the point for every output (log Z = NaN, no flag in d_err).  A point outside the grid is dropped for every output,
+ * counted once, and reports zeros.  d_ytilde_out / d_omega_out / d_pvar and the optional d_mean_out are [C][n] (a skipped site
+ * reports ytilde = mu_c, omega = 0), d_logz_out [n] is log P(y_p); sigma2 [C] is a HOST array, every entry positive and finite.
+ * d_u, d_A_half and d_cnt are required, d_res and d_mean_out optional.  2 <= nout <= WISKI_LABEL_MAX_CLASSES, d = 1..4, symmetric
+ * half stencil, atomic form.  wiski_absorb_label takes the record (its d_y is ignored; nout, w_stride and A_stride are the record's)
+ * plus the label arguments, so that every refused combination (a guard, zero regions, a shard, an owner workspace, channels, a
+ * full stencil) can be reached and tested; wiski_absorb_args has NOT grown.  Everything refused returns WISKI_E_BADARG before a launch.
+ * wiski_label_sites evaluates the sites alone, one wave per point and no scatter, from given means d_mu, latent variances d_pvar and
+ * noise variances d_s, all [C][n]: d_omega_out receives tau.  wiski_label_proba writes P(y = k) for every k into d_proba_out [n][C]
+ * (double): the same integral without its derivatives, once per class; the row is NOT normalised (its sum is 1 to quadrature error). */
+#define WISKI_LABEL_MAX_CLASSES 16
+int wiski_scatter_stats_label_f32(const wiski_grid* grid, const float* d_x, const float* d_labels, const float* d_pvar, const double* sigma2, const float* d_wa, const float* d_wb, const float* d_noise, int64_t n, int32_t nout, int64_t w_stride, float* d_b, float* d_A_half, int64_t A_stride, float* d_cnt, const float* d_u, float* d_res, float* d_mean_out, double* d_stats, int32_t* d_err, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, void* stream);
+int wiski_scatter_stats_label_f64(const wiski_grid* grid, const double* d_x, const double* d_labels, const double* d_pvar, const double* sigma2, const double* d_wa, const double* d_wb, const double* d_noise, int64_t n, int32_t nout, int64_t w_stride, double* d_b, double* d_A_half, int64_t A_stride, double* d_cnt, const double* d_u, double* d_res, double* d_mean_out, double* d_stats, int32_t* d_err, double* d_ytilde_out, double* d_omega_out, double* d_logz_out, void* stream);
+int wiski_absorb_label_f32(const wiski_grid* grid, const wiski_absorb_args* args, const float* d_labels, const float* d_pvar, const double* sigma2, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, void* stream);
+int wiski_absorb_label_f64(const wiski_grid* grid, const wiski_absorb_args* args, const double* d_labels, const double* d_pvar, const double* sigma2, double* d_ytilde_out, double* d_omega_out, double* d_logz_out, void* stream);
+int wiski_label_sites_f32(const float* d_mu, const float* d_pvar, const float* d_s, const float* d_labels, int32_t nout, int64_t n, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, void* stream);
+int wiski_label_sites_f64(const double* d_mu, const double* d_pvar, const double* d_s, const double* d_labels, int32_t nout, int64_t n, double* d_ytilde_out, double* d_omega_out, double* d_logz_out, void* stream);
+int wiski_label_proba_f32(const float* d_mu, const float* d_pvar, const float* d_s, int32_t nout, int64_t n, double* d_proba_out, void* stream);
+int wiski_label_proba_f64(const double* d_mu, const double* d_pvar, const double* d_s, int32_t nout, int64_t n, double* d_proba_out, void* stream);
+
 /* Noisy-input observations: point p was taken at x_p + e_p, e_p ~ N(0, diag(d_xvar_p)), d_xvar [n, d] in the grid's units squared
  * (DESIGN.md 3.24).  To first order the location error is extra output noise grad f^T diag(xvar) grad f, with the slope taken under
  * the posterior BEFORE the batch, inside the launch that absorbs it.  With mu = w_p . u, g_k = (d w_p / d x_k) . u (zero in a

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 _SO = os.path.join(_CSRC, "libwiski_hip.so")
 _SOURCES = ["interp_gather.hip", "scatter_stats.hip", "solve.hip", "spectral.hip", "dense.hip", "collective.hip", "stream_step.hip", "spectral_basis.hip", "hyper_columns.hip", "two_level.hip", "hyper_step.hip", "lookahead.hip", "sample_paths.hip", "decay_stats.hip", "regrid_stats.hip", "trend.hip"]
-_HEADERS = ["wiski_common.h", "spmv_sym_dma.h", "spmv_sym_dma_mc.h", "spmm_sym_cols.h", "spmm_sym_bcast.h", "scatter_half.h", "scatter_owner.h", "scatter_grad.h", "scatter_site.h", "scatter_robust.h", "scatter_window.h", "scatter_interval.h", "scatter_count.h", "scatter_input_noise.h", "scatter_grad_interval.h", "absorb.h", "dense_small.h", "dense_coop.h",
+_HEADERS = ["wiski_common.h", "spmv_sym_dma.h", "spmv_sym_dma_mc.h", "spmm_sym_cols.h", "spmm_sym_bcast.h", "scatter_half.h", "scatter_owner.h", "scatter_grad.h", "scatter_site.h", "scatter_robust.h", "scatter_window.h", "scatter_interval.h", "scatter_count.h", "scatter_label.h", "scatter_input_noise.h", "scatter_grad_interval.h", "absorb.h", "dense_small.h", "dense_coop.h",
             os.path.join("..", "..", "include", "wiski.h")]
 MAX_DIM = 4
 
@@ -104,7 +104,20 @@ def _grad_interval_signatures():
     return {name + suf: sig for name, sig in (("wiski_scatter_stats_grad_interval", flat), ("wiski_absorb_grad_interval", record)) for suf in ("_f32", "_f64")}
 
 
+def _label_signatures():
+    """argtypes of the entries of the categorical-observation absorb (include/wiski.h), as _grad_interval_signatures."""
+    p, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
+    sig2 = ctypes.POINTER(ctypes.c_double)
+    flat = [ctypes.POINTER(wiski_grid)] + [p] * 3 + [sig2] + [p] * 3 + [i64, i32, i64] + [p] * 2 + [i64] + [p] * 9 + [p]
+    record = [ctypes.POINTER(wiski_grid), ctypes.POINTER(wiski_absorb_args)] + [p] * 2 + [sig2] + [p] * 3 + [p]
+    sites = [p] * 4 + [i32, i64] + [p] * 3 + [p]
+    proba = [p] * 3 + [i32, i64] + [p] + [p]
+    return {name + suf: sig for name, sig in (("wiski_scatter_stats_label", flat), ("wiski_absorb_label", record), ("wiski_label_sites", sites),
+                                              ("wiski_label_proba", proba)) for suf in ("_f32", "_f64")}
+
+
 SIGNATURES = _grad_interval_signatures()
+LABEL_SIGNATURES = _label_signatures()
 
 
 def sources():
@@ -214,7 +227,7 @@ def lib():
         _lib = ctypes.CDLL(_SO)
         _lib.wiski_pcg_workspace_bytes.restype = ctypes.c_int64
         _lib.wiski_twolevel_refresh_workspace_bytes.restype = ctypes.c_int64
-        for name, sig in SIGNATURES.items():
+        for name, sig in {**SIGNATURES, **LABEL_SIGNATURES}.items():
             f = getattr(_lib, name)
             f.argtypes, f.restype = sig, ctypes.c_int
     if hasattr(_lib, "wiski_root_update_workspace_elems"):

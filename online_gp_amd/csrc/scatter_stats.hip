@@ -179,6 +179,7 @@ __global__ __launch_bounds__(256) void k_scatter_stats_sym(GridDev<real> G, cons
 #include "scatter_window.h"
 #include "scatter_interval.h"
 #include "scatter_count.h"
+#include "scatter_label.h"
 #include "scatter_input_noise.h"
 #include "scatter_grad_interval.h"
 
@@ -503,6 +504,17 @@ static int entry_absorb_count(const wiski_grid* g, const wiski_absorb_args* p, c
   return p ? entry_count(g, absorb_args<real>(*p), cy, ct, family, pvar, sigma2, ytilde_out, omega_out, logz_out, s) : WISKI_E_BADARG;
 }
 template <typename real>
+static int entry_scatter_label(const wiski_grid* g, const real* x, const real* labels, const real* pvar, const double* sigma2, const real* wa, const real* wb, const real* noise, int64_t n, int32_t nout, int64_t w_stride, real* b, real* A_half, int64_t A_stride, real* cnt, const real* u, real* res, real* mean_out, double* stats, int32_t* err, real* ytilde_out, real* omega_out, double* logz_out, void* s) {
+  AbsorbArgs<real> a = absorb_args(x, (const real*)nullptr, wa, wb, noise, n, b, A_half, true, stats, err);
+  absorb_carry(a, cnt, u, res, mean_out);
+  a.nout = nout; a.bt.w_stride = w_stride; a.bt.A_stride = A_stride;
+  return label_absorb(g, a, labels, pvar, sigma2, ytilde_out, omega_out, logz_out, s);
+}
+template <typename real>
+static int entry_absorb_label(const wiski_grid* g, const wiski_absorb_args* p, const real* labels, const real* pvar, const double* sigma2, real* ytilde_out, real* omega_out, double* logz_out, void* s) {
+  return p ? label_absorb(g, absorb_args<real>(*p), labels, pvar, sigma2, ytilde_out, omega_out, logz_out, s) : WISKI_E_BADARG;
+}
+template <typename real>
 static int entry_input_noise(const wiski_grid* g, AbsorbArgs<real> a, const real* xvar, const real* gvar, const real* pvar, double sigma2, real* omega_out, double* logz_out, real* grad_out, void* s) {
   a.xvar = xvar; a.gvar = gvar; a.grad_out = grad_out; a.pvar = pvar; a.sigma2 = sigma2; a.omega_out = omega_out; a.logz_out = logz_out;
   return xvar ? absorb(g, a, s) : WISKI_E_BADARG;
@@ -586,6 +598,14 @@ int wiski_absorb_count_f32(const wiski_grid* g, const wiski_absorb_args* p, cons
 int wiski_absorb_count_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* y, const double* t, int family, const double* pvar, double sigma2, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return entry_absorb_count(g, p, y, t, family, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
 int wiski_count_sites_f32(const float* mu, const float* pvar, const float* y, const float* t, int family, int64_t n, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return count_sites_impl(mu, pvar, y, t, family, n, ytilde_out, omega_out, logz_out, s); }
 int wiski_count_sites_f64(const double* mu, const double* pvar, const double* y, const double* t, int family, int64_t n, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return count_sites_impl(mu, pvar, y, t, family, n, ytilde_out, omega_out, logz_out, s); }
+int wiski_scatter_stats_label_f32(const wiski_grid* g, const float* x, const float* labels, const float* pvar, const double* sigma2, const float* wa, const float* wb, const float* noise, int64_t n, int32_t nout, int64_t w_stride, float* b, float* A_half, int64_t A_stride, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return entry_scatter_label(g, x, labels, pvar, sigma2, wa, wb, noise, n, nout, w_stride, b, A_half, A_stride, cnt, u, res, mean_out, stats, err, ytilde_out, omega_out, logz_out, s); }
+int wiski_scatter_stats_label_f64(const wiski_grid* g, const double* x, const double* labels, const double* pvar, const double* sigma2, const double* wa, const double* wb, const double* noise, int64_t n, int32_t nout, int64_t w_stride, double* b, double* A_half, int64_t A_stride, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return entry_scatter_label(g, x, labels, pvar, sigma2, wa, wb, noise, n, nout, w_stride, b, A_half, A_stride, cnt, u, res, mean_out, stats, err, ytilde_out, omega_out, logz_out, s); }
+int wiski_absorb_label_f32(const wiski_grid* g, const wiski_absorb_args* p, const float* labels, const float* pvar, const double* sigma2, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return entry_absorb_label(g, p, labels, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
+int wiski_absorb_label_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* labels, const double* pvar, const double* sigma2, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return entry_absorb_label(g, p, labels, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
+int wiski_label_sites_f32(const float* mu, const float* pvar, const float* s_var, const float* labels, int32_t nout, int64_t n, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return label_sites_impl(mu, pvar, s_var, labels, nout, n, ytilde_out, omega_out, logz_out, s); }
+int wiski_label_sites_f64(const double* mu, const double* pvar, const double* s_var, const double* labels, int32_t nout, int64_t n, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return label_sites_impl(mu, pvar, s_var, labels, nout, n, ytilde_out, omega_out, logz_out, s); }
+int wiski_label_proba_f32(const float* mu, const float* pvar, const float* s_var, int32_t nout, int64_t n, double* proba_out, void* s) { return label_proba_impl(mu, pvar, s_var, nout, n, proba_out, s); }
+int wiski_label_proba_f64(const double* mu, const double* pvar, const double* s_var, int32_t nout, int64_t n, double* proba_out, void* s) { return label_proba_impl(mu, pvar, s_var, nout, n, proba_out, s); }
 int wiski_scatter_stats_input_noise_f32(const wiski_grid* g, const float* x, const float* y, const float* xvar, const float* gvar, const float* pvar, double sigma2, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, float* omega_out, double* logz_out, float* grad_out, void* s) { return entry_scatter_input_noise(g, x, y, xvar, gvar, pvar, sigma2, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, omega_out, logz_out, grad_out, s); }
 int wiski_scatter_stats_input_noise_f64(const wiski_grid* g, const double* x, const double* y, const double* xvar, const double* gvar, const double* pvar, double sigma2, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, double* omega_out, double* logz_out, double* grad_out, void* s) { return entry_scatter_input_noise(g, x, y, xvar, gvar, pvar, sigma2, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, omega_out, logz_out, grad_out, s); }
 int wiski_absorb_input_noise_f32(const wiski_grid* g, const wiski_absorb_args* p, const float* xvar, const float* gvar, const float* pvar, double sigma2, float* omega_out, double* logz_out, float* grad_out, void* s) { return entry_absorb_input_noise(g, p, xvar, gvar, pvar, sigma2, omega_out, logz_out, grad_out, s); }

@@ -600,6 +600,97 @@ def count_sites(mean, pvar, counts, t, family):
     return ytilde, tau, log_z
 
 
+LABEL_MAX_CLASSES = 16                              # WISKI_LABEL_MAX_CLASSES
+
+
+def _label_classes(op, C):
+    if not 2 <= C <= LABEL_MAX_CLASSES:
+        raise ValueError(f"{op}: 2 .. {LABEL_MAX_CLASSES} classes, got {C}")
+
+
+def scatter_stats_label(grid, x, labels, pvar, sigma2, wa, wb, noise, b, A_pack, cnt, stats, err, u, res=None, mean_out=None):
+    """The categorical-observation absorb in ONE launch (``wiski_scatter_stats_label``): point i carries the label
+    ``labels_i`` in {0 .. C - 1} (in x's dtype) over the C outputs of b / cnt / u / res [C, m], A_pack [C, H, m] and stats [C, 2].  The
+    multinomial probit likelihood is moment-matched against the posterior before the batch -- the grid means ``u``, the posterior
+    variances ``pvar`` [C, n], the noise variances ``sigma2[c] * noise`` -- by a quadrature over the lanes of the point's wave, and
+    output c takes the point as ytilde_c at noise / omega_c.  wa / wb / noise are [C, n] or [n] (shared by the outputs); ``sigma2``
+    is a sequence of C positive floats.  Returns (ytilde [C, n], omega [C, n], log_z [n] float64): a skipped site has omega = 0 and
+    ytilde = its predictive mean, a point with an invalid label log_z = NaN and no site, a point outside the grid zeros.
+    ``mean_out`` [C, n] receives the predictive means."""
+    op = "scatter_stats_label"
+    x = _x2d(x, grid)
+    n = x.shape[0]
+    if u is None or u.dim() != 2 or u.shape[1] != grid.m or u.dtype != x.dtype:
+        raise ValueError(f"{op}: u must be the grid means [C, {grid.m}] {x.dtype}")
+    C = u.shape[0]
+    _label_classes(op, C)
+    shared = wa.dim() == 1
+    for name, t, shape in (("labels", labels, (n,)), ("pvar", pvar, (C, n)), ("mean_out", mean_out, (C, n)), ("wa", wa, (n,) if shared else (C, n)),
+                           ("wb", wb, (n,) if shared else (C, n)), ("noise", noise, (n,) if shared else (C, n)), ("b", b, (C, grid.m)),
+                           ("cnt", cnt, (C, grid.m)), ("res", res, (C, grid.m))):
+        if (t is None and name not in ("mean_out", "res")) or (t is not None and (tuple(t.shape) != shape or t.dtype != x.dtype)):
+            raise ValueError(f"{op}: {name} must be {list(shape)} {x.dtype}, got {None if t is None else (tuple(t.shape), t.dtype)}")
+    if A_pack.dim() != 3 or A_pack.shape[0] != C or A_pack.dtype != x.dtype or tuple(stats.shape) != (C, 2) or stats.dtype != torch.float64:
+        raise ValueError(f"{op}: A_pack must be [C, H, m] {x.dtype} half stencils and stats [C, 2] float64")
+    sigma2 = [float(v) for v in sigma2]
+    if len(sigma2) != C:
+        raise ValueError(f"{op}: sigma2 must hold {C} values, got {len(sigma2)}")
+    ytilde, omega = torch.empty((C, n), dtype=x.dtype, device=x.device), torch.empty((C, n), dtype=x.dtype, device=x.device)
+    log_z = torch.empty(n, dtype=torch.float64, device=x.device)
+    if n == 0:
+        return ytilde, omega, log_z
+    rc = _hip.fn("wiski_scatter_stats_label", x.dtype)(grid.ref, _hip.dptr(x), _hip.dptr(labels.contiguous()), _hip.dptr(pvar.contiguous()),
+                                                       (ctypes.c_double * C)(*sigma2), _hip.dptr(wa.contiguous()), _hip.dptr(wb.contiguous()),
+                                                       _hip.dptr(noise.contiguous()), n, C, 0 if shared else n, _hip.dptr(b), _hip.dptr(A_pack),
+                                                       A_pack.shape[1] * A_pack.shape[2], _hip.dptr(cnt), _hip.dptr(u), _hip.dptr(res), _hip.dptr(mean_out),
+                                                       _hip.dptr(stats), _hip.dptr(err), _hip.dptr(ytilde), _hip.dptr(omega), _hip.dptr(log_z),
+                                                       _hip.stream_ptr(x.device))
+    _hip.check(rc, "wiski_scatter_stats_label")
+    return ytilde, omega, log_z
+
+
+def _label_inputs(op, mean, pvar, s):
+    if mean.dim() != 2:
+        raise ValueError(f"{op}: mean must be [C, n], got {tuple(mean.shape)}")
+    C, n = mean.shape
+    _label_classes(op, C)
+    for name, v in (("pvar", pvar), ("s", s)):
+        if tuple(v.shape) != (C, n) or v.dtype != mean.dtype:
+            raise ValueError(f"{op}: {name} must be [{C}, {n}] {mean.dtype}, got {tuple(v.shape)} {v.dtype}")
+    return C, n
+
+
+def label_sites(mean, pvar, s, labels):
+    """The sites of labels alone (``wiski_label_sites``: the device function of ``scatter_stats_label``, one wave per point, no
+    scatter) against given class means, latent variances and noise variances [C, n]: (ytilde [C, n], tau [C, n], log_z [n] float64),
+    tau the site precisions (the omega of ``scatter_stats_label`` divided by s)."""
+    C, n = _label_inputs("label_sites", mean, pvar, s)
+    if tuple(labels.shape) != (n,) or labels.dtype != mean.dtype:
+        raise ValueError(f"label_sites: labels must be [{n}] {mean.dtype}, got {tuple(labels.shape)} {labels.dtype}")
+    ytilde, tau = torch.empty_like(mean, memory_format=torch.contiguous_format), torch.empty_like(mean, memory_format=torch.contiguous_format)
+    log_z = torch.empty(n, dtype=torch.float64, device=mean.device)
+    if n == 0:
+        return ytilde, tau, log_z
+    rc = _hip.fn("wiski_label_sites", mean.dtype)(_hip.dptr(mean.contiguous()), _hip.dptr(pvar.contiguous()), _hip.dptr(s.contiguous()),
+                                                  _hip.dptr(labels.contiguous()), C, n, _hip.dptr(ytilde), _hip.dptr(tau), _hip.dptr(log_z),
+                                                  _hip.stream_ptr(mean.device))
+    _hip.check(rc, "wiski_label_sites")
+    return ytilde, tau, log_z
+
+
+def label_proba(mean, pvar, s):
+    """P(y = k) for every class k (``wiski_label_proba``) from class means, latent variances and noise variances [C, n]: [n, C]
+    float64, each entry by its own integral -- the rows sum to 1 to quadrature error and are not normalised."""
+    C, n = _label_inputs("label_proba", mean, pvar, s)
+    out = torch.empty((n, C), dtype=torch.float64, device=mean.device)
+    if n == 0:
+        return out
+    rc = _hip.fn("wiski_label_proba", mean.dtype)(_hip.dptr(mean.contiguous()), _hip.dptr(pvar.contiguous()), _hip.dptr(s.contiguous()), C, n,
+                                                  _hip.dptr(out), _hip.stream_ptr(mean.device))
+    _hip.check(rc, "wiski_label_proba")
+    return out
+
+
 class WindowRing:
     """The device-resident ring of a sliding window (``wiski_window_ring``): x [cap, d], y / wa / wb / noise [cap]
     in the working precision, and on the host ``head`` -- the slot the next entering point takes -- and ``fill``, the number of

@@ -156,6 +156,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         self.last_grad_interval_sites = None
         # count observations (_absorb_count): (ytilde, omega, log_z) [q] of the last batch given as counts
         self.last_count_sites = None
+        # categorical observations (_absorb_labels): (ytilde [C, q], omega [C, q], log_z [q]) of the last batch of labels
+        self.last_label_sites = None
         # noisy-input observations (_absorb_input_noise): the variance of the error of the recorded locations -- a scalar
         # or [d] -- that every unbatched update not given its own `input_var` is absorbed with; None: every path is what it is without
         # the feature.  input_noise_slope: the noise of a point is inflated by input_var E[(d f)^2] under the posterior before its batch
@@ -1480,7 +1482,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
 
     # -------------------------------------------------------------- updates --
     def condition_on_observations(self, X, Y, noise=None, inplace=False, _decay=True, *, grad_Y=None, grad_noise=None, grad_mask=None,
-                                  lower=None, upper=None, counts=None, exposure=None, trials=None, input_var=None, grad_lower=None, grad_upper=None):
+                                  lower=None, upper=None, counts=None, exposure=None, trials=None, input_var=None, grad_lower=None, grad_upper=None,
+                                  labels=None):
         """a7, :258-285.  inplace: the statistics buffers are updated where they
         live (O(4^{2d}) atomics per point); otherwise they are cloned first and a
         sibling model sharing covar_module / likelihood is returned.  With a ``forgetting_factor`` the statistics -- of the clone,
@@ -1530,7 +1533,21 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         channel is moment-matched like a bound on a value, against its own mean and variance under ``posterior_jet`` before the
         batch, and all of them are absorbed in one launch; ``last_grad_interval_sites`` holds ``(ytilde, omega, log_z)``, [n, d + 1]
         each.  ``num_data`` grows by the channels that entered.  No ``grad_Y`` beside them (an exact partial is equal bounds).  Single
-        output, unbatched X."""
+        output, unbatched X.
+
+        ``labels`` [n] with ``Y=None`` on a model of ``C = num_outputs >= 2`` outputs: categorical observations, ``labels_i`` in
+        {0 .. C - 1} the class of ``argmax_c (f_c(x_i) + eps_c)``, ``eps_c ~ N(0, sigma2_c noise_i)`` -- the multinomial probit
+        (``_condition_labels``).  Every point is moment-matched against the C posteriors before the batch and output c
+        takes it as the pseudo-target ``ytilde_ci`` at noise ``noise_i / omega_ci``, all outputs in one launch; ``last_label_sites``
+        holds ``(ytilde [C, n], omega [C, n], log_z [n])``.  A class far below the label's says nothing and is skipped for its output
+        alone; a label that is no class skips the point.  ``num_data`` grows by the points whose label class entered.  Unbatched X."""
+        if labels is not None:
+            given = dict(Y=Y, grad_Y=grad_Y, grad_noise=grad_noise, grad_mask=grad_mask, lower=lower, upper=upper, counts=counts, exposure=exposure,
+                         trials=trials, input_var=input_var, grad_lower=grad_lower, grad_upper=grad_upper)
+            others = [k for k, v in given.items() if v is not None]
+            if others:
+                raise NotImplementedError(f"a batch of labels is given as labels, with noise at most: no {', '.join(others)}")
+            return self._condition_labels(X, labels, noise, inplace, _decay)
         if input_var is None and self.input_var is not None and X.dim() <= 2 and (Y is None or Y.dim() <= 2):
             input_var = self.input_var
         if input_var is not None:
@@ -1893,6 +1910,121 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             cache, X, None, src, "count observations", half_delta=half_delta,
             launch=lambda X, *rest, **kw: grid_ops.scatter_stats_count(self._grid, X, y, t, family, *rest, **kw))
         return grown
+
+    # ---------------------------------------------- categorical observations --
+    def _label_noise(self, noise, n):
+        """The per-point noise of a batch of labels as [n] in the model's dtype, or None: unit noise."""
+        if noise is None:
+            return None
+        noise = noise.to(self._device, self._dtype).reshape(-1).contiguous()
+        if noise.shape[0] != n:
+            raise ValueError(f"noise must hold one value per point ([{n}]), got {tuple(noise.shape)}")
+        return noise
+
+    def _condition_labels(self, X, labels, noise, inplace, _decay):
+        """condition_on_observations with labels: grow, decay, moment-match, absorb -- _condition_count for the one
+        form that couples the outputs.  It refuses what _refuse_for_sites refuses, except several outputs, which it needs; and a
+        trend, as counts do."""
+        C = self.num_outputs
+        if not 2 <= C <= grid_ops.LABEL_MAX_CLASSES:
+            raise NotImplementedError(f"label observations need a model with 2 .. {grid_ops.LABEL_MAX_CLASSES} outputs, one per class; this one has {C}")
+        if self.robust_c is not None:
+            raise NotImplementedError("label observations do not combine with robust_c: a site is a weight already, and no kernel applies both")
+        if self.window is not None:
+            raise NotImplementedError("label observations do not combine with window: the ring stores targets, and a site depends on the "
+                                      "posterior it was matched against")
+        if X.dim() > 2:
+            raise NotImplementedError("batched conditioning (fantasies) takes targets, not labels")
+        if self.input_var is not None:
+            raise NotImplementedError("label observations do not combine with input_var on the model: a label has no target whose noise "
+                                      "the location error could inflate, and the sites would be matched at exact locations")
+        if self._trend_deg is not None:
+            self._refuse_trend("label observations (labels)", "a site is matched against the grid mean alone, which under a trend "
+                               "is not the predictive mean")
+        X = X.reshape(-1, self._grid.d)
+        n = X.shape[0]
+        y = labels.to(self._device, self._dtype).reshape(-1).contiguous()
+        if y.shape[0] != n:
+            raise ValueError(f"labels must hold one class per point ([{n}]), got {tuple(y.shape)}")
+        noise = self._label_noise(noise, n)
+        if self.grow_grid:
+            self.grow_to_cover_(X)
+        return self._condition(lambda model, cache, src: model._absorb_labels(cache, X, y, noise, src), inplace, self._gamma(_decay),
+                               reads_posterior=True)
+
+    def _absorb_labels(self, cache, X, y, noise, src):
+        """_absorb of one batch of labels, one launch for all outputs (wiski_scatter_stats_label): _absorb_matched for the one form
+        that couples the outputs, in its order -- the source posterior is read first (`src` as there: its C grid means from the
+        prediction cache, which finishes whatever is pending and leaves a stencil shard, and its C posterior variances at X), then
+        the launch is prepared (_before_launch, the carried residual) as _site_targets does, then everything that follows the stream
+        per output receives that output's pseudo-targets at the weights wa omega_c, wb omega_c, as _follow_sites does for one output.
+        It is not _absorb_matched itself because that takes one output's operator, vector views and one sigma2 (_native_half_op,
+        _site_targets) where this needs the packed [C, ...] buffers.  Returns what num_data grows by: the points whose label class
+        entered, and those outside the grid."""
+        C = self.num_outputs
+        ops = _wtw_ops(cache["WtW"])
+        pack = self._stencil_pack(ops)
+        b = cache["interpolation_cache"][:, :, 0]
+        if pack is None or "_cnt" not in cache or not b.is_contiguous():
+            raise NotImplementedError("label observations: the native packed half-stencil cache is needed (a full stencil was handed over)")
+        if "path_probes" in cache:                           # (_follow would feed them once per output)
+            raise NotImplementedError("label observations: path probes follow a single output")
+        X = X.to(self._device, self._dtype).contiguous()
+        n = X.shape[0]
+        no, wa, wb = self._batch_weights(noise, False, n)
+        U = src.prediction_cache["pred_mean"][..., 0]        # [C, m]
+        if not U.is_contiguous():
+            U = U.contiguous()
+        with torch.no_grad(), settings.skip_posterior_variances(False):
+            pvar = src._eval_forward(X).variance.reshape(C, n).to(self._dtype).contiguous()
+        ms = self._carried(self._before_launch(cache), u=U)  # (the state's U is [C, m]: its first row starts where U does)
+        flag0 = self._err.clone()
+        sites = grid_ops.scatter_stats_label(self._grid, X, y, pvar, [self._sigma2(c) for c in range(C)], wa, wb, no, b, pack, cache["_cnt"],
+                                             cache["_stats"], self._err, U, res=ms["R"] if ms else None)
+        self.last_label_sites = sites
+        if not n:
+            return 0
+        ytilde, omega = sites[0], sites[1]
+        self._two_level_lose()
+        for c in range(C):
+            self._follow(cache, c, X, wa * omega[c], ytilde[c] * (wb * omega[c]))     # a skipped site, a point outside the grid: omega = 0
+        cls = y.clamp(0, C - 1).nan_to_num(0.0).long()
+        entered, dropped = torch.stack([(omega.gather(0, cls[None])[0] > 0).sum(), (self._err - flag0).reshape(-1)[0] >> 1]).tolist()
+        return int(entered) + int(dropped)
+
+    def _label_moments(self, X, noise):
+        """(mean, variance, noise variance) [C, n] of the C outputs at X under the current posterior, in the model's dtype."""
+        C = self.num_outputs
+        if not 2 <= C <= grid_ops.LABEL_MAX_CLASSES:
+            raise NotImplementedError(f"class probabilities need a model with 2 .. {grid_ops.LABEL_MAX_CLASSES} outputs, one per class; this one has {C}")
+        X = X.reshape(-1, self._grid.d)
+        n = X.shape[0]
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad(), settings.skip_posterior_variances(False):
+                mvn = self(X.to(self._device, self._dtype))
+                mean, var = mvn.mean.reshape(C, n).contiguous(), mvn.variance.reshape(C, n).clamp_min(0.0).contiguous()
+        finally:
+            if was_training:
+                self.train()
+        noise = self._label_noise(noise, n)
+        s2 = torch.tensor([self._sigma2(c) for c in range(C)], dtype=torch.float64, device=self._device)[:, None]
+        s = (s2 * (torch.ones(n, dtype=torch.float64, device=self._device) if noise is None else noise.double())).to(self._dtype).contiguous()
+        return mean, var, s
+
+    def label_probability(self, X, noise=None):
+        """P(label = k | x_i) [n, C] (float64) under the current posterior and the multinomial probit likelihood, with the model's own
+        error bars inside (``wiski_label_proba``: the integral of the absorb's sites, once per class).  ``noise`` [n]: the per-point
+        noise a label at x_i would be given (None: unit).  The rows sum to 1 to quadrature error and are not normalised."""
+        return grid_ops.label_proba(*self._label_moments(X, noise))
+
+    def label_log_probability(self, X, labels, noise=None):
+        """log P(labels_i | x_i) [n] (float64) under the current posterior -- the log Z of the sites a batch of these labels would be
+        absorbed with (``wiski_label_sites``: the device function of the absorb, no scatter); NaN for a label that is no class."""
+        mean, var, s = self._label_moments(X, noise)
+        y = labels.to(self._device, self._dtype).reshape(-1).contiguous()
+        return grid_ops.label_sites(mean, var, s, y)[2]
 
     # --------------------------------------------------- noisy-input observations --
     def _canon_input_var(self, input_var, n):
