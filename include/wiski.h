@@ -592,6 +592,42 @@ int wiski_absorb_count_f64(const wiski_grid* grid, const wiski_absorb_args* args
 int wiski_count_sites_f32(const float* d_mu, const float* d_pvar, const float* d_y, const float* d_t, int family, int64_t n, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, void* stream);
 int wiski_count_sites_f64(const double* d_mu, const double* d_pvar, const double* d_y, const double* d_t, int family, int64_t n, double* d_ytilde_out, double* d_omega_out, double* d_logz_out, void* stream);
 
+/* Heteroscedastic absorb: the noise of a point is not known but learned, as a second field on the same grid:
+ *   y_p = f(x_p) + eps_p,   eps_p ~ N(0, sigma2 noise_p exp g(x_p)),   g ~ GP(g0, k_g).
+ * f and g are two single-output models with a set of statistics each: (d_b, d_A_half, d_cnt, d_stats, d_u, d_res) for f and
+ * (d_b2, d_A2_half, d_cnt2, d_stats2, d_u2, d_res2) for g - g0.  Both are taken against their posteriors BEFORE the batch, inside the
+ * one launch that absorbs it into both: with mu_f = w_p . u, v_f = max(d_pvar_p, 0), mu_g = g0 + w_p . u2, v_g = max(d_pvar2_p, 0),
+ *   e     = exp(mu_g + v_g / 2)                      (the mean of the log-normal multiplier),   dn = sigma2 noise_p e,
+ *   f     takes the point as its own target y_p at noise noise_p / omega_f, omega_f = 1 / e -- NOT capped at 1 --
+ *         and d_logzy_out = log N(y; mu_f, v_f + dn);
+ *   rho   = (y_p - mu_f)^2 / (sigma2 noise_p) * dn / (dn + v_f)
+ *         (the last factor takes out the share of the residual that is f's own uncertainty and keeps the likelihood log-concave);
+ *   g     takes the site of l(g) = (2 pi)^(-nu / 2) exp(-nu g / 2 - rho e^-g / 2), nu = 1, moment-matched against N(mu_g, v_g) by
+ *         the quadrature of the count form as its family WISKI_COUNT_LOGVAR (y = rho, t = nu; valid for rho >= 0, nu > 0, both finite):
+ *         the target ytilde_g - g0 at noise 1 / tau_g.  The noise model's own sigma2 = noise = wa = wb = 1, as for counts.
+ * The site is evaluated in double in both precisions.  d_e_out [n] receives e, d_ytilde_out / d_omega_out / d_logz_out [n] the noise
+ * site (ytilde_g including g0, tau_g, its log Z), d_mean_out (optional) mu_f.  rho = 0 has tau = 0: the noise site is SKIPPED by the
+ * omega < 1e-12 rule (WISKI_COUNT_OMEGA_MIN), it reports ytilde = mu_g, omega = 0, and the point still enters f.  A y that is not
+ * finite, a noise that is not positive and finite, or a multiplier e for which e or 1 / e is not positive and finite IN THE WORKING
+ * PRECISION (|mu_g + v_g / 2| > 87 in fp32: the weight would be 0 or inf) skips the point for both models (both log Z = NaN, no flag
+ * in d_err; d_e_out still reports e as rounded).  A point outside the grid is dropped for both, flagged and counted ONCE in d_err, and reports zeros.  d_stats2[0], the sum
+ * of tau ytilde^2, is dominated by weak sites and is no evidence term: the evidence is the sum of the log Z.
+ * d_u, d_A_half, d_cnt and the whole second set but d_res2 are required; d_res, d_res2 and d_mean_out are optional.  d = 1..4,
+ * symmetric half stencil, atomic form, a single output.  wiski_absorb_hetero takes the record plus the hetero arguments, so that
+ * every refused combination (a guard, zero regions, a shard, an owner workspace, nout > 1, channels, a full stencil) can be reached
+ * and tested; wiski_absorb_args has NOT grown.  Everything refused returns WISKI_E_BADARG before a launch; n = 0 does nothing.
+ * wiski_hetero_sites evaluates the noise sites alone, one wave per site and no scatter, from given d_mu = mu_g, d_pvar = v_g, d_rho
+ * and d_nu [n] (nu is general: replicated readings give a sample variance with nu degrees of freedom): d_omega_out receives tau.
+ * It is wiski_count_sites of the family WISKI_COUNT_LOGVAR (the same kernel with the family fixed at compile time), which the count
+ * absorb and wiski_count_sites themselves do not take.  n = 0 returns WISKI_OK from all three, whatever the other arguments hold. */
+#define WISKI_COUNT_LOGVAR 2
+int wiski_scatter_stats_hetero_f32(const wiski_grid* grid, const float* d_x, const float* d_y, const float* d_pvar, const float* d_pvar2, double sigma2, double g0, const float* d_wa, const float* d_wb, const float* d_noise, int64_t n, float* d_b, float* d_A_half, float* d_cnt, const float* d_u, float* d_res, float* d_mean_out, double* d_stats, float* d_b2, float* d_A2_half, float* d_cnt2, const float* d_u2, float* d_res2, double* d_stats2, int32_t* d_err, float* d_e_out, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, double* d_logzy_out, void* stream);
+int wiski_scatter_stats_hetero_f64(const wiski_grid* grid, const double* d_x, const double* d_y, const double* d_pvar, const double* d_pvar2, double sigma2, double g0, const double* d_wa, const double* d_wb, const double* d_noise, int64_t n, double* d_b, double* d_A_half, double* d_cnt, const double* d_u, double* d_res, double* d_mean_out, double* d_stats, double* d_b2, double* d_A2_half, double* d_cnt2, const double* d_u2, double* d_res2, double* d_stats2, int32_t* d_err, double* d_e_out, double* d_ytilde_out, double* d_omega_out, double* d_logz_out, double* d_logzy_out, void* stream);
+int wiski_absorb_hetero_f32(const wiski_grid* grid, const wiski_absorb_args* args, const float* d_pvar, const float* d_pvar2, double sigma2, double g0, float* d_b2, float* d_A2_half, float* d_cnt2, const float* d_u2, float* d_res2, double* d_stats2, float* d_e_out, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, double* d_logzy_out, void* stream);
+int wiski_absorb_hetero_f64(const wiski_grid* grid, const wiski_absorb_args* args, const double* d_pvar, const double* d_pvar2, double sigma2, double g0, double* d_b2, double* d_A2_half, double* d_cnt2, const double* d_u2, double* d_res2, double* d_stats2, double* d_e_out, double* d_ytilde_out, double* d_omega_out, double* d_logz_out, double* d_logzy_out, void* stream);
+int wiski_hetero_sites_f32(const float* d_mu, const float* d_pvar, const float* d_rho, const float* d_nu, int64_t n, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, void* stream);
+int wiski_hetero_sites_f64(const double* d_mu, const double* d_pvar, const double* d_rho, const double* d_nu, int64_t n, double* d_ytilde_out, double* d_omega_out, double* d_logz_out, void* stream);
+
 /* Categorical observations: point p carries a label d_labels_p in {0 .. C - 1}, C = nout outputs.  The likelihood is
  * the multinomial probit, y = argmax_c (f_c(x) + eps_c), eps_c ~ N(0, s_c), s_c = sigma2[c] noise_c,p.  Every point is moment-matched
  * against the posterior BEFORE the batch, inside the launch that absorbs it: with mu_c = w_p . u_c (u is [C][m]), v_c = max(d_pvar[c][p], 0),

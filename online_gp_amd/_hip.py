@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 _SO = os.path.join(_CSRC, "libwiski_hip.so")
 _SOURCES = ["interp_gather.hip", "scatter_stats.hip", "solve.hip", "spectral.hip", "dense.hip", "collective.hip", "stream_step.hip", "spectral_basis.hip", "hyper_columns.hip", "two_level.hip", "hyper_step.hip", "lookahead.hip", "sample_paths.hip", "decay_stats.hip", "regrid_stats.hip", "trend.hip"]
-_HEADERS = ["wiski_common.h", "spmv_sym_dma.h", "spmv_sym_dma_mc.h", "spmm_sym_cols.h", "spmm_sym_bcast.h", "scatter_half.h", "scatter_owner.h", "scatter_grad.h", "scatter_site.h", "scatter_robust.h", "scatter_window.h", "scatter_interval.h", "scatter_count.h", "scatter_label.h", "scatter_input_noise.h", "scatter_grad_interval.h", "absorb.h", "dense_small.h", "dense_coop.h",
+_HEADERS = ["wiski_common.h", "spmv_sym_dma.h", "spmv_sym_dma_mc.h", "spmm_sym_cols.h", "spmm_sym_bcast.h", "scatter_half.h", "scatter_owner.h", "scatter_grad.h", "scatter_site.h", "scatter_robust.h", "scatter_window.h", "scatter_interval.h", "scatter_count.h", "scatter_hetero.h", "scatter_label.h", "scatter_input_noise.h", "scatter_grad_interval.h", "absorb.h", "dense_small.h", "dense_coop.h",
             os.path.join("..", "..", "include", "wiski.h")]
 MAX_DIM = 4
 
@@ -116,8 +116,19 @@ def _label_signatures():
                                               ("wiski_label_proba", proba)) for suf in ("_f32", "_f64")}
 
 
+def _hetero_signatures():
+    """argtypes of the entries of the heteroscedastic absorb (include/wiski.h), as _grad_interval_signatures."""
+    p, f64, i64 = ctypes.c_void_p, ctypes.c_double, ctypes.c_int64
+    flat = [ctypes.POINTER(wiski_grid)] + [p] * 4 + [f64, f64] + [p] * 3 + [i64] + [p] * 19 + [p]
+    record = [ctypes.POINTER(wiski_grid), ctypes.POINTER(wiski_absorb_args)] + [p] * 2 + [f64, f64] + [p] * 11 + [p]
+    sites = [p] * 4 + [i64] + [p] * 3 + [p]
+    return {name + suf: sig for name, sig in (("wiski_scatter_stats_hetero", flat), ("wiski_absorb_hetero", record), ("wiski_hetero_sites", sites))
+            for suf in ("_f32", "_f64")}
+
+
 SIGNATURES = _grad_interval_signatures()
 LABEL_SIGNATURES = _label_signatures()
+HETERO_SIGNATURES = _hetero_signatures()
 
 
 def sources():
@@ -227,7 +238,7 @@ def lib():
         _lib = ctypes.CDLL(_SO)
         _lib.wiski_pcg_workspace_bytes.restype = ctypes.c_int64
         _lib.wiski_twolevel_refresh_workspace_bytes.restype = ctypes.c_int64
-        for name, sig in {**SIGNATURES, **LABEL_SIGNATURES}.items():
+        for name, sig in {**SIGNATURES, **LABEL_SIGNATURES, **HETERO_SIGNATURES}.items():
             f = getattr(_lib, name)
             f.argtypes, f.restype = sig, ctypes.c_int
     if hasattr(_lib, "wiski_root_update_workspace_elems"):

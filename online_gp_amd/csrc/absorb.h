@@ -3,9 +3,9 @@
 // may be asked to do, as ONE named record.  Every member defaults to "off"; the extern "C" entry points of scatter_stats.hip
 // and the streaming step (stream_step.hip) fill the fields they expose and call absorb().  Which combinations are refused is
 // absorb_validate() in scatter_stats.hip; whoever writes another form of the absorb has to honour every group below.
-// Five half-stencil kernels stand behind it, besides the full-stencil k_scatter_stats and the owner form (where its workspace is
+// Six half-stencil kernels stand behind it, besides the full-stencil k_scatter_stats and the owner form (where its workspace is
 // given and applies): the atomic form (k_scatter_stats_sym), the derivative-observation form (`channels`, scatter_grad.h), its
-// interval-site form (`clo`, scatter_grad_interval.h), the sliding-window form (`ring_*`, scatter_window.h) and the site-weighted form (k_scatter_stats_site, scatter_site.h), which is the
+// interval-site form (`clo`, scatter_grad_interval.h), the sliding-window form (`ring_*`, scatter_window.h), the heteroscedastic form (`b2`, scatter_hetero.h) and the site-weighted form (k_scatter_stats_site, scatter_site.h), which is the
 // outlier-robust (`inv_scale`, scatter_robust.h), the interval (`lo`, scatter_interval.h), the count (`count_y`, scatter_count.h) or
 // the noisy-input absorb (`xvar`, scatter_input_noise.h) by the site it is given.  What they do per point -- the tap tables, the per-tap atomics, the pair loop that
 // encodes the row-interleaved layout, the two scalars -- is stated once, in scatter_half.h.
@@ -117,14 +117,34 @@ struct AbsorbArgs {
   const real* clo = nullptr;        // [n][channels] lower ends (-inf: none)
   const real* chi = nullptr;        // [n][channels] upper ends (+inf: none); clo == chi: an exact value
   const real* cpvar = nullptr;      // [n][channels] posterior variance of each channel before the batch (negative: 0)
+  // hetero: b2 != NULL makes the absorb heteroscedastic (scatter_hetero.h): a second single-output model on the same grid -- the
+  // second target set below, every member of it the counterpart of the first set's -- holds g = log of the noise multiplier, prior
+  // mean g0.  With mu_g = g0 + w_p . u2, v_g = max(pvar2, 0), e = exp(mu_g + v_g / 2), the point enters the first set as its own
+  // target y at noise noise / omega_f, omega_f = 1 / e (not capped), and its deflated squared residual enters the second set as a
+  // log-variance site (ytilde_g - g0 at noise 1 / tau_g; that model's sigma2 = noise = wa = wb = 1).  A NaN y skips the point for
+  // both sets (no flag); a point outside the grid is dropped for both and counted once; a noise site with tau < WISKI_COUNT_OMEGA_MIN
+  // is skipped for the second set alone.  Shares the interval group's pvar / sigma2 / ytilde_out / omega_out / logz_out (the noise
+  // site, tau in omega_out) and needs them, with y, u, A, cnt, b2, A2, cnt2, stats2, u2, pvar2, e_out, logzy_out and a finite g0;
+  // res and res2 are optional
+  real* b2 = nullptr;               // [m]
+  real* A2 = nullptr;               // the second model's symmetric half stencil
+  real* cnt2 = nullptr;             // [m]
+  double* stats2 = nullptr;         // [2]
+  const real* u2 = nullptr;         // [m] posterior mean of g - g0 on the grid
+  real* res2 = nullptr;             // [m] the second model's carried residual; optional
+  const real* pvar2 = nullptr;      // [n] posterior variance of g at the point before the batch (negative: 0)
+  double g0 = 0;                    // prior mean of g
+  real* e_out = nullptr;            // [n] the multiplier each point entered f with; 0 for a point outside the grid
+  double* logzy_out = nullptr;      // [n] log N(y; mu_f, v_f + sigma2 noise e) under the posteriors before the batch
 
   bool sharded() const { return g_lo > 0 || g_hi < (1 << 30); }
   bool windowed() const { return ring_x || ring_y || ring_wa || ring_wb || ring_noise || ring_cap || ring_head || void_left; }
   bool counted() const { return count_y || count_t || count_family != 0; }
   bool input_noise() const { return xvar || gvar || grad_out; }
-  // (the fields the matched forms share belong to whichever of the count, input-noise and channel-interval groups is given, else to the interval group)
+  // (the fields the matched forms share belong to whichever of the count, input-noise, channel-interval and hetero groups is given, else to the interval group)
   bool grad_interval() const { return clo || chi || cpvar; }
-  bool interval() const { return lo || hi || (!counted() && !input_noise() && !grad_interval() && (pvar || sigma2 != 0 || ytilde_out || logz_out)); }
+  bool hetero() const { return b2 || A2 || cnt2 || stats2 || u2 || res2 || pvar2 || g0 != 0 || e_out || logzy_out; }
+  bool interval() const { return lo || hi || (!counted() && !input_noise() && !grad_interval() && !hetero() && (pvar || sigma2 != 0 || ytilde_out || logz_out)); }
   bool site_form() const { return inv_scale || interval() || counted() || input_noise(); }   // the forms of k_scatter_stats_site (scatter_site.h)
 };
 

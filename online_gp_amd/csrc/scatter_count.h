@@ -219,13 +219,17 @@ struct SiteCount : SiteOutputs<real> {
 };
 
 // Sites only (wiski_count_sites): one wave per site, four per block, the same count_site; omega = tau (no noise scale).
-template <typename real>
+// FAM < 0: the family is the run-time argument (Poisson or binomial); FAM >= 0: that family alone, `family` is not looked at
+// (wiski_hetero_sites, scatter_hetero.h: its family is no count and the count entries do not take it).
+template <typename real, int FAM = -1>
 __global__ __launch_bounds__(256) void k_count_sites(const real* __restrict__ mu, const real* __restrict__ pvar, const real* __restrict__ cy,
                                                      const real* __restrict__ ct, int family, int64_t n, real* __restrict__ ytilde_out,
                                                      real* __restrict__ omega_out, double* __restrict__ logz_out) {
   const int lane = threadIdx.x & 63;
   for (int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); p < n; p += (int64_t)gridDim.x * 4) {   // (wave-uniform trip count)
-    const CountSite st = count_site_of(family, (double)cy[p], (double)ct[p], (double)mu[p], (double)pvar[p], 1.0, lane);
+    CountSite st;
+    if constexpr (FAM < 0) st = count_site_of(family, (double)cy[p], (double)ct[p], (double)mu[p], (double)pvar[p], 1.0, lane);
+    else st = count_site<FAM>((double)cy[p], (double)ct[p], (double)mu[p], (double)pvar[p], 1.0, lane);
     if (lane == 0) {
       ytilde_out[p] = (real)st.ytilde;
       omega_out[p] = (real)st.omega;
@@ -234,15 +238,15 @@ __global__ __launch_bounds__(256) void k_count_sites(const real* __restrict__ mu
   }
 }
 
-template <typename real>
+template <typename real, int FAM = -1>
 static int count_sites_impl(const real* mu, const real* pvar, const real* y, const real* t, int family, int64_t n, real* ytilde_out, real* omega_out,
                             double* logz_out, void* stream) {
   if (n == 0) return WISKI_OK;
   if (n < 0 || !mu || !pvar || !y || !t || !ytilde_out || !omega_out || !logz_out) return WISKI_E_BADARG;
-  if (family != WISKI_COUNT_POISSON && family != WISKI_COUNT_BINOMIAL) return WISKI_E_BADARG;
+  if (FAM < 0 && family != WISKI_COUNT_POISSON && family != WISKI_COUNT_BINOMIAL) return WISKI_E_BADARG;
   int64_t blocks = (n + 3) / 4;
   if (blocks > 256 * 8) blocks = 256 * 8;
-  hipLaunchKernelGGL((k_count_sites<real>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, mu, pvar, y, t, family, n, ytilde_out, omega_out,
+  hipLaunchKernelGGL((k_count_sites<real, FAM>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, mu, pvar, y, t, family, n, ytilde_out, omega_out,
                      logz_out);
   WISKI_LAUNCH_CHECK();
   return WISKI_OK;

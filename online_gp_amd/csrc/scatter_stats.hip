@@ -179,6 +179,7 @@ __global__ __launch_bounds__(256) void k_scatter_stats_sym(GridDev<real> G, cons
 #include "scatter_window.h"
 #include "scatter_interval.h"
 #include "scatter_count.h"
+#include "scatter_hetero.h"
 #include "scatter_label.h"
 #include "scatter_input_noise.h"
 #include "scatter_grad_interval.h"
@@ -250,6 +251,17 @@ template <typename real>
 static int absorb_validate(const AbsorbArgs<real>& a, int d) {
   if (a.n == 0) return WISKI_OK;                       // nothing to absorb: not even the pointers are looked at
   if (!a.x || (!a.y && !a.lo && !a.count_y && !a.clo) || !a.wa || !a.wb || !a.noise || !a.b || !a.stats || !a.err) return WISKI_E_BADARG;   // what every form reads and writes (the interval, count and channel-interval forms have no y)
+  if (a.hetero()) {
+    // heteroscedastic (scatter_hetero.h): the plain single-output half-stencil atomic absorb of y with u, A and cnt, twice -- the whole
+    // second target set (res2 optional, as res), both variances, a noise scale, a finite prior mean, the five outputs -- and nothing
+    // of any other group: no full stencil, no channels, no second output, no guard, zero regions, shard or owner workspace
+    if (!a.y || !a.half || !a.u || !a.A || !a.cnt || a.nout != 1 || a.channels) return WISKI_E_BADARG;
+    if (!a.b2 || !a.A2 || !a.cnt2 || !a.stats2 || !a.u2 || !a.pvar || !a.pvar2 || !a.e_out || !a.logzy_out) return WISKI_E_BADARG;
+    if (!a.ytilde_out || !a.omega_out || !a.logz_out || !(a.sigma2 > 0) || !std::isfinite(a.sigma2) || !std::isfinite(a.g0)) return WISKI_E_BADARG;
+    if (a.lo || a.hi || a.counted() || a.input_noise() || a.grad_interval() || a.inv_scale || a.huber_c != (real)0 || a.windowed()) return WISKI_E_BADARG;
+    if (a.guard || a.n1_bytes || a.n2_bytes || a.z1 || a.z2 || a.sharded() || a.bin || a.bin_bytes) return WISKI_E_BADARG;
+    return WISKI_OK;
+  }
   if (a.grad_interval()) {
     // channel intervals (scatter_grad_interval.h): the derivative form's single-output half-stencil atomic absorb with u, A and cnt, the
     // whole group, a noise scale and the three outputs -- and nothing of any other group
@@ -384,6 +396,7 @@ int absorb(const wiski_grid* grid, const AbsorbArgs<real>& a, void* stream) {
   int rc = make_grid_dev<real>(grid, &G);
   if (rc == WISKI_OK) rc = absorb_validate(a, G.d);
   if (rc != WISKI_OK || a.n == 0) return rc;
+  if (a.hetero()) return launch_hetero(G, a, (hipStream_t)stream);
   if (a.grad_interval()) return launch_grad_site(G, a, (hipStream_t)stream);
   if (a.input_noise()) return launch_site(G, a, SiteInputNoise<real>::of(a, *grid), (hipStream_t)stream);
   if (a.counted()) return launch_site(G, a, SiteCount<real>::of(a), (hipStream_t)stream);
@@ -515,6 +528,22 @@ static int entry_absorb_label(const wiski_grid* g, const wiski_absorb_args* p, c
   return p ? label_absorb(g, absorb_args<real>(*p), labels, pvar, sigma2, ytilde_out, omega_out, logz_out, s) : WISKI_E_BADARG;
 }
 template <typename real>
+static int entry_hetero(const wiski_grid* g, AbsorbArgs<real> a, const real* pvar, const real* pvar2, double sigma2, double g0, real* b2, real* A2_half, real* cnt2, const real* u2, real* res2, double* stats2, real* e_out, real* ytilde_out, real* omega_out, double* logz_out, double* logzy_out, void* s) {
+  a.pvar = pvar; a.pvar2 = pvar2; a.sigma2 = sigma2; a.g0 = g0; a.b2 = b2; a.A2 = A2_half; a.cnt2 = cnt2; a.u2 = u2; a.res2 = res2; a.stats2 = stats2;
+  a.e_out = e_out; a.ytilde_out = ytilde_out; a.omega_out = omega_out; a.logz_out = logz_out; a.logzy_out = logzy_out;
+  return b2 || a.n == 0 ? absorb(g, a, s) : WISKI_E_BADARG;   // (without b2 the record would be another form's; n = 0 does nothing)
+}
+template <typename real>
+static int entry_scatter_hetero(const wiski_grid* g, const real* x, const real* y, const real* pvar, const real* pvar2, double sigma2, double g0, const real* wa, const real* wb, const real* noise, int64_t n, real* b, real* A_half, real* cnt, const real* u, real* res, real* mean_out, double* stats, real* b2, real* A2_half, real* cnt2, const real* u2, real* res2, double* stats2, int32_t* err, real* e_out, real* ytilde_out, real* omega_out, double* logz_out, double* logzy_out, void* s) {
+  AbsorbArgs<real> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
+  absorb_carry(a, cnt, u, res, mean_out);
+  return entry_hetero(g, a, pvar, pvar2, sigma2, g0, b2, A2_half, cnt2, u2, res2, stats2, e_out, ytilde_out, omega_out, logz_out, logzy_out, s);
+}
+template <typename real>
+static int entry_absorb_hetero(const wiski_grid* g, const wiski_absorb_args* p, const real* pvar, const real* pvar2, double sigma2, double g0, real* b2, real* A2_half, real* cnt2, const real* u2, real* res2, double* stats2, real* e_out, real* ytilde_out, real* omega_out, double* logz_out, double* logzy_out, void* s) {
+  return p ? entry_hetero(g, absorb_args<real>(*p), pvar, pvar2, sigma2, g0, b2, A2_half, cnt2, u2, res2, stats2, e_out, ytilde_out, omega_out, logz_out, logzy_out, s) : WISKI_E_BADARG;
+}
+template <typename real>
 static int entry_input_noise(const wiski_grid* g, AbsorbArgs<real> a, const real* xvar, const real* gvar, const real* pvar, double sigma2, real* omega_out, double* logz_out, real* grad_out, void* s) {
   a.xvar = xvar; a.gvar = gvar; a.grad_out = grad_out; a.pvar = pvar; a.sigma2 = sigma2; a.omega_out = omega_out; a.logz_out = logz_out;
   return xvar ? absorb(g, a, s) : WISKI_E_BADARG;
@@ -598,6 +627,12 @@ int wiski_absorb_count_f32(const wiski_grid* g, const wiski_absorb_args* p, cons
 int wiski_absorb_count_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* y, const double* t, int family, const double* pvar, double sigma2, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return entry_absorb_count(g, p, y, t, family, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
 int wiski_count_sites_f32(const float* mu, const float* pvar, const float* y, const float* t, int family, int64_t n, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return count_sites_impl(mu, pvar, y, t, family, n, ytilde_out, omega_out, logz_out, s); }
 int wiski_count_sites_f64(const double* mu, const double* pvar, const double* y, const double* t, int family, int64_t n, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return count_sites_impl(mu, pvar, y, t, family, n, ytilde_out, omega_out, logz_out, s); }
+int wiski_scatter_stats_hetero_f32(const wiski_grid* g, const float* x, const float* y, const float* pvar, const float* pvar2, double sigma2, double g0, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, float* cnt, const float* u, float* res, float* mean_out, double* stats, float* b2, float* A2_half, float* cnt2, const float* u2, float* res2, double* stats2, int32_t* err, float* e_out, float* ytilde_out, float* omega_out, double* logz_out, double* logzy_out, void* s) { return entry_scatter_hetero(g, x, y, pvar, pvar2, sigma2, g0, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, b2, A2_half, cnt2, u2, res2, stats2, err, e_out, ytilde_out, omega_out, logz_out, logzy_out, s); }
+int wiski_scatter_stats_hetero_f64(const wiski_grid* g, const double* x, const double* y, const double* pvar, const double* pvar2, double sigma2, double g0, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, double* b2, double* A2_half, double* cnt2, const double* u2, double* res2, double* stats2, int32_t* err, double* e_out, double* ytilde_out, double* omega_out, double* logz_out, double* logzy_out, void* s) { return entry_scatter_hetero(g, x, y, pvar, pvar2, sigma2, g0, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, b2, A2_half, cnt2, u2, res2, stats2, err, e_out, ytilde_out, omega_out, logz_out, logzy_out, s); }
+int wiski_absorb_hetero_f32(const wiski_grid* g, const wiski_absorb_args* p, const float* pvar, const float* pvar2, double sigma2, double g0, float* b2, float* A2_half, float* cnt2, const float* u2, float* res2, double* stats2, float* e_out, float* ytilde_out, float* omega_out, double* logz_out, double* logzy_out, void* s) { return entry_absorb_hetero(g, p, pvar, pvar2, sigma2, g0, b2, A2_half, cnt2, u2, res2, stats2, e_out, ytilde_out, omega_out, logz_out, logzy_out, s); }
+int wiski_absorb_hetero_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* pvar, const double* pvar2, double sigma2, double g0, double* b2, double* A2_half, double* cnt2, const double* u2, double* res2, double* stats2, double* e_out, double* ytilde_out, double* omega_out, double* logz_out, double* logzy_out, void* s) { return entry_absorb_hetero(g, p, pvar, pvar2, sigma2, g0, b2, A2_half, cnt2, u2, res2, stats2, e_out, ytilde_out, omega_out, logz_out, logzy_out, s); }
+int wiski_hetero_sites_f32(const float* mu, const float* pvar, const float* rho, const float* nu, int64_t n, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return count_sites_impl<float, WISKI_COUNT_LOGVAR>(mu, pvar, rho, nu, WISKI_COUNT_LOGVAR, n, ytilde_out, omega_out, logz_out, s); }
+int wiski_hetero_sites_f64(const double* mu, const double* pvar, const double* rho, const double* nu, int64_t n, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return count_sites_impl<double, WISKI_COUNT_LOGVAR>(mu, pvar, rho, nu, WISKI_COUNT_LOGVAR, n, ytilde_out, omega_out, logz_out, s); }
 int wiski_scatter_stats_label_f32(const wiski_grid* g, const float* x, const float* labels, const float* pvar, const double* sigma2, const float* wa, const float* wb, const float* noise, int64_t n, int32_t nout, int64_t w_stride, float* b, float* A_half, int64_t A_stride, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return entry_scatter_label(g, x, labels, pvar, sigma2, wa, wb, noise, n, nout, w_stride, b, A_half, A_stride, cnt, u, res, mean_out, stats, err, ytilde_out, omega_out, logz_out, s); }
 int wiski_scatter_stats_label_f64(const wiski_grid* g, const double* x, const double* labels, const double* pvar, const double* sigma2, const double* wa, const double* wb, const double* noise, int64_t n, int32_t nout, int64_t w_stride, double* b, double* A_half, int64_t A_stride, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return entry_scatter_label(g, x, labels, pvar, sigma2, wa, wb, noise, n, nout, w_stride, b, A_half, A_stride, cnt, u, res, mean_out, stats, err, ytilde_out, omega_out, logz_out, s); }
 int wiski_absorb_label_f32(const wiski_grid* g, const wiski_absorb_args* p, const float* labels, const float* pvar, const double* sigma2, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return entry_absorb_label(g, p, labels, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }

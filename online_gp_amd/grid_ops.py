@@ -600,6 +600,56 @@ def count_sites(mean, pvar, counts, t, family):
     return ytilde, tau, log_z
 
 
+def scatter_stats_hetero(grid, x, y, pvar, pvar2, sigma2, g0, wa, wb, noise, f_set, g_set, err, mean_out=None):
+    """The heteroscedastic absorb in ONE launch (``wiski_scatter_stats_hetero``): two single-output models on the same
+    grid, f and g = log of the noise multiplier (prior mean ``g0``), each given as a set ``(b, A_half, cnt, stats, u, res)`` (res may
+    be None).  Against the two posteriors before the batch -- the grid means, the posterior variances ``pvar`` (of f) and ``pvar2`` (of
+    g) at x [n] -- point i enters f as y_i at noise_i e_i, e = exp(mu_g + v_g / 2), and its deflated squared residual enters g as a
+    log-variance site, the target ytilde_g - g0 at noise 1 / tau.  Returns (e [n], ytilde_g [n], tau [n], log_z_g [n] float64,
+    log_z_y [n] float64): a skipped noise site has tau = 0 and ytilde_g = mu_g (the point still entered f), a point with a NaN y both
+    log Z = NaN and nothing anywhere, a point outside the grid zeros.  ``mean_out`` [n] receives w . u_f."""
+    op = "scatter_stats_hetero"
+    b, A_half, cnt, stats, u, res = f_set
+    b2, A2_half, cnt2, stats2, u2, res2 = g_set
+    x, n, (ytilde, tau, log_z) = _absorb_points(op, grid, x, u, sites=True, u_is="the grid mean of f",
+                                                per_point=dict(y=y, pvar=pvar, pvar2=pvar2, wa=wa, wb=wb, noise=noise, mean_out=mean_out))
+    if u2 is None or tuple(u2.shape) != (grid.m,) or u2.dtype != x.dtype:
+        raise ValueError(f"{op}: the second set's u must be the grid mean of g - g0 [{grid.m}] {x.dtype}")
+    e = torch.empty(n, dtype=x.dtype, device=x.device)
+    log_zy = torch.empty(n, dtype=torch.float64, device=x.device)
+    if n == 0:
+        return e, ytilde, tau, log_z, log_zy
+    rc = _hip.fn("wiski_scatter_stats_hetero", x.dtype)(grid.ref, _hip.dptr(x), _hip.dptr(y.contiguous()), _hip.dptr(pvar.contiguous()),
+                                                        _hip.dptr(pvar2.contiguous()), float(sigma2), float(g0), _hip.dptr(wa.contiguous()),
+                                                        _hip.dptr(wb.contiguous()), _hip.dptr(noise.contiguous()), n, _hip.dptr(b), _hip.dptr(A_half),
+                                                        _hip.dptr(cnt), _hip.dptr(u), _hip.dptr(res), _hip.dptr(mean_out), _hip.dptr(stats),
+                                                        _hip.dptr(b2), _hip.dptr(A2_half), _hip.dptr(cnt2), _hip.dptr(u2), _hip.dptr(res2),
+                                                        _hip.dptr(stats2), _hip.dptr(err), _hip.dptr(e), _hip.dptr(ytilde), _hip.dptr(tau),
+                                                        _hip.dptr(log_z), _hip.dptr(log_zy), _hip.stream_ptr(x.device))
+    _hip.check(rc, "wiski_scatter_stats_hetero")
+    return e, ytilde, tau, log_z, log_zy
+
+
+def hetero_sites(mean, pvar, rho, nu):
+    """The log-variance sites alone (``wiski_hetero_sites``: the device function of ``scatter_stats_hetero``, one wave per site, no
+    scatter): ``rho`` the sum of squares of ``nu`` residuals in units of the known noise, matched against N(mean, pvar) of the log
+    multiplier, all [n].  Returns (ytilde [n], tau [n], log_z [n] float64)."""
+    n = mean.shape[0]
+    for name, v in (("mean", mean), ("pvar", pvar), ("rho", rho), ("nu", nu)):
+        if tuple(v.shape) != (n,) or v.dtype != mean.dtype:
+            raise ValueError(f"hetero_sites: {name} must be [{n}] {mean.dtype}, got {tuple(v.shape)} {v.dtype}")
+    ytilde = torch.empty(n, dtype=mean.dtype, device=mean.device)
+    tau = torch.empty(n, dtype=mean.dtype, device=mean.device)
+    log_z = torch.empty(n, dtype=torch.float64, device=mean.device)
+    if n == 0:
+        return ytilde, tau, log_z
+    rc = _hip.fn("wiski_hetero_sites", mean.dtype)(_hip.dptr(mean.contiguous()), _hip.dptr(pvar.contiguous()), _hip.dptr(rho.contiguous()),
+                                                   _hip.dptr(nu.contiguous()), n, _hip.dptr(ytilde), _hip.dptr(tau), _hip.dptr(log_z),
+                                                   _hip.stream_ptr(mean.device))
+    _hip.check(rc, "wiski_hetero_sites")
+    return ytilde, tau, log_z
+
+
 LABEL_MAX_CLASSES = 16                              # WISKI_LABEL_MAX_CLASSES
 
 

@@ -127,8 +127,13 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         trend_prior_var=None,
         input_var=None,
         input_noise_slope="posterior",
+        heteroscedastic=False,
+        noise_kernel=None,
+        log_noise_mean=0.0,
+        noise_model=None,
     ):
         super().__init__()
+        object.__setattr__(self, "noise_model", None)    # (set at the end: the initial data is absorbed plainly)
         assert train_inputs is not None or kernel_cache is not None
         # following the stream (grow_to_cover_): every update first grows the grid by whole nodes until its batch is interior
         self.grow_grid = bool(grow_grid)
@@ -337,6 +342,28 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
                 # hand-over path (bayesopt.py:86-96): recover sum_p 1/noise_p from the row sums (rows of W sum to one)
                 self._wsum_dev = kernel_cache["_cnt"].sum(dim=1, dtype=torch.float64)
                 self._wsum_dirty = True
+        # heteroscedastic streaming (_absorb_hetero): the noise of a point is sigma2 noise_p exp g(x_p), with g a second
+        # single-output model on the SAME grid object -- `noise_model`, prior mean `log_noise_mean`, its kernel fixed by the caller --
+        # learned from the stream's own residuals in the launch that absorbs the batch.  The initial data is absorbed plainly (at
+        # multiplier 1).  None: every path is what it is without the feature.  The noise model is NOT a registered submodule: its
+        # kernel's hyper-parameters are not among parameters() and no MLL step or zero_grad() touches them; state_dict() /
+        # load_state_dict() do not carry them either (save model.noise_model.covar_module.state_dict() beside the model's); to(),
+        # train() and eval() are passed on by hand.  `noise_model=` hands an existing noise model over instead of building one, as
+        # `kernel_cache=` hands statistics over: it is how the functional form gives a sibling its clone, and it must be a single-output
+        # model on this model's grid object
+        self.log_noise_mean = float(log_noise_mean)
+        self.last_hetero_sites = None                # (e, ytilde_g, tau_g, log_z_g, log_z_y) [q] of the last batch absorbed heteroscedastically
+        if not math.isfinite(self.log_noise_mean):
+            raise ValueError(f"log_noise_mean must be finite, got {log_noise_mean}")
+        if noise_model is None and not heteroscedastic and (noise_kernel is not None or self.log_noise_mean != 0.0):
+            raise ValueError("noise_kernel / log_noise_mean describe the noise model of heteroscedastic=True")
+        if heteroscedastic or noise_model is not None:
+            self._refuse_for_hetero_model()
+            if noise_model is None:
+                noise_model = self._new_noise_model(noise_kernel)
+            if noise_model.num_outputs != 1 or noise_model._grid is not self._grid:
+                raise ValueError("noise_model must be a single-output model on this model's grid object (build it on covar_module.grid_spec)")
+        object.__setattr__(self, "noise_model", noise_model)
 
     # ------------------------------------------------------------ helpers --
     @staticmethod
@@ -882,6 +909,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         if self.window is not None:
             raise NotImplementedError("window does not combine with enter_stencil_shard: the window absorb writes every stencil group")
         self._refuse_trend("enter_stencil_shard", "the trend's solve columns S = M C need the whole stencil at every refresh")
+        if self.noise_model is not None:
+            raise NotImplementedError("heteroscedastic does not combine with enter_stencil_shard: its launch writes every stencil group of both models")
         op = _wtw_ops(self._kernel_cache["WtW"])[0]
         if (world <= 1 and not comm) or self.num_outputs != 1 or self._use_dense() or not op.is_half or self._grid.m % 4 or op.root is not None:
             return False
@@ -1278,6 +1307,12 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         self._dump_caches()
 
     # -------------------------------------------------------------- forward --
+    def train(self, mode=True):
+        """As torch's, and the noise model -- held outside the module tree -- follows."""
+        if self.__dict__.get("noise_model") is not None:
+            self.noise_model.train(mode)
+        return super().train(mode)
+
     def forward(self, X, **kwargs):
         if self.training:
             return self._train_forward(X)
@@ -1540,7 +1575,21 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         (``_condition_labels``).  Every point is moment-matched against the C posteriors before the batch and output c
         takes it as the pseudo-target ``ytilde_ci`` at noise ``noise_i / omega_ci``, all outputs in one launch; ``last_label_sites``
         holds ``(ytilde [C, n], omega [C, n], log_z [n])``.  A class far below the label's says nothing and is skipped for its output
-        alone; a label that is no class skips the point.  ``num_data`` grows by the points whose label class entered.  Unbatched X."""
+        alone; a label that is no class skips the point.  ``num_data`` grows by the points whose label class entered.  Unbatched X.
+
+        On a model built with ``heteroscedastic=True`` the noise of a point is ``sigma2 noise_i exp g(x_i)``, g the field of
+        ``noise_model`` (``_condition_hetero``): against the two posteriors before the batch a point enters f as ``Y_i``
+        at noise ``noise_i e_i``, ``e = E[exp g]``, and its squared residual, deflated by the share that is f's own uncertainty, enters
+        the noise model as a log-variance site, both in one launch; ``last_hetero_sites`` holds ``(e, ytilde_g, tau_g, log_z_g, log_z_y)``.
+        Targets ``Y`` with ``noise`` at most, no other form in the same call.  Single output, unbatched X."""
+        if self.noise_model is not None:
+            given = dict(grad_Y=grad_Y, grad_noise=grad_noise, grad_mask=grad_mask, lower=lower, upper=upper, counts=counts, exposure=exposure,
+                         trials=trials, input_var=input_var, grad_lower=grad_lower, grad_upper=grad_upper, labels=labels)
+            others = [k for k, v in given.items() if v is not None]
+            if others:
+                raise NotImplementedError(f"a heteroscedastic model takes targets Y, with noise at most: no {', '.join(others)} (the noise "
+                                          "site is that of a Gaussian residual, and no kernel applies two forms in one launch)")
+            return self._condition_hetero(X, Y, noise, inplace, _decay)
         if labels is not None:
             given = dict(Y=Y, grad_Y=grad_Y, grad_noise=grad_noise, grad_mask=grad_mask, lower=lower, upper=upper, counts=counts, exposure=exposure,
                          trials=trials, input_var=input_var, grad_lower=grad_lower, grad_upper=grad_upper)
@@ -1679,6 +1728,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             trend_prior_var=self.trend_prior_var,        # (the degree travels with the cache)
             input_var=self.input_var,
             input_noise_slope=self.input_noise_slope,
+            log_noise_mean=self.log_noise_mean,
+            noise_model=self._noise_sibling(),
         )
         new_gp._win_voids, new_gp._win_updates = self._win_voids, self._win_updates
         new_gp._wsum_dev = self._wsum_dev.clone()
@@ -1910,6 +1961,155 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             cache, X, None, src, "count observations", half_delta=half_delta,
             launch=lambda X, *rest, **kw: grid_ops.scatter_stats_count(self._grid, X, y, t, family, *rest, **kw))
         return grown
+
+    # ------------------------------------------------ heteroscedastic noise --
+    def _refuse_for_hetero_model(self):
+        """What heteroscedastic=True does not combine with, each with its reason."""
+        if self.num_outputs > 1:
+            raise NotImplementedError("heteroscedastic is implemented for a single output (one noise field, one residual per point)")
+        if self.robust_c is not None:
+            raise NotImplementedError("heteroscedastic does not combine with robust_c: a large residual is either noise to be learned or an "
+                                      "outlier to be down-weighted, and no kernel decides both")
+        if self.window is not None:
+            raise NotImplementedError("heteroscedastic does not combine with window: the ring stores the weights of one model, and a noise "
+                                      "site depends on the posteriors it was matched against")
+        if self._trend_deg is not None:
+            self._refuse_trend("heteroscedastic", "the residual is taken against the grid mean alone, which under a trend is not the predictive mean")
+        if self.input_var is not None:
+            raise NotImplementedError("heteroscedastic does not combine with input_var: no kernel applies both forms in one launch")
+
+    def _new_noise_model(self, noise_kernel):
+        """The model of g - log_noise_mean: a single output on THIS model's grid object with empty statistics, sigma2 = 1 and unit
+        weights.  noise_kernel None: a deep copy of this model's base kernel -- the same class, its own parameters."""
+        import copy
+
+        g = self._grid
+        if noise_kernel is None:
+            noise_kernel = copy.deepcopy(self.covar_module.base_kernel)
+        if not isinstance(noise_kernel, GridInterpolationKernel):
+            noise_kernel = GridInterpolationKernel(base_kernel=noise_kernel, grid_size=8, num_dims=g.d, grid_bounds=[list(b) for b in g.grid_bounds])
+        noise_kernel.set_grid_spec(g)
+        z = lambda *shape, dtype=self._dtype: torch.zeros(shape, dtype=dtype, device=self._device)
+        pack = z(1, (g.R + 1) // 2, g.m)
+        cache = self._pack_cache(z(1, g.m, 1), z(1, 2, dtype=torch.float64), [StencilWtW(g, pack[0])], z(1, g.m))
+        nm = FixedNoiseOnlineSKIGP(covar_module=noise_kernel, kernel_cache=cache, likelihood=self.likelihood, learn_additional_noise=False, num_data=0)
+        if nm._trend_deg is not None or nm.num_outputs != 1:
+            raise NotImplementedError("the noise model is a single output without a trend")
+        return nm
+
+    def _noise_sibling(self):
+        """The noise model of a functional sibling: a clone of its statistics on the same kernel, with this one's mean state."""
+        nm = self.noise_model
+        if nm is None:
+            return None
+        sib = nm._sibling(nm._clone_cache(nm._kernel_cache), nm.num_data)
+        nm._sibling_mean_state(sib)
+        return sib
+
+    def _log_noise_state(self, X, want_mean=False):
+        """(u_g [m], v_g [n]) of g - log_noise_mean under the noise model's current posterior at X [n, d] -- the prior's while it holds
+        nothing (no solve on empty statistics) -- and, with want_mean, w . u_g [n] as well."""
+        nm = self.noise_model
+        if not nm.num_data:
+            u = torch.zeros(self._grid.m, dtype=self._dtype, device=self._device)
+            var = InterpolatedKernel(self._grid, X, nm._hyper()[0][0], 1.0, nm._err).diag()
+            mean = torch.zeros(X.shape[0], dtype=self._dtype, device=self._device)
+        else:
+            u = nm.prediction_cache["pred_mean"][0, :, 0]
+            with torch.no_grad(), settings.skip_posterior_variances(False):
+                mvn = nm._eval_forward(X)
+                mean, var = mvn.mean.reshape(-1), mvn.variance
+        var = var.reshape(-1).to(self._dtype).clamp_min(0.0).contiguous()
+        return (u, var, mean.to(self._dtype)) if want_mean else (u, var)
+
+    def _condition_hetero(self, X, Y, noise, inplace, _decay):
+        """condition_on_observations of a heteroscedastic model: grow, decay, weigh and match, absorb -- both models
+        together.  Everything is taken against the two posteriors of the statistics the batch is added to."""
+        if Y is None:
+            raise ValueError("a heteroscedastic model takes targets Y")
+        if X.dim() > 2 or Y.dim() > 2:
+            raise NotImplementedError("batched conditioning (fantasies) of a heteroscedastic model: a fantasy batch carries the statistics of f "
+                                      "alone, and its noise would have to be fantasised with it")
+        if self.__dict__.get("_stencil_shard") is not None:
+            raise NotImplementedError("heteroscedastic does not follow a stencil shard: the launch writes every group of both models")
+        X = X.reshape(-1, self._grid.d)
+        n = X.shape[0]
+        Y = Y.reshape(-1)
+        if Y.shape[0] != n:
+            raise ValueError(f"Y must hold one target per point ([{n}]), got {tuple(Y.shape)}")
+        if noise is not None:
+            noise = noise.to(self._device, self._dtype).reshape(-1)
+            if noise.shape[0] != n:
+                raise ValueError(f"noise must hold one value per point ([{n}]), got {tuple(noise.shape)}")
+        if self.grow_grid:
+            self.grow_to_cover_(X)
+        return self._condition(lambda model, cache, src: model._absorb_hetero(cache, X, Y, noise, src), inplace, self._gamma(_decay), reads_posterior=True)
+
+    def _absorb_hetero(self, cache, X, Y, noise, src):
+        """_absorb of one batch into BOTH models, one launch (wiski_scatter_stats_hetero).  `src`: the model whose posteriors -- its own
+        and its noise model's -- everything is taken against: this one, or in the functional form without a decay the parent.  f is
+        followed with (wa omega_f, y wb omega_f), omega_f = 1 / e; the noise model with its sites at unit weights.  Returns what
+        num_data grows by: the points that entered f and those outside the grid (which _raise_out_of_bounds takes off again)."""
+        form = "heteroscedastic observations"
+        nm = self.noise_model
+        ncache = nm._kernel_cache
+        op, nop = self._native_half_op(cache, form), nm._native_half_op(ncache, form + " (the noise model)")
+        X, y, no, wa, wb = self._canon_batch(X, Y, noise)
+        u = src.prediction_cache["pred_mean"][0, :, 0]       # (finishes whatever is pending, leaves a stencil shard)
+        with torch.no_grad(), settings.skip_posterior_variances(False):
+            pvar = src._eval_forward(X).variance.reshape(-1).to(self._dtype).contiguous()
+        u2, pvar2 = src._log_noise_state(X)
+        (b, A, cnt, stats, err, _), res = self._site_targets(cache, op, u)
+        (b2, A2, cnt2, stats2, _, _), res2 = nm._site_targets(ncache, nop, u2)
+        flag0 = self._err.clone()
+        g0 = self.log_noise_mean
+        sites = grid_ops.scatter_stats_hetero(self._grid, X, y, pvar, pvar2, self._sigma2(0), g0, wa, wb, no, (b, A, cnt, stats, u, res),
+                                              (b2, A2, cnt2, stats2, u2, res2), err)
+        self.last_hetero_sites = sites
+        if not X.shape[0]:
+            return 0
+        e, yt, tau, _, lzy = sites
+        in_f = (e > 0) & torch.isfinite(lzy)
+        omega_f = torch.where(in_f, 1.0 / e.clamp_min(torch.finfo(self._dtype).tiny), torch.zeros_like(e))
+        self._follow_sites(cache, X, wa, wb, torch.where(in_f, y, torch.zeros_like(y)), omega_f)
+        one = nm._ones(X.shape[0])
+        nm._follow_sites(ncache, X, one, one, torch.where(tau > 0, yt - g0, torch.zeros_like(yt)), tau)
+        entered, entered_g, dropped = torch.stack([in_f.sum(), (tau > 0).sum(), (self._err - flag0).reshape(-1)[0] >> 1]).tolist()
+        nm.num_data = (nm.num_data or 0) + int(entered_g)
+        nm._dump_caches()
+        return int(entered) + int(dropped)
+
+    def _require_hetero(self, what):
+        if self.noise_model is None:
+            raise RuntimeError(f"{what} needs a model built with heteroscedastic=True")
+
+    def noise_posterior(self, X):
+        """(mean [n], variance [n]) of g(X) = log of the noise multiplier under the noise model's posterior."""
+        self._require_hetero("noise_posterior")
+        X = X.reshape(-1, self._grid.d).to(self._device, self._dtype).contiguous()
+        _, var, mean = self._log_noise_state(X, want_mean=True)
+        return mean + self.log_noise_mean, var
+
+    def predict_noise(self, X, noise=None):
+        """E[sigma2 noise exp g(X)] [n]: the noise variance a point at X is expected to carry (``noise`` None: 1)."""
+        mean, var = self.noise_posterior(X)
+        e = torch.exp(mean.double() + 0.5 * var.double()) * self._sigma2(0)
+        return (e if noise is None else e * noise.to(self._device).reshape(-1).double()).to(self._dtype)
+
+    def predictive(self, X, noise=None):
+        """(mean [n], variance [n]) of a target at X: the posterior of f plus the predicted noise."""
+        self._require_hetero("predictive")
+        Xf = X.reshape(-1, self._grid.d).to(self._device, self._dtype).contiguous()
+        with torch.no_grad(), settings.skip_posterior_variances(False):
+            mvn = self._eval_forward(Xf)
+            mean, var = mvn.mean.reshape(-1), mvn.variance.reshape(-1).clamp_min(0.0)
+        return mean, var + self.predict_noise(Xf, noise)
+
+    def hetero_log_probability(self, X, Y, noise=None):
+        """log N(Y; predictive mean, predictive variance) [n] float64 of held-out targets."""
+        mean, var = self.predictive(X, noise)
+        mean, var, y = mean.double(), var.double(), Y.to(self._device).reshape(-1).double()
+        return -0.5 * torch.log(2.0 * math.pi * var) - 0.5 * (y - mean) ** 2 / var
 
     # ---------------------------------------------- categorical observations --
     def _label_noise(self, noise, n):
@@ -2398,6 +2598,9 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         fallback -- but on large single-output grids the three launches go through ONE C-ABI call (``wiski_stream_step``) with
         the per-step host work reduced to bookkeeping.  Unit noise.  Returns the mean [n] (or None).  With a ``forgetting_factor``
         the statistics decay between the evaluation and the absorb (one more launch, ``wiski_decay_stats``)."""
+        if self.noise_model is not None:
+            raise NotImplementedError("stream_step on a heteroscedastic model: the fused step absorbs at unit noise -- use "
+                                      "condition_on_observations(X, Y, inplace=True), which learns the noise in its launch")
         if self.grow_grid:
             self.grow_to_cover_(X)
         gamma = self._gamma()
@@ -2794,6 +2997,9 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             from .fantasy import BatchedFantasyModel
 
             self._refuse_trend("batched conditioning (fantasies)", "a fantasy batch carries A and b only, not the trend statistics")
+            if self.noise_model is not None:
+                raise NotImplementedError("batched conditioning (fantasies) of a heteroscedastic model: a fantasy batch carries the statistics "
+                                          "of f alone, and its noise would have to be fantasised with it")
             return BatchedFantasyModel(self, inputs, targets, noise_term)
         if targets.dim() == 1:
             targets = targets[:, None]
@@ -2802,7 +3008,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         return self.condition_on_observations(inputs, targets, noise_term, inplace=False, _decay=False)   # a what-if on the current state
 
     # ------------------------------------------------------------ regridding --
-    def regrid_(self, below, above, drop="zero"):
+    def regrid_(self, below, above, drop="zero", _grid=None):
         """Grow, shift or trim the inducing grid by whole nodes, in place and exactly: ``below[q]`` nodes are added in
         front of dim q and ``above[q]`` behind it (ints or per-dim sequences, negative: removed) at unchanged spacing,
         ``GridSpec.shifted``.  A, b, cnt and the path probes are the old arrays at an index shift (new nodes hold zeros) and move in ONE
@@ -2819,11 +3025,16 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         preconditioner, streaming-step cache, PCG workspace, the warm-start state of the mean solve); the regime (dense / PCG) is
         re-decided from the new m.  The kernel module receives the new grid: sibling models that share ``covar_module`` (functional
         ``condition_on_observations``) must not be used afterwards.  Returns the model for ``drop="zero"`` (as ``forget_`` does) and
-        ``(model, dropped_mass)`` -- a float, summed over the outputs -- for ``drop="any"``."""
+        ``(model, dropped_mass)`` -- a float, summed over the outputs -- for ``drop="any"``.
+
+        The noise model of a heteroscedastic model follows by the same nodes, with the same ``drop``, and is handed this model's new grid
+        object (`_grid`: the hand-over).  Its sites sit where f's points do, so ``drop="zero"`` cannot fail on it once f has passed; what
+        ``drop="any"`` cut from it is ``model.noise_model.last_regrid_dropped_mass`` (in the noise model's own units, not added to the
+        float returned)."""
         if drop not in ("zero", "any"):
             raise ValueError(f'drop must be "zero" or "any", got {drop!r}')
         old = self._grid
-        new = old.shifted(below, above)
+        new = old.shifted(below, above) if _grid is None else _grid
         a = [int(below)] * old.d if isinstance(below, int) else [int(v) for v in below]
         bb = [gn - go - aq for gn, go, aq in zip(new.g, old.g, a)]
         if not any(a) and not any(bb):
@@ -2892,6 +3103,15 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         self._mean_state = None                        # (Z = Kt^-1 U does not embed: the next solve starts cold)
         self._last_iters = None
         self.__dict__["_regrid_count"] = self.__dict__.get("_regrid_count", 0) + 1
+        if self.noise_model is not None:
+            # the noise model follows by the same nodes and the same rule, on this model's new grid object: operators, kernel and model
+            # all hold `new` itself (its sites sit where f's points do: A_ii of f is zero wherever its own is)
+            nm = self.noise_model
+            nm.last_regrid_dropped_mass = 0.0
+            if drop == "zero":
+                nm.regrid_(below, above, _grid=new)
+            else:
+                nm.last_regrid_dropped_mass = nm.regrid_(below, above, drop="any", _grid=new)[1]
         return self if drop == "zero" else (self, float(sum(mass)))
 
     def grow_to_cover_(self, X, margin_nodes=1):
@@ -2987,12 +3207,30 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             self._memo.pop("root_space", None)
         else:
             self._dump_caches()
+        if self.noise_model is not None:             # the noise sites age with the points they were taken from
+            self.noise_model._decay(gamma, self.noise_model.num_data or 0)
 
     def set_train_data(self, train_inputs, train_targets, train_noise_term):
         """:420-428 -- rebuild every statistic from scratch."""
         if train_targets.dim() == 1:
             train_targets = train_targets[:, None]
         noise = self._canon_noise(train_noise_term, train_targets)
+        cache = self._clear_statistics()
+        if self.noise_model is not None:             # (the data is absorbed plainly, as the initial data is: the noise model starts empty)
+            nm = self.noise_model
+            nm._clear_statistics()
+            nm.num_data, nm._mean_state = 0, None
+            nm._dump_caches()
+        if self.window is not None:
+            self._window_restart(train_inputs, train_targets, noise)     # the last `window` points only
+        else:
+            self._absorb(cache, train_inputs, train_targets, noise, init=True)
+            self.num_data = train_inputs.reshape(-1, self._grid.d).shape[0]
+        self._mean_state = None
+        self._dump_caches()
+
+    def _clear_statistics(self):
+        """Zero every streamed statistic and drop what was derived from them; returns the kernel cache."""
         self._finish_pending()                      # a deferred solve must not be resumed on zeroed statistics
         self._stream_step_cache = None
         cache = self._kernel_cache
@@ -3012,16 +3250,12 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         self._wsum_dirty = False
         self._memo.pop("precond", None)
         self._drop_spectral()
-        if self.window is not None:
-            self._window_restart(train_inputs, train_targets, noise)     # the last `window` points only
-        else:
-            self._absorb(cache, train_inputs, train_targets, noise, init=True)
-            self.num_data = train_inputs.reshape(-1, self._grid.d).shape[0]
-        self._mean_state = None
-        self._dump_caches()
+        return cache
 
     def to(self, *args, **kwargs):
         res = super().to(*args, **kwargs)
+        if self.noise_model is not None:             # (not a registered submodule: it is moved by hand)
+            self.noise_model.to(*args, **kwargs)
         device = None
         for a in args:
             if isinstance(a, (str, torch.device)):

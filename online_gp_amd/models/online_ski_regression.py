@@ -3,7 +3,8 @@
 
     OnlineSKIRegression(stem, init_x, init_y, lr, grid_size, grid_bound, covar_module=None, **kw)
         (**kw: num_path_probes, path_seed, forgetting_factor, grow_grid, max_grid_size, robust_c, robust_scale, window,
-        window_rebuild_every, input_var, input_noise_slope -- passed to the GP; input_var needs the Identity stem)
+        window_rebuild_every, input_var, input_noise_slope, heteroscedastic, noise_kernel, log_noise_mean -- passed to the GP;
+        input_var needs the Identity stem; with heteroscedastic=True ``predict`` and ``evaluate`` use the noise the GP has learned)
     .fit(x, y, num_epochs, test_dataset=None) -> list of per-epoch dicts
     .update(x, y, update_stem=True, update_gp=True) -> (stem_loss, gp_loss)
     .evaluate(x, y) -> (rmse, nll)        .predict(x) -> (mean [n, out], var [n, out])
@@ -51,6 +52,8 @@ class OnlineSKIRegression(StreamingSKIWrapper):
             robust_c=kwargs.get("robust_c"), robust_scale=kwargs.get("robust_scale", "noise"),
             window=kwargs.get("window"), window_rebuild_every=kwargs.get("window_rebuild_every"),
             input_var=kwargs.get("input_var"), input_noise_slope=kwargs.get("input_noise_slope", "posterior"),
+            heteroscedastic=kwargs.get("heteroscedastic", False), noise_kernel=kwargs.get("noise_kernel"),
+            log_noise_mean=kwargs.get("log_noise_mean", 0.0),
         )
         self._setup(stem, gp, lr, init_x)
 
@@ -64,6 +67,9 @@ class OnlineSKIRegression(StreamingSKIWrapper):
     # ----- prediction
     def predict(self, inputs):
         self._ensure_eval()
+        if self.gp.noise_model is not None:                      # heteroscedastic: the noise is the learned field's
+            mean, var = self.gp.predictive(self.stem(self._as_rows(inputs)))
+            return mean.reshape(-1, 1), var.reshape(-1, 1)
         post = self(inputs)
         mean, var = post.mean, post.variance
         if self.target_dim > 1:                                  # the GP lays several outputs out as [out, n]
@@ -117,11 +123,12 @@ class OnlineSKIRegression(StreamingSKIWrapper):
         inputs = self._as_rows(inputs)
         targets = targets.reshape(-1, self.target_dim)
         self._ensure_eval()
-        fast = self._evaluate_from_factor(inputs, targets)
+        hetero = self.gp.noise_model is not None                 # (the fused metrics take one sigma2: the learned noise goes through predict)
+        fast = None if hetero else self._evaluate_from_factor(inputs, targets)
         if fast is not None:
             return fast
         per_batch = []
-        fused = self.target_dim == 1 and inputs.is_cuda
+        fused = self.target_dim == 1 and inputs.is_cuda and not hetero
         # the out-of-grid check of the queries is read together with the metrics (ONE host sync at the end instead of one inside
         # every posterior call plus one for the metrics: each sync leaves the GPU idle until the host has queued the next launch)
         late_check = fused and settings.deferred_bounds_check.off()
