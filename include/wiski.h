@@ -592,6 +592,52 @@ int wiski_absorb_count_f64(const wiski_grid* grid, const wiski_absorb_args* args
 int wiski_count_sites_f32(const float* d_mu, const float* d_pvar, const float* d_y, const float* d_t, int family, int64_t n, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, void* stream);
 int wiski_count_sites_f64(const double* d_mu, const double* d_pvar, const double* d_y, const double* d_t, int family, int64_t n, double* d_ytilde_out, double* d_omega_out, double* d_logz_out, void* stream);
 
+/* Revisiting stored sites: expectation-propagation sweeps over a ring of interval and count observations.  The
+ * two forms above match a point once and never look at it again.  A ring of `cap` slots, nine device arrays the caller owns and
+ * fills, remembers such points: d_x [cap, d], the two data numbers d_d0 / d_d1 [cap] ((lo, hi) of an interval, (count, exposure)
+ * or (count, trials) of a count), d_noise / d_wa / d_wb [cap], the site d_ytilde / d_omega [cap] the point is in the statistics
+ * with (omega = 0: it was skipped and nothing of it is there) -- all in the working precision -- and int32 d_form [cap], one of
+ * the codes below.  ONE launch revisits the slots whose code is `form`; a sweep over a ring that holds several forms is one launch
+ * per form, every one with the same d_u and d_pvar.  With dn = sigma2 noise, tau = omega / dn, nu = tau ytilde, mu = w . u and
+ * v = d_pvar[s] the posterior variance of f at the slot's point under the CURRENT statistics,
+ *   cavity:  p = 1 / v - tau,   v_ = 1 / p,   mu_ = v_ (mu / v - nu),
+ *   fresh:   (ytilde', omega', log Z') = the site of wiski_scatter_stats_interval / _count at (mu_, v_, dn),
+ *   damped:  tau_new = (1 - damping) tau + damping omega' / dn,   nu_new = (1 - damping) nu + damping (omega' / dn) ytilde',
+ *            omega_new = dn tau_new,   ytilde_new = nu_new / tau_new,
+ * evaluated in double in both precisions, and the slot enters the statistics with the difference of its site: A, cnt with
+ * wa (omega_new - omega_old), b with wb (omega_new ytilde_new - omega_old ytilde_old), the carried residual with that minus
+ * wa (omega_new - omega_old) mu, stats[0] with wb (omega_new ytilde_new^2 - omega_old ytilde_old^2), stats[1] with
+ * log(noise / omega_new) [omega_new > 0] - log(noise / omega_old) [omega_old > 0] -- the differences of the values as the ring holds
+ * them, rounded to the working precision.  The new (ytilde, omega) are written back to the ring.  An omega_new below 1e-12 (the
+ * forms' OMEGA_MIN) becomes exactly 0: the point leaves, ytilde_new = mu.  A slot with omega_old = 0 whose fresh site is positive
+ * enters.  A slot is LEFT EXACTLY AS IT IS -- no atomic, no store to the ring, change 0 -- when it is empty or of another form
+ * (neither output is written for it: the launches of a sweep may share them), when its point lies outside the grid (d_err is not
+ * raised: a stored point), when it holds an exact value (lo == hi), when v is not positive and finite, when p <= 1e-4 / v (the
+ * cavity is a difference of two precisions; below that relative size it is the rounding of d_pvar), or when damping = 0, which
+ * changes nothing bit for bit.  All slots are taken against the same d_u and d_pvar: the result depends neither on the order of the
+ * slots nor on the order of the atomics.
+ * Outputs, per slot of the form: d_change_out [cap] = |omega_new - omega_old| / max(omega_new, omega_old) (0 for a slot left alone),
+ * d_logz_out [cap] (double) = log Z' against the cavity (NaN for a slot left alone).  Required: every ring array, d_pvar, d_u,
+ * d_A_half, d_cnt, d_b, d_stats, d_err, both outputs, a finite sigma2 > 0, 0 <= damping <= 1 and a known form; d_res is optional.
+ * cap = 0 or a ring without a slot of the form does nothing and returns WISKI_OK.  Symmetric half stencil, atomic form, one output,
+ * d = 1..4; anything else is WISKI_E_BADARG before a launch.  wiski_absorb_args has NOT grown: wiski_absorb_revisit takes the record
+ * (its points d_x / d_y / d_wa / d_wb / d_noise / n are not looked at: the points are the ring's slots) plus the revisit arguments, so
+ * that every refused combination (a guard, zero regions, a shard, an owner workspace, nout > 1, channels, a full stencil, d_mean_out)
+ * can be reached and tested. */
+#define WISKI_SITE_EMPTY 0
+#define WISKI_SITE_INTERVAL 1
+#define WISKI_SITE_POISSON 2
+#define WISKI_SITE_BINOMIAL 3
+typedef struct wiski_site_ring {
+  void* d_x; void* d_d0; void* d_d1; void* d_noise; void* d_wa; void* d_wb; void* d_ytilde; void* d_omega;
+  int32_t* d_form;
+  int64_t cap;
+} wiski_site_ring;
+int wiski_revisit_sites_f32(const wiski_grid* grid, const wiski_site_ring* ring, int form, const float* d_pvar, double sigma2, double damping, float* d_b, float* d_A_half, float* d_cnt, const float* d_u, float* d_res, double* d_stats, int32_t* d_err, double* d_logz_out, float* d_change_out, void* stream);
+int wiski_revisit_sites_f64(const wiski_grid* grid, const wiski_site_ring* ring, int form, const double* d_pvar, double sigma2, double damping, double* d_b, double* d_A_half, double* d_cnt, const double* d_u, double* d_res, double* d_stats, int32_t* d_err, double* d_logz_out, double* d_change_out, void* stream);
+int wiski_absorb_revisit_f32(const wiski_grid* grid, const wiski_absorb_args* args, const wiski_site_ring* ring, int form, const float* d_pvar, double sigma2, double damping, double* d_logz_out, float* d_change_out, void* stream);
+int wiski_absorb_revisit_f64(const wiski_grid* grid, const wiski_absorb_args* args, const wiski_site_ring* ring, int form, const double* d_pvar, double sigma2, double damping, double* d_logz_out, double* d_change_out, void* stream);
+
 /* Heteroscedastic absorb: the noise of a point is not known but learned, as a second field on the same grid:
  *   y_p = f(x_p) + eps_p,   eps_p ~ N(0, sigma2 noise_p exp g(x_p)),   g ~ GP(g0, k_g).
  * f and g are two single-output models with a set of statistics each: (d_b, d_A_half, d_cnt, d_stats, d_u, d_res) for f and

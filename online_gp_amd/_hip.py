@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 _SO = os.path.join(_CSRC, "libwiski_hip.so")
 _SOURCES = ["interp_gather.hip", "scatter_stats.hip", "solve.hip", "spectral.hip", "dense.hip", "collective.hip", "stream_step.hip", "spectral_basis.hip", "hyper_columns.hip", "two_level.hip", "hyper_step.hip", "lookahead.hip", "sample_paths.hip", "decay_stats.hip", "regrid_stats.hip", "trend.hip"]
-_HEADERS = ["wiski_common.h", "spmv_sym_dma.h", "spmv_sym_dma_mc.h", "spmm_sym_cols.h", "spmm_sym_bcast.h", "scatter_half.h", "scatter_owner.h", "scatter_grad.h", "scatter_site.h", "scatter_robust.h", "scatter_window.h", "scatter_interval.h", "scatter_count.h", "scatter_hetero.h", "scatter_label.h", "scatter_input_noise.h", "scatter_grad_interval.h", "absorb.h", "dense_small.h", "dense_coop.h",
+_HEADERS = ["wiski_common.h", "spmv_sym_dma.h", "spmv_sym_dma_mc.h", "spmm_sym_cols.h", "spmm_sym_bcast.h", "scatter_half.h", "scatter_owner.h", "scatter_grad.h", "scatter_site.h", "scatter_robust.h", "scatter_window.h", "scatter_interval.h", "scatter_count.h", "scatter_hetero.h", "scatter_label.h", "scatter_input_noise.h", "scatter_grad_interval.h", "scatter_revisit.h", "absorb.h", "dense_small.h", "dense_coop.h",
             os.path.join("..", "..", "include", "wiski.h")]
 MAX_DIM = 4
 
@@ -95,6 +95,19 @@ class wiski_window_ring(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("d_x", "d_y", "d_wa", "d_wb", "d_noise")] + [("cap", ctypes.c_int64), ("head", ctypes.c_int64)]
 
 
+class wiski_site_ring(ctypes.Structure):
+    """The device-resident ring of stored sites (include/wiski.h): nine arrays of `cap` slots."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("d_x", "d_d0", "d_d1", "d_noise", "d_wa", "d_wb", "d_ytilde", "d_omega", "d_form")] + [("cap", ctypes.c_int64)]
+
+
+def _revisit_signatures():
+    """argtypes of the entries of the site revisit (include/wiski.h), as _grad_interval_signatures."""
+    p, f64 = ctypes.c_void_p, ctypes.c_double
+    flat = [ctypes.POINTER(wiski_grid), ctypes.POINTER(wiski_site_ring), ctypes.c_int, p, f64, f64] + [p] * 9 + [p]
+    record = [ctypes.POINTER(wiski_grid), ctypes.POINTER(wiski_absorb_args), ctypes.POINTER(wiski_site_ring), ctypes.c_int, p, f64, f64, p, p, p]
+    return {name + suf: sig for name, sig in (("wiski_revisit_sites", flat), ("wiski_absorb_revisit", record)) for suf in ("_f32", "_f64")}
+
+
 def _grad_interval_signatures():
     """argtypes of the four entries of the channel-interval absorb (include/wiski.h), by name: pointers as
     c_void_p, in the order of the prototypes.  lib() sets them, so that a call with a wrong argument count fails in ctypes."""
@@ -129,6 +142,7 @@ def _hetero_signatures():
 SIGNATURES = _grad_interval_signatures()
 LABEL_SIGNATURES = _label_signatures()
 HETERO_SIGNATURES = _hetero_signatures()
+REVISIT_SIGNATURES = _revisit_signatures()
 
 
 def sources():
@@ -238,7 +252,7 @@ def lib():
         _lib = ctypes.CDLL(_SO)
         _lib.wiski_pcg_workspace_bytes.restype = ctypes.c_int64
         _lib.wiski_twolevel_refresh_workspace_bytes.restype = ctypes.c_int64
-        for name, sig in {**SIGNATURES, **LABEL_SIGNATURES, **HETERO_SIGNATURES}.items():
+        for name, sig in {**SIGNATURES, **LABEL_SIGNATURES, **HETERO_SIGNATURES, **REVISIT_SIGNATURES}.items():
             f = getattr(_lib, name)
             f.argtypes, f.restype = sig, ctypes.c_int
     if hasattr(_lib, "wiski_root_update_workspace_elems"):

@@ -3,9 +3,9 @@
 // may be asked to do, as ONE named record.  Every member defaults to "off"; the extern "C" entry points of scatter_stats.hip
 // and the streaming step (stream_step.hip) fill the fields they expose and call absorb().  Which combinations are refused is
 // absorb_validate() in scatter_stats.hip; whoever writes another form of the absorb has to honour every group below.
-// Six half-stencil kernels stand behind it, besides the full-stencil k_scatter_stats and the owner form (where its workspace is
+// Seven half-stencil kernels stand behind it, besides the full-stencil k_scatter_stats and the owner form (where its workspace is
 // given and applies): the atomic form (k_scatter_stats_sym), the derivative-observation form (`channels`, scatter_grad.h), its
-// interval-site form (`clo`, scatter_grad_interval.h), the sliding-window form (`ring_*`, scatter_window.h), the heteroscedastic form (`b2`, scatter_hetero.h) and the site-weighted form (k_scatter_stats_site, scatter_site.h), which is the
+// interval-site form (`clo`, scatter_grad_interval.h), the sliding-window form (`ring_*`, scatter_window.h), the site-revisiting form (`site_*`, scatter_revisit.h), the heteroscedastic form (`b2`, scatter_hetero.h) and the site-weighted form (k_scatter_stats_site, scatter_site.h), which is the
 // outlier-robust (`inv_scale`, scatter_robust.h), the interval (`lo`, scatter_interval.h), the count (`count_y`, scatter_count.h) or
 // the noisy-input absorb (`xvar`, scatter_input_noise.h) by the site it is given.  What they do per point -- the tap tables, the per-tap atomics, the pair loop that
 // encodes the row-interleaved layout, the two scalars -- is stated once, in scatter_half.h.
@@ -136,15 +136,31 @@ struct AbsorbArgs {
   double g0 = 0;                    // prior mean of g
   real* e_out = nullptr;            // [n] the multiplier each point entered f with; 0 for a point outside the grid
   double* logzy_out = nullptr;      // [n] log N(y; mu_f, v_f + sigma2 noise e) under the posteriors before the batch
+  // revisit: site_codes != NULL makes the launch an expectation-propagation sweep over a ring of stored sites (scatter_revisit.h).
+  // The points ARE the ring's slots: x / wa / wb / noise are its arrays and n its capacity; y is not used.  Every slot whose form code
+  // is site_form_code is re-matched against its cavity under (u, pvar), damped by site_damping, and enters with the difference of
+  // its site; its new (ytilde, omega) are written back to the ring.  A group of its own that shares the interval group's pvar ([n],
+  // at the slots), sigma2 and logz_out ([n], the fresh site's log Z against the cavity; NaN for a slot of the form that was left
+  // alone) and needs them, with u, A, cnt, the whole group, a finite sigma2 > 0 and 0 <= site_damping <= 1; res is optional,
+  // mean_out is not produced; err is never raised (a stored point the grid does not contain is left alone)
+  const real* site_d0 = nullptr;    // [n] lower ends / counts
+  const real* site_d1 = nullptr;    // [n] upper ends / exposure or trials
+  real* site_ytilde = nullptr;      // [n] the pseudo-target each slot is in the statistics with; updated
+  real* site_omega = nullptr;       // [n] its weight (0: the slot's point was skipped and nothing of it is in the statistics); updated
+  const int32_t* site_codes = nullptr; // [n] WISKI_SITE_EMPTY / _INTERVAL / _POISSON / _BINOMIAL
+  int site_form_code = 0;           // the form this launch revisits
+  double site_damping = 0;          // delta; 0 changes nothing bit for bit and issues no atomic
+  real* site_change_out = nullptr;  // [n] |omega_new - omega_old| / max(omega_new, omega_old) of the slots of the form; 0 for one left alone
 
   bool sharded() const { return g_lo > 0 || g_hi < (1 << 30); }
   bool windowed() const { return ring_x || ring_y || ring_wa || ring_wb || ring_noise || ring_cap || ring_head || void_left; }
   bool counted() const { return count_y || count_t || count_family != 0; }
   bool input_noise() const { return xvar || gvar || grad_out; }
-  // (the fields the matched forms share belong to whichever of the count, input-noise, channel-interval and hetero groups is given, else to the interval group)
+  // (the fields the matched forms share belong to whichever of the count, input-noise, channel-interval, hetero and revisit groups is given, else to the interval group)
   bool grad_interval() const { return clo || chi || cpvar; }
   bool hetero() const { return b2 || A2 || cnt2 || stats2 || u2 || res2 || pvar2 || g0 != 0 || e_out || logzy_out; }
-  bool interval() const { return lo || hi || (!counted() && !input_noise() && !grad_interval() && !hetero() && (pvar || sigma2 != 0 || ytilde_out || logz_out)); }
+  bool revisit() const { return site_d0 || site_d1 || site_ytilde || site_omega || site_codes || site_form_code != 0 || site_damping != 0 || site_change_out; }
+  bool interval() const { return lo || hi || (!counted() && !input_noise() && !grad_interval() && !hetero() && !revisit() && (pvar || sigma2 != 0 || ytilde_out || logz_out)); }
   bool site_form() const { return inv_scale || interval() || counted() || input_noise(); }   // the forms of k_scatter_stats_site (scatter_site.h)
 };
 

@@ -183,6 +183,7 @@ __global__ __launch_bounds__(256) void k_scatter_stats_sym(GridDev<real> G, cons
 #include "scatter_label.h"
 #include "scatter_input_noise.h"
 #include "scatter_grad_interval.h"
+#include "scatter_revisit.h"
 
 // Unpacks the row-interleaved half stencil into a full offset-major stencil full[o][i] = A[i, i + off(o)]
 // (diagnostics, tests, and models handed a full-stencil cache):
@@ -250,6 +251,20 @@ static int64_t owner_min_points() {
 template <typename real>
 static int absorb_validate(const AbsorbArgs<real>& a, int d) {
   if (a.n == 0) return WISKI_OK;                       // nothing to absorb: not even the pointers are looked at
+  if (a.revisit()) {
+    // revisit (scatter_revisit.h): the points are the slots of a ring of stored sites -- its x, wa, wb and noise, no y -- and the
+    // launch is the single-output half-stencil atomic sweep with u, A and cnt: the whole group with a known form code, the
+    // posterior variance at the slots, a noise scale, a damping in [0, 1], log Z -- and nothing of any other group: no full stencil,
+    // no channels, no second output, no mean_out, no guard, zero regions, shard or owner workspace
+    if (!a.x || !a.wa || !a.wb || !a.noise || !a.b || !a.stats || !a.err) return WISKI_E_BADARG;
+    if (!a.half || !a.u || !a.A || !a.cnt || a.nout != 1 || a.channels || a.mean_out) return WISKI_E_BADARG;
+    if (!a.site_d0 || !a.site_d1 || !a.site_ytilde || !a.site_omega || !a.site_codes || !a.site_change_out || !a.pvar || !a.logz_out) return WISKI_E_BADARG;
+    if (a.site_form_code != WISKI_SITE_INTERVAL && a.site_form_code != WISKI_SITE_POISSON && a.site_form_code != WISKI_SITE_BINOMIAL) return WISKI_E_BADARG;
+    if (!(a.sigma2 > 0) || !std::isfinite(a.sigma2) || !(a.site_damping >= 0 && a.site_damping <= 1)) return WISKI_E_BADARG;
+    if (a.lo || a.hi || a.ytilde_out || a.omega_out || a.counted() || a.input_noise() || a.grad_interval() || a.hetero() || a.inv_scale || a.huber_c != (real)0 || a.windowed()) return WISKI_E_BADARG;
+    if (a.guard || a.n1_bytes || a.n2_bytes || a.z1 || a.z2 || a.sharded() || a.bin || a.bin_bytes) return WISKI_E_BADARG;
+    return WISKI_OK;
+  }
   if (!a.x || (!a.y && !a.lo && !a.count_y && !a.clo) || !a.wa || !a.wb || !a.noise || !a.b || !a.stats || !a.err) return WISKI_E_BADARG;   // what every form reads and writes (the interval, count and channel-interval forms have no y)
   if (a.hetero()) {
     // heteroscedastic (scatter_hetero.h): the plain single-output half-stencil atomic absorb of y with u, A and cnt, twice -- the whole
@@ -396,6 +411,7 @@ int absorb(const wiski_grid* grid, const AbsorbArgs<real>& a, void* stream) {
   int rc = make_grid_dev<real>(grid, &G);
   if (rc == WISKI_OK) rc = absorb_validate(a, G.d);
   if (rc != WISKI_OK || a.n == 0) return rc;
+  if (a.revisit()) return launch_revisit(G, a, (hipStream_t)stream);
   if (a.hetero()) return launch_hetero(G, a, (hipStream_t)stream);
   if (a.grad_interval()) return launch_grad_site(G, a, (hipStream_t)stream);
   if (a.input_noise()) return launch_site(G, a, SiteInputNoise<real>::of(a, *grid), (hipStream_t)stream);
@@ -575,6 +591,26 @@ template <typename real>
 static int entry_absorb_grad_interval(const wiski_grid* g, const wiski_absorb_args* p, const real* lo, const real* hi, const real* pvar, double sigma2, real* ytilde_out, real* omega_out, double* logz_out, void* s) {
   return p ? entry_grad_interval(g, absorb_args<real>(*p), lo, hi, pvar, sigma2, ytilde_out, omega_out, logz_out, s) : WISKI_E_BADARG;
 }
+// the revisit: the record's points are replaced by the ring's slots (its d_x / d_y / d_wa / d_wb / d_noise / n are not looked at)
+template <typename real>
+static int entry_revisit(const wiski_grid* g, AbsorbArgs<real> a, const wiski_site_ring* r, int form, const real* pvar, double sigma2, double damping, double* logz_out, real* change_out, void* s) {
+  if (!r || r->cap < 0) return WISKI_E_BADARG;
+  a.x = (const real*)r->d_x; a.y = nullptr; a.wa = (const real*)r->d_wa; a.wb = (const real*)r->d_wb; a.noise = (const real*)r->d_noise; a.n = r->cap;
+  a.site_d0 = (const real*)r->d_d0; a.site_d1 = (const real*)r->d_d1; a.site_ytilde = (real*)r->d_ytilde; a.site_omega = (real*)r->d_omega;
+  a.site_codes = r->d_form; a.site_form_code = form; a.site_damping = damping; a.site_change_out = change_out;
+  a.pvar = pvar; a.sigma2 = sigma2; a.logz_out = logz_out;
+  return a.n == 0 || a.site_codes ? absorb(g, a, s) : WISKI_E_BADARG;   // (without the form codes the record would be another form's)
+}
+template <typename real>
+static int entry_revisit_sites(const wiski_grid* g, const wiski_site_ring* r, int form, const real* pvar, double sigma2, double damping, real* b, real* A_half, real* cnt, const real* u, real* res, double* stats, int32_t* err, double* logz_out, real* change_out, void* s) {
+  AbsorbArgs<real> a = absorb_args((const real*)nullptr, (const real*)nullptr, (const real*)nullptr, (const real*)nullptr, (const real*)nullptr, 0, b, A_half, true, stats, err);
+  absorb_carry(a, cnt, u, res);
+  return entry_revisit(g, a, r, form, pvar, sigma2, damping, logz_out, change_out, s);
+}
+template <typename real>
+static int entry_absorb_revisit(const wiski_grid* g, const wiski_absorb_args* p, const wiski_site_ring* r, int form, const real* pvar, double sigma2, double damping, double* logz_out, real* change_out, void* s) {
+  return p ? entry_revisit(g, absorb_args<real>(*p), r, form, pvar, sigma2, damping, logz_out, change_out, s) : WISKI_E_BADARG;
+}
 template <typename real>
 static int entry_plain(const wiski_grid* g, const real* x, const real* y, const real* wa, const real* wb, const real* noise, int64_t n, real* b, real* A, bool half, double* stats, int32_t* err, void* s) {
   return absorb(g, absorb_args(x, y, wa, wb, noise, n, b, A, half, stats, err), s);
@@ -649,6 +685,10 @@ int wiski_scatter_stats_grad_interval_f32(const wiski_grid* g, const float* x, c
 int wiski_scatter_stats_grad_interval_f64(const wiski_grid* g, const double* x, const double* lo, const double* hi, const double* pvar, double sigma2, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return entry_scatter_grad_interval(g, x, lo, hi, pvar, sigma2, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, ytilde_out, omega_out, logz_out, s); }
 int wiski_absorb_grad_interval_f32(const wiski_grid* g, const wiski_absorb_args* p, const float* lo, const float* hi, const float* pvar, double sigma2, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return entry_absorb_grad_interval(g, p, lo, hi, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
 int wiski_absorb_grad_interval_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* lo, const double* hi, const double* pvar, double sigma2, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return entry_absorb_grad_interval(g, p, lo, hi, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
+int wiski_revisit_sites_f32(const wiski_grid* g, const wiski_site_ring* ring, int form, const float* pvar, double sigma2, double damping, float* b, float* A_half, float* cnt, const float* u, float* res, double* stats, int32_t* err, double* logz_out, float* change_out, void* s) { return entry_revisit_sites(g, ring, form, pvar, sigma2, damping, b, A_half, cnt, u, res, stats, err, logz_out, change_out, s); }
+int wiski_revisit_sites_f64(const wiski_grid* g, const wiski_site_ring* ring, int form, const double* pvar, double sigma2, double damping, double* b, double* A_half, double* cnt, const double* u, double* res, double* stats, int32_t* err, double* logz_out, double* change_out, void* s) { return entry_revisit_sites(g, ring, form, pvar, sigma2, damping, b, A_half, cnt, u, res, stats, err, logz_out, change_out, s); }
+int wiski_absorb_revisit_f32(const wiski_grid* g, const wiski_absorb_args* p, const wiski_site_ring* ring, int form, const float* pvar, double sigma2, double damping, double* logz_out, float* change_out, void* s) { return entry_absorb_revisit(g, p, ring, form, pvar, sigma2, damping, logz_out, change_out, s); }
+int wiski_absorb_revisit_f64(const wiski_grid* g, const wiski_absorb_args* p, const wiski_site_ring* ring, int form, const double* pvar, double sigma2, double damping, double* logz_out, double* change_out, void* s) { return entry_absorb_revisit(g, p, ring, form, pvar, sigma2, damping, logz_out, change_out, s); }
 int wiski_scatter_stats_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A, double* stats, int32_t* err, void* s) { return entry_plain(g, x, y, wa, wb, noise, n, b, A, false, stats, err, s); }
 int wiski_scatter_stats_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A, double* stats, int32_t* err, void* s) { return entry_plain(g, x, y, wa, wb, noise, n, b, A, false, stats, err, s); }
 int wiski_scatter_stats_sym_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, double* stats, int32_t* err, void* s) { return entry_plain(g, x, y, wa, wb, noise, n, b, A_half, true, stats, err, s); }

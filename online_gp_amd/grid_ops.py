@@ -839,6 +839,115 @@ def scatter_stats_window(grid, x, y, wa, wb, noise, ring, b, A_half, cnt, stats,
     ring.advance(n)
 
 
+SITE_FORMS = {"interval": 1, "poisson": 2, "binomial": 3}     # WISKI_SITE_INTERVAL, _POISSON, _BINOMIAL (0: an empty slot)
+
+
+class SiteRing:
+    """The device-resident ring of stored sites (``wiski_site_ring``): per slot the point ``x`` [cap, d], its two
+    data numbers ``d0`` / ``d1`` ((lower, upper) of an interval, (count, exposure or trials) of a count), ``noise`` / ``wa`` / ``wb``,
+    the site ``ytilde`` / ``omega`` it is in the statistics with -- all [cap] in the working precision -- and ``form`` [cap] int32
+    (SITE_FORMS; 0: empty).  On the host ``head``, the slot the next stored point takes, ``fill``, the number of slots written so far
+    (at most cap), and ``forms``, the set of form names stored so far (which launches a sweep needs; never shrinks until clear())."""
+
+    _REAL = ("x", "d0", "d1", "noise", "wa", "wb", "ytilde", "omega")
+
+    def __init__(self, cap, d, dtype, device):
+        cap = int(cap)
+        if cap < 1:
+            raise ValueError(f"SiteRing: cap must be at least 1, got {cap}")
+        self.cap, self.d, self.head, self.fill, self.forms = cap, int(d), 0, 0, set()
+        self.x = torch.zeros((cap, self.d), dtype=dtype, device=device)
+        for k in self._REAL[1:]:
+            setattr(self, k, torch.zeros(cap, dtype=dtype, device=device))
+        self.noise.fill_(1)
+        self.form = torch.zeros(cap, dtype=torch.int32, device=device)
+
+    def tensors(self):
+        return tuple(getattr(self, k) for k in self._REAL) + (self.form,)
+
+    def clone(self):
+        new = object.__new__(SiteRing)
+        new.cap, new.d, new.head, new.fill, new.forms = self.cap, self.d, self.head, self.fill, set(self.forms)
+        for k in self._REAL + ("form",):
+            setattr(new, k, getattr(self, k).clone())
+        return new
+
+    def to(self, device):
+        new = self.clone()
+        for k in self._REAL + ("form",):
+            setattr(new, k, getattr(new, k).to(device))
+        return new
+
+    def clear(self):
+        """Every slot empty again."""
+        self.head = self.fill = 0
+        self.forms = set()
+        for t in self.tensors():
+            t.zero_()
+        self.noise.fill_(1)
+
+    def store(self, form, x, d0, d1, noise, wa, wb, ytilde, omega, keep=None):
+        """Write the points into the slots head, head + 1, ... (mod cap) with plain index copies and advance; of more than cap
+        points the last cap are stored.  ``keep`` (bool [n], device): only these are stored -- this costs one host read of their
+        number.  What an overwritten slot held stays in the statistics as it was."""
+        cols = [x.reshape(-1, self.d), d0, d1, noise, wa, wb, ytilde, omega]
+        if keep is not None:
+            idx = torch.nonzero(keep.reshape(-1)).reshape(-1)
+            cols = [c[idx] for c in cols]
+        n = cols[0].shape[0]
+        if n > self.cap:
+            cols = [c[n - self.cap:] for c in cols]
+            n = self.cap
+        if n == 0:
+            return 0
+        slots = (torch.arange(n, device=self.x.device) + self.head) % self.cap
+        for k, c in zip(self._REAL, cols):
+            getattr(self, k)[slots] = c.to(self.x.dtype)
+        self.form[slots] = SITE_FORMS[form]
+        self.forms.add(form)
+        self.head = (self.head + n) % self.cap
+        self.fill = min(self.cap, self.fill + n)
+        return n
+
+    def order(self):
+        """Slot indices of the written slots, oldest first (a host list)."""
+        first = self.head if self.fill == self.cap else 0
+        return [(first + i) % self.cap for i in range(self.fill)]
+
+    def ref(self):
+        return _hip.wiski_site_ring(*(t.data_ptr() for t in self.tensors()), self.cap)
+
+
+def revisit_sites(grid, ring, form, pvar, sigma2, damping, b, A_half, cnt, stats, err, u, res=None, log_z=None, change=None):
+    """One expectation-propagation launch over the stored sites of one form (``wiski_revisit_sites``): every slot
+    of ``ring`` whose form is ``form`` ("interval", "poisson", "binomial") is re-matched against its cavity under the grid mean ``u``
+    [m] and the posterior variance ``pvar`` [cap] of f at the slots' points, damped by ``damping`` in [0, 1], and enters
+    (b, A_half, cnt, stats) -- and the carried residual ``res``, if given -- with the difference of its site; the ring's ytilde /
+    omega are updated in place.  Returns (log_z [cap] float64, change [cap]): log Z of the fresh site against the cavity (NaN for a
+    slot left alone) and |omega_new - omega_old| / max(omega_new, omega_old).  The slots of other forms and empty slots are not
+    written: pass the pair returned by one launch on as ``log_z`` / ``change`` to the next form's launch of the same sweep."""
+    if form not in SITE_FORMS:
+        raise ValueError(f"revisit_sites: form must be one of {sorted(SITE_FORMS)}, got {form!r}")
+    dtype, device = ring.x.dtype, ring.x.device
+    if ring.d != grid.d:
+        raise ValueError(f"revisit_sites: the ring holds {ring.d}-d points, the grid has {grid.d} dims")
+    for name, t, dt in (("pvar", pvar, dtype), ("change", change, dtype), ("log_z", log_z, torch.float64)):
+        if (t is None and name == "pvar") or (t is not None and (tuple(t.shape) != (ring.cap,) or t.dtype != dt)):
+            raise ValueError(f"revisit_sites: {name} must be [{ring.cap}] {dt}, got {None if t is None else (tuple(t.shape), t.dtype)}")
+    if u is None or tuple(u.shape) != (grid.m,) or u.dtype != dtype:
+        raise ValueError(f"revisit_sites: u must be the grid mean [{grid.m}] {dtype}")
+    if log_z is None:
+        log_z = torch.full((ring.cap,), float("nan"), dtype=torch.float64, device=device)
+    if change is None:
+        change = torch.zeros(ring.cap, dtype=dtype, device=device)
+    r = ring.ref()
+    rc = _hip.fn("wiski_revisit_sites", dtype)(grid.ref, ctypes.byref(r), SITE_FORMS[form], _hip.dptr(pvar.contiguous()), float(sigma2), float(damping),
+                                               _hip.dptr(b), _hip.dptr(A_half), _hip.dptr(cnt), _hip.dptr(u), _hip.dptr(res), _hip.dptr(stats),
+                                               _hip.dptr(err), _hip.dptr(log_z), _hip.dptr(change), _hip.stream_ptr(device))
+    _hip.check(rc, "wiski_revisit_sites")
+    return log_z, change
+
+
 def scatter_probes(grid, x, wa, first_index, seed, P, err):
     """P [m, S] += the probe increments sum_i sqrt(wa_i) eps(first_index + i, s) w(x_i) of the points x [q, d]
     (``wiski_scatter_probes``; wa [q] or None = unit weights; the normals are a function of (seed, global point index, s):

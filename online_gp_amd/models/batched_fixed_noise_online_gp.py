@@ -131,6 +131,9 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         noise_kernel=None,
         log_noise_mean=0.0,
         noise_model=None,
+        site_memory=None,
+        site_refine_sweeps=0,
+        site_refine_damping=1.0,
     ):
         super().__init__()
         object.__setattr__(self, "noise_model", None)    # (set at the end: the initial data is absorbed plainly)
@@ -200,6 +203,41 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         self.window_rebuild_every = window_rebuild_every
         self._win_voids = 0                          # void slots of the ring, as far as check_bounds() has been told
         self._win_updates = 0
+        # site memory (refine_sites_): the last `site_memory` interval and count observations are kept, with their sites,
+        # in a device-resident ring, and expectation-propagation sweeps re-match them against their cavities; site_refine_sweeps of them
+        # follow every interval or count update.  None: every path is what it is without the feature
+        if site_memory is not None:
+            if isinstance(site_memory, bool) or int(site_memory) != site_memory or int(site_memory) < 1:
+                raise ValueError(f"site_memory must be an integer >= 1, got {site_memory!r}")
+            site_memory = int(site_memory)
+            if forgetting_factor is not None:
+                raise NotImplementedError("site_memory does not combine with forgetting_factor: a decayed site is no longer the stored one, "
+                                          "and a sweep would take out more than is still in the statistics")
+            if window is not None:
+                raise NotImplementedError("site_memory does not combine with window: the window's ring stores targets, and the moment-matched "
+                                          "forms do not pass through it")
+            if robust_c is not None:
+                raise NotImplementedError("site_memory does not combine with robust_c: a site is a weight already, and no kernel applies both")
+            if trend is not None or (kernel_cache is not None and "trend_C" in kernel_cache):
+                raise NotImplementedError("site_memory does not combine with a trend: a site is matched against the grid mean alone, which "
+                                          "under a trend is not the predictive mean")
+            if heteroscedastic or noise_model is not None:
+                raise NotImplementedError("site_memory does not combine with heteroscedastic: the ring stores the sites of one model, and a "
+                                          "noise site moves with the f site it was deflated by")
+            if int(num_path_probes) > 0 or (kernel_cache is not None and "path_probes" in kernel_cache):
+                raise NotImplementedError("site_memory does not combine with path probes (num_path_probes > 0): a probe increment is random "
+                                          "and cannot follow a site whose weight shrinks")
+        if isinstance(site_refine_sweeps, bool) or int(site_refine_sweeps) != site_refine_sweeps or int(site_refine_sweeps) < 0:
+            raise ValueError(f"site_refine_sweeps must be an integer >= 0, got {site_refine_sweeps!r}")
+        site_refine_damping = float(site_refine_damping)
+        if not (0.0 <= site_refine_damping <= 1.0):
+            raise ValueError(f"site_refine_damping must lie in [0, 1], got {site_refine_damping}")
+        if site_memory is None and (int(site_refine_sweeps) != 0 or site_refine_damping != 1.0):
+            raise ValueError("site_refine_sweeps / site_refine_damping describe the sweeps of site_memory, which was not given")
+        self.site_memory = site_memory
+        self.site_refine_sweeps = int(site_refine_sweeps)
+        self.site_refine_damping = site_refine_damping
+        self.last_refined_sites = None               # (ytilde, omega, log_z) over the filled slots, oldest first, after the last sweep
 
         if train_targets is not None:
             if train_targets.dim() == 1:
@@ -219,6 +257,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             raise NotImplementedError("robust_c is implemented for a single output (the robust absorb weights one target per point)")
         if window is not None and num_outputs > 1:
             raise NotImplementedError("window is implemented for a single output (the ring stores one target per point)")
+        if site_memory is not None and num_outputs > 1:
+            raise NotImplementedError("site_memory is implemented for a single output (the interval and count forms it stores are)")
         if window is not None and (int(num_path_probes) > 0 or (kernel_cache is not None and "path_probes" in kernel_cache)):
             raise NotImplementedError("window does not combine with path probes (num_path_probes > 0): a probe increment is random and "
                                       "cannot be taken out again from the ring")
@@ -320,12 +360,18 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
 
         if kernel_cache is None:
             self._kernel_cache = self._fresh_cache()
+            if site_memory is not None:                  # (the initial data are values: they take their usual path and are not stored)
+                self._kernel_cache["_site_ring"] = grid_ops.SiteRing(site_memory, self._grid.d, dtype, device)
             if window is not None:
                 self._kernel_cache["_ring"] = grid_ops.WindowRing(window, self._grid.d, dtype, device)
                 self._window_restart(train_inputs, train_targets, train_noise_term)
             else:
                 self._absorb(self._kernel_cache, train_inputs, train_targets, train_noise_term, init=True)
         else:
+            if site_memory is not None and (kernel_cache.get("_site_ring") is None or kernel_cache["_site_ring"].cap != site_memory):
+                raise ValueError(f"site_memory={site_memory}, but the kernel cache handed over carries "
+                                 + ("no site ring: statistics do not remember their points" if kernel_cache.get("_site_ring") is None
+                                    else f"a site ring of {kernel_cache['_site_ring'].cap} slots"))
             if window is not None and (kernel_cache.get("_ring") is None or kernel_cache["_ring"].cap != window):
                 raise ValueError(f"window={window}, but the kernel cache handed over carries "
                                  + ("no ring: statistics do not remember their points" if kernel_cache.get("_ring") is None
@@ -442,6 +488,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             new.update(path_probes=cache["path_probes"].clone(), path_seed=cache["path_seed"], path_count=cache["path_count"])
         if cache.get("_ring") is not None:              # the window's points follow the statistics they are the points of
             new["_ring"] = cache["_ring"].clone()
+        if cache.get("_site_ring") is not None:         # the stored sites follow the statistics they are in
+            new["_site_ring"] = cache["_site_ring"].clone()
         new.update(self._trend_entries(cache, move=torch.clone))    # a child's increments never reach the parent's statistics
         facs = cache.get("_spectral")
         if facs:
@@ -489,6 +537,9 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         if self.window is not None and half_delta is not None:
             raise NotImplementedError("window does not follow the data-parallel statistics exchange (half_delta): the ring of a replica "
                                       "would hold its own shard only, and what leaves must leave every replica")
+        if self.site_memory is not None and half_delta is not None:
+            raise NotImplementedError("site_memory does not follow the data-parallel statistics exchange (half_delta): the ring of a replica "
+                                      "would hold its own shard only, and a sweep must move every replica's statistics")
         if self._trend_deg is not None and half_delta is not None:
             # (keyed on the model, as robust_c and window are: the updater absorbs into a delta dict of its own, which carries no trend entries)
             raise NotImplementedError("trend does not follow the data-parallel statistics exchange (half_delta): the deltas that are "
@@ -908,6 +959,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         the LDS-window kernel restricted to the replica's group range."""
         if self.window is not None:
             raise NotImplementedError("window does not combine with enter_stencil_shard: the window absorb writes every stencil group")
+        if self.site_memory is not None:
+            raise NotImplementedError("site_memory does not combine with enter_stencil_shard: a sweep of refine_sites_ writes every stencil group")
         self._refuse_trend("enter_stencil_shard", "the trend's solve columns S = M C need the whole stencil at every refresh")
         if self.noise_model is not None:
             raise NotImplementedError("heteroscedastic does not combine with enter_stencil_shard: its launch writes every stencil group of both models")
@@ -1725,6 +1778,9 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             robust_scale=self.robust_scale,
             window=self.window,
             window_rebuild_every=self.window_rebuild_every,
+            site_memory=self.site_memory,
+            site_refine_sweeps=self.site_refine_sweeps,
+            site_refine_damping=self.site_refine_damping,
             trend_prior_var=self.trend_prior_var,        # (the degree travels with the cache)
             input_var=self.input_var,
             input_noise_slope=self.input_noise_slope,
@@ -1861,7 +1917,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
 
     # ------------------------------------------------ interval observations --
     def _refuse_for_sites(self, X, form, given):
-        """What a moment-matched form (`form` observations, given as `given`) does not combine with."""
+        """What a moment-matched form (`form` observations, given as `given`) does not combine with.  (A site is matched once and never
+        revisited -- unless the model keeps it: site_memory and refine_sites_, DESIGN.md 3.28, which has refusals of its own.)"""
         if self.num_outputs > 1:
             raise NotImplementedError(f"{form} observations are implemented for a single output")
         if self.robust_c is not None:
@@ -1892,10 +1949,12 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
                 raise ValueError(f"noise must hold one value per point ([{n}]), got {tuple(noise.shape)}")
         if self.grow_grid:
             self.grow_to_cover_(X)
-        return self._condition(lambda model, cache, src: model._absorb_interval(cache, X, lo, hi, noise, src), inplace, self._gamma(_decay),
-                               reads_posterior=True)
+        new_gp = self._condition(lambda model, cache, src: model._absorb_interval(cache, X, lo, hi, noise, src), inplace, self._gamma(_decay),
+                                 reads_posterior=True)
+        (self if inplace else new_gp)._refine_after_update()
+        return new_gp
 
-    def _absorb_matched(self, cache, X, noise, src, form, launch, half_delta=None, pvar_of=None):
+    def _absorb_matched(self, cache, X, noise, src, form, launch, half_delta=None, pvar_of=None, store=None):
         """_absorb of one batch of moment-matched observations (`form`: what _native_half_op calls them), one launch:
         ``launch(X, pvar, sigma2, wa, wb, noise, b, A_half, cnt, stats, err, u, res=)`` is grid_ops.scatter_stats_interval or
         _count with its data bound.  `src`: the model whose posterior the sites are matched against -- this one, or in the
@@ -1904,7 +1963,10 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         the stream point by point receives the effective weights wa omega, wb omega and the pseudo-targets: a carried root pair,
         the spectral factor, the path probes, the noise-weight sum.  The two-level block is given up and the dense rank-update
         seed is skipped, as in _absorb_robust.  Returns the sites and the number of points num_data grows by: those that entered,
-        and those outside the grid (which _raise_out_of_bounds takes off again when the flag is read)."""
+        and those outside the grid (which _raise_out_of_bounds takes off again when the flag is read).
+        `store`: (form name, d0, d1) of a form the site memory keeps.  On a model built with site_memory the batch is
+        then written, with its sites, into the cache's ring behind the launch -- index copies, no further launch of the library; a
+        point outside the grid is not stored."""
         op = self._native_half_op(cache, form, half_delta)
         X, _, no, wa, wb = self._canon_batch(X, None, noise)
         u = src.prediction_cache["pred_mean"][0, :, 0]       # (finishes whatever is pending, leaves a stencil shard)
@@ -1919,12 +1981,21 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         if not self._follow_sites(cache, X, wa, wb, *sites[:2]):
             return sites, 0
         entered, dropped = torch.stack([(sites[1] > 0).sum(), (self._err - flag0).reshape(-1)[0] >> 1]).tolist()
+        if store is not None and cache.get("_site_ring") is not None:
+            keep = None
+            if dropped:                                      # (the kernels' own test: g0 <= x <= last node, in the working precision)
+                g = self._grid
+                first = torch.tensor(g.g0, dtype=self._dtype, device=self._device)
+                last = torch.tensor([g0 + h * (n - 1) for g0, h, n in zip(g.g0, g.h, g.g)], dtype=self._dtype, device=self._device)
+                keep = ((X >= first) & (X <= last)).all(dim=1)
+            name, d0, d1 = store
+            cache["_site_ring"].store(name, X, d0, d1, no, wa, wb, sites[0], sites[1], keep=keep)
         return sites, int(entered) + int(dropped)
 
     def _absorb_interval(self, cache, X, lo, hi, noise, src, half_delta=None):
         """_absorb_matched with the interval launch (wiski_scatter_stats_interval)."""
         self.last_interval_sites, grown = self._absorb_matched(
-            cache, X, noise, src, "interval observations", half_delta=half_delta,
+            cache, X, noise, src, "interval observations", half_delta=half_delta, store=("interval", lo, hi),
             launch=lambda X, *rest, **kw: grid_ops.scatter_stats_interval(self._grid, X, lo.contiguous(), hi.contiguous(), *rest, **kw))
         return grown
 
@@ -1951,16 +2022,88 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         y, t, family = self._count_batch(X.shape[0], counts, exposure, trials)
         if self.grow_grid:
             self.grow_to_cover_(X)
-        return self._condition(lambda model, cache, src: model._absorb_count(cache, X, y, t, family, src), inplace, self._gamma(_decay),
-                               reads_posterior=True)
+        new_gp = self._condition(lambda model, cache, src: model._absorb_count(cache, X, y, t, family, src), inplace, self._gamma(_decay),
+                                 reads_posterior=True)
+        (self if inplace else new_gp)._refine_after_update()
+        return new_gp
 
     def _absorb_count(self, cache, X, y, t, family, src, half_delta=None):
         """_absorb_matched with the count launch (wiski_scatter_stats_count), at noise = wa = wb = 1 -- the effective noise
         variance of a point is sigma2 / omega = 1 / tau."""
         self.last_count_sites, grown = self._absorb_matched(
-            cache, X, None, src, "count observations", half_delta=half_delta,
+            cache, X, None, src, "count observations", half_delta=half_delta, store=(family, y, t),
             launch=lambda X, *rest, **kw: grid_ops.scatter_stats_count(self._grid, X, y, t, family, *rest, **kw))
         return grown
+
+    # ------------------------------------------------------- site memory --
+    def _refine_after_update(self):
+        """site_refine_sweeps sweeps behind an interval or count update of a model with site memory."""
+        if self.site_memory is not None and self.site_refine_sweeps > 0:
+            self.refine_sites_(self.site_refine_sweeps, self.site_refine_damping)
+
+    def _site_ring(self, what):
+        if self.site_memory is None:
+            raise RuntimeError(f"{what}: the model was built without site_memory")
+        return self._kernel_cache["_site_ring"]
+
+    def refine_sites_(self, sweeps=1, damping=1.0, tol=None):
+        """Expectation-propagation sweeps over the stored interval and count observations, in place.  Per sweep the
+        grid mean is taken from the prediction cache and the posterior variance at the stored points from the path every posterior
+        call takes (one more solve); then ONE launch per form present in the ring (``wiski_revisit_sites``) re-matches every stored
+        site against its cavity, damped by ``damping`` in [0, 1], and scatters only the difference of the site -- all slots against
+        the same mean and variance (parallel EP).  The carried residual follows in the launch; the noise-weight sum moves by the
+        weight deltas on the device; what cannot follow a weight that shrinks is given up, as after a point has left a window: a
+        carried root pair, the spectral factor (rebuilt from the stencil, exactly), the two-level block; no dense rank update is
+        seeded.  ``num_data`` follows the points that entered or left -- one host read per sweep, the read that fetches
+        max(change).  ``tol``: stop after the sweep whose max(change) is at most tol.  Returns the list of max(change) per sweep,
+        change = |omega_new - omega_old| / max(omega_new, omega_old); ``last_refined_sites`` then holds (ytilde, omega, log_z) over
+        the filled slots, oldest first (log_z against the cavity of the last sweep; NaN for a slot it left alone).  A hyper-parameter
+        step needs nothing: the next sweep re-matches under the new kernel."""
+        ring = self._site_ring("refine_sites_")
+        if isinstance(sweeps, bool) or int(sweeps) != sweeps or int(sweeps) < 0:
+            raise ValueError(f"sweeps must be an integer >= 0, got {sweeps!r}")
+        damping = float(damping)
+        if not (0.0 <= damping <= 1.0):
+            raise ValueError(f"damping must lie in [0, 1], got {damping}")
+        cache = self._kernel_cache
+        op = self._native_half_op(cache, "site revisit")
+        changes = []
+        for _ in range(int(sweeps)):
+            if ring.fill == 0:
+                changes.append(0.0)
+                continue
+            idx = torch.as_tensor(ring.order(), dtype=torch.long, device=self._device)
+            u = self.prediction_cache["pred_mean"][0, :, 0]      # (finishes whatever is pending)
+            with torch.no_grad(), settings.skip_posterior_variances(False):
+                pv = self._eval_forward(ring.x[idx].contiguous()).variance.reshape(-1).to(self._dtype)
+            pvar = torch.zeros(ring.cap, dtype=self._dtype, device=self._device)
+            pvar[idx] = pv
+            targets, res = self._site_targets(cache, op, u)
+            before = ring.omega.clone()
+            log_z = change = None
+            for form in sorted(ring.forms):                  # every launch of the sweep against the same u and pvar
+                log_z, change = grid_ops.revisit_sites(self._grid, ring, form, pvar, self._sigma2(0), damping, *targets, res=res, log_z=log_z, change=change)
+            self._wsum_dev[0] += (ring.wa * (ring.omega - before)).sum(dtype=torch.float64)
+            self._wsum_dirty = True
+            self._give_up(cache)
+            top, entered, left = torch.stack([change.max().double(), ((before == 0) & (ring.omega > 0)).sum().double(),
+                                              ((before > 0) & (ring.omega == 0)).sum().double()]).tolist()
+            self.num_data = self.num_data + int(entered) - int(left)
+            self._dump_caches()
+            self.last_refined_sites = (ring.ytilde[idx], ring.omega[idx], log_z[idx])
+            changes.append(float(top))
+            if tol is not None and top <= tol:
+                break
+        return changes
+
+    def site_memory_points(self):
+        """What the ring holds, oldest first: dict of X [k, d], d0, d1 [k] (lower / upper, or count and exposure / trials), form (list
+        of "interval" / "poisson" / "binomial"), noise, ytilde, omega [k]."""
+        ring = self._site_ring("site_memory_points")
+        idx = torch.as_tensor(ring.order(), dtype=torch.long, device=self._device)
+        names = {v: k for k, v in grid_ops.SITE_FORMS.items()}
+        return dict(X=ring.x[idx], d0=ring.d0[idx], d1=ring.d1[idx], form=[names[int(c)] for c in ring.form[idx].tolist()], noise=ring.noise[idx],
+                    ytilde=ring.ytilde[idx], omega=ring.omega[idx])
 
     # ------------------------------------------------ heteroscedastic noise --
     def _refuse_for_hetero_model(self):
@@ -2773,7 +2916,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
 
     def _stream_fast_state(self, X, Y):
         """(prepared StreamStep, mean state, preconditioner state) when the one-call streaming step applies, else None."""
-        if (self.robust_c is not None or self.window is not None or self._trend_deg is not None or self.input_var is not None or self.num_outputs != 1 or self._use_dense() or settings.spectral_preconditioner.off() or settings.residual_carry_over.off()
+        if (self.robust_c is not None or self.window is not None or self.site_memory is not None or self._trend_deg is not None or self.input_var is not None or self.num_outputs != 1 or self._use_dense() or settings.spectral_preconditioner.off() or settings.residual_carry_over.off()
                 or X.dim() != 2 or not X.is_cuda or X.dtype != self._dtype or not X.is_contiguous() or Y.dtype != self._dtype):
             return None
         ms = self._mean_state
@@ -3088,6 +3231,10 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             fresh.update(path_probes=new_P, path_seed=cache["path_seed"], path_count=cache["path_count"])
         if cache.get("_ring") is not None:
             fresh["_ring"] = cache["_ring"]              # coordinates, not node indices: the ring is the same on the grown grid
+        if cache.get("_site_ring") is not None:
+            fresh["_site_ring"] = cache["_site_ring"]    # coordinates too; where nodes were removed the sites stay in what remains, frozen
+            if any(v < 0 for v in a) or any(v < 0 for v in bb):
+                fresh["_site_ring"].clear()
         if new_C is not None:
             fresh.update(self._trend_entries(cache, trend_C=new_C))
         self._drop_spectral()
@@ -3164,6 +3311,9 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         if self.window is not None:
             raise NotImplementedError("forget_ on a model with window: the ring keeps the weights its points entered with, and a point that "
                                       "left after a decay would take out more than is still there -- the two are alternatives")
+        if self.site_memory is not None:
+            raise NotImplementedError("forget_ on a model with site_memory: a decayed site is no longer the stored one, and a sweep would "
+                                      "take out more than is still in the statistics")
         if gamma != 1.0:
             if self.num_data is None:
                 raise RuntimeError("forget_ needs the number of absorbed points (log|D| moves by -n log gamma): hand num_data over with the kernel cache")
@@ -3250,6 +3400,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         self._wsum_dirty = False
         self._memo.pop("precond", None)
         self._drop_spectral()
+        if cache.get("_site_ring") is not None:         # nothing of the stored points is in the statistics any more
+            cache["_site_ring"].clear()
         return cache
 
     def to(self, *args, **kwargs):
@@ -3279,6 +3431,8 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
                 self._kernel_cache.update(path_probes=c["path_probes"].to(device), path_seed=c["path_seed"], path_count=c["path_count"])
             if c.get("_ring") is not None:
                 self._kernel_cache["_ring"] = c["_ring"].to(device)
+            if c.get("_site_ring") is not None:
+                self._kernel_cache["_site_ring"] = c["_site_ring"].to(device)
             self._kernel_cache.update(self._trend_entries(c, move=lambda t: t.to(device)))
             self._device = torch.device(device)
             self._err = grid_ops.new_err_flag(device)

@@ -3,7 +3,8 @@
 
     OnlineSKIRegression(stem, init_x, init_y, lr, grid_size, grid_bound, covar_module=None, **kw)
         (**kw: num_path_probes, path_seed, forgetting_factor, grow_grid, max_grid_size, robust_c, robust_scale, window,
-        window_rebuild_every, input_var, input_noise_slope, heteroscedastic, noise_kernel, log_noise_mean -- passed to the GP;
+        window_rebuild_every, input_var, input_noise_slope, heteroscedastic, noise_kernel, log_noise_mean, site_memory,
+        site_refine_sweeps, site_refine_damping -- passed to the GP;
         input_var needs the Identity stem; with heteroscedastic=True ``predict`` and ``evaluate`` use the noise the GP has learned)
     .fit(x, y, num_epochs, test_dataset=None) -> list of per-epoch dicts
     .update(x, y, update_stem=True, update_gp=True) -> (stem_loss, gp_loss)
@@ -54,6 +55,8 @@ class OnlineSKIRegression(StreamingSKIWrapper):
             input_var=kwargs.get("input_var"), input_noise_slope=kwargs.get("input_noise_slope", "posterior"),
             heteroscedastic=kwargs.get("heteroscedastic", False), noise_kernel=kwargs.get("noise_kernel"),
             log_noise_mean=kwargs.get("log_noise_mean", 0.0),
+            site_memory=kwargs.get("site_memory"), site_refine_sweeps=kwargs.get("site_refine_sweeps", 0),
+            site_refine_damping=kwargs.get("site_refine_damping", 1.0),
         )
         self._setup(stem, gp, lr, init_x)
 
