@@ -420,6 +420,9 @@ typedef struct wiski_stream_args_f32 {
   const wiski_twolevel* two_level;               /* NULL, or: exact block on the dominant modes in the preconditioner (see wiski_twolevel) */
   int32_t keep[3];                               /* eigenmodes per dimension the preconditioner transforms (the last keep[q] columns of the
                                                   * eigen tables; on all others t = r and y = 0), or all 0: every mode.  See wiski_precond_keep_ok */
+  float* d_tap_stage;                            /* NULL, or [m][4] floats, all zero: the absorb's tap adds on b / cnt / R go through it as one
+                                                  * 16-byte record per node and the step's solve folds it in (wiski_absorb_staged_f32); all zero
+                                                  * again when the call returns (in stream order).  d = 3, carry != 0, d_cnt, no shard; ignored otherwise */
 } wiski_stream_args_f32;
 typedef struct wiski_stream_args_f64 {
   double* d_A_half; double* d_b; double* d_cnt; double* d_stats; int32_t* d_err;
@@ -430,6 +433,7 @@ typedef struct wiski_stream_args_f64 {
   const wiski_shard* shard;
   const wiski_twolevel* two_level;               /* must be NULL (the two-level block exists for the fused fp32 path only) */
   int32_t keep[3];                               /* must be 0 (the truncated transforms exist for the fused fp32 path only) */
+  double* d_tap_stage;                           /* must be NULL (the staged tap adds exist in fp32 only) */
 } wiski_stream_args_f64;
 int wiski_stream_step_f32(const wiski_grid* grid, const wiski_stream_args_f32* args, const float* d_x, const float* d_y, const float* d_wa, const float* d_wb, const float* d_noise, int64_t q, float* d_mean_out, int32_t carry, int32_t first_check, int32_t* h_iters, double* h_relres, int32_t* h_err, void* stream, wiski_pcg_async* handle, int32_t defer, int32_t* h_resumed);
 int wiski_stream_step_f64(const wiski_grid* grid, const wiski_stream_args_f64* args, const double* d_x, const double* d_y, const double* d_wa, const double* d_wb, const double* d_noise, int64_t q, double* d_mean_out, int32_t carry, int32_t first_check, int32_t* h_iters, double* h_relres, int32_t* h_err, void* stream, wiski_pcg_async* handle, int32_t defer, int32_t* h_resumed);
@@ -473,6 +477,19 @@ typedef struct wiski_absorb_args {
 } wiski_absorb_args;
 int wiski_absorb_f32(const wiski_grid* grid, const wiski_absorb_args* args, void* stream);
 int wiski_absorb_f64(const wiski_grid* grid, const wiski_absorb_args* args, void* stream);
+
+/* Staged tap adds.  The per-tap adds of a point on d_b, d_cnt and d_res are three runs of 16 bytes per tap row of 4:
+ * 16 % of the atomic form's 64-byte memory-side requests for 8 % of its adds.  With d_tap_stage -- [m][4] floats, node-major records
+ * {delta b, delta cnt, delta res, unused}, ALL ZERO on entry -- wiski_absorb_staged_f32 adds the three into the node's record instead
+ * (one run of 64 bytes per tap row) and leaves d_b / d_cnt / d_res untouched; wiski_tap_fold_f32 then adds every record to the three
+ * arrays with plain stores and zeroes it (d_cnt, d_res: each may be NULL).  Until the fold the three arrays lack the batch.
+ * The record is that of wiski_absorb_f32; the plain single-output fp32 half-stencil atomic form at d = 3 with d_cnt, d_u and d_res, no
+ * shard and channels = 0 only -- anything else, or d_tap_stage = NULL, is WISKI_E_BADARG before a launch.  A closed guard stages
+ * nothing; a batch the owner-computes form takes (d_bin) is added directly, the stage stays zero.  wiski_stream_step_f32 does both
+ * steps by itself (wiski_stream_args_f32.d_tap_stage), the fold inside the first kernel of its solve where that is the truncated
+ * forward transform of a carried residual. */
+int wiski_absorb_staged_f32(const wiski_grid* grid, const wiski_absorb_args* args, float* d_tap_stage, void* stream);
+int wiski_tap_fold_f32(float* d_tap_stage, float* d_b, float* d_cnt, float* d_res, int64_t m, void* stream);
 
 /* Outlier-robust absorb: every point is Huber-weighted against the posterior BEFORE the batch, inside the launch that absorbs it
  * (DESIGN.md 3.16).  The arguments of wiski_scatter_stats_grad (for a value per point: d_y / d_wa / d_wb / d_noise / d_mean_out

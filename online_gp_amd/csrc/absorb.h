@@ -42,6 +42,11 @@ struct AbsorbArgs {
   const real* u = nullptr;      // [m] current posterior mean on the grid
   real* res = nullptr;          // [m] res += W^T (wb y - wa (W u)): keeps res = b - z - A u exact under the increment
   real* mean_out = nullptr;     // [n] w_p . u, the predictive mean of the batch BEFORE this update (saves the gather launch of a step); [n][channels] with channels
+  // tap stage: [m][4], node-major records {delta b, delta cnt, delta res, unused}, all zero on entry.  The per-tap adds of the atomic
+  // form go into the node's record instead of b / cnt / res (scatter_half.h: half_tap_stage) and the caller folds the records in
+  // afterwards (pcg.h: tap_fold, or the first kernel of the solve that follows).  fp32, d = 3, the plain single-output atomic form
+  // with cnt, u and res, no shard, no channels; the owner-computes form, where it applies, adds directly and leaves the stage zero
+  real* tap_stage = nullptr;
   // zero regions: two word arrays of the solve that follows in the same streaming step (its scalar block, its partial vector)
   void* z1 = nullptr;
   int64_t n1_bytes = 0;         // multiples of 4

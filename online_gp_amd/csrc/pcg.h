@@ -53,6 +53,14 @@ struct PcgArgs {
   // summed over the ranks by ONE all-reduce of an m-vector (+ the p . Ap slots) on the solve's stream.  Preconditioner, vector
   // updates and scalars are replicated, so all ranks take identical iterations.  k = 1, half stencil, m % 4 == 0
   const wiski_shard* shard = nullptr;
+  // tap stage (AbsorbArgs::tap_stage): the absorb queued before this solve left its per-tap adds on RHS, the density row sums and R
+  // in tap_stage [m][4] instead of the three arrays.  The solve adds them in and zeroes the records before anything reads RHS or R:
+  // inside its first kernel where that is the truncated forward transform of a carried residual (fp32, keep, warm = 2), else by a
+  // launch of tap_fold() first.  Whatever pcg() returns -- a refusal included -- the records have been folded and are zero again.
+  // fp32, k = 1, not RESUME; tap_b (the writable RHS) always, tap_cnt optional
+  real* tap_stage = nullptr;
+  real* tap_b = nullptr;
+  real* tap_cnt = nullptr;
 };
 
 // Where everything lies in a solve's workspace: 20 slots of one 256-byte-aligned [k][m] vector each, then the scalar block.
@@ -99,3 +107,7 @@ int pcg(const wiski_grid* grid, const PcgArgs<real>& args, void* stream);
 template <typename real>
 int pcg_zero_regions(const wiski_grid* grid, int k, int max_iter, void* work, bool a_sym, void** p1, int64_t* n1_bytes, void** p2, int64_t* n2_bytes);
 int pcg_guard(const wiski_pcg_async* handle, const void** d_guard, int64_t* expect);
+
+// b += stage[.][0], cnt += stage[.][1], res += stage[.][2] (cnt, res: each may be NULL) with plain stores, and stage = 0: one launch
+// on `stream`.  What a solve does with PcgArgs::tap_stage when its first kernel cannot.
+int tap_fold(float* stage, float* b, float* cnt, float* res, int64_t m, void* stream);

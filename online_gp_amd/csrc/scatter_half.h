@@ -287,6 +287,23 @@ __device__ __forceinline__ void half_tap_atomics(bool valid, const int flat_t[Ha
   }
 }
 
+// The same adds of a single-channel fp32 point at d = 3 through the tap stage (AbsorbArgs::tap_stage): b, cnt and res of a node are
+// floats 0..2 of its 16-byte record, so the 4 taps of a row run (consecutive rows) are 64 contiguous bytes -- 1.75 memory-side requests
+// of 64 bytes per run on average with 12 lanes each, against 2 x 3 with 4 lanes each on the three arrays (the atomics are
+// request-bound, scatter_owner.h).  Four wave instructions per point: instruction k covers the taps 16 k .. 16 k + 15, lane l the
+// component l & 3 of tap 16 k + (l >> 2), read from the wave's tables -- call it behind the barrier that follows half_tap_table.
+__device__ __forceinline__ void half_tap_stage(bool valid, int lane, const float* sv, const int* si, float yw, float wac, float innov,
+                                               float* __restrict__ stage) {
+  const int c = lane & 3;
+  const float coef = c == 0 ? yw : (c == 1 ? wac : innov);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int a = 16 * k + (lane >> 2);
+    const float v = sv[a];
+    if (valid && c != 3 && v != 0.f) unsafeAtomicAdd(stage + (int64_t)si[a] * 4 + c, v * coef);
+  }
+}
+
 // A[a, b] += sum_c wa_c v_c[a] v_c[b] over the tap pairs of the first `npair` prefix pairs of s_pair, one atomic per tap pair.
 // The symmetric half stencil (the model's native W^T D^-1 W storage) is "row-interleaved":
 // with P = the leading d-1 stencil digits of an offset and s its innermost digit, only offsets >= centre

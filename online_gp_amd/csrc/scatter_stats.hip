@@ -122,7 +122,9 @@ __global__ __launch_bounds__(256) void k_scatter_stats(GridDev<real> G, const re
 
 // Symmetric half-stencil accumulation (the model's native W^T D^-1 W storage; the row-interleaved layout and the point sweep are
 // scatter_half.h), with everything the plain form carries besides: the guard, the zero regions, stencil shards, batched outputs.
-template <typename real, int D>
+// STAGE (float, D = 3, one output, whole stencil, cnt / u / res given -- absorb_validate): the per-tap adds go into the records of
+// tap_stage instead of b / cnt / res (half_tap_stage); a kernel of its own, so that the direct form keeps its registers.
+template <typename real, int D, bool STAGE = false>
 __global__ __launch_bounds__(256) void k_scatter_stats_sym(GridDev<real> G, const real* __restrict__ x, const real* __restrict__ y,
                                                            const real* __restrict__ wa, const real* __restrict__ wb,
                                                            const real* __restrict__ noise, int64_t n, real* __restrict__ b,
@@ -130,7 +132,8 @@ __global__ __launch_bounds__(256) void k_scatter_stats_sym(GridDev<real> G, cons
                                                            real* __restrict__ cnt, const real* __restrict__ u, real* __restrict__ res,
                                                            real* __restrict__ mean_out, uint32_t* __restrict__ z1, int64_t n1,
                                                            uint32_t* __restrict__ z2, int64_t n2, const long long* __restrict__ guard,
-                                                           long long guard_expect, int g_lo, int g_hi, ScatterBatch bt) {
+                                                           long long guard_expect, int g_lo, int g_hi, ScatterBatch bt,
+                                                           real* __restrict__ tap_stage) {
   // the parameters are the members of AbsorbArgs (absorb.h), which documents them
   // several independent outputs in ONE launch (BFN:37-55 carries num_outputs as a batch dimension): blockIdx.y = output
   {
@@ -163,8 +166,9 @@ __global__ __launch_bounds__(256) void k_scatter_stats_sym(GridDev<real> G, cons
     }
     half_tap_table<real, D, 1>(G, j0, w, nullptr, lane, u, s_val[loc], s_idx[loc], flat_t, val_t, wu);
     half_carry<real, 1>(u, yw, wac, wu, mean_out, p, lane == 0 && valid, innov);
-    half_tap_atomics<real, D, 1>(valid, flat_t, val_t, yw, wac, innov, b, cnt, res);
+    if constexpr (!STAGE) half_tap_atomics<real, D, 1>(valid, flat_t, val_t, yw, wac, innov, b, cnt, res);
     __syncthreads();
+    if constexpr (STAGE) half_tap_stage(valid, lane, s_val[loc], s_idx[loc], yw[0], wac[0], innov[0], tap_stage);
     if (valid && A) half_pair_loop<real, D, 1>(lane, npair, s_pair, s_val[loc], s_idx[loc], wac, 1, A, G.m);
     __syncthreads();
   }
@@ -251,6 +255,10 @@ static int64_t owner_min_points() {
 template <typename real>
 static int absorb_validate(const AbsorbArgs<real>& a, int d) {
   if (a.n == 0) return WISKI_OK;                       // nothing to absorb: not even the pointers are looked at
+  // the tap stage: the plain single-output fp32 half-stencil atomic form at d = 3 with cnt and the carry pair, the whole stencil, only
+  if (a.tap_stage && (sizeof(real) != 4 || d != 3 || !a.half || !a.cnt || !a.u || !a.res || a.nout != 1 || a.channels || a.sharded() ||
+                      a.revisit() || a.hetero() || a.grad_interval() || a.site_form() || a.windowed()))
+    return WISKI_E_BADARG;
   if (a.revisit()) {
     // revisit (scatter_revisit.h): the points are the slots of a ring of stored sites -- its x, wa, wb and noise, no y -- and the
     // launch is the single-output half-stencil atomic sweep with u, A and cnt: the whole group with a known form code, the
@@ -391,11 +399,20 @@ static int launch_atomic(const GridDev<real>& G, const AbsorbArgs<real>& a, hipS
   dim3 grd((unsigned)blocks, (unsigned)a.nout);
   ScatterBatch bt = a.bt;
   bt.vec_stride = G.m;                                 // b / cnt / u / res of consecutive outputs are one grid vector apart
+  if constexpr (sizeof(real) == 4) {
+    if (a.tap_stage) {                                 // (absorb_validate: d = 3, half, one output, cnt / u / res, the whole stencil)
+      hipLaunchKernelGGL((k_scatter_stats_sym<float, 3, true>), grd, dim3(256), 0, stream, G, a.x, a.y, a.wa, a.wb, a.noise, a.n, a.b, a.A, a.stats, a.err,
+                         a.cnt, a.u, a.res, a.mean_out, (uint32_t*)a.z1, a.n1_bytes / 4, (uint32_t*)a.z2, a.n2_bytes / 4, (const long long*)a.guard,
+                         (long long)a.guard_expect, a.g_lo, a.g_hi, bt, a.tap_stage);
+      WISKI_LAUNCH_CHECK();
+      return WISKI_OK;
+    }
+  }
 #define CALL(DD)                                                                                                                                             \
   do {                                                                                                                                                       \
     if (a.half) hipLaunchKernelGGL((k_scatter_stats_sym<real, DD>), grd, dim3(256), 0, stream, G, a.x, a.y, a.wa, a.wb, a.noise, a.n, a.b, a.A, a.stats, a.err, \
                                    a.cnt, a.u, a.res, a.mean_out, (uint32_t*)a.z1, a.n1_bytes / 4, (uint32_t*)a.z2, a.n2_bytes / 4, (const long long*)a.guard,  \
-                                   (long long)a.guard_expect, a.g_lo, a.g_hi, bt);                                                                              \
+                                   (long long)a.guard_expect, a.g_lo, a.g_hi, bt, (real*)nullptr);                                                              \
     else hipLaunchKernelGGL((k_scatter_stats<real, DD>), grd, dim3(256), 0, stream, G, a.x, a.y, a.wa, a.wb, a.noise, a.n, a.b, a.A, a.stats, a.err, a.cnt);     \
   } while (0)
   WISKI_DISPATCH_D(G.d, CALL)
@@ -643,6 +660,12 @@ constexpr int32_t G_ALL = 1 << 30;                     // AbsorbArgs::g_hi of an
 extern "C" {
 int wiski_absorb_f32(const wiski_grid* g, const wiski_absorb_args* p, void* s) { return entry_absorb<float>(g, p, s); }
 int wiski_absorb_f64(const wiski_grid* g, const wiski_absorb_args* p, void* s) { return entry_absorb<double>(g, p, s); }
+int wiski_absorb_staged_f32(const wiski_grid* g, const wiski_absorb_args* p, float* d_tap_stage, void* s) {
+  if (!p || !d_tap_stage) return WISKI_E_BADARG;
+  AbsorbArgs<float> a = absorb_args<float>(*p);
+  a.tap_stage = d_tap_stage;
+  return absorb(g, a, s);
+}
 int wiski_scatter_stats_grad_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, void* s) { return entry_grad(g, x, y, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, s); }
 int wiski_scatter_stats_grad_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, void* s) { return entry_grad(g, x, y, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, s); }
 int wiski_scatter_stats_robust_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, const float* inv_scale, float huber_c, float* omega_out, void* s) { return entry_scatter_robust(g, x, y, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, inv_scale, huber_c, omega_out, s); }

@@ -2045,6 +2045,9 @@ static int pcg_validate(const GridDev<real>& G, const PcgArgs<real>& a, const Pc
     if (!a.shard->comm && !a.shard->allreduce) return WISKI_E_BADARG;
   }
   if (a.mode != 2 && a.warm == 2 && !a.R) return WISKI_E_BADARG;             // the carried residual is the caller's R
+  // the tap stage belongs to RHS and R of one fp32 column, and to the solve that starts here
+  if (a.tap_stage && (sizeof(real) != 4 || a.k != 1 || a.mode == 2 || a.tap_b != a.RHS || !a.R)) return WISKI_E_BADARG;
+  if (!a.tap_stage && (a.tap_b || a.tap_cnt)) return WISKI_E_BADARG;
   // the exact block lives in the fused fp32 slab kernels (k > 1: launch_slab checks the scratch)
   if (a.two_level && !(path.fused_cg && sizeof(real) == 4)) return WISKI_E_BADARG;
   // kept-mode counts: all three or none, one fp32 column on the fused path, within the truncated kernels' cap and LDS budget
@@ -2085,9 +2088,11 @@ struct PcgPlan {
   dim3 egrid, vgrid;            // the vector kernels' grids: one element / one 16-byte group per thread, grid-stride
   const double tol2;
   bool init_in_fwd;             // fp32 fused path with a carried residual: the norms are formed by the first forward transform of r
+  bool fold_in_fwd;             // ... and that transform is the truncated one, which folds the tap stage in as well (spectral_keep.h)
+  bool* folded;                 // set once a kernel that folds the tap stage has been queued (pcg() folds by itself otherwise)
 
-  PcgPlan(const GridDev<real>& G_, const PcgArgs<real>& a_, const PcgPath& path_, hipStream_t s_)
-      : G(G_), a(a_), path(path_), s(s_), m(G_.m), k(a_.k), L(G_.m, a_.k, a_.max_iter, a_.work), tol2(a_.tol * a_.tol) {
+  PcgPlan(const GridDev<real>& G_, const PcgArgs<real>& a_, const PcgPath& path_, hipStream_t s_, bool* folded_)
+      : G(G_), a(a_), path(path_), s(s_), m(G_.m), k(a_.k), L(G_.m, a_.k, a_.max_iter, a_.work), tol2(a_.tol * a_.tol), folded(folded_) {
     r = a.R ? a.R : L.r;
     nch = pcg_partials<real>(G, k, path.sym, &zl);
     if (path.sharded) {
@@ -2112,6 +2117,7 @@ struct PcgPlan {
     if (vb > bcap) vb = bcap;
     vgrid = dim3((unsigned)vb, (unsigned)k);
     init_in_fwd = a.mode != 2 && a.warm == 2 && sizeof(real) == 4 && path.fused_cg;
+    fold_in_fwd = a.tap_stage && a.tap_cnt && init_in_fwd && a.keep[0] != 0 && a.max_iter >= 1;
   }
 
   // A . v on the wide kernels: partial vectors in L.part, or (sharded) this rank's share summed into L.hp and all-reduced
@@ -2162,6 +2168,12 @@ static int pcg_start(const PcgPlan<real>& plan) {
   const PcgLayout<real>& L = plan.L;
   const hipStream_t s = plan.s;
   const int m = plan.m, k = plan.k;
+  if constexpr (sizeof(real) == 4) {
+    if (a.tap_stage && !plan.fold_in_fwd) {        // nothing below may read RHS or R without the batch
+      if (int rc = tap_fold(a.tap_stage, a.tap_b, a.tap_cnt, plan.r, m, s)) return rc;
+      *plan.folded = true;
+    }
+  }
   if (a.handle && a.handle->prezeroed) {
     a.handle->prezeroed = 0;      // wiski_stream_step had the step's first kernel zero both regions (pcg_zero_regions)
   } else {
@@ -2300,10 +2312,13 @@ static int pcg_iterate(const PcgPlan<real>& plan) {
       constexpr bool fuse_upd = sizeof(real) == 4;
       if (!fuse_upd) flush_update();
       const bool init_now = plan.init_in_fwd && it == 0;
+      const TapFold<real> fold{a.tap_stage, a.tap_b, a.tap_cnt};
+      const bool fold_now = init_now && plan.fold_in_fwd;
       rc = launch_spectral_fused_cg<real>(G, a.evec, a.evec2, a.eval, a.kscale, a.shift, r, k, L.sa, L.sb, it, pending ? 1 : 0, tol2, p, pt, cpart, cnch,
-                                          czl, a.U, a.Z, S, s, init_now ? a.RHS : (const real*)nullptr, a.two_level, a.keep);
+                                          czl, a.U, a.Z, S, s, init_now ? a.RHS : (const real*)nullptr, a.two_level, a.keep, fold_now ? &fold : nullptr);
       pending = false;
       if (rc) return rc;
+      if (fold_now) *plan.folded = true;
       rc = plan.product_wide(p, pt, (real)1, S.php(it));
       if (rc) return rc;
       pending = true;
@@ -2363,17 +2378,54 @@ static int pcg_iterate(const PcgPlan<real>& plan) {
 #undef PCG_VEC_LAUNCH
 
 template <typename real>
-int pcg(const wiski_grid* grid, const PcgArgs<real>& a, void* stream) {
+static int pcg_run(const GridDev<real>& G, const PcgArgs<real>& a, void* stream, bool* folded) {
   // validation comes first: nothing is queued and no handle field written on arguments a later step would have refused
+  const PcgPath path(G, a);
+  int rc = pcg_validate(G, a, path);
+  if (rc) return rc;
+  const PcgPlan<real> plan(G, a, path, (hipStream_t)stream, folded);
+  if (a.mode != 2) rc = pcg_start(plan);     // RESUME: the start call queued everything up to its poll
+  return rc ? rc : pcg_iterate(plan);
+}
+
+// One launch for the tap stage where the solve's first kernel does not fold it (PcgArgs::tap_stage, pcg.h: tap_fold).
+__global__ __launch_bounds__(256) void k_tap_fold(int64_t m, float* __restrict__ stage, float* __restrict__ b, float* __restrict__ cnt,
+                                                  float* __restrict__ res) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
+    const float4 sg = *reinterpret_cast<const float4*>(stage + 4 * i);
+    if (__float_as_uint(sg.x) | __float_as_uint(sg.y) | __float_as_uint(sg.z)) {
+      b[i] += sg.x;
+      if (cnt) cnt[i] += sg.y;
+      if (res) res[i] += sg.z;
+      *reinterpret_cast<float4*>(stage + 4 * i) = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+}
+
+int tap_fold(float* stage, float* b, float* cnt, float* res, int64_t m, void* stream) {
+  if (!stage || !b || m < 0) return WISKI_E_BADARG;
+  if (m == 0) return WISKI_OK;
+  int64_t blocks = (m + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(k_tap_fold, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, m, stage, b, cnt, res);
+  return hipGetLastError() == hipSuccess ? WISKI_OK : WISKI_E_LAUNCH;
+}
+
+template <typename real>
+int pcg(const wiski_grid* grid, const PcgArgs<real>& a, void* stream) {
   GridDev<real> G;
   int rc = make_grid_dev<real>(grid, &G);
   if (rc) return rc;
-  const PcgPath path(G, a);
-  rc = pcg_validate(G, a, path);
-  if (rc) return rc;
-  const PcgPlan<real> plan(G, a, path, (hipStream_t)stream);
-  if (a.mode != 2) rc = pcg_start(plan);     // RESUME: the start call queued everything up to its poll
-  return rc ? rc : pcg_iterate(plan);
+  bool folded = false;
+  rc = pcg_run(G, a, stream, &folded);
+  if constexpr (sizeof(real) == 4) {
+    // a staged batch never stays behind: a refusal, or an error before the folding kernel was queued, leaves the statistics whole
+    if (a.tap_stage && a.tap_b && !folded) {
+      const int frc = tap_fold(a.tap_stage, a.tap_b, a.tap_cnt, a.R, G.m, stream);
+      if (rc == WISKI_OK) rc = frc;
+    }
+  }
+  return rc;
 }
 template int pcg<float>(const wiski_grid*, const PcgArgs<float>&, void*);
 template int pcg<double>(const wiski_grid*, const PcgArgs<double>&, void*);
@@ -2589,6 +2641,7 @@ int wiski_pcg_async_free(wiski_pcg_async* as) {
   return WISKI_OK;
 }
 int wiski_pcg_async_guard(const wiski_pcg_async* as, const void** d_guard, int64_t* expect) { return pcg_guard(as, d_guard, expect); }
+int wiski_tap_fold_f32(float* d_tap_stage, float* d_b, float* d_cnt, float* d_res, int64_t m, void* s) { return tap_fold(d_tap_stage, d_b, d_cnt, d_res, m, s); }
 int wiski_pcg_f32(const wiski_grid* g, PCG_ABI(float), void* s) { return pcg(g, pcg_args<float>(PCG_ABI_NAMES), s); }
 int wiski_pcg_f64(const wiski_grid* g, PCG_ABI(double), void* s) { return pcg(g, pcg_args<double>(PCG_ABI_NAMES), s); }
 }

@@ -1551,16 +1551,19 @@ int launch_spectral_fused(const GridDev<real>& G, const real* evec, const real* 
 template <typename real>
 int launch_spectral_fused_cg(const GridDev<real>& G, const real* evec, const real* evec2, const real* evals, real kscale, real shift, real* r,
                              int k, real* w0, real* w1, int it, int apply, double tol2, real* p, real* pt, real* part, int nch, int zl, real* u,
-                             real* z, PcgScal S, hipStream_t s, const real* rhs0, const wiski_twolevel* two_level, const int* keep) {
+                             real* z, PcgScal S, hipStream_t s, const real* rhs0, const wiski_twolevel* two_level, const int* keep,
+                             const TapFold<real>* fold) {
   const int g0 = G.g[0], g1 = G.g[1];
   if (keep && keep[0] != 0) {
     if constexpr (sizeof(real) == 4) {
       if (k != 1) return WISKI_E_BADARG;
-      return launch_spectral_keep_cg(G, evec, evec2, evals, kscale, shift, r, w1, it, apply, tol2, p, pt, part, nch, zl, u, z, S, s, rhs0, two_level, keep);
+      return launch_spectral_keep_cg(G, evec, evec2, evals, kscale, shift, r, w1, it, apply, tol2, p, pt, part, nch, zl, u, z, S, s, rhs0, two_level, keep,
+                                     fold);
     } else {
       return WISKI_E_BADARG;
     }
   }
+  if (fold) return WISKI_E_BADARG;                  // only the truncated forward kernel folds
   if (!evec2) evec2 = evec;
   const real* V0 = evec;
   const real* V1 = evec + g0 * g0;
@@ -1585,10 +1588,10 @@ int launch_spectral_fused_cg(const GridDev<real>& G, const real* evec, const rea
 template bool spectral_fused_ok<float>(const GridDev<float>&);
 template int launch_spectral_fused_cg<float>(const GridDev<float>&, const float*, const float*, const float*, float, float, float*, int, float*,
                                              float*, int, int, double, float*, float*, float*, int, int, float*, float*, PcgScal, hipStream_t,
-                                             const float*, const wiski_twolevel*, const int*);
+                                             const float*, const wiski_twolevel*, const int*, const TapFold<float>*);
 template int launch_spectral_fused_cg<double>(const GridDev<double>&, const double*, const double*, const double*, double, double, double*, int,
                                               double*, double*, int, int, double, double*, double*, double*, int, int, double*, double*, PcgScal,
-                                              hipStream_t, const double*, const wiski_twolevel*, const int*);
+                                              hipStream_t, const double*, const wiski_twolevel*, const int*, const TapFold<double>*);
 template bool spectral_fused_ok<double>(const GridDev<double>&);
 template int launch_spectral_fused<float>(const GridDev<float>&, const float*, const float*, const float*, float, float, const float*, int, float*,
                                           float*, float*, double*, hipStream_t);

@@ -15,7 +15,8 @@
 // Two launches, and no workgroup ever waits on another (the slab kernel's exchange of the block's coefficients between
 // co-resident workgroups is gone: every backward workgroup holds the whole cube):
 //   k_keep_fwd  (g0 x 2 workgroups, a contiguous half slab of r each): every duty of k_spec_mode0_mfma<.., 2> -- the previous
-//               iteration's u / z / r update, the norms, the ring clear -- then T[i0] = X1_L^T R[i0] X2_L of the updated slab; the
+//               iteration's u / z / r update, the norms, the ring clear; at the head of a carried solve also the fold of the
+//               absorb's tap stage into b, cnt and r (each element has exactly one owner: plain stores) -- then T[i0] = X1_L^T R[i0] X2_L of the updated slab; the
 //               two halves of a slab write their partial sums side by side
 //   k_keep_bwd  (g0 workgroups of 16 waves): c[k0] = sum_i0 X0[i0, k0] T[i0] straight from the partial sums, scaling, the block's
 //               N c_S, rho (workgroup 0), this slab's row of mode 0 backward, Y = X1_L S_y X2_L^T and the t-correction with Z1, Z2,
@@ -111,7 +112,8 @@ template <int KS, int W>
 __global__ __launch_bounds__(256) void k_keep_fwd(GridDev<float> G, KeepDev kp, const float* __restrict__ X1, const float* __restrict__ X2,
                                                   float* __restrict__ r, float* __restrict__ T, int it, int apply, double tol2,
                                                   const float* __restrict__ p, const float* __restrict__ pt, PcgScal S,
-                                                  float* __restrict__ part, int nch, int zl, float* __restrict__ u, float* __restrict__ z) {
+                                                  float* __restrict__ part, int nch, int zl, float* __restrict__ u, float* __restrict__ z,
+                                                  float* __restrict__ stage, float* __restrict__ bw, float* __restrict__ cnt) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ double s_red[16];
   float* sR = reinterpret_cast<float*>(smem);     // R[i1][i2], stride LDN: zero outside this workgroup's half
@@ -144,7 +146,33 @@ __global__ __launch_bounds__(256) void k_keep_fwd(GridDev<float> G, KeepDev kp, 
     tin[q] = *reinterpret_cast<const float4*>(r + e);
     if (!ok) tin[q] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (apply == 2 && ok) {                         // carried residual: ||r||^2 and ||rhs||^2 (`p` carries the right-hand side)
-      const float4 f4 = *reinterpret_cast<const float4*>(p + e), rv = tin[q];
+      float4 f4, rv = tin[q];
+      if (stage) {
+        // the tap stage (AbsorbArgs::tap_stage): records {delta b, delta cnt, delta res, -} of these four nodes.  bw is the right-hand
+        // side again, writable (p is not read: it is the same memory).  Every load is issued before the first use -- cnt too, although
+        // only a touched group needs it: behind the test it would be one more trip to memory; a group the batch did not touch stores nothing
+        float4 sg[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) sg[j] = *reinterpret_cast<const float4*>(stage + 4 * (e + j));
+        f4 = *reinterpret_cast<const float4*>(bw + e);
+        float4 cv = *reinterpret_cast<const float4*>(cnt + e);
+        unsigned any = 0u;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) any |= __float_as_uint(sg[j].x) | __float_as_uint(sg[j].y) | __float_as_uint(sg[j].z);
+        if (any) {
+          f4.x += sg[0].x; f4.y += sg[1].x; f4.z += sg[2].x; f4.w += sg[3].x;
+          cv.x += sg[0].y; cv.y += sg[1].y; cv.z += sg[2].y; cv.w += sg[3].y;
+          rv.x += sg[0].z; rv.y += sg[1].z; rv.z += sg[2].z; rv.w += sg[3].z;
+          *reinterpret_cast<float4*>(bw + e) = f4;
+          *reinterpret_cast<float4*>(cnt + e) = cv;
+          *reinterpret_cast<float4*>(r + e) = rv;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) *reinterpret_cast<float4*>(stage + 4 * (e + j)) = make_float4(0.f, 0.f, 0.f, 0.f);
+          tin[q] = rv;
+        }
+      } else {
+        f4 = *reinterpret_cast<const float4*>(p + e);
+      }
       rhs_part += f4.x * f4.x + f4.y * f4.y + f4.z * f4.z + f4.w * f4.w;
       rn_part += rv.x * rv.x + rv.y * rv.y + rv.z * rv.z + rv.w * rv.w;
     }
@@ -518,12 +546,15 @@ __global__ __launch_bounds__(1024) void k_keep_bwd(GridDev<float> G, KeepDev kp,
 // w1: 2 m floats of scratch (T, the forward partial sums: 2 g0 K1 K2 <= 2 m)
 static int launch_spectral_keep_cg(const GridDev<float>& G, const float* evec, const float* evec2, const float* evals, float kscale, float shift,
                                    float* r, float* w1, int it, int apply, double tol2, float* p, float* pt, float* part, int nch, int zl,
-                                   float* u, float* z, PcgScal S, hipStream_t s, const float* rhs0, const wiski_twolevel* two_level, const int* keep) {
+                                   float* u, float* z, PcgScal S, hipStream_t s, const float* rhs0, const wiski_twolevel* two_level, const int* keep,
+                                   const TapFold<float>* fold = nullptr) {
   const int g0 = G.g[0], g1 = G.g[1], g2 = G.g[2];
   if (!keep_counts_ok(G, keep, two_level != nullptr) || S.k != 1 || nch > 8) return WISKI_E_BADARG;
   if (two_level && (two_level->r < 1 || two_level->r > SPEC_TL_MAXR || !two_level->d_mask || !two_level->d_off || !two_level->d_pos || !two_level->d_N))
     return WISKI_E_BADARG;
   if (rhs0 && apply) return WISKI_E_BADARG;
+  if (fold && (!fold->stage || !fold->b || !fold->cnt || fold->b != rhs0)) return WISKI_E_BADARG;   // the fold rides on the norms of a carried residual
+  float *const fstage = fold ? fold->stage : nullptr, *const fb = fold ? fold->b : nullptr, *const fcnt = fold ? fold->cnt : nullptr;
   if (!evec2) evec2 = evec;
   const float *X0 = evec, *X1 = evec + g0 * g0, *X2 = X1 + g1 * g1;
   const float *Z0 = evec2, *Z1 = evec2 + g0 * g0, *Z2 = Z1 + g1 * g1;
@@ -555,7 +586,7 @@ static int launch_spectral_keep_cg(const GridDev<float>& G, const float* evec, c
   do {                                                                                                                                     \
     KEEP_LDS_OPT_IN((k_keep_fwd<KS, WW>), KEEP_FWD_LDS);                                                                                   \
     hipLaunchKernelGGL((k_keep_fwd<KS, WW>), grd, dim3(256), KEEP_FWD_LDS, s, G, kp, X1, X2, r, w1, it, ap, tol2, pin, (const float*)pt, S, \
-                       part, nch, zl, u, z);                                                                                               \
+                       part, nch, zl, u, z, fstage, fb, fcnt);                                                                             \
   } while (0)
 #define KEEP_FWD(KS, VW_UNUSED)          \
   do {                                   \

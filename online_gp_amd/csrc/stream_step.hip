@@ -6,6 +6,8 @@
 // With a deferred solve pending, the absorb of the NEXT batch is queued before the host has read that solve's convergence
 // poll, guarded on the device by the poll's own verdict (wiski_pcg_async_guard): the GPU goes from the last iteration
 // straight into the absorb instead of idling through the host's poll round trip (~20 us of a 220 us step).
+// With a tap stage (wiski_stream_args_f32.d_tap_stage) the absorb leaves its per-tap adds on b / cnt / R in the stage's records and
+// the solve queued behind it in the same call folds them in (PcgArgs::tap_stage): the stage is zero again whenever a call returns.
 // Pure host code: it fills the two argument records (absorb.h, pcg.h) and sequences absorb() and pcg().
 #include "absorb.h"
 #include "pcg.h"
@@ -21,11 +23,24 @@ struct StreamArgs<double> { using type = wiski_stream_args_f64; };
 // kernel -- it reads U whether or not it carries the residual, takes the owner-computes form or this rank's stencil groups
 // where they apply and, with `zero`, does the zeroing the following solve would do in a launch of its own; `guard`: see
 // wiski_pcg_async_guard.  Without mean_out: the plain absorb, U read for the residual carry only.
+// The stage this call's absorb and solve share, or NULL: fp32 at d = 3 with the carry and cnt, the whole stencil on this replica
+// (AbsorbArgs::tap_stage).  One rule for both sides: the absorb is handed the stage only where the solve is handed it too.
+static float* step_tap_stage(const wiski_grid* g, const wiski_stream_args_f32* a, int carry) {
+  return g->d == 3 && carry && a->d_cnt && !wiski_shard_active(a->shard) ? a->d_tap_stage : nullptr;
+}
+static double* step_tap_stage(const wiski_grid*, const wiski_stream_args_f64*, int) { return nullptr; }
+static int64_t grid_nodes(const wiski_grid* g) {
+  int64_t m = 1;
+  for (int q = 0; q < g->d; ++q) m *= g->g[q];
+  return m;
+}
+
 template <typename real>
 static int absorb_batch(const wiski_grid* g, const typename StreamArgs<real>::type* a, AbsorbArgs<real> r, int carry, int zero, void* s) {
   r.b = a->d_b; r.A = a->d_A_half; r.half = true; r.cnt = a->d_cnt; r.stats = a->d_stats; r.err = a->d_err;
   r.u = carry || r.mean_out ? a->d_U : nullptr;
   r.res = carry ? a->d_R : nullptr;
+  r.tap_stage = step_tap_stage(g, a, carry);
   if (!r.mean_out) return absorb(g, r, s);
   if (zero) {
     if (int rc = pcg_zero_regions<real>(g, 1, a->max_iter, a->d_work, true, &r.z1, &r.n1_bytes, &r.z2, &r.n2_bytes)) return rc;
@@ -68,6 +83,7 @@ static int stream_step_impl(const wiski_grid* grid, const typename StreamArgs<re
   if (first_check < -1 || (first_check == -1 && !as)) return WISKI_E_BADARG;
   int rc = WISKI_OK;
   if (h_resumed) *h_resumed = 0;
+  if (sizeof(real) == 8 && a->d_tap_stage) return WISKI_E_BADARG;
   PcgArgs<real> solve = solve_args<real>(a, carry, first_check);   // this stream's solve, reporting into the caller's outputs
   solve.h_iters = h_iters; solve.h_relres = h_relres; solve.h_err = h_err; solve.handle = as;
   AbsorbArgs<real> batch;                    // the points of this call; absorb_batch adds the targets
@@ -98,7 +114,12 @@ static int stream_step_impl(const wiski_grid* grid, const typename StreamArgs<re
       rc = pcg(grid, resume, stream);
     }
     if (h_resumed) *h_resumed = 1;
-    if (rc != WISKI_OK && rc != WISKI_E_NOTCONV) return rc;
+    if (rc != WISKI_OK && rc != WISKI_E_NOTCONV) {
+      if constexpr (sizeof(real) == 4) {           // the speculative absorb may have staged its batch: no solve of this call will fold it
+        if (spec && step_tap_stage(grid, a, carry)) (void)tap_fold(a->d_tap_stage, a->d_b, a->d_cnt, a->d_R, grid_nodes(grid), stream);
+      }
+      return rc;
+    }
     absorbed = spec && as->guard_ok;          // else the guarded kernel was a no-op (and RESUME may have queued more iterations)
     if (q == 0) return rc;
     if (!absorbed && h_err && *h_err) return rc;   // out-of-grid points in the previous batch: let the caller deal with them first
@@ -106,6 +127,10 @@ static int stream_step_impl(const wiski_grid* grid, const typename StreamArgs<re
     return WISKI_OK;
   }
   const int resumed_rc = rc;
+  if (q > 0) {                                 // this call's absorb stages its tap adds (or has done so): its solve folds them
+    solve.tap_stage = step_tap_stage(grid, a, carry);
+    if (solve.tap_stage) { solve.tap_b = a->d_b; solve.tap_cnt = a->d_cnt; }
+  }
   if (absorbed) {
     as->prezeroed = 1;
   } else if (q > 0) {

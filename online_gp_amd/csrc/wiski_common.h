@@ -299,12 +299,22 @@ template <typename real>
 int launch_spectral_fused(const GridDev<real>& G, const real* evec, const real* evec2, const real* evals, real kscale, real shift, const real* r,
                           int k, real* w0, real* w1, real* ty, double* rho, hipStream_t s);
 
+// The tap stage of a streaming step on its way into the solve that folds it in (AbsorbArgs::tap_stage, PcgArgs::tap_stage): the
+// [m][4] records and the b / cnt they belong to; the third array is the solve's own residual.
+template <typename real>
+struct TapFold {
+  real* stage;
+  real* b;
+  real* cnt;
+};
+
 // Fused CG-iteration front end (d = 3): [apply update_x(it-1)] + mode-0 fwd -> slab (+rho) -> mode-0 bwd (+update_p)
+// fold (with rhs0 and keep only, rhs0 == fold->b): the forward kernel also folds the tap stage into rhs0, cnt and r (spectral_keep.h)
 template <typename real>
 int launch_spectral_fused_cg(const GridDev<real>& G, const real* evec, const real* evec2, const real* evals, real kscale, real shift, real* r,
                              int k, real* w0, real* w1, int it, int apply, double tol2, real* p, real* pt, real* part, int nch, int zl, real* u,
                              real* z, PcgScal S, hipStream_t s, const real* rhs0 = nullptr, const wiski_twolevel* two_level = nullptr,
-                             const int* keep = nullptr);
+                             const int* keep = nullptr, const TapFold<real>* fold = nullptr);
 // ... with `keep` counts (fp32, one column): would a solve on G accept them?  (multiples of 4 in [4, min(g_q, 24)], the backward
 // kernel's cubes within its LDS budget -- spectral_keep.h)
 bool spectral_keep_ok(const GridDev<float>& G, const int* keep, bool two_level);

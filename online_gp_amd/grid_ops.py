@@ -1363,7 +1363,7 @@ class _StreamArgs32(ctypes.Structure):
                 ("d_eval", ctypes.c_void_p), ("shift", ctypes.c_float), ("tol", ctypes.c_double), ("max_iter", ctypes.c_int32),
                 ("check_every", ctypes.c_int32), ("d_work", ctypes.c_void_p), ("work_bytes", ctypes.c_int64),
                 ("d_bin", ctypes.c_void_p), ("bin_bytes", ctypes.c_int64), ("shard", ctypes.c_void_p), ("two_level", ctypes.c_void_p),
-                ("keep", ctypes.c_int32 * 3)]
+                ("keep", ctypes.c_int32 * 3), ("d_tap_stage", ctypes.c_void_p)]
 
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
@@ -1427,6 +1427,9 @@ class StreamStep:
         self.keep += (buf,)
         a.d_work, a.work_bytes, a.max_iter = buf.data_ptr(), need, max_iter
         self.bin_buf = None                    # binning workspace of the owner-computes absorb: grown on demand, zeroed once
+        # tap stage of the absorb (include/wiski.h: d_tap_stage): [m][4], zero between calls -- the step's own solve folds it in
+        self.tap_stage = torch.zeros(grid.m * 4, dtype=dtype, device=device) if dtype == torch.float32 and grid.d == 3 else None
+        a.d_tap_stage = self.tap_stage.data_ptr() if self.tap_stage is not None else None
         self.fn = _hip.fn("wiski_stream_step", dtype)
         self.it, self.herr, self.rr = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_double(0)
         self.eig_keep = None
