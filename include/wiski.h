@@ -799,9 +799,22 @@ int wiski_precond_apply_cols_f32(const wiski_grid* grid, const float* d_evec, co
  *                row) -- what a consumer wants that solves against the factor many times (the spectral and the dense Woodbury
  *                factor: mean, variances, MLL terms are then single GEMM / GEMV launches)
  *   wiski_trsm   in-place solve  L X = B (trans = 0)  or  L^T X = B (trans = 1), B is n x nrhs
- *   wiski_logdiag  *d_out += sum_i log A[i,i]   (double) */
+ *   wiski_logdiag  *d_out += sum_i log A[i,i]   (double)
+ * wiski_gemm answers WISKI_E_BADARG for a NULL operand, K < 0, lda < (ta ? M : K), ldb < (tb ? K : N) or ldc < N and touches nothing;
+ * M <= 0 or N <= 0 is WISKI_OK (nothing to do); K == 0 is legal and gives C = beta C (exact zeros for beta == 0: C is not read then,
+ * whatever it holds).  Operands and C may be windows of larger matrices: any base pointer aligned to the element, any leading dimension
+ * from the bounds above.  wiski_trsm references the lower triangle of L only (the strict upper triangle may hold anything). */
 int wiski_gemm_f32(int32_t ta, int32_t tb, int32_t M, int32_t N, int32_t K, float alpha, const float* d_A, int32_t lda, const float* d_B, int32_t ldb, float beta, float* d_C, int32_t ldc, void* stream);
 int wiski_gemm_f64(int32_t ta, int32_t tb, int32_t M, int32_t N, int32_t K, double alpha, const double* d_A, int32_t lda, const double* d_B, int32_t ldb, double beta, double* d_C, int32_t ldc, void* stream);
+/* Which kernel wiski_gemm (and every internal product of the library) takes for an M x N output over K terms of elem_bytes (4 or 8) wide
+ * reals; launches nothing, reads the same once-per-process switch (WISKI_GEMM32_MAX_TILES) as the launcher.  t64 = ceil(M/64) ceil(N/64),
+ * t128 = ceil(M/128) ceil(N/128), tested in this order:
+ *   2 k_gemm128 on 64 x 64 tiles, 8 waves    K >= 128 and 240 <= t64 <= 900 (fp64) / 110 <= t64 <= 800 (fp32)
+ *   1 k_gemm32  (32 x 32 tiles)              K >= 64, M N >= 8192 and t64 < 500 (fp64) / 300 (fp32) (or WISKI_GEMM32_MAX_TILES)
+ *   3 k_gemm128 on 128 x 128 tiles, 8 waves  K >= 256 and t128 >= 128 (fp64) / 32 (fp32)
+ *   0 k_gemm    (64 x 64 tiles)              everything else
+ * WISKI_E_BADARG: M < 1, N < 1, K < 0, elem_bytes other than 4 or 8. */
+int wiski_gemm_path(int32_t M, int32_t N, int32_t K, int32_t elem_bytes);
 int wiski_potrf_f32(int32_t n, float* d_A, int32_t lda, int32_t* d_info, void* stream);
 int wiski_potrf_f64(int32_t n, double* d_A, int32_t lda, int32_t* d_info, void* stream);
 int wiski_potrf_inverse_f32(int32_t n, float* d_A, int32_t lda, float* d_X, int32_t ldx, int32_t* d_info, void* stream);

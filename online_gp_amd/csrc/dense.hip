@@ -315,75 +315,73 @@ __global__ __launch_bounds__(256) void k_gemm32(int M, int N, int K, real alpha,
   }
 }
 
+// Which of the four kernels a product takes: ONE host function, read by launch_gemm and by wiski_gemm_path (include/wiski.h), so that
+// a test can name the kernel it means to reach.  Codes as documented there.
+enum { GEMM_PATH_64 = 0, GEMM_PATH_32 = 1, GEMM_PATH_P64 = 2, GEMM_PATH_P128 = 3 };
+static int gemm_path(int M, int N, int K, int elem_bytes) {
+  const bool f64 = elem_bytes == 8;
+  // Small tiles while the 64 x 64 grid is about one tile per CU or less (and there is enough K to matter).  Round 4 (tools/gemm_mid_probe.py,
+  // profiles/r04_gemm_mid.txt): a 64 x 64 tile is ONE 4-wave workgroup, so up to ~256 tiles a CU holds one wave per SIMD and nothing hides
+  // the LDS / global latency of its K loop; the 32 x 32 kernel puts 4 workgroups on a CU for the same output.  fp64 n = 800 / 1000 / 1200 /
+  // 1400: 92 / 116 / 157 / 198 us -> 38 / 62 / 105 / 178 us (27..33 TF instead of 11..28); fp32: 65 / 84 / 101 / 117 -> 34 / 50 / 103 / 131 us.
+  // Hence below 500 (fp64) / 300 (fp32) tiles of 64 x 64; it was 128 for both.  WISKI_GEMM32_MAX_TILES overrides.
+  const int64_t nb64 = (int64_t)((N + GBN - 1) / GBN) * ((M + GBM - 1) / GBM);
+  // (round 5) the pipelined kernel on a 64 x 64 tile with 8 waves, between p_min and p_max output tiles
+  // where it wins (tools/gemm_mid_probe.py, profiles/r05_gemm_mid.txt; n = side of a square product):
+  //   fp32  n = 800 .. 1600: 35 / 50 / 98 / 116 / 132 us -> 29 / 37 / 65 / 75 / 109 us (n = 1000: 40 -> 54 TF, TN 62 TF)   => 110 .. 800 tiles
+  //   fp64  n = 1000 / 1400 / 1600: 61 / 178 / 249 us -> 57 / 124 / 189 us (A^T B 53 / 116 / 175, A B^T 71 -> 60 at 1000)   => 240 .. 900 tiles
+  const int p_min = f64 ? 240 : 110;
+  const int p_max = f64 ? 900 : 800;
+  if (nb64 >= p_min && nb64 <= p_max && K >= 128) return GEMM_PATH_P64;
+  static const int small_max_env = [] { const char* e = getenv("WISKI_GEMM32_MAX_TILES"); return e ? atoi(e) : 0; }();
+  const int small_max = small_max_env > 0 ? small_max_env : (f64 ? 500 : 300);
+  if (nb64 < small_max && K >= 64 && (int64_t)M * N >= 32 * 32 * 8) return GEMM_PATH_32;
+  // the 128 x 128 kernel once its grid covers at least half the chip (n >= ~1500 square): below that the 64 x 64 tiles fill more CUs
+  const int64_t nb = (int64_t)((N + G2N - 1) / G2N) * ((M + G2M - 1) / G2M);
+  const int minb = gemm128_min_blocks();
+  // (K >= 256: the rank-64 trailing updates of wiski_potrf / wiski_trsm are 4 K tiles of fp64 -- prologue-bound here, faster on the
+  // small kernel; fp64 needs twice the grid before the large tile wins: 24 vs 27 TF at n = 1536, 42 vs 39 at 2048)
+  // (round 3, 8-wave form: fp32 wins from 32 blocks -- 24 vs 21 TF at n = 1024 --, fp64 from 128 -- 31 vs 27 TF at n = 1536, but 14 vs 18 at 1024)
+  if (minb > 0 && nb >= (f64 ? 4 * minb : minb) && K >= 256) return GEMM_PATH_P128;
+  return GEMM_PATH_64;
+}
+
 template <typename real>
 static int launch_gemm(int ta, int tb, int M, int N, int K, real alpha, const real* A, int lda, const real* B, int ldb, real beta, real* C,
                        int ldc, hipStream_t s) {
   if (M <= 0 || N <= 0) return WISKI_OK;
-  {
-    // Small tiles while the 64 x 64 grid is about one tile per CU or less (and there is enough K to matter).  Round 4 (tools/gemm_mid_probe.py,
-    // profiles/r04_gemm_mid.txt): a 64 x 64 tile is ONE 4-wave workgroup, so up to ~256 tiles a CU holds one wave per SIMD and nothing hides
-    // the LDS / global latency of its K loop; the 32 x 32 kernel puts 4 workgroups on a CU for the same output.  fp64 n = 800 / 1000 / 1200 /
-    // 1400: 92 / 116 / 157 / 198 us -> 38 / 62 / 105 / 178 us (27..33 TF instead of 11..28); fp32: 65 / 84 / 101 / 117 -> 34 / 50 / 103 / 131 us.
-    // Hence below 500 (fp64) / 300 (fp32) tiles of 64 x 64; it was 128 for both.  WISKI_GEMM32_MAX_TILES overrides.
-    const int64_t nb64 = (int64_t)((N + GBN - 1) / GBN) * ((M + GBM - 1) / GBM);
-    {
-      // (round 5) the pipelined kernel on a 64 x 64 tile with 8 waves, between WISKI_GEMM64P_MIN and _MAX output tiles
-      // where it wins (tools/gemm_mid_probe.py, profiles/r05_gemm_mid.txt; n = side of a square product):
-      //   fp32  n = 800 .. 1600: 35 / 50 / 98 / 116 / 132 us -> 29 / 37 / 65 / 75 / 109 us (n = 1000: 40 -> 54 TF, TN 62 TF)   => 110 .. 800 tiles
-      //   fp64  n = 1000 / 1400 / 1600: 61 / 178 / 249 us -> 57 / 124 / 189 us (A^T B 53 / 116 / 175, A B^T 71 -> 60 at 1000)   => 240 .. 900 tiles
-      const int p_min = sizeof(real) == 4 ? 110 : 240;
-      const int p_max = sizeof(real) == 4 ? 800 : 900;
-      if (nb64 >= p_min && nb64 <= p_max && K >= 128) {
-        dim3 g6((unsigned)((N + 63) / 64), (unsigned)((M + 63) / 64));
-#define G64P(NWV)                                                                                                                                      \
+#define GEMM_LAUNCH(KERNEL, GRID, THREADS, ...)                                                                                                        \
   do {                                                                                                                                                 \
-    if (!ta && !tb) hipLaunchKernelGGL((k_gemm128<real, false, false, NWV, 64>), g6, dim3(64 * NWV), 0, s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);      \
-    else if (ta && !tb) hipLaunchKernelGGL((k_gemm128<real, true, false, NWV, 64>), g6, dim3(64 * NWV), 0, s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);   \
-    else if (!ta && tb) hipLaunchKernelGGL((k_gemm128<real, false, true, NWV, 64>), g6, dim3(64 * NWV), 0, s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);   \
-    else hipLaunchKernelGGL((k_gemm128<real, true, true, NWV, 64>), g6, dim3(64 * NWV), 0, s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);                   \
+    if (!ta && !tb) hipLaunchKernelGGL((KERNEL<real, false, false __VA_ARGS__>), GRID, dim3(THREADS), 0, s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);     \
+    else if (ta && !tb) hipLaunchKernelGGL((KERNEL<real, true, false __VA_ARGS__>), GRID, dim3(THREADS), 0, s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);  \
+    else if (!ta && tb) hipLaunchKernelGGL((KERNEL<real, false, true __VA_ARGS__>), GRID, dim3(THREADS), 0, s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);  \
+    else hipLaunchKernelGGL((KERNEL<real, true, true __VA_ARGS__>), GRID, dim3(THREADS), 0, s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);                  \
   } while (0)
-        G64P(8);
-#undef G64P
-        return hipGetLastError() == hipSuccess ? WISKI_OK : WISKI_E_LAUNCH;
-      }
+  switch (gemm_path(M, N, K, (int)sizeof(real))) {
+    case GEMM_PATH_P64: {
+      dim3 g6((unsigned)((N + 63) / 64), (unsigned)((M + 63) / 64));
+      GEMM_LAUNCH(k_gemm128, g6, 512, , 8, 64);
+      break;
     }
-    constexpr bool small_on = true;
-    static const int small_max_env = [] { const char* e = getenv("WISKI_GEMM32_MAX_TILES"); return e ? atoi(e) : 0; }();
-    const int small_max = small_max_env > 0 ? small_max_env : (sizeof(real) == 8 ? 500 : 300);
-    if (small_on && nb64 < small_max && K >= 64 && (int64_t)M * N >= 32 * 32 * 8) {
+    case GEMM_PATH_32: {
       dim3 g3((unsigned)((N + 31) / 32), (unsigned)((M + 31) / 32));
-      if (!ta && !tb) hipLaunchKernelGGL((k_gemm32<real, false, false>), g3, dim3(256), 0, s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);
-      else if (ta && !tb) hipLaunchKernelGGL((k_gemm32<real, true, false>), g3, dim3(256), 0, s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);
-      else if (!ta && tb) hipLaunchKernelGGL((k_gemm32<real, false, true>), g3, dim3(256), 0, s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);
-      else hipLaunchKernelGGL((k_gemm32<real, true, true>), g3, dim3(256), 0, s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);
-      return hipGetLastError() == hipSuccess ? WISKI_OK : WISKI_E_LAUNCH;
+      GEMM_LAUNCH(k_gemm32, g3, 256);
+      break;
     }
-  }
-  {
-    // the 128 x 128 kernel once its grid covers at least half the chip (n >= ~1500 square): below that the 64 x 64 tiles fill more CUs
-    const int64_t nb = (int64_t)((N + G2N - 1) / G2N) * ((M + G2M - 1) / G2M);
-    const int minb = gemm128_min_blocks();
-    // (K >= 256: the rank-64 trailing updates of wiski_potrf / wiski_trsm are 4 K tiles of fp64 -- prologue-bound here, faster on the
-    // small kernel; fp64 needs twice the grid before the large tile wins: 24 vs 27 TF at n = 1536, 42 vs 39 at 2048)
-    // (round 3, 8-wave form: fp32 wins from 32 blocks -- 24 vs 21 TF at n = 1024 --, fp64 from 128 -- 31 vs 27 TF at n = 1536, but 14 vs 18 at 1024)
-    if (minb > 0 && nb >= (sizeof(real) == 8 ? 4 * minb : minb) && K >= 256) {
-      dim3 g2((unsigned)((N + G2N - 1) / G2N), (unsigned)((M + G2M - 1) / G2M));
+    case GEMM_PATH_P128: {
       // 8 waves per 128 x 128 tile (64 x 32 per wave) beat 4 at every size measured: twice the waves per CU hide the LDS and
       // barrier latency of the K loop (fp32 n = 2048: 89 -> 100 TF, fp64 n = 4096: 45 -> 61 TF)
-      {
-        if (!ta && !tb) hipLaunchKernelGGL((k_gemm128<real, false, false, 8>), g2, dim3(512), 0, s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);
-        else if (ta && !tb) hipLaunchKernelGGL((k_gemm128<real, true, false, 8>), g2, dim3(512), 0, s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);
-        else if (!ta && tb) hipLaunchKernelGGL((k_gemm128<real, false, true, 8>), g2, dim3(512), 0, s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);
-        else hipLaunchKernelGGL((k_gemm128<real, true, true, 8>), g2, dim3(512), 0, s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);
-        return hipGetLastError() == hipSuccess ? WISKI_OK : WISKI_E_LAUNCH;
-      }
+      dim3 g2((unsigned)((N + G2N - 1) / G2N), (unsigned)((M + G2M - 1) / G2M));
+      GEMM_LAUNCH(k_gemm128, g2, 512, , 8);
+      break;
+    }
+    default: {
+      dim3 grd((unsigned)((N + GBN - 1) / GBN), (unsigned)((M + GBM - 1) / GBM));
+      GEMM_LAUNCH(k_gemm, grd, 256);
+      break;
     }
   }
-  dim3 grd((unsigned)((N + GBN - 1) / GBN), (unsigned)((M + GBM - 1) / GBM));
-  if (!ta && !tb) hipLaunchKernelGGL((k_gemm<real, false, false>), grd, dim3(256), 0, s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);
-  else if (ta && !tb) hipLaunchKernelGGL((k_gemm<real, true, false>), grd, dim3(256), 0, s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);
-  else if (!ta && tb) hipLaunchKernelGGL((k_gemm<real, false, true>), grd, dim3(256), 0, s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);
-  else hipLaunchKernelGGL((k_gemm<real, true, true>), grd, dim3(256), 0, s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);
+#undef GEMM_LAUNCH
   return hipGetLastError() == hipSuccess ? WISKI_OK : WISKI_E_LAUNCH;
 }
 
@@ -1031,14 +1029,26 @@ static int dense_factor_impl(const wiski_grid* grid, const real* d_A_half, const
   return rc;
 }
 
+// The C entry of wiski_gemm: the arguments launch_gemm's internal callers get right by construction are checked here.  An empty output is
+// no error (nothing to do); a leading dimension shorter than the stored row would make rows overlap or run past the operand.
+template <typename real>
+static int gemm_entry(int ta, int tb, int M, int N, int K, real alpha, const real* A, int lda, const real* B, int ldb, real beta, real* C, int ldc, void* s) {
+  if (!A || !B || !C || K < 0) return WISKI_E_BADARG;
+  if (M <= 0 || N <= 0) return WISKI_OK;
+  if (lda < (ta ? M : K) || ldb < (tb ? K : N) || ldc < N) return WISKI_E_BADARG;
+  return launch_gemm<real>(ta, tb, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, (hipStream_t)s);
+}
+
 extern "C" {
 int wiski_gemm_f32(int32_t ta, int32_t tb, int32_t M, int32_t N, int32_t K, float alpha, const float* A, int32_t lda, const float* B, int32_t ldb, float beta, float* C, int32_t ldc, void* s) {
-  if (!A || !B || !C || K < 0) return WISKI_E_BADARG;
-  return launch_gemm<float>(ta, tb, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, (hipStream_t)s);
+  return gemm_entry<float>(ta, tb, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, s);
 }
 int wiski_gemm_f64(int32_t ta, int32_t tb, int32_t M, int32_t N, int32_t K, double alpha, const double* A, int32_t lda, const double* B, int32_t ldb, double beta, double* C, int32_t ldc, void* s) {
-  if (!A || !B || !C || K < 0) return WISKI_E_BADARG;
-  return launch_gemm<double>(ta, tb, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, (hipStream_t)s);
+  return gemm_entry<double>(ta, tb, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, s);
+}
+int wiski_gemm_path(int32_t M, int32_t N, int32_t K, int32_t elem_bytes) {
+  if (M < 1 || N < 1 || K < 0 || (elem_bytes != 4 && elem_bytes != 8)) return WISKI_E_BADARG;
+  return gemm_path(M, N, K, elem_bytes);
 }
 int wiski_dense_factor_f32(const wiski_grid* g, const float* A_half, const float* evec, const float* eval, float kscale, float* work, int64_t work_elems, float* chol, float* M, double* logdiag, int32_t* info, void* s) { return dense_factor_impl<float>(g, A_half, evec, eval, kscale, work, work_elems, chol, M, logdiag, info, s); }
 int wiski_dense_factor_f64(const wiski_grid* g, const double* A_half, const double* evec, const double* eval, double kscale, double* work, int64_t work_elems, double* chol, double* M, double* logdiag, int32_t* info, void* s) { return dense_factor_impl<double>(g, A_half, evec, eval, kscale, work, work_elems, chol, M, logdiag, info, s); }

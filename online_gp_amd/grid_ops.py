@@ -1762,6 +1762,15 @@ def gemm(A, B, ta=False, tb=False, alpha=1.0, beta=0.0, C=None):
     return C
 
 
+def gemm_path(M, N, K, dtype):
+    """The kernel ``wiski_gemm`` takes for an M x N output over K terms (``wiski_gemm_path``; host only, launches nothing):
+    0 k_gemm, 1 k_gemm32, 2 k_gemm128 on 64-tiles, 3 k_gemm128 on 128-tiles."""
+    rc = _hip.lib().wiski_gemm_path(ctypes.c_int32(M), ctypes.c_int32(N), ctypes.c_int32(K), ctypes.c_int32(4 if dtype == torch.float32 else 8))
+    if rc < 0:
+        _hip.check(rc, "wiski_gemm_path")
+    return rc
+
+
 def potrf_(A, info=None):
     """In-place lower Cholesky; returns the device info flag (non-zero: not positive definite)."""
     assert A.dim() == 2 and A.shape[0] == A.shape[1] and A.is_contiguous()
