@@ -11,7 +11,12 @@ online_gp/models/batched_fixed_noise_online_gp.py:107-120), and the
 The grid kernel itself is never formed: :meth:`GridInterpolationKernel.toeplitz_columns`
 returns the first columns of the d symmetric-Toeplitz Kronecker factors
 (ScaleKernel inside => outputscale enters once per dim, i.e. s**d overall).
+
+Beyond RBF / Matern / spectral mixture: ``PeriodicKernel``, ``RQKernel``, ``ProductKernel`` (element-wise product of
+columns) and ``SeparableKernel`` (one 1-D kernel per input dimension) -- each still one symmetric Toeplitz factor per
+dimension; their columns are the closed forms evaluated on the cached lags, on every device.
 """
+import collections
 import math
 
 import torch
@@ -113,6 +118,154 @@ class MaternKernel(Kernel):
             return (1.0 + s) * torch.exp(-s)
         s = math.sqrt(5.0) * r
         return (1.0 + s + s * s / 3.0) * torch.exp(-s)
+
+
+def _dim_value(value, index, batch_index):
+    """Entry `index` (an int or a long tensor of dims) of a [..., 1, nd] hyper-parameter, in fp64; nd = 1 serves every dim."""
+    if batch_index is not None and value.dim() > 2:
+        value = value[batch_index]
+    v = value.reshape(-1).double()
+    return v[index] if v.numel() > 1 else v[0]
+
+
+class _ExtraPositive:
+    """Registration, property access and setter of one more constrained raw parameter next to the lengthscale
+    (``period_length``, ``alpha``), with the conventions of ``Kernel.lengthscale``."""
+
+    def _register_extra(self, name, shape, prior, constraint):
+        self.register_parameter(f"raw_{name}", torch.nn.Parameter(torch.zeros(shape)))
+        setattr(self, f"raw_{name}_constraint", constraint if constraint is not None else Positive())
+        if prior is not None:
+            self.register_prior(f"{name}_prior", prior, lambda: getattr(self, name))
+
+    def _get_extra(self, name):
+        return getattr(self, f"raw_{name}_constraint").transform(getattr(self, f"raw_{name}"))
+
+    def _set_extra(self, name, value):
+        raw = getattr(self, f"raw_{name}")
+        v = torch.as_tensor(value, dtype=torch.float64).expand(raw.shape)
+        with torch.no_grad():
+            raw.copy_(getattr(self, f"raw_{name}_constraint").inverse_transform(v).to(raw))
+
+
+class PeriodicKernel(_ExtraPositive, Kernel):
+    """k(tau) = exp(-2 sin^2(pi tau / p) / ell^2) per dimension (MacKay's periodic kernel; the ``ell^2`` form -- gpytorch's
+    releases have differed on ``ell`` against ``ell^2``).  ``lengthscale`` and ``period_length`` are [..., 1, nd]."""
+
+    has_lengthscale = True
+
+    def __init__(self, ard_num_dims=None, batch_shape=torch.Size([]), period_length_prior=None, period_length_constraint=None, **kwargs):
+        super().__init__(ard_num_dims=ard_num_dims, batch_shape=batch_shape, **kwargs)
+        nd = 1 if ard_num_dims is None else ard_num_dims
+        self._register_extra("period_length", self.batch_shape + torch.Size([1, nd]), period_length_prior, period_length_constraint)
+
+    period_length = property(lambda self: self._get_extra("period_length"), lambda self, v: self._set_extra("period_length", v))
+
+    def _column(self, lags, index, batch_index):
+        ell = _dim_value(self.lengthscale, index, batch_index)
+        p = _dim_value(self.period_length, index, batch_index)
+        s = torch.sin(math.pi * lags.double() / p)
+        return torch.exp(-2.0 * s * s / (ell * ell))
+
+    def lag_column(self, dim, lags, batch_index=None):
+        return self._column(lags, dim, batch_index)
+
+    def lag_columns_cat(self, lags_cat, dim_index, batch_index=None):
+        return self._column(lags_cat, dim_index, batch_index)
+
+
+class RQKernel(_ExtraPositive, Kernel):
+    """Rational quadratic: (1 + tau^2 / (2 alpha ell^2))^-alpha per dimension, evaluated as exp(-alpha log1p(.)); a scale mixture
+    of RBF profiles (alpha -> inf: RBF).  ``lengthscale`` [..., 1, nd]; one ``alpha`` [..., 1] for all dimensions.  On a grid the
+    kernel is the product of the per-dimension profiles, as with Matern here."""
+
+    has_lengthscale = True
+
+    def __init__(self, ard_num_dims=None, batch_shape=torch.Size([]), alpha_prior=None, alpha_constraint=None, **kwargs):
+        super().__init__(ard_num_dims=ard_num_dims, batch_shape=batch_shape, **kwargs)
+        self._register_extra("alpha", self.batch_shape + torch.Size([1]), alpha_prior, alpha_constraint)
+
+    alpha = property(lambda self: self._get_extra("alpha"), lambda self, v: self._set_extra("alpha", v))
+
+    def _alpha_value(self, batch_index):
+        a = self.alpha
+        if batch_index is not None and a.dim() > 1:
+            a = a[batch_index]
+        return a.reshape(-1).double()[0]
+
+    def _column(self, lags, index, batch_index):
+        ell = _dim_value(self.lengthscale, index, batch_index)
+        a = self._alpha_value(batch_index)
+        tau = lags.double()
+        return torch.exp(-a * torch.log1p(tau * tau / (2.0 * a * ell * ell)))
+
+    def lag_column(self, dim, lags, batch_index=None):
+        return self._column(lags, dim, batch_index)
+
+    def lag_columns_cat(self, lags_cat, dim_index, batch_index=None):
+        return self._column(lags_cat, dim_index, batch_index)
+
+
+class ProductKernel(Kernel):
+    """Element-wise product of its members' columns in every dimension (a product of stationary kernels on one input is
+    stationary, and the element-wise product of symmetric Toeplitz matrices is symmetric Toeplitz).  Locally periodic:
+    ``ProductKernel(PeriodicKernel(), RBFKernel())``."""
+
+    def __init__(self, *kernels, **kwargs):
+        if len(kernels) < 1 or not all(isinstance(k, Kernel) for k in kernels):
+            raise TypeError("ProductKernel takes one or more kernels of this module")
+        super().__init__(batch_shape=kernels[0].batch_shape, **kwargs)
+        self.kernels = torch.nn.ModuleList(kernels)
+
+    def lag_column(self, dim, lags, batch_index=None):
+        out = self.kernels[0].lag_column(dim, lags, batch_index)
+        for k in list(self.kernels)[1:]:
+            out = out * k.lag_column(dim, lags, batch_index)
+        return out
+
+    def lag_columns_cat(self, lags_cat, dim_index, batch_index=None):
+        out = self.kernels[0].lag_columns_cat(lags_cat, dim_index, batch_index)
+        for k in list(self.kernels)[1:]:
+            out = out * k.lag_columns_cat(lags_cat, dim_index, batch_index)
+        return out
+
+
+_ONE_DIM_FAMILIES = (RBFKernel, MaternKernel, PeriodicKernel, RQKernel)      # what a separable factor may be (or a product of)
+
+
+def _one_dim_factor(k):
+    if isinstance(k, ProductKernel):
+        return all(_one_dim_factor(m) for m in k.kernels)
+    return type(k) in _ONE_DIM_FAMILIES and k.ard_num_dims in (None, 1)
+
+
+class SeparableKernel(Kernel):
+    """One 1-D kernel per input dimension: the column of dimension q is ``factors[q].lag_column(0, lags)`` ("periodic in
+    dimension 0, Matern in the rest").  Each factor is an RBF / Matern / periodic / RQ kernel with ``ard_num_dims`` None or 1, or
+    a ``ProductKernel`` of such; the same object may stand in several places (tied hyper-parameters)."""
+
+    def __init__(self, factors, **kwargs):
+        factors = list(factors)
+        if len(factors) < 1:
+            raise ValueError("SeparableKernel needs one factor per input dimension")
+        for q, f in enumerate(factors):
+            if not isinstance(f, Kernel) or not _one_dim_factor(f):
+                raise TypeError(f"SeparableKernel: factor {q} must be an RBF, Matern, periodic or RQ kernel with ard_num_dims None or 1, "
+                                f"or a ProductKernel of such, got {type(f).__name__}")
+        super().__init__(batch_shape=factors[0].batch_shape, **kwargs)
+        self.factors = torch.nn.ModuleList(factors)
+
+    def lag_column(self, dim, lags, batch_index=None):
+        return self.factors[dim].lag_column(0, lags, batch_index)
+
+    def lag_columns_cat(self, lags_cat, dim_index, batch_index=None):
+        # every factor over all entries, selected by dimension: no data-dependent shapes, so the graph can be captured
+        zero = torch.zeros_like(dim_index)
+        out = None
+        for q, f in enumerate(self.factors):
+            col = f.lag_columns_cat(lags_cat, zero, batch_index)
+            out = col if out is None else torch.where(dim_index == q, col, out)
+        return out
 
 
 class SpectralMixtureKernel(Kernel):
@@ -258,11 +411,28 @@ def _fused_stationary(kernel, batch_index):
     return ls.reshape(-1), scale, kind
 
 
+KernelFamilies = collections.namedtuple("KernelFamilies", "periodic any")
+
+
+def kernel_families(kernel):
+    """KernelFamilies(periodic, any): does `kernel` contain a PeriodicKernel; does it contain a periodic, RQ, product or separable
+    kernel at all?  The MLL of a kernel with a periodic member is not taken from the truncated spectral factor (the
+    gradient the factor returns for a period is not the MLL's); the captured hyper-parameter step declines all four."""
+    mods = list(kernel.modules()) if isinstance(kernel, torch.nn.Module) else []
+    return KernelFamilies(any(isinstance(m, PeriodicKernel) for m in mods),
+                          any(isinstance(m, (PeriodicKernel, RQKernel, ProductKernel, SeparableKernel)) for m in mods))
+
+
 def _native_stationary(kernel):
-    """Scale(...(RBF | Matern)) chains of this module: their columns have the closed form used by lag_columns_cat."""
+    """Scale(...(RBF | Matern | Periodic | RQ | SpectralMixture | Product / Separable of those)) of this module: their columns
+    have the closed forms that lag_columns_cat evaluates on the cached lags."""
     while isinstance(kernel, ScaleKernel):
         kernel = kernel.base_kernel
-    return type(kernel) in (RBFKernel, MaternKernel, SpectralMixtureKernel)
+    if isinstance(kernel, ProductKernel):
+        return all(_native_stationary(k) for k in kernel.kernels)
+    if isinstance(kernel, SeparableKernel):
+        return all(_native_stationary(k) for k in kernel.factors)
+    return type(kernel) in _ONE_DIM_FAMILIES + (SpectralMixtureKernel,)
 
 
 def _lag_column_any(kernel, dim, lags, num_dims, batch_index=None):
@@ -298,6 +468,9 @@ class GridInterpolationKernel(Kernel):
         self.base_kernel = base_kernel
         self.num_dims = num_dims
         self.grid_spec = GridSpec(gb.tolist(), grid_size)
+        for sep in (base_kernel.modules() if isinstance(base_kernel, torch.nn.Module) else ()):       # (also one inside a ProductKernel)
+            if isinstance(sep, SeparableKernel) and len(sep.factors) != self.grid_spec.d:
+                raise ValueError(f"SeparableKernel has {len(sep.factors)} factors but the grid has {self.grid_spec.d} dimensions")
         self.grid_bounds = tuple((float(lo), float(hi)) for lo, hi in gb.tolist())
         self.grid_sizes = list(self.grid_spec.g)
         self.grid_is_dynamic = False

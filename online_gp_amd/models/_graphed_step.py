@@ -78,6 +78,8 @@ class GraphedHyperStep:
             return None
         if max(gp._grid.g) > 64:                      # (the one-launch lag gradient; larger factors take the op-by-op form)
             return None
+        if gp._kernel_families().any:               # (periodic / RQ / product / separable: the op-by-op step)
+            return None
         gp._finish_pending()
         # the eager MLL checks the out-of-grid flag first (a host read; it may not happen inside a capture) -- unless evaluate() has
         # just read it clean with the same statistics (models/online_ski_regression.py)

@@ -855,7 +855,26 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             return False
         if not self._use_dense():
             return True
-        return settings.spectral_dense_regime.on() and bool(self.__dict__.get("_stream_owner"))
+        return settings.spectral_dense_regime.on() and bool(self.__dict__.get("_stream_owner")) and not self._kernel_families().periodic
+
+    def _kernel_families(self):
+        """kernels.KernelFamilies(periodic, any) of the covariance module, looked up once per covariance module object (the per-step
+        path reads the memo; assigning another module looks again)."""
+        cm = self.covar_module
+        memo = self.__dict__.get("_families_memo")
+        if memo is None or memo[0] is not cm:
+            from ..kernels import kernel_families
+
+            memo = self.__dict__["_families_memo"] = (cm, kernel_families(cm))
+        return memo[1]
+
+    def _mll_spectral_state(self, o):
+        """The spectral factor's state for the MLL terms of output o and their gradient, or None where the MLL has to come from the
+        nodal dense factor or the PCG terms: wherever the factor does not serve at all, and for a covariance with a PeriodicKernel, whose
+        period gradient from the truncated factor is not the MLL's.  Predictions may still use the factor."""
+        if not self._spectral_allowed() or self._kernel_families().periodic:
+            return None
+        return self._spectral_state(o)
 
     def _precond(self, o, tcol):
         """(eigen tuple, shift) of wiski_pcg's preconditioner (Kt^-1 + a kron_q diag(t_q))^-1.
