@@ -21,51 +21,14 @@ import math
 import torch
 
 from .. import grid_ops, settings
-from ..distributions import MultivariateNormal, ZeroLazyTensor, DenseLazyTensor, LazyCovariance
+from ..distributions import MultivariateNormal, ZeroLazyTensor, DenseLazyTensor
 from ..kernels import GridInterpolationKernel, RBFKernel, ScaleKernel
-from ..lazy.operators import (InducingPosterior, InterpolatedKernel, KroneckerToeplitz, PredictiveCovariance, StencilWtW, with_input_grad)
+from ..lazy.operators import (InducingPosterior, InterpolatedKernel, KroneckerToeplitz, PredictiveCovariance, with_input_grad)
 from ..lazy.dense_woodbury import DenseInducingPosterior
 from ..likelihoods import FNMGLikelihood
+from . import kernel_cache as kc
+from .kernel_cache import BatchOperator, _wtw_ops
 from .step_pacing import PollPacing, basis_kept, basis_slow, density_profiles, profiles_moved
-
-
-class BatchOperator(LazyCovariance):
-    """Stack of per-output operators: shape [out, n, n]."""
-
-    def __init__(self, ops):
-        self.ops = list(ops)
-        self.shape = torch.Size([len(self.ops)]) + self.ops[0].shape
-        self.dtype = self.ops[0].dtype
-        self.device = self.ops[0].device
-
-    def __getitem__(self, i):
-        return self.ops[i]
-
-    def __len__(self):
-        return len(self.ops)
-
-    def matmul(self, rhs):
-        if rhs.dim() == 2:
-            return torch.stack([op.matmul(rhs) for op in self.ops])
-        return torch.stack([op.matmul(rhs[i]) for i, op in enumerate(self.ops)])
-
-    __matmul__ = matmul
-
-    def evaluate(self):
-        return torch.stack([op.evaluate() for op in self.ops])
-
-    def diag(self):
-        return torch.stack([op.diag() for op in self.ops])
-
-    def clone(self):
-        return BatchOperator([op.clone() for op in self.ops])
-
-    def to(self, device):
-        return BatchOperator([op.to(device) for op in self.ops])
-
-
-def _wtw_ops(wtw):
-    return wtw.ops if isinstance(wtw, BatchOperator) else [wtw]
 
 
 def _default_tol(dtype):
@@ -359,7 +322,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         self._pacing = PollPacing(1e-7 if dtype == torch.float32 else 1e-11)     # where the mean solve polls first, refresh count
 
         if kernel_cache is None:
-            self._kernel_cache = self._fresh_cache()
+            self._kernel_cache = kc.fresh(self._grid, num_outputs, dtype, device, self._path_probes_init, self._trend_deg)
             if site_memory is not None:                  # (the initial data are values: they take their usual path and are not stored)
                 self._kernel_cache["_site_ring"] = grid_ops.SiteRing(site_memory, self._grid.d, dtype, device)
             if window is not None:
@@ -421,97 +384,11 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             noise = noise.transpose(-1, -2)
         return noise.expand_as(targets) if noise.shape != targets.shape else noise
 
-    def _fresh_cache(self):
-        out, m = self.num_outputs, self._grid.m
-        b = torch.zeros((out, m, 1), dtype=self._dtype, device=self._device)
-        stats = torch.zeros((out, 2), dtype=torch.float64, device=self._device)
-        # the half stencils of all outputs live in ONE [out, H, m] tensor (each operator holds a view), so that an absorb of
-        # several outputs is a single launch (wiski_scatter_stats_multi)
-        pack = torch.zeros((out, (self._grid.R + 1) // 2, m), dtype=self._dtype, device=self._device)
-        ops = [StencilWtW(self._grid, pack[o]) for o in range(out)]
-        cnt = torch.zeros((out, m), dtype=self._dtype, device=self._device)
-        cache = self._pack_cache(b, stats, ops, cnt)
-        S, seed = self._path_probes_init
-        if S > 0:
-            # P [m, S], probe-minor; path_count: global index of the next point (the generator is keyed on (seed, index, s))
-            cache.update(path_probes=torch.zeros((m, S), dtype=self._dtype, device=self._device), path_seed=seed, path_count=0)
-        if self._trend_deg is not None:
-            # C [m, p] trend-minor in the model's dtype (the layout of P), G [p, p] and g [p] in fp64 (as _stats); the basis is
-            # normalised by the centre and half-extent of THIS grid, for good: a property of the basis, which regrid_ leaves alone
-            g = self._grid
-            p = grid_ops.trend_size(g.d, self._trend_deg)
-            half = [0.5 * hq * (gq - 1) for hq, gq in zip(g.h, g.g)]
-            f64 = dict(dtype=torch.float64, device=self._device)
-            cache.update(trend_C=torch.zeros((m, p), dtype=self._dtype, device=self._device), trend_G=torch.zeros((p, p), **f64),
-                         trend_g=torch.zeros(p, **f64), trend_deg=self._trend_deg,
-                         trend_center=torch.tensor([g0 + hf for g0, hf in zip(g.g0, half)], **f64), trend_scale=torch.tensor(half, **f64))
-        return cache
-
-    _TREND_KEYS = ("trend_C", "trend_G", "trend_g", "trend_deg", "trend_center", "trend_scale")
-
-    @classmethod
-    def _trend_entries(cls, cache, move=None, **replace):
-        """The trend's entries of `cache` for a cache that takes its place ({} without a trend): each tensor through `move` (clone,
-        to(device); None: as it is), `replace` naming those that come new."""
-        if "trend_C" not in cache:
-            return {}
-        ent = {k: (move(cache[k]) if move is not None and torch.is_tensor(cache[k]) else cache[k]) for k in cls._TREND_KEYS}
-        ent.update(replace)
-        return ent
-
-    def _pack_cache(self, b, stats, ops, cnt=None):
-        out = b.shape[0]
-        if cnt is None:
-            cnt = torch.zeros((out, b.shape[1]), dtype=b.dtype, device=b.device)
-        return {
-            "_cnt": cnt,                                     # W^T D^-1 1 = row sums of W^T D^-1 W (preconditioner density model)
-            "response_cache": stats[:, 0].view(out, 1, 1),   # y^T D^-1 y     (:45)   [float64 view]
-            "interpolation_cache": b,                        # W^T D^-1 y     (:46)
-            "WtW": ops[0] if out == 1 else BatchOperator(ops),  # W^T D^-1 W  (:50-53)
-            "D_logdet": stats[:, 1],                         # logdet D       (:55)   [float64 view]
-            "_stats": stats,
-        }
-
     def _clone_cache(self, cache):
-        stats = cache["_stats"].clone()
-        cnt = cache["_cnt"].clone() if "_cnt" in cache else None
-        ops = _wtw_ops(cache["WtW"])
-        pack = self._stencil_pack(ops)
-        if pack is not None and len(ops) > 1:           # keep the outputs' stencils in one tensor (see _fresh_cache)
-            cp = pack.clone()
-            cl = lambda t: None if t is None else t.clone()
-            new_ops = [StencilWtW(self._grid, cp[o], cl(op.root), cl(op.inv_root)) for o, op in enumerate(ops)]
-        else:
-            new_ops = [op.clone() for op in ops]
-        new = self._pack_cache(cache["interpolation_cache"].clone(), stats, new_ops, cnt)
-        if "path_probes" in cache:                      # a child's increments never reach the parent's buffer
-            new.update(path_probes=cache["path_probes"].clone(), path_seed=cache["path_seed"], path_count=cache["path_count"])
-        if cache.get("_ring") is not None:              # the window's points follow the statistics they are the points of
-            new["_ring"] = cache["_ring"].clone()
-        if cache.get("_site_ring") is not None:         # the stored sites follow the statistics they are in
-            new["_site_ring"] = cache["_site_ring"].clone()
-        new.update(self._trend_entries(cache, move=torch.clone))    # a child's increments never reach the parent's statistics
-        facs = cache.get("_spectral")
-        if facs:
-            new["_spectral"] = {o: fac.clone() for o, fac in facs.items() if fac.ref is not None and not fac.stale}
-        return new
+        return kc.clone(cache, self._grid)
 
     def _stencil_pack(self, ops):
-        """The [out, H, m] tensor the outputs' half stencils are views of, if they (still) are: consecutive, same shape."""
-        st = [op.stencil for op in ops]
-        if not all(grid_ops.is_half_stencil(self._grid, t) and t.is_contiguous() for t in st):
-            return None
-        H, m = st[0].shape
-        es = st[0].element_size()
-        base = st[0].data_ptr()
-        if any(t.shape != (H, m) or t.data_ptr() != base + o * H * m * es for o, t in enumerate(st)):
-            return None
-        if len(st) == 1:
-            return st[0][None]
-        root = st[0]._base if st[0]._base is not None else None
-        if root is None or root.dim() != 3 or root.shape != (len(st), H, m) or root.data_ptr() != base:
-            return None
-        return root
+        return kc.stencil_pack(self._grid, ops)
 
     def _half_buffers(self):
         """Per-output symmetric half-stencil delta buffers [(R+1)/2, m] for the data-parallel
@@ -2151,10 +2028,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         if not isinstance(noise_kernel, GridInterpolationKernel):
             noise_kernel = GridInterpolationKernel(base_kernel=noise_kernel, grid_size=8, num_dims=g.d, grid_bounds=[list(b) for b in g.grid_bounds])
         noise_kernel.set_grid_spec(g)
-        z = lambda *shape, dtype=self._dtype: torch.zeros(shape, dtype=dtype, device=self._device)
-        pack = z(1, (g.R + 1) // 2, g.m)
-        cache = self._pack_cache(z(1, g.m, 1), z(1, 2, dtype=torch.float64), [StencilWtW(g, pack[0])], z(1, g.m))
-        nm = FixedNoiseOnlineSKIGP(covar_module=noise_kernel, kernel_cache=cache, likelihood=self.likelihood, learn_additional_noise=False, num_data=0)
+        nm = FixedNoiseOnlineSKIGP(covar_module=noise_kernel, kernel_cache=kc.fresh(g, 1, self._dtype, self._device), likelihood=self.likelihood, learn_additional_noise=False, num_data=0)
         if nm._trend_deg is not None or nm.num_outputs != 1:
             raise NotImplementedError("the noise model is a single output without a trend")
         return nm
@@ -3206,59 +3080,15 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
                                       "be taken out of the statistics again")
         self._finish_pending()
         self.leave_stencil_shard()
-        cache = self._kernel_cache
-        ops = _wtw_ops(cache["WtW"])
-        out, m2 = self.num_outputs, new.m
-        mk = lambda *shape: torch.empty(shape, dtype=self._dtype, device=self._device)      # (the kernel writes every element)
-        pack = self._stencil_pack(ops)
-        if pack is not None:
-            new_pack = mk(out, pack.shape[1], m2)         # the outputs' half stencils stay in one tensor
-            new_st = [new_pack[o] for o in range(out)]
-        else:
-            new_st = [mk(op.stencil.shape[0], m2) for op in ops]     # (an offset-major stencil is regridded in that layout)
-        regions = []
-        for o, op in enumerate(ops):
-            regions += grid_ops.stencil_regrid_regions(old, new, op.stencil.contiguous(), new_st[o], report=o)
-        b = cache["interpolation_cache"]
-        new_b = mk(out, m2, 1)
-        regions.append((b.contiguous(), new_b, out, 1))
-        new_cnt = None
-        if "_cnt" in cache:
-            new_cnt = mk(out, m2)
-            regions.append((cache["_cnt"].contiguous(), new_cnt, out, 1))
-        new_P = None
-        if "path_probes" in cache:
-            P = cache["path_probes"]
-            new_P = mk(m2, P.shape[1])
-            regions.append((P.contiguous(), new_P, 1, P.shape[1]))
-        new_C = None
-        if "trend_C" in cache:                       # probe-shaped; G, g and the basis' centre and scale do not depend on the grid
-            tC = cache["trend_C"]
-            new_C = mk(m2, tC.shape[1])
-            regions.append((tC.contiguous(), new_C, 1, tC.shape[1]))
+        regions, fresh = kc.regrid_plan(self._kernel_cache, old, new)
         rows, mass = grid_ops.regrid_stats(old, new, a, regions)
         if sum(rows) > 0 and drop == "zero":
             dims = [q for q in range(old.d) if a[q] < 0 or bb[q] < 0]
             raise ValueError(f"regrid_: trimming dims {dims} (below {a}, above {bb}) would drop {sum(rows)} inducing nodes that carry data, "
                              f"dropped mass sum A_ii = {sum(mass):.6g}; pass drop=\"any\" to cut anyway (an approximation)")
         # ---- commit: swap the buffers, hand the new grid round, drop what was derived from the old size
-        new_ops = [StencilWtW(new, new_st[o]) for o in range(out)]
-        fresh = self._pack_cache(new_b, cache["_stats"], new_ops, new_cnt)
-        if new_cnt is None:
-            fresh.pop("_cnt")
-        if new_P is not None:
-            fresh.update(path_probes=new_P, path_seed=cache["path_seed"], path_count=cache["path_count"])
-        if cache.get("_ring") is not None:
-            fresh["_ring"] = cache["_ring"]              # coordinates, not node indices: the ring is the same on the grown grid
-        if cache.get("_site_ring") is not None:
-            fresh["_site_ring"] = cache["_site_ring"]    # coordinates too; where nodes were removed the sites stay in what remains, frozen
-            if any(v < 0 for v in a) or any(v < 0 for v in bb):
-                fresh["_site_ring"].clear()
-        if new_C is not None:
-            fresh.update(self._trend_entries(cache, trend_C=new_C))
         self._drop_spectral()
-        cache.clear()
-        cache.update(fresh)
+        kc.regrid_commit(self._kernel_cache, fresh, trimmed=any(v < 0 for v in a + bb))
         self.covar_module.set_grid_spec(new)
         self._grid = new
         self._memo = {}                                # Toeplitz columns, preconditioner, prediction cache, root space, ...
@@ -3345,18 +3175,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         self._finish_pending()
         self.leave_stencil_shard()
         cache = self._kernel_cache
-        ops = _wtw_ops(cache["WtW"])
-        pack = self._stencil_pack(ops)
-        regions = [(pack, gamma)] if pack is not None else [(op.stencil, gamma) for op in ops]
-        regions.append((cache["interpolation_cache"], gamma))
-        if "_cnt" in cache:
-            regions.append((cache["_cnt"], gamma))
-        if "path_probes" in cache:
-            regions.append((cache["path_probes"], math.sqrt(gamma)))          # cov(P_s) = A stays exact
-        if "trend_C" in cache:                       # C, G, g are sums of wa- and wb-weighted terms, like A and b
-            regions.append((cache["trend_C"], gamma))    # (rides on the launch below; G and g, <= 240 fp64 scalars, take two small ones of their own)
-            cache["trend_G"].mul_(gamma)
-            cache["trend_g"].mul_(gamma)
+        regions = kc.decay_regions(cache, self._grid, gamma)    # (a trend's G and g are scaled there, beside the launch below)
         # R = b - Z - A U of the mean state: Z = Kt^-1 U does not depend on the data, so gamma R - (1 - gamma) Z is the residual of the
         # same (U, Z) in the decayed system -- the next refresh starts warm and without an A U product
         ms = self._carried(True)
@@ -3402,26 +3221,14 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         """Zero every streamed statistic and drop what was derived from them; returns the kernel cache."""
         self._finish_pending()                      # a deferred solve must not be resumed on zeroed statistics
         self._stream_step_cache = None
-        cache = self._kernel_cache
-        cache["interpolation_cache"].zero_()
-        cache["_stats"].zero_()
-        if "_cnt" in cache:
-            cache["_cnt"].zero_()
-        for k in ("trend_C", "trend_G", "trend_g"):
-            if k in cache:
-                cache[k].zero_()
-        for op in _wtw_ops(cache["WtW"]):
-            op.stencil.zero_()
-            op.root = op.inv_root = None            # L L^T described the old matrix
+        kc.zero_(self._kernel_cache)
         self._wsum_dev.zero_()
         self._wsum_host = [0.0] * self.num_outputs
         self._wsum_dev_host = [0.0] * self.num_outputs
         self._wsum_dirty = False
         self._memo.pop("precond", None)
         self._drop_spectral()
-        if cache.get("_site_ring") is not None:         # nothing of the stored points is in the statistics any more
-            cache["_site_ring"].clear()
-        return cache
+        return self._kernel_cache
 
     def to(self, *args, **kwargs):
         res = super().to(*args, **kwargs)
@@ -3435,24 +3242,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
                 device = a.device
         device = kwargs.get("device", device)
         if device is not None and self._kernel_cache is not None and torch.device(device) != self._device:
-            c = self._kernel_cache
-            stats = c["_stats"].to(device)
-            ops = _wtw_ops(c["WtW"])
-            pack = self._stencil_pack(ops)
-            if pack is not None and len(ops) > 1:
-                pk = pack.to(device)
-                mv = lambda t: None if t is None else t.to(device)
-                new_ops = [StencilWtW(self._grid, pk[o], mv(op.root), mv(op.inv_root)) for o, op in enumerate(ops)]
-            else:
-                new_ops = [op.to(device) for op in ops]
-            self._kernel_cache = self._pack_cache(c["interpolation_cache"].to(device), stats, new_ops, c["_cnt"].to(device) if "_cnt" in c else None)
-            if "path_probes" in c:
-                self._kernel_cache.update(path_probes=c["path_probes"].to(device), path_seed=c["path_seed"], path_count=c["path_count"])
-            if c.get("_ring") is not None:
-                self._kernel_cache["_ring"] = c["_ring"].to(device)
-            if c.get("_site_ring") is not None:
-                self._kernel_cache["_site_ring"] = c["_site_ring"].to(device)
-            self._kernel_cache.update(self._trend_entries(c, move=lambda t: t.to(device)))
+            self._kernel_cache = kc.to(self._kernel_cache, self._grid, device)
             self._device = torch.device(device)
             self._err = grid_ops.new_err_flag(device)
             self._mean_state = None
