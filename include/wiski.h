@@ -1123,6 +1123,38 @@ typedef struct wiski_regrid_plan {
 int wiski_regrid_stats_f32(const wiski_grid* grid, const int32_t* below, const int32_t* above, const int32_t* g_new, const wiski_regrid_plan* plan, double* d_record, void* stream);
 int wiski_regrid_stats_f64(const wiski_grid* grid, const int32_t* below, const int32_t* above, const int32_t* g_new, const wiski_regrid_plan* plan, double* d_record, void* stream);
 
+/* ---- checkpoint, restore and merge of the streamed statistics through their touched nodes (pack_stats.hip) ----
+ * Regions as above: k blocks of m nodes of w reals, element (c, node i, s) at c m w + i w + s; in the COMPACT form of a region m is replaced
+ * by n_sel, and its node j is the full region's node d_nodes[j].  Plain loads and stores, no workgroup waits for another.
+ * wiski_stats_select: marks in d_flags [m] (int32, zeroed ONCE by the caller) every node at which any element of any plan->src region is not
+ *   == 0 (a NaN is kept; dst and factor are not looked at).  With d_nodes != NULL it then writes d_nodes[0 .. n_sel), the ASCENDING list of
+ *   the marked nodes (d_nodes holds m), and d_count[0] = n_sel: three more launches -- counts per 256 nodes into d_work, a one-workgroup scan
+ *   of them, the write -- with d_work of work_elems >= ceil(m / 256) int32 (less: WISKI_E_WORKSPACE).  A table of more than
+ *   WISKI_STATS_MAX_REGIONS regions takes several calls on the same d_flags, all but the last with d_nodes = NULL.
+ * wiski_stats_gather:      dst[c n_sel w + j w + s] = src[c m w + d_nodes[j] w + s]
+ * wiski_stats_scatter_add: dst[c m w + d_nodes[j] w + s] += f src[c n_sel w + j w + s], f = (real)factor rounded once; f == 1 is a plain
+ *   add, otherwise a rounded product and a rounded add (never one fused multiply-add).  src_full != 0: src is a FULL region and is read at
+ *   the index dst is written at (a merge straight from another cache).  The list must be free of duplicates (select's is).
+ * Both check every node index in the kernel: one outside [0, m) is skipped and sets bit 0 of *d_err (may be NULL), so a bad list never
+ * reads or writes out of bounds.  n_sel = 0 launches nothing.  16-byte vectors where w is a multiple of the vector and both pointers are
+ * 16-byte aligned.  WISKI_E_BADARG, with nothing launched: a null or misaligned pointer, k or w < 1, k m w >= 2^31, m < 1, n_sel outside
+ * [0, m], a region whose src and dst overlap (or whose dst overlaps d_nodes), a NaN factor, count outside 0 .. WISKI_STATS_MAX_REGIONS. */
+#define WISKI_STATS_MAX_REGIONS 16
+typedef struct wiski_stats_plan {
+  const void* src[WISKI_STATS_MAX_REGIONS];    /* DEVICE pointers to `real`s */
+  void* dst[WISKI_STATS_MAX_REGIONS];
+  int64_t k[WISKI_STATS_MAX_REGIONS];
+  int64_t w[WISKI_STATS_MAX_REGIONS];
+  double factor[WISKI_STATS_MAX_REGIONS];      /* scatter_add only */
+  int32_t count, reserved;
+} wiski_stats_plan;
+int wiski_stats_select_f32(const wiski_stats_plan* plan, int64_t m, int32_t* d_flags, int32_t* d_nodes, int32_t* d_count, int32_t* d_work, int64_t work_elems, void* stream);
+int wiski_stats_select_f64(const wiski_stats_plan* plan, int64_t m, int32_t* d_flags, int32_t* d_nodes, int32_t* d_count, int32_t* d_work, int64_t work_elems, void* stream);
+int wiski_stats_gather_f32(const wiski_stats_plan* plan, int64_t m, const int32_t* d_nodes, int64_t n_sel, int32_t* d_err, void* stream);
+int wiski_stats_gather_f64(const wiski_stats_plan* plan, int64_t m, const int32_t* d_nodes, int64_t n_sel, int32_t* d_err, void* stream);
+int wiski_stats_scatter_add_f32(const wiski_stats_plan* plan, int64_t m, const int32_t* d_nodes, int64_t n_sel, int32_t src_full, int32_t* d_err, void* stream);
+int wiski_stats_scatter_add_f64(const wiski_stats_plan* plan, int64_t m, const int32_t* d_nodes, int64_t n_sel, int32_t src_full, int32_t* d_err, void* stream);
+
 /* ---- polynomial trend with marginalised coefficients (trend.hip) ----
  * y_i = h(x_i)^T beta + w(x_i)^T u + eps_i with beta ~ N(0, tau^2 I): h(x) holds the p monomials of total degree <= deg (0, 1 or 2) in the
  * normalised coordinates t_k = (x_k - center[k]) / scale[k], graded lexicographic -- 1, t_1 .. t_d, t_1^2, t_1 t_2, .., t_1 t_d, t_2^2, ..

@@ -13,7 +13,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 _SO = os.path.join(_CSRC, "libwiski_hip.so")
-_SOURCES = ["interp_gather.hip", "scatter_stats.hip", "solve.hip", "spectral.hip", "dense.hip", "collective.hip", "stream_step.hip", "spectral_basis.hip", "hyper_columns.hip", "two_level.hip", "hyper_step.hip", "lookahead.hip", "sample_paths.hip", "decay_stats.hip", "regrid_stats.hip", "trend.hip"]
+_SOURCES = ["interp_gather.hip", "scatter_stats.hip", "solve.hip", "spectral.hip", "dense.hip", "collective.hip", "stream_step.hip", "spectral_basis.hip", "hyper_columns.hip", "two_level.hip", "hyper_step.hip", "lookahead.hip", "sample_paths.hip", "decay_stats.hip", "regrid_stats.hip", "trend.hip", "pack_stats.hip"]
 _HEADERS = ["wiski_common.h", "spmv_sym_dma.h", "spmv_sym_dma_mc.h", "spmm_sym_cols.h", "spmm_sym_bcast.h", "scatter_half.h", "scatter_owner.h", "scatter_grad.h", "scatter_site.h", "scatter_robust.h", "scatter_window.h", "scatter_interval.h", "scatter_count.h", "scatter_hetero.h", "scatter_label.h", "scatter_input_noise.h", "scatter_grad_interval.h", "scatter_revisit.h", "absorb.h", "dense_small.h", "dense_coop.h",
             os.path.join("..", "..", "include", "wiski.h")]
 MAX_DIM = 4
@@ -77,6 +77,14 @@ class wiski_regrid_plan(ctypes.Structure):
     _fields_ = [("src", ctypes.c_void_p * REGRID_MAX_REGIONS), ("dst", ctypes.c_void_p * REGRID_MAX_REGIONS), ("k", ctypes.c_int64 * REGRID_MAX_REGIONS),
                 ("r0", ctypes.c_int64 * REGRID_MAX_REGIONS), ("w", ctypes.c_int32 * REGRID_MAX_REGIONS), ("report", ctypes.c_int32 * REGRID_MAX_REGIONS),
                 ("count", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+STATS_MAX_REGIONS = 16
+
+
+class wiski_stats_plan(ctypes.Structure):
+    _fields_ = [("src", ctypes.c_void_p * STATS_MAX_REGIONS), ("dst", ctypes.c_void_p * STATS_MAX_REGIONS), ("k", ctypes.c_int64 * STATS_MAX_REGIONS),
+                ("w", ctypes.c_int64 * STATS_MAX_REGIONS), ("factor", ctypes.c_double * STATS_MAX_REGIONS), ("count", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 class wiski_absorb_args(ctypes.Structure):

@@ -1157,6 +1157,135 @@ def regrid_stats(old_grid, new_grid, below, regions):
     return [int(r[0]) for r in rec], [float(r[1]) for r in rec]
 
 
+def stencil_node_regions(grid, st):
+    """The ``(flat tensor, k, w)`` node regions of one stencil ``[rows, m']`` in the layout of `grid` (m' = m, or n_sel for a compact one):
+    the native half stencil is group 0 (k = 1, w = 4) plus the groups >= 1 (w = 7, starting at 4 m'); an offset-major one is k = 7^d, w = 1."""
+    rows, mm = st.shape
+    flat = st.reshape(-1)
+    if not is_half_stencil(grid, st):
+        return [(flat, rows, 1)]
+    regions = [(flat[:4 * mm], 1, 4)]
+    if rows > 4:
+        regions.append((flat[4 * mm:], (rows - 4) // 7, 7))
+    return regions
+
+
+def _stats_regions(what, m, regions, n_src, n_dst):
+    """Checked ``(src, dst, k, w, factor)`` list of the three stats_* functions; n_src / n_dst: nodes of the two sides (None: no such side)."""
+    regs = []
+    for reg in regions:
+        src, dst, k, w = reg[:4]
+        k, w = int(k), int(w)
+        fac = float(reg[4]) if len(reg) > 4 else 1.0
+        if k < 1 or w < 1 or k * m * w >= 2 ** 31:
+            raise _hip.WiskiError(f"{what}: a region needs k, w >= 1 and k m w < 2^31, got k = {k}, w = {w}, m = {m}")
+        for t, n, name in ((src, n_src, "src"), (dst, n_dst, "dst")):
+            if n is not None and (t.numel() != k * n * w or not t.is_contiguous()):
+                raise _hip.WiskiError(f"{what}: {name} of {t.numel()} elements is no contiguous region of k = {k} blocks of {n} nodes of w = {w}")
+        if dst is not None and (src.dtype != dst.dtype or src.device != dst.device):
+            raise _hip.WiskiError(f"{what}: src and dst of a region must have one dtype and device")
+        regs.append((src, dst, k, w, fac))
+    if regs and any(r[0].dtype != regs[0][0].dtype or r[0].device != regs[0][0].device for r in regs):
+        raise _hip.WiskiError(f"{what}: the regions must have one dtype and device")
+    return regs
+
+
+def _stats_plans(regs):
+    for i in range(0, len(regs), _hip.STATS_MAX_REGIONS):
+        part = regs[i:i + _hip.STATS_MAX_REGIONS]
+        plan = _hip.wiski_stats_plan()
+        plan.count = len(part)
+        for n, (src, dst, k, w, fac) in enumerate(part):
+            plan.src[n], plan.k[n], plan.w[n], plan.factor[n] = _hip.dptr(src).value, k, w, fac
+            plan.dst[n] = _hip.dptr(dst).value if dst is not None else None
+        yield plan, i + len(part) >= len(regs)
+
+
+def _check_nodes(what, nodes, m):
+    if nodes.dtype != torch.int32 or nodes.dim() != 1 or nodes.numel() > m or not nodes.is_contiguous():
+        raise _hip.WiskiError(f"{what}: nodes is a contiguous int32 vector of at most m = {m} node indices")
+
+
+def stats_select(m, regions):
+    """The touched nodes of a set of node regions (``wiski_stats_select``): `regions` is a list of ``(tensor, k, w)``, each k
+    blocks of m nodes of w reals (element (c, node i, s) at ``c m w + i w + s``), contiguous, of one dtype and device.  Returns ``(nodes,
+    n_sel)``: the ascending int32 list of the nodes at which any element of any region is not ``== 0`` (a NaN counts), and its length (the
+    one host read).  ROCm tensors: flags, block counts, a one-workgroup scan and the write, four launches (more than 16 regions: one more flag
+    launch per 16).  CPU tensors take a plain torch path (``any``), so that a host without a GPU can pack and merge states."""
+    m = int(m)
+    regs = _stats_regions("stats_select", m, [(t, None, k, w) for t, k, w in regions], m, None)
+    if not regs:
+        raise _hip.WiskiError("stats_select: no region")
+    dtype, dev = regs[0][0].dtype, regs[0][0].device
+    if not regs[0][0].is_cuda:
+        on = torch.zeros(m, dtype=torch.bool)
+        for src, _, k, w, _ in regs:
+            on |= (src.reshape(k, m, w) != 0).any(dim=2).any(dim=0)
+        nodes = on.nonzero().reshape(-1).to(torch.int32)
+        return nodes, int(nodes.numel())
+    f = _hip.fn("wiski_stats_select", dtype)
+    nb = -(-m // 256)
+    flags = torch.zeros(m, dtype=torch.int32, device=dev)
+    nodes = torch.empty(m, dtype=torch.int32, device=dev)
+    work = torch.empty(nb + 1, dtype=torch.int32, device=dev)      # block counts, and n_sel behind them
+    for plan, is_last in _stats_plans(regs):
+        rc = f(ctypes.byref(plan), ctypes.c_int64(m), _hip.dptr(flags), _hip.dptr(nodes) if is_last else None, _hip.dptr(work[nb:]) if is_last else None,
+               _hip.dptr(work) if is_last else None, ctypes.c_int64(nb), _hip.stream_ptr(dev))
+        _hip.check(rc, "wiski_stats_select")
+    n_sel = int(work[nb].item())
+    return nodes[:n_sel], n_sel
+
+
+def stats_gather(m, nodes, regions, err=None):
+    """``dst[c n_sel w + j w + s] = src[c m w + nodes[j] w + s]`` for every region ``(src, dst, k, w)`` in one launch per 16
+    (``wiski_stats_gather``): src holds k m w elements, dst k n_sel w.  A node index outside [0, m) is skipped and sets bit 0
+    of `err` (an int32 device flag).  CPU tensors: ``index_select`` (a bad index raises)."""
+    m = int(m)
+    _check_nodes("stats_gather", nodes, m)
+    n_sel = nodes.numel()
+    regs = _stats_regions("stats_gather", m, regions, m, n_sel)
+    if not regs or n_sel == 0:
+        return
+    dtype, dev = regs[0][0].dtype, regs[0][0].device
+    if not regs[0][0].is_cuda:
+        idx = nodes.long()
+        for src, dst, k, w, _ in regs:
+            dst.reshape(k, n_sel, w).copy_(src.reshape(k, m, w).index_select(1, idx))
+        return
+    f = _hip.fn("wiski_stats_gather", dtype)
+    for plan, _ in _stats_plans(regs):
+        rc = f(ctypes.byref(plan), ctypes.c_int64(m), _hip.dptr(nodes), ctypes.c_int64(n_sel), _hip.dptr(err), _hip.stream_ptr(dev))
+        _hip.check(rc, "wiski_stats_gather")
+
+
+def stats_scatter_add(m, nodes, regions, err=None, src_full=False):
+    """``dst[c m w + nodes[j] w + s] += f src[c n_sel w + j w + s]`` for every region ``(src, dst, k, w[, f])`` in one launch per 16
+    (``wiski_stats_scatter_add``).  f is rounded once to the tensors' dtype; f = 1 is a plain add, otherwise a rounded
+    product and a rounded add.  `nodes` is free of duplicates (``stats_select``'s list is), so no atomics are needed.  src_full: src is a full
+    region of k m w elements, read at the index dst is written at.  A node index outside [0, m) is skipped and sets bit 0 of `err`.  CPU
+    tensors: ``index_add_`` of the rounded product (a bad index raises)."""
+    m = int(m)
+    _check_nodes("stats_scatter_add", nodes, m)
+    n_sel = nodes.numel()
+    regs = _stats_regions("stats_scatter_add", m, regions, m if src_full else n_sel, m)
+    if not regs or n_sel == 0:
+        return
+    dtype, dev = regs[0][0].dtype, regs[0][0].device
+    if not regs[0][0].is_cuda:
+        idx = nodes.long()
+        for src, dst, k, w, fac in regs:
+            s = src.reshape(k, -1, w)
+            s = s.index_select(1, idx) if src_full else s
+            fr = torch.tensor(fac, dtype=dtype)
+            dst.reshape(k, m, w).index_add_(1, idx, s if bool(fr == 1) else s * fr)
+        return
+    f = _hip.fn("wiski_stats_scatter_add", dtype)
+    for plan, _ in _stats_plans(regs):
+        rc = f(ctypes.byref(plan), ctypes.c_int64(m), _hip.dptr(nodes), ctypes.c_int64(n_sel), ctypes.c_int32(1 if src_full else 0), _hip.dptr(err),
+               _hip.stream_ptr(dev))
+        _hip.check(rc, "wiski_stats_scatter_add")
+
+
 def stencil_expand_add(grid, A_half, A_st):
     """A_st += expand(A_half) (delta and its mirror image); A_half is zeroed."""
     rc = _hip.fn("wiski_stencil_expand_add", A_st.dtype)(grid.ref, _hip.dptr(A_half), _hip.dptr(A_st), _hip.stream_ptr(A_st.device))

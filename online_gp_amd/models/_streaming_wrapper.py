@@ -22,6 +22,7 @@ from ..mlls import BatchedWoodburyMarginalLogLikelihood, mll_feature_surrogate, 
 _LR_FLOOR = 1e-4          # eta_min of the cosine schedules
 _REPLAY = 1024            # replay sample size of the BatchNorm refresh
 EVAL_CHUNK = 1024         # evaluate() batch size
+WRAPPER_STATE_FORMAT = "online_gp_amd.wrapper_state"
 
 
 def _cosine_lr(base, floor, step, total):
@@ -128,6 +129,32 @@ class StreamingSKIWrapper(torch.nn.Module):
             noise = torch.ones_like(gp_targets)
         self.gp.set_train_data(features.detach(), gp_targets.to(dt), noise.to(dt))
         self.gp.zero_grad()
+
+    # ------------------------------------------------------- checkpoint, restore
+    def stream_state(self, device="cpu"):
+        """The live stream as a state: the GP's ``stream_state()`` and the stem's ``state_dict()``, nested; tensors on
+        `device`, and nothing but tensors, numbers, strings, lists and dicts (``torch.load(..., weights_only=True)`` reads it back).
+        The Adam moments of the two optimisers and the BatchNorm replay buffer are NOT carried: after a restore the optimisers restart."""
+        return {"format": WRAPPER_STATE_FORMAT, "version": 1, "gp": self.gp.stream_state(device),
+                "stem": {k: v.detach().to(device).clone() for k, v in self.stem.state_dict().items()}}
+
+    def load_stream_state_(self, state, load_module=True):
+        """Restore a ``stream_state()`` into this wrapper, built with the same configuration, in place: the GP through its own
+        ``load_stream_state_`` (into the tensors it holds), the stem through ``load_state_dict`` (load_module=False: statistics only).
+        The optimisers keep their moments -- loading others would replace tensors whose addresses a captured hyper step has recorded
+        -- and a captured step stays valid or is re-captured on its next use.  Returns the wrapper."""
+        if not isinstance(state, dict) or state.get("format") != WRAPPER_STATE_FORMAT or state.get("version") != 1:
+            raise ValueError(f"stream state: 'format' / 'version' is not {WRAPPER_STATE_FORMAT!r} version 1")
+        if not isinstance(state.get("gp"), dict) or not isinstance(state.get("stem"), dict):
+            raise ValueError("stream state: 'gp' and 'stem' must be the nested states of the GP and of the stem")
+        if load_module:
+            missing = set(self.stem.state_dict()) ^ set(state["stem"])
+            if missing:
+                raise ValueError(f"stream state: 'stem' does not hold this stem's entries (differing: {sorted(missing)})")
+        self.gp.load_stream_state_(state["gp"], load_module=load_module)
+        if load_module:
+            self.stem.load_state_dict(state["stem"])
+        return self
 
     # ------------------------------------------------------------------ update
     def update(self, inputs, targets, update_stem=True, update_gp=True):

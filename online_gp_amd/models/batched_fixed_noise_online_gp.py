@@ -3251,6 +3251,127 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
             self._drop_spectral()
         return res
 
+    # ------------------------------------------- checkpoint, restore and merge --
+    def _refuse_rings(self, what):
+        if self.window is not None or self.site_memory is not None:
+            raise NotImplementedError(f"{what} on a model with {'window' if self.window is not None else 'site_memory'}: its ring holds points, "
+                                      "not statistics, with host-side bookkeeping on the model beside it (the void slots, the unit / explicit "
+                                      "split of the weight sum), and two rings have no union -- a state carries streamed statistics only")
+
+    def _settle(self):
+        """check_bounds()'s recipe before the statistics leave the model or are added to: nothing pending, no stencil shard, the out-of-grid
+        flag read -- so that num_data counts exactly the points the statistics hold."""
+        self.leave_stencil_shard()
+        self.check_bounds()
+
+    def _wsum_from_cnt(self):
+        """The noise-weight sums from the row sums of W^T D^-1 W, as _raise_out_of_bounds rebuilds them (in place: the device part's address stays)."""
+        cnt = self._kernel_cache.get("_cnt")
+        self._wsum_host = [0.0] * self.num_outputs
+        self._wsum_dev_host = [0.0] * self.num_outputs
+        if cnt is not None:
+            self._wsum_dev.copy_(cnt.sum(dim=1, dtype=torch.float64))
+            self._wsum_dirty = True
+
+    def stream_state(self, device="cpu"):
+        """The live model as a state: ``kernel_cache.pack`` of its statistics -- every node region in compact form, only the
+        nodes that hold anything, found and moved on the device -- plus ``num_data``, ``module`` (this model's ``state_dict()``) and, for
+        a heteroscedastic model, ``noise_model``: the nested state of ``model.noise_model`` with its kernel's parameters, which this
+        model's ``state_dict()`` does not carry.  The dict holds tensors (on `device`, default the host), ints, floats, strings, lists
+        and dicts only: ``torch.save`` and ``torch.load(..., weights_only=True)`` round-trip it.  As ``check_bounds()``: pending work is
+        finished, a stencil shard is left, and the out-of-grid flag is read -- a stream that left the grid raises its RuntimeError here,
+        with ``num_data`` corrected, and the next call packs what was absorbed.  Spectral factors, root pairs, the warm-start state and
+        the two-level block are not carried.  window / site_memory: NotImplementedError."""
+        self._refuse_rings("stream_state")
+        self._settle()
+        state = kc.pack(self._kernel_cache, self._grid, device=device)
+        state["num_data"] = None if self.num_data is None else int(self.num_data)
+        state["module"] = {k: v.detach().to(device).clone() for k, v in self.state_dict().items()}
+        if self.noise_model is not None:
+            state["noise_model"] = self.noise_model.stream_state(device)
+        return state
+
+    def _check_stream_state(self, state, what):
+        kc._check_state(state)
+        kc._check_fits(self._kernel_cache, self._grid, state, what)
+        if (self.noise_model is None) != (state.get("noise_model") is None):
+            raise ValueError(f"{what}: 'noise_model' is {'missing from' if self.noise_model is not None else 'present in'} the state, but this model is "
+                             f"{'' if self.noise_model is not None else 'not '}heteroscedastic")
+        if self.noise_model is not None:
+            self.noise_model._check_stream_state(state["noise_model"], what + " (noise model)")
+
+    def load_stream_state_(self, state, load_module=True):
+        """Restore a ``stream_state()`` into this model, built with the same configuration on the state's grid, in place:
+        the statistics are zeroed and the state is scattered INTO the tensors the model already holds, and ``load_state_dict`` copies
+        into the existing parameters (load_module=False leaves the hyper-parameters alone) -- no address changes, so a captured hyper step
+        keeps replaying.  ``num_data`` is the state's, the noise-weight sums are rebuilt from cnt; everything derived (spectral factors,
+        root pairs, preconditioner, two-level block, the warm-start state) is rebuilt on next use: the first solve is cold.  The state
+        is checked as a whole before anything is written (ValueError names the field).  Returns the model."""
+        self._refuse_rings("load_stream_state_")
+        self._check_stream_state(state, "load_stream_state_")
+        self.leave_stencil_shard()
+        cache = self._clear_statistics()
+        kc.load_into_(cache, self._grid, state)
+        if load_module and state.get("module") is not None:
+            self.load_state_dict(state["module"])
+            self.hyperparameters_changed()
+        self.num_data = state.get("num_data")
+        self._wsum_from_cnt()
+        self._give_up(cache)
+        self._mean_state = None
+        self._last_iters = None
+        self._dump_caches()
+        if self.noise_model is not None:
+            self.noise_model.load_stream_state_(state["noise_model"], load_module=load_module)
+        return self
+
+    def merge_(self, other, weight=1.0):
+        """Add the statistics of `other` -- a model, or a ``stream_state()`` -- to this model's, in place.  The statistics
+        are additive and independent of the kernel, so the model is afterwards exactly the GP of both sets of points under THIS model's
+        hyper-parameters, the other's points at noise d_i / weight (weight in (0, 1]; 1: as they were absorbed).  The hyper-parameters
+        of `other` are ignored.  Only the nodes `other` touched are read and added (a model is not packed first).  ``num_data`` adds,
+        the noise-weight sums are rebuilt from cnt.  Path probes add at sqrt(weight), and the two streams must have been built with
+        different ``path_seed`` (ValueError otherwise); the receiver keeps its seed and count.  weight != 1 needs the other side's
+        ``num_data`` (log|D| moves by -n log weight) and raises like ``forget_`` without it.  Refused with NotImplementedError: window /
+        site_memory on either side, a heteroscedastic model on either side (the noise sites of one model were matched against its own
+        posterior), different grids (``regrid_`` moves a model onto the other's grid first).  Returns the model."""
+        weight = float(weight)
+        if not (0.0 < weight <= 1.0):
+            raise ValueError(f"weight must lie in (0, 1], got {weight}")
+        self._refuse_rings("merge_")
+        is_model = isinstance(other, FixedNoiseOnlineSKIGP)
+        if is_model:
+            other._refuse_rings("merge_")
+        if self.noise_model is not None or (other.noise_model if is_model else other.get("noise_model")) is not None:
+            raise NotImplementedError("merge_ on or with a heteroscedastic model: the noise sites of a model were matched against its own posterior "
+                                      "of f, and the sum of two noise models is the noise model of neither stream")
+        if is_model:
+            other._settle()
+            src, n_other, og = other._kernel_cache, other.num_data, kc._grid_dict(other._grid)
+        else:
+            kc._check_state(other)
+            src, n_other, og = other, other.get("num_data"), other["grid"]
+        mine = kc._grid_dict(self._grid)
+        if any(list(og[f]) != mine[f] for f in ("size", "g0", "h")):
+            raise NotImplementedError(f"merge_ across different grids (size {og['size']}, g0 {og['g0']}, h {og['h']} against this model's "
+                                      f"{mine['size']}, {mine['g0']}, {mine['h']}): statistics add node by node -- regrid_ moves one model onto "
+                                      "the other's grid first, by whole nodes at equal spacing")
+        if weight != 1.0 and n_other is None:
+            raise RuntimeError("merge_ with weight != 1 needs the number of points the other side absorbed (log|D| moves by -n log weight): "
+                               "hand num_data over with the kernel cache")
+        self._settle()
+        cache = self._kernel_cache
+        kc.merge_into_(cache, self._grid, src, weight, n_other)
+        self.num_data = None if self.num_data is None or n_other is None else self.num_data + n_other
+        self._wsum_from_cnt()
+        self._give_up(cache)
+        self._memo.pop("precond", None)
+        self._stream_step_cache = None
+        self._mean_state = None
+        self._last_iters = None
+        self._dump_caches()
+        return self
+
     # ------------------------------------------------- distributed statistics --
     def stats_buffers(self):
         """Tensors that are additive over data shards (what RCCL all-reduces):
