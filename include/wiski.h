@@ -455,16 +455,30 @@ int wiski_scatter_stats_multi_f64(const wiski_grid* grid, const double* d_x, con
  * adds its wb y^2 and log noise only (the model calls it pure noise).  A point outside the grid is dropped for every channel and
  * counted once in d_err.  d_cnt (optional; feeds the preconditioner's density model only) += wa_0 v_0[a] + sum_{c >= 1} wa_c v_c[a]^2.
  * The carry (optional, d_u with d_res and / or d_mean_out): d_mean_out[p][c] = v_c . u, the predictive mean and gradient of the
- * point before the update, and d_res[a] += sum_c v_c[a] (wb_c y_c - wa_c (v_c . u)).  Symmetric half stencil, atomic form, d = 1..4. */
-int wiski_scatter_stats_grad_f32(const wiski_grid* grid, const float* d_x, const float* d_y, const float* d_wa, const float* d_wb, const float* d_noise, int64_t n, float* d_b, float* d_A_half, float* d_cnt, const float* d_u, float* d_res, float* d_mean_out, double* d_stats, int32_t* d_err, void* stream);
-int wiski_scatter_stats_grad_f64(const wiski_grid* grid, const double* d_x, const double* d_y, const double* d_wa, const double* d_wb, const double* d_noise, int64_t n, double* d_b, double* d_A_half, double* d_cnt, const double* d_u, double* d_res, double* d_mean_out, double* d_stats, int32_t* d_err, void* stream);
+ * point before the update, and d_res[a] += sum_c v_c[a] (wb_c y_c - wa_c (v_c . u)).  Symmetric half stencil, atomic form, d = 1..4.
+ * Entry: wiski_absorb_f32 / _f64 below with channels = d + 1.  The form has no argument beyond the record, so it has no entry of its
+ * own: a wiski_absorb_grad would be wiski_absorb under a second name. */
 
 /* The absorb with every option it has, as one record: what each wiski_scatter_stats_* entry above fills a part of.  Pointers are
  * device pointers to float (wiski_absorb_f32) or double (wiski_absorb_f64) unless typed; a zeroed record with the points, d_b,
  * d_stats, d_err and nout = 1 set is the plain absorb.  half: d_A is the symmetric half stencil (else offset-major); channels: 0,
- * or d + 1 (wiski_scatter_stats_grad); g_hi = 0: every stencil group, else the groups [g_lo, g_hi) (wiski_scatter_stats_step_sharded);
+ * or d + 1 (derivative observations, above); g_hi = 0: every stencil group, else the groups [g_lo, g_hi) (wiski_scatter_stats_step_sharded);
  * nout / *_stride as wiski_scatter_stats_multi.  Combinations no form of the absorb implements return WISKI_E_BADARG before
- * anything is launched -- channels, for one, with a full stencil, a guard, zero regions, a shard or nout > 1. */
+ * anything is launched -- channels, for one, with a full stencil, a guard, zero regions, a shard or nout > 1.
+ *
+ * The observation forms below (wiski_absorb_robust, _window, _interval, _grad_interval, _count, _revisit, _hetero, _label,
+ * _input_noise) each take this record plus the form's own few arguments; the record is the one way in, from C and from the Python
+ * package alike.  The record is passed by pointer without a size field and has NOT grown a group per form: callers built against
+ * today's header hand over records of today's size.  No entry fills in a field of the record for the caller.  Every form needs
+ *   half = 1 and nout = 1 (label: nout = C), everything not named here zero;
+ *   the points d_x / d_wa / d_wb / d_noise, n, and d_y where the form has targets of its own kind (robust, window, hetero,
+ *     input_noise, derivative observations); the interval, grad_interval, count and label forms ignore d_y (it may be NULL);
+ *   d_b, d_A (the half stencil), d_cnt, d_stats, d_err and d_u; d_res and d_mean_out are optional;
+ *   grad_interval (as the derivative observations): channels = d + 1;
+ *   label: w_stride = 0 (weights shared by the outputs) or n, A_stride = H * m (H the rows of a half stencil);
+ *   revisit: d_x / d_y / d_wa / d_wb / d_noise / n are ignored (the ring's slots are the points), d_mean_out must be NULL.
+ * A record that asks for more -- a guard, zero regions, a shard, an owner workspace, nout > 1 (but for label), channels (but for
+ * grad_interval), a full stencil -- is WISKI_E_BADARG before a launch, as is a NULL record. */
 typedef struct wiski_absorb_args {
   const void* d_x; const void* d_y; const void* d_wa; const void* d_wb; const void* d_noise; int64_t n;
   void* d_b; void* d_A; int32_t half; int32_t channels; void* d_cnt; double* d_stats; int32_t* d_err;
@@ -492,21 +506,15 @@ int wiski_absorb_staged_f32(const wiski_grid* grid, const wiski_absorb_args* arg
 int wiski_tap_fold_f32(float* d_tap_stage, float* d_b, float* d_cnt, float* d_res, int64_t m, void* stream);
 
 /* Outlier-robust absorb: every point is Huber-weighted against the posterior BEFORE the batch, inside the launch that absorbs it
- * (DESIGN.md 3.16).  The arguments of wiski_scatter_stats_grad (for a value per point: d_y / d_wa / d_wb / d_noise / d_mean_out
- * are [n]) plus d_inv_scale [n], huber_c and d_omega_out [n].  With u the posterior mean on the grid,
+ * (DESIGN.md 3.16).  The record (a value per point: d_y / d_wa / d_wb / d_noise / d_mean_out are [n]; half = 1, nout = 1) plus
+ * d_inv_scale [n], huber_c and d_omega_out [n].  With u the posterior mean on the grid,
  *   z_p = (y_p - w_p . u) inv_scale_p,   omega_p = min(1, huber_c / |z_p|)      (exactly 1 for |z_p| <= huber_c),
  * and the point enters A, cnt and the carried residual with omega_p wa_p, b and sum wb y^2 with omega_p wb_p, log|D| with
  * log(noise_p / omega_p): the absorb of the same point at noise noise_p / omega_p, so everything downstream stays an exact GP.
  * d_omega_out receives omega_p (0 for a point outside the grid, which is flagged, counted and dropped as everywhere);
- * inv_scale_p = 0 exempts a point.  Required: d_u, d_A_half, d_cnt, d_omega_out, d_inv_scale, a finite huber_c > 0; d_res and
+ * inv_scale_p = 0 exempts a point.  Required: d_u, d_A, d_cnt, d_omega_out, d_inv_scale, a finite huber_c > 0; d_res and
  * d_mean_out are optional.  Symmetric half stencil, atomic form, one output, d = 1..4; anything else is WISKI_E_BADARG before
- * a launch.
- * wiski_absorb_args has NOT grown a robust group: it is passed by pointer without a size field, and callers built against
- * today's header hand over records of today's size.  The robust form is reached through these entries only.
- * wiski_absorb_robust takes the record plus the three robust arguments; it exists so that every combination absorb_validate
- * refuses (a guard, zero regions, a shard, an owner workspace, nout > 1, channels, a full stencil) can be reached and tested. */
-int wiski_scatter_stats_robust_f32(const wiski_grid* grid, const float* d_x, const float* d_y, const float* d_wa, const float* d_wb, const float* d_noise, int64_t n, float* d_b, float* d_A_half, float* d_cnt, const float* d_u, float* d_res, float* d_mean_out, double* d_stats, int32_t* d_err, const float* d_inv_scale, float huber_c, float* d_omega_out, void* stream);
-int wiski_scatter_stats_robust_f64(const wiski_grid* grid, const double* d_x, const double* d_y, const double* d_wa, const double* d_wb, const double* d_noise, int64_t n, double* d_b, double* d_A_half, double* d_cnt, const double* d_u, double* d_res, double* d_mean_out, double* d_stats, int32_t* d_err, const double* d_inv_scale, double huber_c, double* d_omega_out, void* stream);
+ * a launch -- a NULL d_inv_scale and every record field the form has no use for (see wiski_absorb_args) included. */
 int wiski_absorb_robust_f32(const wiski_grid* grid, const wiski_absorb_args* args, const float* d_inv_scale, float huber_c, float* d_omega_out, void* stream);
 int wiski_absorb_robust_f64(const wiski_grid* grid, const wiski_absorb_args* args, const double* d_inv_scale, double huber_c, double* d_omega_out, void* stream);
 
@@ -522,19 +530,15 @@ int wiski_absorb_robust_f64(const wiski_grid* grid, const wiski_absorb_args* arg
  *   4. absorbs the old occupant, if it holds weight, with (-wa, -wb); a void or empty slot gives nothing back.
  * stats += (sum wb y^2, sum log noise) of the points that entered minus those of the points that left.  *d_void_left += the
  * number of overwritten slots that were void, so that a caller can keep its point count without reading the ring.  n <= cap is
- * required (the slots of one launch are then distinct: a slot has one reader and one writer, the same wave), as are d_u, d_A_half,
+ * required (the slots of one launch are then distinct: a slot has one reader and one writer, the same wave), as are d_u, d_A,
  * d_cnt and d_void_left; d_res and d_mean_out are optional.  Both sweeps use the same u, so the result does not depend on the
  * order of points or atomics.  The caller advances head by n (mod cap) afterwards.  Symmetric half stencil, atomic form, one
  * output, d = 1..4; anything else -- n > cap, head outside [0, cap), a missing ring array -- is WISKI_E_BADARG before a launch.
- * As with the robust form, wiski_absorb_args has NOT grown a ring group (it is passed by pointer without a size field), and
- * wiski_absorb_window takes the record plus the ring so that every combination absorb_validate refuses (a guard, zero regions, a
- * shard, an owner workspace, nout > 1, channels, a full stencil) can be reached and tested. */
+ * wiski_absorb_window takes the record (the entering points, as for the robust form) plus the ring and d_void_left. */
 typedef struct wiski_window_ring {
   void* d_x; void* d_y; void* d_wa; void* d_wb; void* d_noise;
   int64_t cap; int64_t head;
 } wiski_window_ring;
-int wiski_scatter_stats_window_f32(const wiski_grid* grid, const float* d_x, const float* d_y, const float* d_wa, const float* d_wb, const float* d_noise, int64_t n, const wiski_window_ring* ring, float* d_b, float* d_A_half, float* d_cnt, const float* d_u, float* d_res, float* d_mean_out, double* d_stats, int32_t* d_err, int32_t* d_void_left, void* stream);
-int wiski_scatter_stats_window_f64(const wiski_grid* grid, const double* d_x, const double* d_y, const double* d_wa, const double* d_wb, const double* d_noise, int64_t n, const wiski_window_ring* ring, double* d_b, double* d_A_half, double* d_cnt, const double* d_u, double* d_res, double* d_mean_out, double* d_stats, int32_t* d_err, int32_t* d_void_left, void* stream);
 int wiski_absorb_window_f32(const wiski_grid* grid, const wiski_absorb_args* args, const wiski_window_ring* ring, int32_t* d_void_left, void* stream);
 int wiski_absorb_window_f64(const wiski_grid* grid, const wiski_absorb_args* args, const wiski_window_ring* ring, int32_t* d_void_left, void* stream);
 
@@ -553,32 +557,26 @@ int wiski_absorb_window_f64(const wiski_grid* grid, const wiski_absorb_args* arg
  * Outputs, [n] each: d_ytilde_out (mu for a skipped point), d_omega_out (0 for a skipped point), d_logz_out (double in both
  * precisions): log Z, the log predictive probability of the interval -- the Gaussian log density for lo == hi, -inf for lo > hi,
  * NaN for a NaN bound.  A point outside the grid is flagged, counted and dropped as everywhere and reports (0, 0, 0).
- * Arguments otherwise as wiski_scatter_stats_robust, without d_y.  Required: d_hi, d_pvar, d_u, d_A_half, d_cnt, the three
- * outputs and a finite sigma2 > 0; d_res and d_mean_out are optional.  Symmetric half stencil, atomic form, one output, d = 1..4;
- * anything else is WISKI_E_BADARG before a launch.  As with the robust form wiski_absorb_args has NOT grown: wiski_absorb_interval
- * takes the record (its d_y is ignored) plus the interval arguments, so that every combination absorb_validate refuses (a guard,
- * zero regions, a shard, an owner workspace, nout > 1, channels, a full stencil) can be reached and tested. */
-int wiski_scatter_stats_interval_f32(const wiski_grid* grid, const float* d_x, const float* d_lo, const float* d_hi, const float* d_pvar, double sigma2, const float* d_wa, const float* d_wb, const float* d_noise, int64_t n, float* d_b, float* d_A_half, float* d_cnt, const float* d_u, float* d_res, float* d_mean_out, double* d_stats, int32_t* d_err, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, void* stream);
-int wiski_scatter_stats_interval_f64(const wiski_grid* grid, const double* d_x, const double* d_lo, const double* d_hi, const double* d_pvar, double sigma2, const double* d_wa, const double* d_wb, const double* d_noise, int64_t n, double* d_b, double* d_A_half, double* d_cnt, const double* d_u, double* d_res, double* d_mean_out, double* d_stats, int32_t* d_err, double* d_ytilde_out, double* d_omega_out, double* d_logz_out, void* stream);
+ * wiski_absorb_interval takes the record as wiski_absorb_robust does (its d_y is ignored) plus the interval arguments.  Required:
+ * d_lo, d_hi, d_pvar, d_u, d_A, d_cnt, the three outputs and a finite sigma2 > 0; d_res and d_mean_out are optional.  Symmetric
+ * half stencil, atomic form, one output, d = 1..4; anything else is WISKI_E_BADARG before a launch. */
 int wiski_absorb_interval_f32(const wiski_grid* grid, const wiski_absorb_args* args, const float* d_lo, const float* d_hi, const float* d_pvar, double sigma2, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, void* stream);
 int wiski_absorb_interval_f64(const wiski_grid* grid, const wiski_absorb_args* args, const double* d_lo, const double* d_hi, const double* d_pvar, double sigma2, double* d_ytilde_out, double* d_omega_out, double* d_logz_out, void* stream);
 
 /* Interval observations of the value AND the partial derivatives of a point: the C = d + 1 channels of
- * wiski_scatter_stats_grad (0: f(x_p), 1 + q: df/dx_q (x_p)), each present one (d_wa[p][c] != 0) an interval
+ * the derivative observations (0: f(x_p), 1 + q: df/dx_q (x_p)), each present one (d_wa[p][c] != 0) an interval
  *   d_lo[p][c] <= (row_c . u) + eps <= d_hi[p][c]   at noise sigma2 d_noise[p][c]
  * -- "f increases in x_q" is d_lo = 0 on channel 1 + q, a slope bound is [-L, L].  Every channel is moment-matched as in
- * wiski_scatter_stats_interval, against its own predictive mean row_c . u and its posterior variance d_pvar[p][c] before the
+ * wiski_absorb_interval, against its own predictive mean row_c . u and its posterior variance d_pvar[p][c] before the
  * batch (the channels of a point independently of each other), and all of them enter in the one launch of the derivative
  * form: one atomic per tap pair.  The skip rules are those of the interval form, per channel; lo == hi is an exact value and
  * enters with omega = 1 exactly.  All per-point arrays, the three outputs and d_mean_out are [n][d + 1].  A skipped channel
  * reports (row_c . u, 0, log Z), an absent one and every channel of a point outside the grid (0, 0, 0); such a point is flagged
  * and counted once.  A derivative channel in a boundary cell of its dim has a zero row: its site is evaluated at mean 0 and
- * enters the two scalars only.  Required: d_hi, d_pvar, d_u, d_A_half, d_cnt, the three outputs and a finite sigma2 > 0; d_res
+ * enters the two scalars only.  Required: d_hi, d_pvar, d_u, d_A, d_cnt, the three outputs and a finite sigma2 > 0; d_res
  * and d_mean_out are optional.  Symmetric half stencil, atomic form, one output, d = 1..4; anything else is WISKI_E_BADARG
- * before a launch.  wiski_absorb_args has NOT grown: wiski_absorb_grad_interval takes the record (its d_y is ignored, its
- * channels must be d + 1) plus the form's arguments, so that every refused combination can be reached and tested. */
-int wiski_scatter_stats_grad_interval_f32(const wiski_grid* grid, const float* d_x, const float* d_lo, const float* d_hi, const float* d_pvar, double sigma2, const float* d_wa, const float* d_wb, const float* d_noise, int64_t n, float* d_b, float* d_A_half, float* d_cnt, const float* d_u, float* d_res, float* d_mean_out, double* d_stats, int32_t* d_err, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, void* stream);
-int wiski_scatter_stats_grad_interval_f64(const wiski_grid* grid, const double* d_x, const double* d_lo, const double* d_hi, const double* d_pvar, double sigma2, const double* d_wa, const double* d_wb, const double* d_noise, int64_t n, double* d_b, double* d_A_half, double* d_cnt, const double* d_u, double* d_res, double* d_mean_out, double* d_stats, int32_t* d_err, double* d_ytilde_out, double* d_omega_out, double* d_logz_out, void* stream);
+ * before a launch.  wiski_absorb_grad_interval takes the record (its d_y is ignored, its channels must be d + 1) plus the
+ * form's arguments. */
 int wiski_absorb_grad_interval_f32(const wiski_grid* grid, const wiski_absorb_args* args, const float* d_lo, const float* d_hi, const float* d_pvar, double sigma2, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, void* stream);
 int wiski_absorb_grad_interval_f64(const wiski_grid* grid, const wiski_absorb_args* args, const double* d_lo, const double* d_hi, const double* d_pvar, double sigma2, double* d_ytilde_out, double* d_omega_out, double* d_logz_out, void* stream);
 
@@ -595,15 +593,12 @@ int wiski_absorb_grad_interval_f64(const wiski_grid* grid, const wiski_absorb_ar
  * Gaussian noise of its own, callers pass noise = wa = wb = 1.  v = 0 gives the Laplace site at mu.  A point is SKIPPED -- it enters
  * nothing and is not flagged in d_err -- when omega < 1e-12 (WISKI_COUNT_OMEGA_MIN), when beta is not positive and finite, or when
  * the datum is invalid (y < 0, t <= 0, y > t for the binomial, a NaN: log Z = NaN).  Outputs and every other argument as
- * wiski_scatter_stats_interval; d_logz_out is the log predictive probability of the count.  wiski_absorb_count takes the record
- * (its d_y is ignored) plus the count arguments, so that every refused combination (a guard, zero regions, a shard, an owner
- * workspace, nout > 1, channels, a full stencil) can be reached and tested; wiski_absorb_args has NOT grown.
+ * wiski_absorb_interval; d_logz_out is the log predictive probability of the count.  wiski_absorb_count takes the record
+ * (its d_y is ignored: the counts are the argument d_y of the entry) plus the count arguments.
  * wiski_count_sites evaluates the sites alone, one wave per site and no scatter, from given means d_mu and variances d_pvar [n]:
  * d_omega_out receives tau (sigma2 noise = 1). */
 #define WISKI_COUNT_POISSON 0
 #define WISKI_COUNT_BINOMIAL 1
-int wiski_scatter_stats_count_f32(const wiski_grid* grid, const float* d_x, const float* d_y, const float* d_t, int family, const float* d_pvar, double sigma2, const float* d_wa, const float* d_wb, const float* d_noise, int64_t n, float* d_b, float* d_A_half, float* d_cnt, const float* d_u, float* d_res, float* d_mean_out, double* d_stats, int32_t* d_err, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, void* stream);
-int wiski_scatter_stats_count_f64(const wiski_grid* grid, const double* d_x, const double* d_y, const double* d_t, int family, const double* d_pvar, double sigma2, const double* d_wa, const double* d_wb, const double* d_noise, int64_t n, double* d_b, double* d_A_half, double* d_cnt, const double* d_u, double* d_res, double* d_mean_out, double* d_stats, int32_t* d_err, double* d_ytilde_out, double* d_omega_out, double* d_logz_out, void* stream);
 int wiski_absorb_count_f32(const wiski_grid* grid, const wiski_absorb_args* args, const float* d_y, const float* d_t, int family, const float* d_pvar, double sigma2, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, void* stream);
 int wiski_absorb_count_f64(const wiski_grid* grid, const wiski_absorb_args* args, const double* d_y, const double* d_t, int family, const double* d_pvar, double sigma2, double* d_ytilde_out, double* d_omega_out, double* d_logz_out, void* stream);
 int wiski_count_sites_f32(const float* d_mu, const float* d_pvar, const float* d_y, const float* d_t, int family, int64_t n, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, void* stream);
@@ -618,7 +613,7 @@ int wiski_count_sites_f64(const double* d_mu, const double* d_pvar, const double
  * per form, every one with the same d_u and d_pvar.  With dn = sigma2 noise, tau = omega / dn, nu = tau ytilde, mu = w . u and
  * v = d_pvar[s] the posterior variance of f at the slot's point under the CURRENT statistics,
  *   cavity:  p = 1 / v - tau,   v_ = 1 / p,   mu_ = v_ (mu / v - nu),
- *   fresh:   (ytilde', omega', log Z') = the site of wiski_scatter_stats_interval / _count at (mu_, v_, dn),
+ *   fresh:   (ytilde', omega', log Z') = the site of wiski_absorb_interval / _count at (mu_, v_, dn),
  *   damped:  tau_new = (1 - damping) tau + damping omega' / dn,   nu_new = (1 - damping) nu + damping (omega' / dn) ytilde',
  *            omega_new = dn tau_new,   ytilde_new = nu_new / tau_new,
  * evaluated in double in both precisions, and the slot enters the statistics with the difference of its site: A, cnt with
@@ -635,12 +630,10 @@ int wiski_count_sites_f64(const double* d_mu, const double* d_pvar, const double
  * slots nor on the order of the atomics.
  * Outputs, per slot of the form: d_change_out [cap] = |omega_new - omega_old| / max(omega_new, omega_old) (0 for a slot left alone),
  * d_logz_out [cap] (double) = log Z' against the cavity (NaN for a slot left alone).  Required: every ring array, d_pvar, d_u,
- * d_A_half, d_cnt, d_b, d_stats, d_err, both outputs, a finite sigma2 > 0, 0 <= damping <= 1 and a known form; d_res is optional.
+ * d_A, d_cnt, d_b, d_stats, d_err, both outputs, a finite sigma2 > 0, 0 <= damping <= 1 and a known form; d_res is optional.
  * cap = 0 or a ring without a slot of the form does nothing and returns WISKI_OK.  Symmetric half stencil, atomic form, one output,
- * d = 1..4; anything else is WISKI_E_BADARG before a launch.  wiski_absorb_args has NOT grown: wiski_absorb_revisit takes the record
- * (its points d_x / d_y / d_wa / d_wb / d_noise / n are not looked at: the points are the ring's slots) plus the revisit arguments, so
- * that every refused combination (a guard, zero regions, a shard, an owner workspace, nout > 1, channels, a full stencil, d_mean_out)
- * can be reached and tested. */
+ * d = 1..4; anything else is WISKI_E_BADARG before a launch.  wiski_absorb_revisit takes the record (its points d_x / d_y / d_wa /
+ * d_wb / d_noise / n are not looked at: the points are the ring's slots; its d_mean_out must be NULL) plus the revisit arguments. */
 #define WISKI_SITE_EMPTY 0
 #define WISKI_SITE_INTERVAL 1
 #define WISKI_SITE_POISSON 2
@@ -650,14 +643,12 @@ typedef struct wiski_site_ring {
   int32_t* d_form;
   int64_t cap;
 } wiski_site_ring;
-int wiski_revisit_sites_f32(const wiski_grid* grid, const wiski_site_ring* ring, int form, const float* d_pvar, double sigma2, double damping, float* d_b, float* d_A_half, float* d_cnt, const float* d_u, float* d_res, double* d_stats, int32_t* d_err, double* d_logz_out, float* d_change_out, void* stream);
-int wiski_revisit_sites_f64(const wiski_grid* grid, const wiski_site_ring* ring, int form, const double* d_pvar, double sigma2, double damping, double* d_b, double* d_A_half, double* d_cnt, const double* d_u, double* d_res, double* d_stats, int32_t* d_err, double* d_logz_out, double* d_change_out, void* stream);
 int wiski_absorb_revisit_f32(const wiski_grid* grid, const wiski_absorb_args* args, const wiski_site_ring* ring, int form, const float* d_pvar, double sigma2, double damping, double* d_logz_out, float* d_change_out, void* stream);
 int wiski_absorb_revisit_f64(const wiski_grid* grid, const wiski_absorb_args* args, const wiski_site_ring* ring, int form, const double* d_pvar, double sigma2, double damping, double* d_logz_out, double* d_change_out, void* stream);
 
 /* Heteroscedastic absorb: the noise of a point is not known but learned, as a second field on the same grid:
  *   y_p = f(x_p) + eps_p,   eps_p ~ N(0, sigma2 noise_p exp g(x_p)),   g ~ GP(g0, k_g).
- * f and g are two single-output models with a set of statistics each: (d_b, d_A_half, d_cnt, d_stats, d_u, d_res) for f and
+ * f and g are two single-output models with a set of statistics each: (d_b, d_A, d_cnt, d_stats, d_u, d_res) for f and
  * (d_b2, d_A2_half, d_cnt2, d_stats2, d_u2, d_res2) for g - g0.  Both are taken against their posteriors BEFORE the batch, inside the
  * one launch that absorbs it into both: with mu_f = w_p . u, v_f = max(d_pvar_p, 0), mu_g = g0 + w_p . u2, v_g = max(d_pvar2_p, 0),
  *   e     = exp(mu_g + v_g / 2)                      (the mean of the log-normal multiplier),   dn = sigma2 noise_p e,
@@ -675,17 +666,15 @@ int wiski_absorb_revisit_f64(const wiski_grid* grid, const wiski_absorb_args* ar
  * PRECISION (|mu_g + v_g / 2| > 87 in fp32: the weight would be 0 or inf) skips the point for both models (both log Z = NaN, no flag
  * in d_err; d_e_out still reports e as rounded).  A point outside the grid is dropped for both, flagged and counted ONCE in d_err, and reports zeros.  d_stats2[0], the sum
  * of tau ytilde^2, is dominated by weak sites and is no evidence term: the evidence is the sum of the log Z.
- * d_u, d_A_half, d_cnt and the whole second set but d_res2 are required; d_res, d_res2 and d_mean_out are optional.  d = 1..4,
- * symmetric half stencil, atomic form, a single output.  wiski_absorb_hetero takes the record plus the hetero arguments, so that
- * every refused combination (a guard, zero regions, a shard, an owner workspace, nout > 1, channels, a full stencil) can be reached
- * and tested; wiski_absorb_args has NOT grown.  Everything refused returns WISKI_E_BADARG before a launch; n = 0 does nothing.
+ * d_u, d_A, d_cnt and the whole second set but d_res2 are required; d_res, d_res2 and d_mean_out are optional.  d = 1..4,
+ * symmetric half stencil, atomic form, a single output.  wiski_absorb_hetero takes the record (the set of f and the points) plus
+ * the hetero arguments (the set of g, the variances, the outputs).  Everything refused returns WISKI_E_BADARG before a launch; n = 0
+ * does nothing.
  * wiski_hetero_sites evaluates the noise sites alone, one wave per site and no scatter, from given d_mu = mu_g, d_pvar = v_g, d_rho
  * and d_nu [n] (nu is general: replicated readings give a sample variance with nu degrees of freedom): d_omega_out receives tau.
  * It is wiski_count_sites of the family WISKI_COUNT_LOGVAR (the same kernel with the family fixed at compile time), which the count
  * absorb and wiski_count_sites themselves do not take.  n = 0 returns WISKI_OK from all three, whatever the other arguments hold. */
 #define WISKI_COUNT_LOGVAR 2
-int wiski_scatter_stats_hetero_f32(const wiski_grid* grid, const float* d_x, const float* d_y, const float* d_pvar, const float* d_pvar2, double sigma2, double g0, const float* d_wa, const float* d_wb, const float* d_noise, int64_t n, float* d_b, float* d_A_half, float* d_cnt, const float* d_u, float* d_res, float* d_mean_out, double* d_stats, float* d_b2, float* d_A2_half, float* d_cnt2, const float* d_u2, float* d_res2, double* d_stats2, int32_t* d_err, float* d_e_out, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, double* d_logzy_out, void* stream);
-int wiski_scatter_stats_hetero_f64(const wiski_grid* grid, const double* d_x, const double* d_y, const double* d_pvar, const double* d_pvar2, double sigma2, double g0, const double* d_wa, const double* d_wb, const double* d_noise, int64_t n, double* d_b, double* d_A_half, double* d_cnt, const double* d_u, double* d_res, double* d_mean_out, double* d_stats, double* d_b2, double* d_A2_half, double* d_cnt2, const double* d_u2, double* d_res2, double* d_stats2, int32_t* d_err, double* d_e_out, double* d_ytilde_out, double* d_omega_out, double* d_logz_out, double* d_logzy_out, void* stream);
 int wiski_absorb_hetero_f32(const wiski_grid* grid, const wiski_absorb_args* args, const float* d_pvar, const float* d_pvar2, double sigma2, double g0, float* d_b2, float* d_A2_half, float* d_cnt2, const float* d_u2, float* d_res2, double* d_stats2, float* d_e_out, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, double* d_logzy_out, void* stream);
 int wiski_absorb_hetero_f64(const wiski_grid* grid, const wiski_absorb_args* args, const double* d_pvar, const double* d_pvar2, double sigma2, double g0, double* d_b2, double* d_A2_half, double* d_cnt2, const double* d_u2, double* d_res2, double* d_stats2, double* d_e_out, double* d_ytilde_out, double* d_omega_out, double* d_logz_out, double* d_logzy_out, void* stream);
 int wiski_hetero_sites_f32(const float* d_mu, const float* d_pvar, const float* d_rho, const float* d_nu, int64_t n, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, void* stream);
@@ -702,22 +691,19 @@ int wiski_hetero_sites_f64(const double* d_mu, const double* d_pvar, const doubl
  * evaluated in double in both precisions by the quadrature of the count form (its nodes are the 64 lanes of the point's wave), and
  * output c takes the point as the target ytilde_c at noise noise_c,p / omega_c.  This is the one form that couples outputs: a kernel
  * of its own, one wave per point, which builds the point's stencil once, reduces the C means, and runs the atomics of every output
- * whose site enters into d_b / d_cnt / d_res at + c m, d_A_half + c A_stride, d_stats + 2 c; d_wa / d_wb / d_noise of output c are at
+ * whose site enters into d_b / d_cnt / d_res at + c m, d_A + c A_stride, d_stats + 2 c; d_wa / d_wb / d_noise of output c are at
  * + c w_stride (0: shared by all outputs).  A site is SKIPPED for its output only when beta_c is not positive and finite or
  * omega_c < 1e-12 (WISKI_COUNT_OMEGA_MIN: a class far below the label's says nothing).  A label that is not an integer in [0, C),
  * or NaN, skips the point for every output (log Z = NaN, no flag in d_err).  A point outside the grid is dropped for every output,
  * counted once, and reports zeros.  d_ytilde_out / d_omega_out / d_pvar and the optional d_mean_out are [C][n] (a skipped site
  * reports ytilde = mu_c, omega = 0), d_logz_out [n] is log P(y_p); sigma2 [C] is a HOST array, every entry positive and finite.
- * d_u, d_A_half and d_cnt are required, d_res and d_mean_out optional.  2 <= nout <= WISKI_LABEL_MAX_CLASSES, d = 1..4, symmetric
- * half stencil, atomic form.  wiski_absorb_label takes the record (its d_y is ignored; nout, w_stride and A_stride are the record's)
- * plus the label arguments, so that every refused combination (a guard, zero regions, a shard, an owner workspace, channels, a
- * full stencil) can be reached and tested; wiski_absorb_args has NOT grown.  Everything refused returns WISKI_E_BADARG before a launch.
+ * d_u, d_A and d_cnt are required, d_res and d_mean_out optional.  2 <= nout <= WISKI_LABEL_MAX_CLASSES, d = 1..4, symmetric
+ * half stencil, atomic form.  wiski_absorb_label takes the record (its d_y is ignored; nout = C, w_stride and A_stride are the
+ * record's) plus the label arguments.  Everything refused returns WISKI_E_BADARG before a launch.
  * wiski_label_sites evaluates the sites alone, one wave per point and no scatter, from given means d_mu, latent variances d_pvar and
  * noise variances d_s, all [C][n]: d_omega_out receives tau.  wiski_label_proba writes P(y = k) for every k into d_proba_out [n][C]
  * (double): the same integral without its derivatives, once per class; the row is NOT normalised (its sum is 1 to quadrature error). */
 #define WISKI_LABEL_MAX_CLASSES 16
-int wiski_scatter_stats_label_f32(const wiski_grid* grid, const float* d_x, const float* d_labels, const float* d_pvar, const double* sigma2, const float* d_wa, const float* d_wb, const float* d_noise, int64_t n, int32_t nout, int64_t w_stride, float* d_b, float* d_A_half, int64_t A_stride, float* d_cnt, const float* d_u, float* d_res, float* d_mean_out, double* d_stats, int32_t* d_err, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, void* stream);
-int wiski_scatter_stats_label_f64(const wiski_grid* grid, const double* d_x, const double* d_labels, const double* d_pvar, const double* sigma2, const double* d_wa, const double* d_wb, const double* d_noise, int64_t n, int32_t nout, int64_t w_stride, double* d_b, double* d_A_half, int64_t A_stride, double* d_cnt, const double* d_u, double* d_res, double* d_mean_out, double* d_stats, int32_t* d_err, double* d_ytilde_out, double* d_omega_out, double* d_logz_out, void* stream);
 int wiski_absorb_label_f32(const wiski_grid* grid, const wiski_absorb_args* args, const float* d_labels, const float* d_pvar, const double* sigma2, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, void* stream);
 int wiski_absorb_label_f64(const wiski_grid* grid, const wiski_absorb_args* args, const double* d_labels, const double* d_pvar, const double* sigma2, double* d_ytilde_out, double* d_omega_out, double* d_logz_out, void* stream);
 int wiski_label_sites_f32(const float* d_mu, const float* d_pvar, const float* d_s, const float* d_labels, int32_t nout, int64_t n, float* d_ytilde_out, float* d_omega_out, double* d_logz_out, void* stream);
@@ -735,11 +721,8 @@ int wiski_label_proba_f64(const double* d_mu, const double* d_pvar, const double
  * omega = 1 exactly: the plain absorb.  A point is SKIPPED -- it enters nothing, reports omega = 0 and is not flagged in d_err --
  * when an xvar_k is negative or NaN or s_in is not finite (log Z = NaN), or when omega < 1e-12 (WISKI_INPUT_NOISE_OMEGA_MIN).
  * d_omega_out [n], d_logz_out [n] (double) and, optionally, d_grad_out [n, d] (the slopes g as reduced by the kernel) are written
- * for every point; a point outside the grid reports zeros.  Every other argument as wiski_scatter_stats_interval.
- * wiski_absorb_input_noise takes the record plus the group, so that every refused combination (a guard, zero regions, a shard, an
- * owner workspace, nout > 1, channels, a full stencil, no d_y) can be reached and tested; wiski_absorb_args has NOT grown. */
-int wiski_scatter_stats_input_noise_f32(const wiski_grid* grid, const float* d_x, const float* d_y, const float* d_xvar, const float* d_gvar, const float* d_pvar, double sigma2, const float* d_wa, const float* d_wb, const float* d_noise, int64_t n, float* d_b, float* d_A_half, float* d_cnt, const float* d_u, float* d_res, float* d_mean_out, double* d_stats, int32_t* d_err, float* d_omega_out, double* d_logz_out, float* d_grad_out, void* stream);
-int wiski_scatter_stats_input_noise_f64(const wiski_grid* grid, const double* d_x, const double* d_y, const double* d_xvar, const double* d_gvar, const double* d_pvar, double sigma2, const double* d_wa, const double* d_wb, const double* d_noise, int64_t n, double* d_b, double* d_A_half, double* d_cnt, const double* d_u, double* d_res, double* d_mean_out, double* d_stats, int32_t* d_err, double* d_omega_out, double* d_logz_out, double* d_grad_out, void* stream);
+ * for every point; a point outside the grid reports zeros.  Every other argument as wiski_absorb_interval.
+ * wiski_absorb_input_noise takes the record (with d_y: the targets are the points' own) plus the group. */
 int wiski_absorb_input_noise_f32(const wiski_grid* grid, const wiski_absorb_args* args, const float* d_xvar, const float* d_gvar, const float* d_pvar, double sigma2, float* d_omega_out, double* d_logz_out, float* d_grad_out, void* stream);
 int wiski_absorb_input_noise_f64(const wiski_grid* grid, const wiski_absorb_args* args, const double* d_xvar, const double* d_gvar, const double* d_pvar, double sigma2, double* d_omega_out, double* d_logz_out, double* d_grad_out, void* stream);
 

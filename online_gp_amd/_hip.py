@@ -108,49 +108,35 @@ class wiski_site_ring(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("d_x", "d_d0", "d_d1", "d_noise", "d_wa", "d_wb", "d_ytilde", "d_omega", "d_form")] + [("cap", ctypes.c_int64)]
 
 
-def _revisit_signatures():
-    """argtypes of the entries of the site revisit (include/wiski.h), as _grad_interval_signatures."""
-    p, f64 = ctypes.c_void_p, ctypes.c_double
-    flat = [ctypes.POINTER(wiski_grid), ctypes.POINTER(wiski_site_ring), ctypes.c_int, p, f64, f64] + [p] * 9 + [p]
-    record = [ctypes.POINTER(wiski_grid), ctypes.POINTER(wiski_absorb_args), ctypes.POINTER(wiski_site_ring), ctypes.c_int, p, f64, f64, p, p, p]
-    return {name + suf: sig for name, sig in (("wiski_revisit_sites", flat), ("wiski_absorb_revisit", record)) for suf in ("_f32", "_f64")}
+def _absorb_signatures():
+    """argtypes of every entry of the absorb's observation forms (include/wiski.h), by name: pointers as c_void_p, in the order of
+    the prototypes.  A form's entry is (grid, record, the form's own arguments, stream) and only the own arguments are spelt out
+    here; "real" is the one scalar in the working precision (c_float / c_double by suffix).  The site-only entries take neither
+    grid nor record.  lib() sets them all, so that a call with a wrong argument count or kind fails in ctypes, and
+    tests/test_host.py holds the table against the header."""
+    p, f64, i32, i64, cint = ctypes.c_void_p, ctypes.c_double, ctypes.c_int32, ctypes.c_int64, ctypes.c_int
+    own = {
+        "wiski_absorb": [],
+        "wiski_absorb_robust": [p, "real", p],
+        "wiski_absorb_window": [ctypes.POINTER(wiski_window_ring), p],
+        "wiski_absorb_interval": [p, p, p, f64, p, p, p],
+        "wiski_absorb_grad_interval": [p, p, p, f64, p, p, p],
+        "wiski_absorb_count": [p, p, cint, p, f64, p, p, p],
+        "wiski_absorb_revisit": [ctypes.POINTER(wiski_site_ring), cint, p, f64, f64, p, p],
+        "wiski_absorb_hetero": [p, p, f64, f64] + [p] * 11,
+        "wiski_absorb_label": [p, p, ctypes.POINTER(f64), p, p, p],
+        "wiski_absorb_input_noise": [p, p, p, f64, p, p, p],
+        "wiski_count_sites": [p] * 4 + [cint, i64] + [p] * 3,
+        "wiski_hetero_sites": [p] * 4 + [i64] + [p] * 3,
+        "wiski_label_sites": [p] * 4 + [i32, i64] + [p] * 3,
+        "wiski_label_proba": [p] * 3 + [i32, i64, p],
+    }
+    record = [ctypes.POINTER(wiski_grid), ctypes.POINTER(wiski_absorb_args)]
+    return {name + suf: (record if name.startswith("wiski_absorb") else []) + [real if t == "real" else t for t in args] + [p]
+            for name, args in own.items() for suf, real in (("_f32", ctypes.c_float), ("_f64", f64))}
 
 
-def _grad_interval_signatures():
-    """argtypes of the four entries of the channel-interval absorb (include/wiski.h), by name: pointers as
-    c_void_p, in the order of the prototypes.  lib() sets them, so that a call with a wrong argument count fails in ctypes."""
-    p, f64, i64 = ctypes.c_void_p, ctypes.c_double, ctypes.c_int64
-    flat = [ctypes.POINTER(wiski_grid)] + [p] * 4 + [f64] + [p] * 3 + [i64] + [p] * 11 + [p]
-    record = [ctypes.POINTER(wiski_grid), ctypes.POINTER(wiski_absorb_args)] + [p] * 3 + [f64] + [p] * 3 + [p]
-    return {name + suf: sig for name, sig in (("wiski_scatter_stats_grad_interval", flat), ("wiski_absorb_grad_interval", record)) for suf in ("_f32", "_f64")}
-
-
-def _label_signatures():
-    """argtypes of the entries of the categorical-observation absorb (include/wiski.h), as _grad_interval_signatures."""
-    p, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    sig2 = ctypes.POINTER(ctypes.c_double)
-    flat = [ctypes.POINTER(wiski_grid)] + [p] * 3 + [sig2] + [p] * 3 + [i64, i32, i64] + [p] * 2 + [i64] + [p] * 9 + [p]
-    record = [ctypes.POINTER(wiski_grid), ctypes.POINTER(wiski_absorb_args)] + [p] * 2 + [sig2] + [p] * 3 + [p]
-    sites = [p] * 4 + [i32, i64] + [p] * 3 + [p]
-    proba = [p] * 3 + [i32, i64] + [p] + [p]
-    return {name + suf: sig for name, sig in (("wiski_scatter_stats_label", flat), ("wiski_absorb_label", record), ("wiski_label_sites", sites),
-                                              ("wiski_label_proba", proba)) for suf in ("_f32", "_f64")}
-
-
-def _hetero_signatures():
-    """argtypes of the entries of the heteroscedastic absorb (include/wiski.h), as _grad_interval_signatures."""
-    p, f64, i64 = ctypes.c_void_p, ctypes.c_double, ctypes.c_int64
-    flat = [ctypes.POINTER(wiski_grid)] + [p] * 4 + [f64, f64] + [p] * 3 + [i64] + [p] * 19 + [p]
-    record = [ctypes.POINTER(wiski_grid), ctypes.POINTER(wiski_absorb_args)] + [p] * 2 + [f64, f64] + [p] * 11 + [p]
-    sites = [p] * 4 + [i64] + [p] * 3 + [p]
-    return {name + suf: sig for name, sig in (("wiski_scatter_stats_hetero", flat), ("wiski_absorb_hetero", record), ("wiski_hetero_sites", sites))
-            for suf in ("_f32", "_f64")}
-
-
-SIGNATURES = _grad_interval_signatures()
-LABEL_SIGNATURES = _label_signatures()
-HETERO_SIGNATURES = _hetero_signatures()
-REVISIT_SIGNATURES = _revisit_signatures()
+ABSORB_SIGNATURES = _absorb_signatures()
 
 
 def sources():
@@ -251,6 +237,9 @@ def lib():
             _lib.wiski_pcg_workspace_bytes.restype = ctypes.c_int64
             if hasattr(_lib, "wiski_root_update_workspace_elems"):
                 _lib.wiski_root_update_workspace_elems.restype = ctypes.c_int64
+            for name, sig in ABSORB_SIGNATURES.items():      # (a variant need not have every form; the ones it has take plain floats and ints)
+                if hasattr(_lib, name):
+                    getattr(_lib, name).argtypes = sig
             return _lib
         if not os.path.exists(_SO):
             raise WiskiError(
@@ -260,7 +249,7 @@ def lib():
         _lib = ctypes.CDLL(_SO)
         _lib.wiski_pcg_workspace_bytes.restype = ctypes.c_int64
         _lib.wiski_twolevel_refresh_workspace_bytes.restype = ctypes.c_int64
-        for name, sig in {**SIGNATURES, **LABEL_SIGNATURES, **HETERO_SIGNATURES, **REVISIT_SIGNATURES}.items():
+        for name, sig in ABSORB_SIGNATURES.items():
             f = getattr(_lib, name)
             f.argtypes, f.restype = sig, ctypes.c_int
     if hasattr(_lib, "wiski_root_update_workspace_elems"):

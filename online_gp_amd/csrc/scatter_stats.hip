@@ -478,155 +478,76 @@ static AbsorbArgs<real> absorb_args(const wiski_absorb_args& p) {
 // The bodies of the extern "C" entry points below (include/wiski.h documents each), once for both scalar types.
 template <typename real>
 static int entry_absorb(const wiski_grid* g, const wiski_absorb_args* p, void* s) { return p ? absorb(g, absorb_args<real>(*p), s) : WISKI_E_BADARG; }
+// One per observation form: the record plus the form's own arguments.  The argument that makes the record this form's (without it
+// absorb_validate would read another form's request) is required here; everything else is absorb_validate's to refuse.
 template <typename real>
-static int entry_grad(const wiski_grid* g, const real* x, const real* y, const real* wa, const real* wb, const real* noise, int64_t n, real* b, real* A_half, real* cnt, const real* u, real* res, real* mean_out, double* stats, int32_t* err, void* s) {
-  AbsorbArgs<real> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
-  absorb_carry(a, cnt, u, res, mean_out);
-  a.channels = g ? g->d + 1 : 0;
+static int entry_robust(const wiski_grid* g, const wiski_absorb_args* p, const real* inv_scale, real huber_c, real* omega_out, void* s) {
+  if (!p || !inv_scale) return WISKI_E_BADARG;
+  AbsorbArgs<real> a = absorb_args<real>(*p);
+  a.inv_scale = inv_scale; a.huber_c = huber_c; a.omega_out = omega_out;
   return absorb(g, a, s);
 }
 template <typename real>
-static int entry_robust(const wiski_grid* g, AbsorbArgs<real> a, const real* inv_scale, real huber_c, real* omega_out, void* s) {
-  a.inv_scale = inv_scale; a.huber_c = huber_c; a.omega_out = omega_out;
-  return inv_scale ? absorb(g, a, s) : WISKI_E_BADARG;
-}
-template <typename real>
-static int entry_scatter_robust(const wiski_grid* g, const real* x, const real* y, const real* wa, const real* wb, const real* noise, int64_t n, real* b, real* A_half, real* cnt, const real* u, real* res, real* mean_out, double* stats, int32_t* err, const real* inv_scale, real huber_c, real* omega_out, void* s) {
-  AbsorbArgs<real> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
-  absorb_carry(a, cnt, u, res, mean_out);
-  return entry_robust(g, a, inv_scale, huber_c, omega_out, s);
-}
-template <typename real>
-static int entry_absorb_robust(const wiski_grid* g, const wiski_absorb_args* p, const real* inv_scale, real huber_c, real* omega_out, void* s) {
-  return p ? entry_robust(g, absorb_args<real>(*p), inv_scale, huber_c, omega_out, s) : WISKI_E_BADARG;
-}
-template <typename real>
-static int entry_window(const wiski_grid* g, AbsorbArgs<real> a, const wiski_window_ring* r, int32_t* void_left, void* s) {
-  if (!r) return WISKI_E_BADARG;
+static int entry_window(const wiski_grid* g, const wiski_absorb_args* p, const wiski_window_ring* r, int32_t* void_left, void* s) {
+  if (!p || !r || !r->d_x) return WISKI_E_BADARG;
+  AbsorbArgs<real> a = absorb_args<real>(*p);
   a.ring_x = (real*)r->d_x; a.ring_y = (real*)r->d_y; a.ring_wa = (real*)r->d_wa; a.ring_wb = (real*)r->d_wb; a.ring_noise = (real*)r->d_noise;
   a.ring_cap = r->cap; a.ring_head = r->head; a.void_left = void_left;
-  return a.ring_x ? absorb(g, a, s) : WISKI_E_BADARG;
+  return absorb(g, a, s);
 }
 template <typename real>
-static int entry_scatter_window(const wiski_grid* g, const real* x, const real* y, const real* wa, const real* wb, const real* noise, int64_t n, const wiski_window_ring* r, real* b, real* A_half, real* cnt, const real* u, real* res, real* mean_out, double* stats, int32_t* err, int32_t* void_left, void* s) {
-  AbsorbArgs<real> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
-  absorb_carry(a, cnt, u, res, mean_out);
-  return entry_window(g, a, r, void_left, s);
-}
-template <typename real>
-static int entry_absorb_window(const wiski_grid* g, const wiski_absorb_args* p, const wiski_window_ring* r, int32_t* void_left, void* s) {
-  return p ? entry_window(g, absorb_args<real>(*p), r, void_left, s) : WISKI_E_BADARG;
-}
-template <typename real>
-static int entry_interval(const wiski_grid* g, AbsorbArgs<real> a, const real* lo, const real* hi, const real* pvar, double sigma2, real* ytilde_out, real* omega_out, double* logz_out, void* s) {
+static int entry_interval(const wiski_grid* g, const wiski_absorb_args* p, const real* lo, const real* hi, const real* pvar, double sigma2, real* ytilde_out, real* omega_out, double* logz_out, void* s) {
+  if (!p || !lo) return WISKI_E_BADARG;
+  AbsorbArgs<real> a = absorb_args<real>(*p);
   a.y = nullptr;                                       // ignored by the form
   a.lo = lo; a.hi = hi; a.pvar = pvar; a.sigma2 = sigma2; a.ytilde_out = ytilde_out; a.omega_out = omega_out; a.logz_out = logz_out;
-  return lo ? absorb(g, a, s) : WISKI_E_BADARG;
+  return absorb(g, a, s);
 }
 template <typename real>
-static int entry_scatter_interval(const wiski_grid* g, const real* x, const real* lo, const real* hi, const real* pvar, double sigma2, const real* wa, const real* wb, const real* noise, int64_t n, real* b, real* A_half, real* cnt, const real* u, real* res, real* mean_out, double* stats, int32_t* err, real* ytilde_out, real* omega_out, double* logz_out, void* s) {
-  AbsorbArgs<real> a = absorb_args(x, (const real*)nullptr, wa, wb, noise, n, b, A_half, true, stats, err);
-  absorb_carry(a, cnt, u, res, mean_out);
-  return entry_interval(g, a, lo, hi, pvar, sigma2, ytilde_out, omega_out, logz_out, s);
+static int entry_grad_interval(const wiski_grid* g, const wiski_absorb_args* p, const real* lo, const real* hi, const real* pvar, double sigma2, real* ytilde_out, real* omega_out, double* logz_out, void* s) {
+  if (!p || !lo) return WISKI_E_BADARG;
+  AbsorbArgs<real> a = absorb_args<real>(*p);
+  a.y = nullptr;                                       // ignored by the form
+  a.clo = lo; a.chi = hi; a.cpvar = pvar; a.sigma2 = sigma2; a.ytilde_out = ytilde_out; a.omega_out = omega_out; a.logz_out = logz_out;
+  return absorb(g, a, s);
 }
 template <typename real>
-static int entry_absorb_interval(const wiski_grid* g, const wiski_absorb_args* p, const real* lo, const real* hi, const real* pvar, double sigma2, real* ytilde_out, real* omega_out, double* logz_out, void* s) {
-  return p ? entry_interval(g, absorb_args<real>(*p), lo, hi, pvar, sigma2, ytilde_out, omega_out, logz_out, s) : WISKI_E_BADARG;
-}
-template <typename real>
-static int entry_count(const wiski_grid* g, AbsorbArgs<real> a, const real* cy, const real* ct, int family, const real* pvar, double sigma2, real* ytilde_out, real* omega_out, double* logz_out, void* s) {
+static int entry_count(const wiski_grid* g, const wiski_absorb_args* p, const real* cy, const real* ct, int family, const real* pvar, double sigma2, real* ytilde_out, real* omega_out, double* logz_out, void* s) {
+  if (!p || !cy) return WISKI_E_BADARG;
+  AbsorbArgs<real> a = absorb_args<real>(*p);
   a.y = nullptr;                                       // ignored by the form
   a.count_y = cy; a.count_t = ct; a.count_family = family; a.pvar = pvar; a.sigma2 = sigma2; a.ytilde_out = ytilde_out; a.omega_out = omega_out; a.logz_out = logz_out;
-  return cy ? absorb(g, a, s) : WISKI_E_BADARG;
+  return absorb(g, a, s);
 }
 template <typename real>
-static int entry_scatter_count(const wiski_grid* g, const real* x, const real* cy, const real* ct, int family, const real* pvar, double sigma2, const real* wa, const real* wb, const real* noise, int64_t n, real* b, real* A_half, real* cnt, const real* u, real* res, real* mean_out, double* stats, int32_t* err, real* ytilde_out, real* omega_out, double* logz_out, void* s) {
-  AbsorbArgs<real> a = absorb_args(x, (const real*)nullptr, wa, wb, noise, n, b, A_half, true, stats, err);
-  absorb_carry(a, cnt, u, res, mean_out);
-  return entry_count(g, a, cy, ct, family, pvar, sigma2, ytilde_out, omega_out, logz_out, s);
-}
-template <typename real>
-static int entry_absorb_count(const wiski_grid* g, const wiski_absorb_args* p, const real* cy, const real* ct, int family, const real* pvar, double sigma2, real* ytilde_out, real* omega_out, double* logz_out, void* s) {
-  return p ? entry_count(g, absorb_args<real>(*p), cy, ct, family, pvar, sigma2, ytilde_out, omega_out, logz_out, s) : WISKI_E_BADARG;
-}
-template <typename real>
-static int entry_scatter_label(const wiski_grid* g, const real* x, const real* labels, const real* pvar, const double* sigma2, const real* wa, const real* wb, const real* noise, int64_t n, int32_t nout, int64_t w_stride, real* b, real* A_half, int64_t A_stride, real* cnt, const real* u, real* res, real* mean_out, double* stats, int32_t* err, real* ytilde_out, real* omega_out, double* logz_out, void* s) {
-  AbsorbArgs<real> a = absorb_args(x, (const real*)nullptr, wa, wb, noise, n, b, A_half, true, stats, err);
-  absorb_carry(a, cnt, u, res, mean_out);
-  a.nout = nout; a.bt.w_stride = w_stride; a.bt.A_stride = A_stride;
-  return label_absorb(g, a, labels, pvar, sigma2, ytilde_out, omega_out, logz_out, s);
-}
-template <typename real>
-static int entry_absorb_label(const wiski_grid* g, const wiski_absorb_args* p, const real* labels, const real* pvar, const double* sigma2, real* ytilde_out, real* omega_out, double* logz_out, void* s) {
+static int entry_label(const wiski_grid* g, const wiski_absorb_args* p, const real* labels, const real* pvar, const double* sigma2, real* ytilde_out, real* omega_out, double* logz_out, void* s) {
   return p ? label_absorb(g, absorb_args<real>(*p), labels, pvar, sigma2, ytilde_out, omega_out, logz_out, s) : WISKI_E_BADARG;
 }
 template <typename real>
-static int entry_hetero(const wiski_grid* g, AbsorbArgs<real> a, const real* pvar, const real* pvar2, double sigma2, double g0, real* b2, real* A2_half, real* cnt2, const real* u2, real* res2, double* stats2, real* e_out, real* ytilde_out, real* omega_out, double* logz_out, double* logzy_out, void* s) {
+static int entry_hetero(const wiski_grid* g, const wiski_absorb_args* p, const real* pvar, const real* pvar2, double sigma2, double g0, real* b2, real* A2_half, real* cnt2, const real* u2, real* res2, double* stats2, real* e_out, real* ytilde_out, real* omega_out, double* logz_out, double* logzy_out, void* s) {
+  if (!p || (!b2 && p->n != 0)) return WISKI_E_BADARG;  // (n = 0 does nothing)
+  AbsorbArgs<real> a = absorb_args<real>(*p);
   a.pvar = pvar; a.pvar2 = pvar2; a.sigma2 = sigma2; a.g0 = g0; a.b2 = b2; a.A2 = A2_half; a.cnt2 = cnt2; a.u2 = u2; a.res2 = res2; a.stats2 = stats2;
   a.e_out = e_out; a.ytilde_out = ytilde_out; a.omega_out = omega_out; a.logz_out = logz_out; a.logzy_out = logzy_out;
-  return b2 || a.n == 0 ? absorb(g, a, s) : WISKI_E_BADARG;   // (without b2 the record would be another form's; n = 0 does nothing)
+  return absorb(g, a, s);
 }
 template <typename real>
-static int entry_scatter_hetero(const wiski_grid* g, const real* x, const real* y, const real* pvar, const real* pvar2, double sigma2, double g0, const real* wa, const real* wb, const real* noise, int64_t n, real* b, real* A_half, real* cnt, const real* u, real* res, real* mean_out, double* stats, real* b2, real* A2_half, real* cnt2, const real* u2, real* res2, double* stats2, int32_t* err, real* e_out, real* ytilde_out, real* omega_out, double* logz_out, double* logzy_out, void* s) {
-  AbsorbArgs<real> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
-  absorb_carry(a, cnt, u, res, mean_out);
-  return entry_hetero(g, a, pvar, pvar2, sigma2, g0, b2, A2_half, cnt2, u2, res2, stats2, e_out, ytilde_out, omega_out, logz_out, logzy_out, s);
-}
-template <typename real>
-static int entry_absorb_hetero(const wiski_grid* g, const wiski_absorb_args* p, const real* pvar, const real* pvar2, double sigma2, double g0, real* b2, real* A2_half, real* cnt2, const real* u2, real* res2, double* stats2, real* e_out, real* ytilde_out, real* omega_out, double* logz_out, double* logzy_out, void* s) {
-  return p ? entry_hetero(g, absorb_args<real>(*p), pvar, pvar2, sigma2, g0, b2, A2_half, cnt2, u2, res2, stats2, e_out, ytilde_out, omega_out, logz_out, logzy_out, s) : WISKI_E_BADARG;
-}
-template <typename real>
-static int entry_input_noise(const wiski_grid* g, AbsorbArgs<real> a, const real* xvar, const real* gvar, const real* pvar, double sigma2, real* omega_out, double* logz_out, real* grad_out, void* s) {
+static int entry_input_noise(const wiski_grid* g, const wiski_absorb_args* p, const real* xvar, const real* gvar, const real* pvar, double sigma2, real* omega_out, double* logz_out, real* grad_out, void* s) {
+  if (!p || !xvar) return WISKI_E_BADARG;
+  AbsorbArgs<real> a = absorb_args<real>(*p);
   a.xvar = xvar; a.gvar = gvar; a.grad_out = grad_out; a.pvar = pvar; a.sigma2 = sigma2; a.omega_out = omega_out; a.logz_out = logz_out;
-  return xvar ? absorb(g, a, s) : WISKI_E_BADARG;
-}
-template <typename real>
-static int entry_scatter_input_noise(const wiski_grid* g, const real* x, const real* y, const real* xvar, const real* gvar, const real* pvar, double sigma2, const real* wa, const real* wb, const real* noise, int64_t n, real* b, real* A_half, real* cnt, const real* u, real* res, real* mean_out, double* stats, int32_t* err, real* omega_out, double* logz_out, real* grad_out, void* s) {
-  AbsorbArgs<real> a = absorb_args(x, y, wa, wb, noise, n, b, A_half, true, stats, err);
-  absorb_carry(a, cnt, u, res, mean_out);
-  return entry_input_noise(g, a, xvar, gvar, pvar, sigma2, omega_out, logz_out, grad_out, s);
-}
-template <typename real>
-static int entry_absorb_input_noise(const wiski_grid* g, const wiski_absorb_args* p, const real* xvar, const real* gvar, const real* pvar, double sigma2, real* omega_out, double* logz_out, real* grad_out, void* s) {
-  return p ? entry_input_noise(g, absorb_args<real>(*p), xvar, gvar, pvar, sigma2, omega_out, logz_out, grad_out, s) : WISKI_E_BADARG;
-}
-template <typename real>
-static int entry_grad_interval(const wiski_grid* g, AbsorbArgs<real> a, const real* lo, const real* hi, const real* pvar, double sigma2, real* ytilde_out, real* omega_out, double* logz_out, void* s) {
-  a.y = nullptr;                                       // ignored by the form
-  a.clo = lo; a.chi = hi; a.cpvar = pvar; a.sigma2 = sigma2; a.ytilde_out = ytilde_out; a.omega_out = omega_out; a.logz_out = logz_out;
-  return lo ? absorb(g, a, s) : WISKI_E_BADARG;
-}
-template <typename real>
-static int entry_scatter_grad_interval(const wiski_grid* g, const real* x, const real* lo, const real* hi, const real* pvar, double sigma2, const real* wa, const real* wb, const real* noise, int64_t n, real* b, real* A_half, real* cnt, const real* u, real* res, real* mean_out, double* stats, int32_t* err, real* ytilde_out, real* omega_out, double* logz_out, void* s) {
-  AbsorbArgs<real> a = absorb_args(x, (const real*)nullptr, wa, wb, noise, n, b, A_half, true, stats, err);
-  absorb_carry(a, cnt, u, res, mean_out);
-  a.channels = g ? g->d + 1 : 0;
-  return entry_grad_interval(g, a, lo, hi, pvar, sigma2, ytilde_out, omega_out, logz_out, s);
-}
-template <typename real>
-static int entry_absorb_grad_interval(const wiski_grid* g, const wiski_absorb_args* p, const real* lo, const real* hi, const real* pvar, double sigma2, real* ytilde_out, real* omega_out, double* logz_out, void* s) {
-  return p ? entry_grad_interval(g, absorb_args<real>(*p), lo, hi, pvar, sigma2, ytilde_out, omega_out, logz_out, s) : WISKI_E_BADARG;
+  return absorb(g, a, s);
 }
 // the revisit: the record's points are replaced by the ring's slots (its d_x / d_y / d_wa / d_wb / d_noise / n are not looked at)
 template <typename real>
-static int entry_revisit(const wiski_grid* g, AbsorbArgs<real> a, const wiski_site_ring* r, int form, const real* pvar, double sigma2, double damping, double* logz_out, real* change_out, void* s) {
-  if (!r || r->cap < 0) return WISKI_E_BADARG;
+static int entry_revisit(const wiski_grid* g, const wiski_absorb_args* p, const wiski_site_ring* r, int form, const real* pvar, double sigma2, double damping, double* logz_out, real* change_out, void* s) {
+  if (!p || !r || r->cap < 0 || (r->cap != 0 && !r->d_form)) return WISKI_E_BADARG;
+  AbsorbArgs<real> a = absorb_args<real>(*p);
   a.x = (const real*)r->d_x; a.y = nullptr; a.wa = (const real*)r->d_wa; a.wb = (const real*)r->d_wb; a.noise = (const real*)r->d_noise; a.n = r->cap;
   a.site_d0 = (const real*)r->d_d0; a.site_d1 = (const real*)r->d_d1; a.site_ytilde = (real*)r->d_ytilde; a.site_omega = (real*)r->d_omega;
   a.site_codes = r->d_form; a.site_form_code = form; a.site_damping = damping; a.site_change_out = change_out;
   a.pvar = pvar; a.sigma2 = sigma2; a.logz_out = logz_out;
-  return a.n == 0 || a.site_codes ? absorb(g, a, s) : WISKI_E_BADARG;   // (without the form codes the record would be another form's)
-}
-template <typename real>
-static int entry_revisit_sites(const wiski_grid* g, const wiski_site_ring* r, int form, const real* pvar, double sigma2, double damping, real* b, real* A_half, real* cnt, const real* u, real* res, double* stats, int32_t* err, double* logz_out, real* change_out, void* s) {
-  AbsorbArgs<real> a = absorb_args((const real*)nullptr, (const real*)nullptr, (const real*)nullptr, (const real*)nullptr, (const real*)nullptr, 0, b, A_half, true, stats, err);
-  absorb_carry(a, cnt, u, res);
-  return entry_revisit(g, a, r, form, pvar, sigma2, damping, logz_out, change_out, s);
-}
-template <typename real>
-static int entry_absorb_revisit(const wiski_grid* g, const wiski_absorb_args* p, const wiski_site_ring* r, int form, const real* pvar, double sigma2, double damping, double* logz_out, real* change_out, void* s) {
-  return p ? entry_revisit(g, absorb_args<real>(*p), r, form, pvar, sigma2, damping, logz_out, change_out, s) : WISKI_E_BADARG;
+  return absorb(g, a, s);
 }
 template <typename real>
 static int entry_plain(const wiski_grid* g, const real* x, const real* y, const real* wa, const real* wb, const real* noise, int64_t n, real* b, real* A, bool half, double* stats, int32_t* err, void* s) {
@@ -666,52 +587,32 @@ int wiski_absorb_staged_f32(const wiski_grid* g, const wiski_absorb_args* p, flo
   a.tap_stage = d_tap_stage;
   return absorb(g, a, s);
 }
-int wiski_scatter_stats_grad_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, void* s) { return entry_grad(g, x, y, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, s); }
-int wiski_scatter_stats_grad_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, void* s) { return entry_grad(g, x, y, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, s); }
-int wiski_scatter_stats_robust_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, const float* inv_scale, float huber_c, float* omega_out, void* s) { return entry_scatter_robust(g, x, y, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, inv_scale, huber_c, omega_out, s); }
-int wiski_scatter_stats_robust_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, const double* inv_scale, double huber_c, double* omega_out, void* s) { return entry_scatter_robust(g, x, y, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, inv_scale, huber_c, omega_out, s); }
-int wiski_absorb_robust_f32(const wiski_grid* g, const wiski_absorb_args* p, const float* inv_scale, float huber_c, float* omega_out, void* s) { return entry_absorb_robust(g, p, inv_scale, huber_c, omega_out, s); }
-int wiski_absorb_robust_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* inv_scale, double huber_c, double* omega_out, void* s) { return entry_absorb_robust(g, p, inv_scale, huber_c, omega_out, s); }
-int wiski_scatter_stats_window_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, const wiski_window_ring* ring, float* b, float* A_half, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, int32_t* void_left, void* s) { return entry_scatter_window(g, x, y, wa, wb, noise, n, ring, b, A_half, cnt, u, res, mean_out, stats, err, void_left, s); }
-int wiski_scatter_stats_window_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, const wiski_window_ring* ring, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, int32_t* void_left, void* s) { return entry_scatter_window(g, x, y, wa, wb, noise, n, ring, b, A_half, cnt, u, res, mean_out, stats, err, void_left, s); }
-int wiski_absorb_window_f32(const wiski_grid* g, const wiski_absorb_args* p, const wiski_window_ring* ring, int32_t* void_left, void* s) { return entry_absorb_window<float>(g, p, ring, void_left, s); }
-int wiski_absorb_window_f64(const wiski_grid* g, const wiski_absorb_args* p, const wiski_window_ring* ring, int32_t* void_left, void* s) { return entry_absorb_window<double>(g, p, ring, void_left, s); }
-int wiski_scatter_stats_interval_f32(const wiski_grid* g, const float* x, const float* lo, const float* hi, const float* pvar, double sigma2, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return entry_scatter_interval(g, x, lo, hi, pvar, sigma2, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, ytilde_out, omega_out, logz_out, s); }
-int wiski_scatter_stats_interval_f64(const wiski_grid* g, const double* x, const double* lo, const double* hi, const double* pvar, double sigma2, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return entry_scatter_interval(g, x, lo, hi, pvar, sigma2, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, ytilde_out, omega_out, logz_out, s); }
-int wiski_absorb_interval_f32(const wiski_grid* g, const wiski_absorb_args* p, const float* lo, const float* hi, const float* pvar, double sigma2, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return entry_absorb_interval(g, p, lo, hi, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
-int wiski_absorb_interval_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* lo, const double* hi, const double* pvar, double sigma2, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return entry_absorb_interval(g, p, lo, hi, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
-int wiski_scatter_stats_count_f32(const wiski_grid* g, const float* x, const float* y, const float* t, int family, const float* pvar, double sigma2, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return entry_scatter_count(g, x, y, t, family, pvar, sigma2, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, ytilde_out, omega_out, logz_out, s); }
-int wiski_scatter_stats_count_f64(const wiski_grid* g, const double* x, const double* y, const double* t, int family, const double* pvar, double sigma2, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return entry_scatter_count(g, x, y, t, family, pvar, sigma2, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, ytilde_out, omega_out, logz_out, s); }
-int wiski_absorb_count_f32(const wiski_grid* g, const wiski_absorb_args* p, const float* y, const float* t, int family, const float* pvar, double sigma2, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return entry_absorb_count(g, p, y, t, family, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
-int wiski_absorb_count_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* y, const double* t, int family, const double* pvar, double sigma2, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return entry_absorb_count(g, p, y, t, family, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
+int wiski_absorb_robust_f32(const wiski_grid* g, const wiski_absorb_args* p, const float* inv_scale, float huber_c, float* omega_out, void* s) { return entry_robust(g, p, inv_scale, huber_c, omega_out, s); }
+int wiski_absorb_robust_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* inv_scale, double huber_c, double* omega_out, void* s) { return entry_robust(g, p, inv_scale, huber_c, omega_out, s); }
+int wiski_absorb_window_f32(const wiski_grid* g, const wiski_absorb_args* p, const wiski_window_ring* ring, int32_t* void_left, void* s) { return entry_window<float>(g, p, ring, void_left, s); }
+int wiski_absorb_window_f64(const wiski_grid* g, const wiski_absorb_args* p, const wiski_window_ring* ring, int32_t* void_left, void* s) { return entry_window<double>(g, p, ring, void_left, s); }
+int wiski_absorb_interval_f32(const wiski_grid* g, const wiski_absorb_args* p, const float* lo, const float* hi, const float* pvar, double sigma2, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return entry_interval(g, p, lo, hi, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
+int wiski_absorb_interval_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* lo, const double* hi, const double* pvar, double sigma2, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return entry_interval(g, p, lo, hi, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
+int wiski_absorb_count_f32(const wiski_grid* g, const wiski_absorb_args* p, const float* y, const float* t, int family, const float* pvar, double sigma2, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return entry_count(g, p, y, t, family, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
+int wiski_absorb_count_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* y, const double* t, int family, const double* pvar, double sigma2, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return entry_count(g, p, y, t, family, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
 int wiski_count_sites_f32(const float* mu, const float* pvar, const float* y, const float* t, int family, int64_t n, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return count_sites_impl(mu, pvar, y, t, family, n, ytilde_out, omega_out, logz_out, s); }
 int wiski_count_sites_f64(const double* mu, const double* pvar, const double* y, const double* t, int family, int64_t n, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return count_sites_impl(mu, pvar, y, t, family, n, ytilde_out, omega_out, logz_out, s); }
-int wiski_scatter_stats_hetero_f32(const wiski_grid* g, const float* x, const float* y, const float* pvar, const float* pvar2, double sigma2, double g0, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, float* cnt, const float* u, float* res, float* mean_out, double* stats, float* b2, float* A2_half, float* cnt2, const float* u2, float* res2, double* stats2, int32_t* err, float* e_out, float* ytilde_out, float* omega_out, double* logz_out, double* logzy_out, void* s) { return entry_scatter_hetero(g, x, y, pvar, pvar2, sigma2, g0, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, b2, A2_half, cnt2, u2, res2, stats2, err, e_out, ytilde_out, omega_out, logz_out, logzy_out, s); }
-int wiski_scatter_stats_hetero_f64(const wiski_grid* g, const double* x, const double* y, const double* pvar, const double* pvar2, double sigma2, double g0, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, double* b2, double* A2_half, double* cnt2, const double* u2, double* res2, double* stats2, int32_t* err, double* e_out, double* ytilde_out, double* omega_out, double* logz_out, double* logzy_out, void* s) { return entry_scatter_hetero(g, x, y, pvar, pvar2, sigma2, g0, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, b2, A2_half, cnt2, u2, res2, stats2, err, e_out, ytilde_out, omega_out, logz_out, logzy_out, s); }
-int wiski_absorb_hetero_f32(const wiski_grid* g, const wiski_absorb_args* p, const float* pvar, const float* pvar2, double sigma2, double g0, float* b2, float* A2_half, float* cnt2, const float* u2, float* res2, double* stats2, float* e_out, float* ytilde_out, float* omega_out, double* logz_out, double* logzy_out, void* s) { return entry_absorb_hetero(g, p, pvar, pvar2, sigma2, g0, b2, A2_half, cnt2, u2, res2, stats2, e_out, ytilde_out, omega_out, logz_out, logzy_out, s); }
-int wiski_absorb_hetero_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* pvar, const double* pvar2, double sigma2, double g0, double* b2, double* A2_half, double* cnt2, const double* u2, double* res2, double* stats2, double* e_out, double* ytilde_out, double* omega_out, double* logz_out, double* logzy_out, void* s) { return entry_absorb_hetero(g, p, pvar, pvar2, sigma2, g0, b2, A2_half, cnt2, u2, res2, stats2, e_out, ytilde_out, omega_out, logz_out, logzy_out, s); }
+int wiski_absorb_hetero_f32(const wiski_grid* g, const wiski_absorb_args* p, const float* pvar, const float* pvar2, double sigma2, double g0, float* b2, float* A2_half, float* cnt2, const float* u2, float* res2, double* stats2, float* e_out, float* ytilde_out, float* omega_out, double* logz_out, double* logzy_out, void* s) { return entry_hetero(g, p, pvar, pvar2, sigma2, g0, b2, A2_half, cnt2, u2, res2, stats2, e_out, ytilde_out, omega_out, logz_out, logzy_out, s); }
+int wiski_absorb_hetero_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* pvar, const double* pvar2, double sigma2, double g0, double* b2, double* A2_half, double* cnt2, const double* u2, double* res2, double* stats2, double* e_out, double* ytilde_out, double* omega_out, double* logz_out, double* logzy_out, void* s) { return entry_hetero(g, p, pvar, pvar2, sigma2, g0, b2, A2_half, cnt2, u2, res2, stats2, e_out, ytilde_out, omega_out, logz_out, logzy_out, s); }
 int wiski_hetero_sites_f32(const float* mu, const float* pvar, const float* rho, const float* nu, int64_t n, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return count_sites_impl<float, WISKI_COUNT_LOGVAR>(mu, pvar, rho, nu, WISKI_COUNT_LOGVAR, n, ytilde_out, omega_out, logz_out, s); }
 int wiski_hetero_sites_f64(const double* mu, const double* pvar, const double* rho, const double* nu, int64_t n, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return count_sites_impl<double, WISKI_COUNT_LOGVAR>(mu, pvar, rho, nu, WISKI_COUNT_LOGVAR, n, ytilde_out, omega_out, logz_out, s); }
-int wiski_scatter_stats_label_f32(const wiski_grid* g, const float* x, const float* labels, const float* pvar, const double* sigma2, const float* wa, const float* wb, const float* noise, int64_t n, int32_t nout, int64_t w_stride, float* b, float* A_half, int64_t A_stride, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return entry_scatter_label(g, x, labels, pvar, sigma2, wa, wb, noise, n, nout, w_stride, b, A_half, A_stride, cnt, u, res, mean_out, stats, err, ytilde_out, omega_out, logz_out, s); }
-int wiski_scatter_stats_label_f64(const wiski_grid* g, const double* x, const double* labels, const double* pvar, const double* sigma2, const double* wa, const double* wb, const double* noise, int64_t n, int32_t nout, int64_t w_stride, double* b, double* A_half, int64_t A_stride, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return entry_scatter_label(g, x, labels, pvar, sigma2, wa, wb, noise, n, nout, w_stride, b, A_half, A_stride, cnt, u, res, mean_out, stats, err, ytilde_out, omega_out, logz_out, s); }
-int wiski_absorb_label_f32(const wiski_grid* g, const wiski_absorb_args* p, const float* labels, const float* pvar, const double* sigma2, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return entry_absorb_label(g, p, labels, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
-int wiski_absorb_label_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* labels, const double* pvar, const double* sigma2, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return entry_absorb_label(g, p, labels, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
+int wiski_absorb_label_f32(const wiski_grid* g, const wiski_absorb_args* p, const float* labels, const float* pvar, const double* sigma2, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return entry_label(g, p, labels, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
+int wiski_absorb_label_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* labels, const double* pvar, const double* sigma2, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return entry_label(g, p, labels, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
 int wiski_label_sites_f32(const float* mu, const float* pvar, const float* s_var, const float* labels, int32_t nout, int64_t n, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return label_sites_impl(mu, pvar, s_var, labels, nout, n, ytilde_out, omega_out, logz_out, s); }
 int wiski_label_sites_f64(const double* mu, const double* pvar, const double* s_var, const double* labels, int32_t nout, int64_t n, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return label_sites_impl(mu, pvar, s_var, labels, nout, n, ytilde_out, omega_out, logz_out, s); }
 int wiski_label_proba_f32(const float* mu, const float* pvar, const float* s_var, int32_t nout, int64_t n, double* proba_out, void* s) { return label_proba_impl(mu, pvar, s_var, nout, n, proba_out, s); }
 int wiski_label_proba_f64(const double* mu, const double* pvar, const double* s_var, int32_t nout, int64_t n, double* proba_out, void* s) { return label_proba_impl(mu, pvar, s_var, nout, n, proba_out, s); }
-int wiski_scatter_stats_input_noise_f32(const wiski_grid* g, const float* x, const float* y, const float* xvar, const float* gvar, const float* pvar, double sigma2, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, float* omega_out, double* logz_out, float* grad_out, void* s) { return entry_scatter_input_noise(g, x, y, xvar, gvar, pvar, sigma2, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, omega_out, logz_out, grad_out, s); }
-int wiski_scatter_stats_input_noise_f64(const wiski_grid* g, const double* x, const double* y, const double* xvar, const double* gvar, const double* pvar, double sigma2, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, double* omega_out, double* logz_out, double* grad_out, void* s) { return entry_scatter_input_noise(g, x, y, xvar, gvar, pvar, sigma2, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, omega_out, logz_out, grad_out, s); }
-int wiski_absorb_input_noise_f32(const wiski_grid* g, const wiski_absorb_args* p, const float* xvar, const float* gvar, const float* pvar, double sigma2, float* omega_out, double* logz_out, float* grad_out, void* s) { return entry_absorb_input_noise(g, p, xvar, gvar, pvar, sigma2, omega_out, logz_out, grad_out, s); }
-int wiski_absorb_input_noise_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* xvar, const double* gvar, const double* pvar, double sigma2, double* omega_out, double* logz_out, double* grad_out, void* s) { return entry_absorb_input_noise(g, p, xvar, gvar, pvar, sigma2, omega_out, logz_out, grad_out, s); }
-int wiski_scatter_stats_grad_interval_f32(const wiski_grid* g, const float* x, const float* lo, const float* hi, const float* pvar, double sigma2, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, float* cnt, const float* u, float* res, float* mean_out, double* stats, int32_t* err, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return entry_scatter_grad_interval(g, x, lo, hi, pvar, sigma2, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, ytilde_out, omega_out, logz_out, s); }
-int wiski_scatter_stats_grad_interval_f64(const wiski_grid* g, const double* x, const double* lo, const double* hi, const double* pvar, double sigma2, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A_half, double* cnt, const double* u, double* res, double* mean_out, double* stats, int32_t* err, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return entry_scatter_grad_interval(g, x, lo, hi, pvar, sigma2, wa, wb, noise, n, b, A_half, cnt, u, res, mean_out, stats, err, ytilde_out, omega_out, logz_out, s); }
-int wiski_absorb_grad_interval_f32(const wiski_grid* g, const wiski_absorb_args* p, const float* lo, const float* hi, const float* pvar, double sigma2, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return entry_absorb_grad_interval(g, p, lo, hi, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
-int wiski_absorb_grad_interval_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* lo, const double* hi, const double* pvar, double sigma2, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return entry_absorb_grad_interval(g, p, lo, hi, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
-int wiski_revisit_sites_f32(const wiski_grid* g, const wiski_site_ring* ring, int form, const float* pvar, double sigma2, double damping, float* b, float* A_half, float* cnt, const float* u, float* res, double* stats, int32_t* err, double* logz_out, float* change_out, void* s) { return entry_revisit_sites(g, ring, form, pvar, sigma2, damping, b, A_half, cnt, u, res, stats, err, logz_out, change_out, s); }
-int wiski_revisit_sites_f64(const wiski_grid* g, const wiski_site_ring* ring, int form, const double* pvar, double sigma2, double damping, double* b, double* A_half, double* cnt, const double* u, double* res, double* stats, int32_t* err, double* logz_out, double* change_out, void* s) { return entry_revisit_sites(g, ring, form, pvar, sigma2, damping, b, A_half, cnt, u, res, stats, err, logz_out, change_out, s); }
-int wiski_absorb_revisit_f32(const wiski_grid* g, const wiski_absorb_args* p, const wiski_site_ring* ring, int form, const float* pvar, double sigma2, double damping, double* logz_out, float* change_out, void* s) { return entry_absorb_revisit(g, p, ring, form, pvar, sigma2, damping, logz_out, change_out, s); }
-int wiski_absorb_revisit_f64(const wiski_grid* g, const wiski_absorb_args* p, const wiski_site_ring* ring, int form, const double* pvar, double sigma2, double damping, double* logz_out, double* change_out, void* s) { return entry_absorb_revisit(g, p, ring, form, pvar, sigma2, damping, logz_out, change_out, s); }
+int wiski_absorb_input_noise_f32(const wiski_grid* g, const wiski_absorb_args* p, const float* xvar, const float* gvar, const float* pvar, double sigma2, float* omega_out, double* logz_out, float* grad_out, void* s) { return entry_input_noise(g, p, xvar, gvar, pvar, sigma2, omega_out, logz_out, grad_out, s); }
+int wiski_absorb_input_noise_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* xvar, const double* gvar, const double* pvar, double sigma2, double* omega_out, double* logz_out, double* grad_out, void* s) { return entry_input_noise(g, p, xvar, gvar, pvar, sigma2, omega_out, logz_out, grad_out, s); }
+int wiski_absorb_grad_interval_f32(const wiski_grid* g, const wiski_absorb_args* p, const float* lo, const float* hi, const float* pvar, double sigma2, float* ytilde_out, float* omega_out, double* logz_out, void* s) { return entry_grad_interval(g, p, lo, hi, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
+int wiski_absorb_grad_interval_f64(const wiski_grid* g, const wiski_absorb_args* p, const double* lo, const double* hi, const double* pvar, double sigma2, double* ytilde_out, double* omega_out, double* logz_out, void* s) { return entry_grad_interval(g, p, lo, hi, pvar, sigma2, ytilde_out, omega_out, logz_out, s); }
+int wiski_absorb_revisit_f32(const wiski_grid* g, const wiski_absorb_args* p, const wiski_site_ring* ring, int form, const float* pvar, double sigma2, double damping, double* logz_out, float* change_out, void* s) { return entry_revisit(g, p, ring, form, pvar, sigma2, damping, logz_out, change_out, s); }
+int wiski_absorb_revisit_f64(const wiski_grid* g, const wiski_absorb_args* p, const wiski_site_ring* ring, int form, const double* pvar, double sigma2, double damping, double* logz_out, double* change_out, void* s) { return entry_revisit(g, p, ring, form, pvar, sigma2, damping, logz_out, change_out, s); }
 int wiski_scatter_stats_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A, double* stats, int32_t* err, void* s) { return entry_plain(g, x, y, wa, wb, noise, n, b, A, false, stats, err, s); }
 int wiski_scatter_stats_f64(const wiski_grid* g, const double* x, const double* y, const double* wa, const double* wb, const double* noise, int64_t n, double* b, double* A, double* stats, int32_t* err, void* s) { return entry_plain(g, x, y, wa, wb, noise, n, b, A, false, stats, err, s); }
 int wiski_scatter_stats_sym_f32(const wiski_grid* g, const float* x, const float* y, const float* wa, const float* wb, const float* noise, int64_t n, float* b, float* A_half, double* stats, int32_t* err, void* s) { return entry_plain(g, x, y, wa, wb, noise, n, b, A_half, true, stats, err, s); }

@@ -5,7 +5,7 @@
 
 #include "../../include/wiski.h"
 
-#define WISKI_VERSION 1
+#define WISKI_VERSION 2
 
 // Grid geometry as a by-value kernel argument (lives in SGPRs / kernarg).
 template <typename real>

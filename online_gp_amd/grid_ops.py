@@ -418,80 +418,94 @@ def scatter_stats_multi(grid, x, Yt, wa, wb, noise, b, A_pack, cnt, stats, err, 
     _hip.check(rc, "wiski_scatter_stats_multi")
 
 
-def scatter_stats_grad(grid, x, Y, wa, wb, noise, b, A_half, cnt, stats, err, u=None, res=None, mean_out=None):
-    """Values and gradients in ONE absorb launch (``wiski_scatter_stats_grad``): Y / wa / wb / noise (and mean_out)
-    are [n, d + 1] -- column 0 the observation of f, column 1 + q that of df/dx_q; an absent one has wa = wb = 0, noise = 1.
-    (b, A_half, cnt, stats) accumulate in place; with u given, mean_out receives the predictive mean and gradient of every point
-    before the update and res the carried residual's increment."""
-    x = _x2d(x, grid)
-    n, C = x.shape[0], grid.d + 1
-    for name, t in (("Y", Y), ("wa", wa), ("wb", wb), ("noise", noise), ("mean_out", mean_out)):
-        if t is not None and (tuple(t.shape) != (n, C) or t.dtype != x.dtype):
-            raise ValueError(f"scatter_stats_grad: {name} must be [{n}, {C}] {x.dtype}, got {tuple(t.shape)} {t.dtype}")
-    rc = _hip.fn("wiski_scatter_stats_grad", x.dtype)(grid.ref, _hip.dptr(x), _hip.dptr(Y.contiguous()), _hip.dptr(wa.contiguous()),
-                                                      _hip.dptr(wb.contiguous()), _hip.dptr(noise.contiguous()), ctypes.c_int64(n), _hip.dptr(b),
-                                                      _hip.dptr(A_half), _hip.dptr(cnt), _hip.dptr(u), _hip.dptr(res), _hip.dptr(mean_out),
-                                                      _hip.dptr(stats), _hip.dptr(err), _hip.stream_ptr(x.device))
-    _hip.check(rc, "wiski_scatter_stats_grad")
-
-
-def _absorb_points(op, grid, x, u, per_point, u_is="the grid mean", sites=False):
-    """What the absorbs taken against ``u`` check alike: x as [n, d], every given ``per_point`` tensor [n] in x's dtype, u [m].
-    Returns (x, n) and, with ``sites``, the outputs of a moment-matched form as well: (ytilde [n], omega [n], log_z [n] float64)."""
+def _absorb_points(op, grid, x, u, groups, u_is="the grid mean"):
+    """What the forms of the absorb check alike: x as [n, d]; every tensor of ``groups`` -- (shape, {name: tensor}, optional)
+    triples, a shape spelling the number of points as "n" -- of its shape in x's dtype; u [m] (``u_is`` None: the form checks its
+    own).  ``optional`` None: an absent tensor is not looked at; else the names that may be absent.  Returns (x, n)."""
     x = _x2d(x, grid)
     n = x.shape[0]
-    for name, t in per_point.items():
-        if t is not None and (tuple(t.shape) != (n,) or t.dtype != x.dtype):
-            raise ValueError(f"{op}: {name} must be [{n}] {x.dtype}, got {tuple(t.shape)} {t.dtype}")
-    if u is None or tuple(u.shape) != (grid.m,) or u.dtype != x.dtype:
+    for shape, tensors, optional in groups:
+        shape = tuple(n if k == "n" else k for k in shape)
+        for name, t in tensors.items():
+            if t is None and (optional is None or name in optional):
+                continue
+            if t is not None and tuple(t.shape) == shape and t.dtype == x.dtype:
+                continue
+            got = f"{tuple(t.shape)} {t.dtype}" if optional is None else None if t is None else (tuple(t.shape), t.dtype)
+            raise ValueError(f"{op}: {name} must be {list(shape)} {x.dtype}, got {got}")
+    if u_is is not None and (u is None or tuple(u.shape) != (grid.m,) or u.dtype != x.dtype):
         raise ValueError(f"{op}: u must be {u_is} [{grid.m}] {x.dtype}")
-    if not sites:
-        return x, n
-    return x, n, (torch.empty(n, dtype=x.dtype, device=x.device), torch.empty(n, dtype=x.dtype, device=x.device),
-                  torch.empty(n, dtype=torch.float64, device=x.device))
+    return x, n
+
+
+def _site_outputs(x, shape, logz_shape=None):
+    """The outputs of a moment-matched form: (ytilde, omega) of ``shape`` in x's dtype, log_z float64 (of ``logz_shape``, if it differs)."""
+    return (torch.empty(shape, dtype=x.dtype, device=x.device), torch.empty(shape, dtype=x.dtype, device=x.device),
+            torch.empty(shape if logz_shape is None else logz_shape, dtype=torch.float64, device=x.device))
+
+
+def _absorb_record(x, points, targets, carry, nout=1, w_stride=0, A_stride=0, channels=0):
+    """The argument record (``wiski_absorb_args``) of one form call on the symmetric half stencil, from tensors: ``x`` [n, d] as
+    _absorb_points returned it (None: the form brings its own points, n = 0); ``points`` = (y, wa, wb, noise), made contiguous here,
+    None where the form ignores one; ``targets`` = (b, A_half, cnt, stats, err), accumulated in place, and ``carry`` = (u, res,
+    mean_out), both taken as they are.  What the record has besides (guard, zero regions, shard, owner workspace) stays zero."""
+    y, wa, wb, noise = (None if t is None else _hip.dptr(t.contiguous()) for t in points)
+    b, A_half, cnt, stats, err = (_hip.dptr(t) for t in targets)
+    u, res, mean_out = (_hip.dptr(t) for t in carry)
+    return _hip.wiski_absorb_args(d_x=_hip.dptr(x), d_y=y, d_wa=wa, d_wb=wb, d_noise=noise, n=0 if x is None else x.shape[0], d_b=b, d_A=A_half, half=1,
+                                  channels=channels, d_cnt=cnt, d_stats=stats, d_err=err, d_u=u, d_res=res, d_mean_out=mean_out, nout=nout,
+                                  w_stride=w_stride, A_stride=A_stride)
+
+
+def _absorb_call(entry, grid, dtype, device, rec, *own):
+    """Run the record through ``entry`` (a ``wiski_absorb*`` name) with the form's own arguments, on the current stream of ``device``."""
+    _hip.check(_hip.fn(entry, dtype)(grid.ref, ctypes.byref(rec), *own, _hip.stream_ptr(device)), entry)
+
+
+def scatter_stats_grad(grid, x, Y, wa, wb, noise, b, A_half, cnt, stats, err, u=None, res=None, mean_out=None):
+    """Values and gradients in ONE absorb launch (``wiski_absorb`` with channels = d + 1): Y / wa / wb / noise (and
+    mean_out) are [n, d + 1] -- column 0 the observation of f, column 1 + q that of df/dx_q; an absent one has wa = wb = 0, noise = 1.
+    (b, A_half, cnt, stats) accumulate in place; with u given, mean_out receives the predictive mean and gradient of every point
+    before the update and res the carried residual's increment."""
+    C = grid.d + 1
+    x, n = _absorb_points("scatter_stats_grad", grid, x, u, [(("n", C), dict(Y=Y, wa=wa, wb=wb, noise=noise, mean_out=mean_out), None)], u_is=None)
+    _absorb_call("wiski_absorb", grid, x.dtype, x.device, _absorb_record(x, (Y, wa, wb, noise), (b, A_half, cnt, stats, err), (u, res, mean_out), channels=C))
 
 
 def scatter_stats_robust(grid, x, y, wa, wb, noise, inv_scale, c, b, A_half, cnt, stats, err, u, res=None, mean_out=None):
-    """The outlier-robust absorb in ONE launch (``wiski_scatter_stats_robust``): every point is Huber-weighted
+    """The outlier-robust absorb in ONE launch (``wiski_absorb_robust``): every point is Huber-weighted
     against the posterior mean ``u`` [m] before the batch, z = (y - w . u) inv_scale, omega = min(1, c / |z|), and enters
     (b, A_half, cnt, stats) -- and the carried residual ``res``, if given -- as the same point at noise / omega.  ``inv_scale``
     [n] (0 exempts a point).  Returns omega [n] (0 for a point outside the grid); ``mean_out`` [n] receives w . u."""
-    x, n = _absorb_points("scatter_stats_robust", grid, x, u, dict(y=y, wa=wa, wb=wb, noise=noise, inv_scale=inv_scale, mean_out=mean_out))
+    x, n = _absorb_points("scatter_stats_robust", grid, x, u, [(("n",), dict(y=y, wa=wa, wb=wb, noise=noise, inv_scale=inv_scale, mean_out=mean_out), None)])
     omega = torch.empty(n, dtype=x.dtype, device=x.device)
     if n == 0:
         return omega
-    rc = _hip.fn("wiski_scatter_stats_robust", x.dtype)(grid.ref, _hip.dptr(x), _hip.dptr(y.contiguous()), _hip.dptr(wa.contiguous()),
-                                                        _hip.dptr(wb.contiguous()), _hip.dptr(noise.contiguous()), ctypes.c_int64(n), _hip.dptr(b),
-                                                        _hip.dptr(A_half), _hip.dptr(cnt), _hip.dptr(u), _hip.dptr(res), _hip.dptr(mean_out),
-                                                        _hip.dptr(stats), _hip.dptr(err), _hip.dptr(inv_scale.contiguous()),
-                                                        _hip.creal(x.dtype)(float(c)), _hip.dptr(omega), _hip.stream_ptr(x.device))
-    _hip.check(rc, "wiski_scatter_stats_robust")
+    _absorb_call("wiski_absorb_robust", grid, x.dtype, x.device, _absorb_record(x, (y, wa, wb, noise), (b, A_half, cnt, stats, err), (u, res, mean_out)),
+                 _hip.dptr(inv_scale.contiguous()), float(c), _hip.dptr(omega))
     return omega
 
 
 def scatter_stats_interval(grid, x, lower, upper, pvar, sigma2, wa, wb, noise, b, A_half, cnt, stats, err, u, res=None, mean_out=None):
-    """The interval-observation absorb in ONE launch (``wiski_scatter_stats_interval``): point i says
+    """The interval-observation absorb in ONE launch (``wiski_absorb_interval``): point i says
     lower_i <= f(x_i) + eps_i <= upper_i (either end may be infinite; equal ends are an exact value).  It is moment-matched against
     the posterior before the batch -- the grid mean ``u`` [m], the posterior variance ``pvar`` [n] of f at x, the noise
     ``sigma2 * noise`` -- and enters (b, A_half, cnt, stats) -- and the carried residual ``res``, if given -- as the target ytilde_i
     at noise_i / omega_i.  Returns (ytilde [n], omega [n], log_z [n] float64); a skipped point (nothing to say: omega below 1e-12,
     lower > upper, a NaN bound) has omega = 0 and ytilde = w . u, a point outside the grid (0, 0, 0).  ``mean_out`` [n] receives w . u."""
-    x, n, (ytilde, omega, log_z) = _absorb_points("scatter_stats_interval", grid, x, u, sites=True,
-                                                  per_point=dict(lower=lower, upper=upper, pvar=pvar, wa=wa, wb=wb, noise=noise, mean_out=mean_out))
+    x, n = _absorb_points("scatter_stats_interval", grid, x, u,
+                          [(("n",), dict(lower=lower, upper=upper, pvar=pvar, wa=wa, wb=wb, noise=noise, mean_out=mean_out), None)])
+    ytilde, omega, log_z = _site_outputs(x, (n,))
     if n == 0:
         return ytilde, omega, log_z
-    rc = _hip.fn("wiski_scatter_stats_interval", x.dtype)(grid.ref, _hip.dptr(x), _hip.dptr(lower.contiguous()), _hip.dptr(upper.contiguous()),
-                                                          _hip.dptr(pvar.contiguous()), ctypes.c_double(float(sigma2)), _hip.dptr(wa.contiguous()),
-                                                          _hip.dptr(wb.contiguous()), _hip.dptr(noise.contiguous()), ctypes.c_int64(n), _hip.dptr(b),
-                                                          _hip.dptr(A_half), _hip.dptr(cnt), _hip.dptr(u), _hip.dptr(res), _hip.dptr(mean_out),
-                                                          _hip.dptr(stats), _hip.dptr(err), _hip.dptr(ytilde), _hip.dptr(omega), _hip.dptr(log_z),
-                                                          _hip.stream_ptr(x.device))
-    _hip.check(rc, "wiski_scatter_stats_interval")
+    _absorb_call("wiski_absorb_interval", grid, x.dtype, x.device, _absorb_record(x, (None, wa, wb, noise), (b, A_half, cnt, stats, err), (u, res, mean_out)),
+                 _hip.dptr(lower.contiguous()), _hip.dptr(upper.contiguous()), _hip.dptr(pvar.contiguous()), float(sigma2), _hip.dptr(ytilde),
+                 _hip.dptr(omega), _hip.dptr(log_z))
     return ytilde, omega, log_z
 
 
 def scatter_stats_grad_interval(grid, x, lower, upper, pvar, sigma2, wa, wb, noise, b, A_half, cnt, stats, err, u, res=None, mean_out=None):
-    """Interval sites on values AND partial derivatives in ONE absorb launch (``wiski_scatter_stats_grad_interval``).
+    """Interval sites on values AND partial derivatives in ONE absorb launch (``wiski_absorb_grad_interval``).
     lower / upper / pvar / wa / wb / noise (and mean_out) are [n, d + 1] -- column 0 the channel of f, column 1 + q that of df/dx_q;
     an absent channel has wa = wb = 0, noise = 1.  Every present channel says lower <= (its row . f) + eps <= upper (either end may be
     infinite; equal ends are an exact value) and is moment-matched, independently of the point's other channels, against the
@@ -499,25 +513,16 @@ def scatter_stats_grad_interval(grid, x, lower, upper, pvar, sigma2, wa, wb, noi
     noise`` -- and enters (b, A_half, cnt, stats) -- and the carried residual ``res``, if given -- as the target ytilde at noise /
     omega.  Returns (ytilde, omega, log_z float64), [n, d + 1] each: a skipped channel has omega = 0 and ytilde = its predictive mean,
     an absent channel and every channel of a point outside the grid (0, 0, 0).  ``mean_out`` receives the predictive mean and gradient."""
-    op = "scatter_stats_grad_interval"
-    x = _x2d(x, grid)
-    n, C = x.shape[0], grid.d + 1
-    for name, t in (("lower", lower), ("upper", upper), ("pvar", pvar), ("wa", wa), ("wb", wb), ("noise", noise), ("mean_out", mean_out)):
-        if (t is None and name != "mean_out") or (t is not None and (tuple(t.shape) != (n, C) or t.dtype != x.dtype)):
-            raise ValueError(f"{op}: {name} must be [{n}, {C}] {x.dtype}, got {None if t is None else (tuple(t.shape), t.dtype)}")
-    if u is None or tuple(u.shape) != (grid.m,) or u.dtype != x.dtype:
-        raise ValueError(f"{op}: u must be the grid mean [{grid.m}] {x.dtype}")
-    ytilde, omega = torch.empty((n, C), dtype=x.dtype, device=x.device), torch.empty((n, C), dtype=x.dtype, device=x.device)
-    log_z = torch.empty((n, C), dtype=torch.float64, device=x.device)
+    C = grid.d + 1
+    per_channel = dict(lower=lower, upper=upper, pvar=pvar, wa=wa, wb=wb, noise=noise, mean_out=mean_out)
+    x, n = _absorb_points("scatter_stats_grad_interval", grid, x, u, [(("n", C), per_channel, ("mean_out",))])
+    ytilde, omega, log_z = _site_outputs(x, (n, C))
     if n == 0:
         return ytilde, omega, log_z
-    rc = _hip.fn("wiski_scatter_stats_grad_interval", x.dtype)(grid.ref, _hip.dptr(x), _hip.dptr(lower.contiguous()), _hip.dptr(upper.contiguous()),
-                                                               _hip.dptr(pvar.contiguous()), ctypes.c_double(float(sigma2)), _hip.dptr(wa.contiguous()),
-                                                               _hip.dptr(wb.contiguous()), _hip.dptr(noise.contiguous()), ctypes.c_int64(n), _hip.dptr(b),
-                                                               _hip.dptr(A_half), _hip.dptr(cnt), _hip.dptr(u), _hip.dptr(res), _hip.dptr(mean_out),
-                                                               _hip.dptr(stats), _hip.dptr(err), _hip.dptr(ytilde), _hip.dptr(omega), _hip.dptr(log_z),
-                                                               _hip.stream_ptr(x.device))
-    _hip.check(rc, "wiski_scatter_stats_grad_interval")
+    _absorb_call("wiski_absorb_grad_interval", grid, x.dtype, x.device,
+                 _absorb_record(x, (None, wa, wb, noise), (b, A_half, cnt, stats, err), (u, res, mean_out), channels=C),
+                 _hip.dptr(lower.contiguous()), _hip.dptr(upper.contiguous()), _hip.dptr(pvar.contiguous()), float(sigma2), _hip.dptr(ytilde),
+                 _hip.dptr(omega), _hip.dptr(log_z))
     return ytilde, omega, log_z
 
 
@@ -525,7 +530,7 @@ COUNT_FAMILIES = {"poisson": 0, "binomial": 1}      # WISKI_COUNT_POISSON, WISKI
 
 
 def scatter_stats_count(grid, x, counts, t, family, pvar, sigma2, wa, wb, noise, b, A_half, cnt, stats, err, u, res=None, mean_out=None):
-    """The count-observation absorb in ONE launch (``wiski_scatter_stats_count``): point i carries the count
+    """The count-observation absorb in ONE launch (``wiski_absorb_count``): point i carries the count
     ``counts_i`` at exposure (``family`` "poisson": y ~ Poisson(t exp f)) or out of trials (``"binomial"``, logit link) ``t_i``.  It is
     moment-matched against the posterior before the batch -- the grid mean ``u`` [m], the posterior variance ``pvar`` [n] of f at x --
     by a quadrature over the lanes of its wave and enters (b, A_half, cnt, stats) -- and the carried residual ``res``, if given -- as
@@ -534,23 +539,20 @@ def scatter_stats_count(grid, x, counts, t, family, pvar, sigma2, wa, wb, noise,
     a point outside the grid (0, 0, 0).  ``mean_out`` [n] receives w . u."""
     if family not in COUNT_FAMILIES:
         raise ValueError(f"scatter_stats_count: family must be one of {sorted(COUNT_FAMILIES)}, got {family!r}")
-    x, n, (ytilde, omega, log_z) = _absorb_points("scatter_stats_count", grid, x, u, sites=True,
-                                                  per_point=dict(counts=counts, t=t, pvar=pvar, wa=wa, wb=wb, noise=noise, mean_out=mean_out))
+    x, n = _absorb_points("scatter_stats_count", grid, x, u,
+                          [(("n",), dict(counts=counts, t=t, pvar=pvar, wa=wa, wb=wb, noise=noise, mean_out=mean_out), None)])
+    ytilde, omega, log_z = _site_outputs(x, (n,))
     if n == 0:
         return ytilde, omega, log_z
-    rc = _hip.fn("wiski_scatter_stats_count", x.dtype)(grid.ref, _hip.dptr(x), _hip.dptr(counts.contiguous()), _hip.dptr(t.contiguous()),
-                                                       ctypes.c_int(COUNT_FAMILIES[family]), _hip.dptr(pvar.contiguous()), ctypes.c_double(float(sigma2)),
-                                                       _hip.dptr(wa.contiguous()), _hip.dptr(wb.contiguous()), _hip.dptr(noise.contiguous()), ctypes.c_int64(n),
-                                                       _hip.dptr(b), _hip.dptr(A_half), _hip.dptr(cnt), _hip.dptr(u), _hip.dptr(res), _hip.dptr(mean_out),
-                                                       _hip.dptr(stats), _hip.dptr(err), _hip.dptr(ytilde), _hip.dptr(omega), _hip.dptr(log_z),
-                                                       _hip.stream_ptr(x.device))
-    _hip.check(rc, "wiski_scatter_stats_count")
+    _absorb_call("wiski_absorb_count", grid, x.dtype, x.device, _absorb_record(x, (None, wa, wb, noise), (b, A_half, cnt, stats, err), (u, res, mean_out)),
+                 _hip.dptr(counts.contiguous()), _hip.dptr(t.contiguous()), COUNT_FAMILIES[family], _hip.dptr(pvar.contiguous()), float(sigma2),
+                 _hip.dptr(ytilde), _hip.dptr(omega), _hip.dptr(log_z))
     return ytilde, omega, log_z
 
 
 def scatter_stats_input_noise(grid, x, y, xvar, gvar, pvar, sigma2, wa, wb, noise, b, A_half, cnt, stats, err, u, res=None, mean_out=None,
                               want_grad=False):
-    """The noisy-input absorb in ONE launch (``wiski_scatter_stats_input_noise``): point i was taken at x_i + e_i,
+    """The noisy-input absorb in ONE launch (``wiski_absorb_input_noise``): point i was taken at x_i + e_i,
     e_i ~ N(0, diag(xvar_i)) (``xvar`` [n, d], in the grid's units squared).  Against the posterior before the batch -- the grid mean
     ``u`` [m] with its slope g_i at x_i, the posterior variances ``pvar`` [n] of f and ``gvar`` [n, d] of its partial derivatives
     (None: 0, the slope of the mean alone) -- the location error is the extra output noise s_in = sum_k xvar_k (g_k^2 + gvar_k), and the
@@ -558,23 +560,15 @@ def scatter_stats_input_noise(grid, x, y, xvar, gvar, pvar, sigma2, wa, wb, nois
     (dn + s_in), dn = sigma2 noise_i.  Returns (omega [n], log_z [n] float64) and, with ``want_grad``, the slopes g [n, d] as the
     kernel reduced them; a skipped point (omega below 1e-12, a negative or NaN xvar) has omega = 0, a point outside the grid zeros.
     ``mean_out`` [n] receives w . u."""
-    op = "scatter_stats_input_noise"
-    x, n = _absorb_points(op, grid, x, u, dict(y=y, pvar=pvar, wa=wa, wb=wb, noise=noise, mean_out=mean_out))
-    for name, t in (("xvar", xvar), ("gvar", gvar)):
-        if (t is None and name == "xvar") or (t is not None and (tuple(t.shape) != (n, grid.d) or t.dtype != x.dtype)):
-            raise ValueError(f"{op}: {name} must be [{n}, {grid.d}] {x.dtype}, got {None if t is None else (tuple(t.shape), t.dtype)}")
+    x, n = _absorb_points("scatter_stats_input_noise", grid, x, u, [(("n",), dict(y=y, pvar=pvar, wa=wa, wb=wb, noise=noise, mean_out=mean_out), None),
+                                                                    (("n", grid.d), dict(xvar=xvar, gvar=gvar), ("gvar",))])
     omega = torch.empty(n, dtype=x.dtype, device=x.device)
     log_z = torch.empty(n, dtype=torch.float64, device=x.device)
     grad = torch.empty((n, grid.d), dtype=x.dtype, device=x.device) if want_grad else None
     if n:
-        rc = _hip.fn("wiski_scatter_stats_input_noise", x.dtype)(grid.ref, _hip.dptr(x), _hip.dptr(y.contiguous()), _hip.dptr(xvar.contiguous()),
-                                                                 _hip.dptr(None if gvar is None else gvar.contiguous()), _hip.dptr(pvar.contiguous()),
-                                                                 ctypes.c_double(float(sigma2)), _hip.dptr(wa.contiguous()), _hip.dptr(wb.contiguous()),
-                                                                 _hip.dptr(noise.contiguous()), ctypes.c_int64(n), _hip.dptr(b), _hip.dptr(A_half),
-                                                                 _hip.dptr(cnt), _hip.dptr(u), _hip.dptr(res), _hip.dptr(mean_out), _hip.dptr(stats),
-                                                                 _hip.dptr(err), _hip.dptr(omega), _hip.dptr(log_z), _hip.dptr(grad),
-                                                                 _hip.stream_ptr(x.device))
-        _hip.check(rc, "wiski_scatter_stats_input_noise")
+        _absorb_call("wiski_absorb_input_noise", grid, x.dtype, x.device, _absorb_record(x, (y, wa, wb, noise), (b, A_half, cnt, stats, err), (u, res, mean_out)),
+                     _hip.dptr(xvar.contiguous()), _hip.dptr(None if gvar is None else gvar.contiguous()), _hip.dptr(pvar.contiguous()), float(sigma2),
+                     _hip.dptr(omega), _hip.dptr(log_z), _hip.dptr(grad))
     return (omega, log_z, grad) if want_grad else (omega, log_z)
 
 
@@ -601,7 +595,7 @@ def count_sites(mean, pvar, counts, t, family):
 
 
 def scatter_stats_hetero(grid, x, y, pvar, pvar2, sigma2, g0, wa, wb, noise, f_set, g_set, err, mean_out=None):
-    """The heteroscedastic absorb in ONE launch (``wiski_scatter_stats_hetero``): two single-output models on the same
+    """The heteroscedastic absorb in ONE launch (``wiski_absorb_hetero``): two single-output models on the same
     grid, f and g = log of the noise multiplier (prior mean ``g0``), each given as a set ``(b, A_half, cnt, stats, u, res)`` (res may
     be None).  Against the two posteriors before the batch -- the grid means, the posterior variances ``pvar`` (of f) and ``pvar2`` (of
     g) at x [n] -- point i enters f as y_i at noise_i e_i, e = exp(mu_g + v_g / 2), and its deflated squared residual enters g as a
@@ -611,22 +605,18 @@ def scatter_stats_hetero(grid, x, y, pvar, pvar2, sigma2, g0, wa, wb, noise, f_s
     op = "scatter_stats_hetero"
     b, A_half, cnt, stats, u, res = f_set
     b2, A2_half, cnt2, stats2, u2, res2 = g_set
-    x, n, (ytilde, tau, log_z) = _absorb_points(op, grid, x, u, sites=True, u_is="the grid mean of f",
-                                                per_point=dict(y=y, pvar=pvar, pvar2=pvar2, wa=wa, wb=wb, noise=noise, mean_out=mean_out))
+    x, n = _absorb_points(op, grid, x, u, [(("n",), dict(y=y, pvar=pvar, pvar2=pvar2, wa=wa, wb=wb, noise=noise, mean_out=mean_out), None)],
+                          u_is="the grid mean of f")
     if u2 is None or tuple(u2.shape) != (grid.m,) or u2.dtype != x.dtype:
         raise ValueError(f"{op}: the second set's u must be the grid mean of g - g0 [{grid.m}] {x.dtype}")
+    ytilde, tau, log_z = _site_outputs(x, (n,))
     e = torch.empty(n, dtype=x.dtype, device=x.device)
     log_zy = torch.empty(n, dtype=torch.float64, device=x.device)
     if n == 0:
         return e, ytilde, tau, log_z, log_zy
-    rc = _hip.fn("wiski_scatter_stats_hetero", x.dtype)(grid.ref, _hip.dptr(x), _hip.dptr(y.contiguous()), _hip.dptr(pvar.contiguous()),
-                                                        _hip.dptr(pvar2.contiguous()), float(sigma2), float(g0), _hip.dptr(wa.contiguous()),
-                                                        _hip.dptr(wb.contiguous()), _hip.dptr(noise.contiguous()), n, _hip.dptr(b), _hip.dptr(A_half),
-                                                        _hip.dptr(cnt), _hip.dptr(u), _hip.dptr(res), _hip.dptr(mean_out), _hip.dptr(stats),
-                                                        _hip.dptr(b2), _hip.dptr(A2_half), _hip.dptr(cnt2), _hip.dptr(u2), _hip.dptr(res2),
-                                                        _hip.dptr(stats2), _hip.dptr(err), _hip.dptr(e), _hip.dptr(ytilde), _hip.dptr(tau),
-                                                        _hip.dptr(log_z), _hip.dptr(log_zy), _hip.stream_ptr(x.device))
-    _hip.check(rc, "wiski_scatter_stats_hetero")
+    _absorb_call("wiski_absorb_hetero", grid, x.dtype, x.device, _absorb_record(x, (y, wa, wb, noise), (b, A_half, cnt, stats, err), (u, res, mean_out)),
+                 _hip.dptr(pvar.contiguous()), _hip.dptr(pvar2.contiguous()), float(sigma2), float(g0), _hip.dptr(b2), _hip.dptr(A2_half), _hip.dptr(cnt2),
+                 _hip.dptr(u2), _hip.dptr(res2), _hip.dptr(stats2), _hip.dptr(e), _hip.dptr(ytilde), _hip.dptr(tau), _hip.dptr(log_z), _hip.dptr(log_zy))
     return e, ytilde, tau, log_z, log_zy
 
 
@@ -659,7 +649,7 @@ def _label_classes(op, C):
 
 
 def scatter_stats_label(grid, x, labels, pvar, sigma2, wa, wb, noise, b, A_pack, cnt, stats, err, u, res=None, mean_out=None):
-    """The categorical-observation absorb in ONE launch (``wiski_scatter_stats_label``): point i carries the label
+    """The categorical-observation absorb in ONE launch (``wiski_absorb_label``): point i carries the label
     ``labels_i`` in {0 .. C - 1} (in x's dtype) over the C outputs of b / cnt / u / res [C, m], A_pack [C, H, m] and stats [C, 2].  The
     multinomial probit likelihood is moment-matched against the posterior before the batch -- the grid means ``u``, the posterior
     variances ``pvar`` [C, n], the noise variances ``sigma2[c] * noise`` -- by a quadrature over the lanes of the point's wave, and
@@ -669,33 +659,27 @@ def scatter_stats_label(grid, x, labels, pvar, sigma2, wa, wb, noise, b, A_pack,
     ``mean_out`` [C, n] receives the predictive means."""
     op = "scatter_stats_label"
     x = _x2d(x, grid)
-    n = x.shape[0]
     if u is None or u.dim() != 2 or u.shape[1] != grid.m or u.dtype != x.dtype:
         raise ValueError(f"{op}: u must be the grid means [C, {grid.m}] {x.dtype}")
     C = u.shape[0]
     _label_classes(op, C)
     shared = wa.dim() == 1
-    for name, t, shape in (("labels", labels, (n,)), ("pvar", pvar, (C, n)), ("mean_out", mean_out, (C, n)), ("wa", wa, (n,) if shared else (C, n)),
-                           ("wb", wb, (n,) if shared else (C, n)), ("noise", noise, (n,) if shared else (C, n)), ("b", b, (C, grid.m)),
-                           ("cnt", cnt, (C, grid.m)), ("res", res, (C, grid.m))):
-        if (t is None and name not in ("mean_out", "res")) or (t is not None and (tuple(t.shape) != shape or t.dtype != x.dtype)):
-            raise ValueError(f"{op}: {name} must be {list(shape)} {x.dtype}, got {None if t is None else (tuple(t.shape), t.dtype)}")
+    weights = ("n",) if shared else (C, "n")
+    x, n = _absorb_points(op, grid, x, u, u_is=None, groups=[
+        (("n",), dict(labels=labels), ()), ((C, "n"), dict(pvar=pvar, mean_out=mean_out), ("mean_out",)), (weights, dict(wa=wa, wb=wb, noise=noise), ()),
+        ((C, grid.m), dict(b=b, cnt=cnt, res=res), ("res",))])
     if A_pack.dim() != 3 or A_pack.shape[0] != C or A_pack.dtype != x.dtype or tuple(stats.shape) != (C, 2) or stats.dtype != torch.float64:
         raise ValueError(f"{op}: A_pack must be [C, H, m] {x.dtype} half stencils and stats [C, 2] float64")
     sigma2 = [float(v) for v in sigma2]
     if len(sigma2) != C:
         raise ValueError(f"{op}: sigma2 must hold {C} values, got {len(sigma2)}")
-    ytilde, omega = torch.empty((C, n), dtype=x.dtype, device=x.device), torch.empty((C, n), dtype=x.dtype, device=x.device)
-    log_z = torch.empty(n, dtype=torch.float64, device=x.device)
+    ytilde, omega, log_z = _site_outputs(x, (C, n), logz_shape=(n,))
     if n == 0:
         return ytilde, omega, log_z
-    rc = _hip.fn("wiski_scatter_stats_label", x.dtype)(grid.ref, _hip.dptr(x), _hip.dptr(labels.contiguous()), _hip.dptr(pvar.contiguous()),
-                                                       (ctypes.c_double * C)(*sigma2), _hip.dptr(wa.contiguous()), _hip.dptr(wb.contiguous()),
-                                                       _hip.dptr(noise.contiguous()), n, C, 0 if shared else n, _hip.dptr(b), _hip.dptr(A_pack),
-                                                       A_pack.shape[1] * A_pack.shape[2], _hip.dptr(cnt), _hip.dptr(u), _hip.dptr(res), _hip.dptr(mean_out),
-                                                       _hip.dptr(stats), _hip.dptr(err), _hip.dptr(ytilde), _hip.dptr(omega), _hip.dptr(log_z),
-                                                       _hip.stream_ptr(x.device))
-    _hip.check(rc, "wiski_scatter_stats_label")
+    rec = _absorb_record(x, (None, wa, wb, noise), (b, A_pack, cnt, stats, err), (u, res, mean_out), nout=C, w_stride=0 if shared else n,
+                         A_stride=A_pack.shape[1] * A_pack.shape[2])
+    _absorb_call("wiski_absorb_label", grid, x.dtype, x.device, rec, _hip.dptr(labels.contiguous()), _hip.dptr(pvar.contiguous()),
+                 (ctypes.c_double * C)(*sigma2), _hip.dptr(ytilde), _hip.dptr(omega), _hip.dptr(log_z))
     return ytilde, omega, log_z
 
 
@@ -819,23 +803,19 @@ class WindowRing:
 
 
 def scatter_stats_window(grid, x, y, wa, wb, noise, ring, b, A_half, cnt, stats, err, u, res=None, mean_out=None):
-    """The sliding-window absorb in ONE launch (``wiski_scatter_stats_window``): the n <= ring.cap points enter
+    """The sliding-window absorb in ONE launch (``wiski_absorb_window``): the n <= ring.cap points enter
     (b, A_half, cnt, stats) -- and the carried residual ``res``, if given -- and the slots ring.head, ring.head + 1, ... (mod cap)
     of ``ring``; what those slots held leaves the statistics again, with its weights negated.  ``u`` [m]: the posterior mean on the
     grid both sweeps are taken against (any vector when neither ``res`` nor ``mean_out`` is asked for); ``mean_out`` [n] receives
     w . u of the entering points.  Advances ``ring.head`` and ``ring.fill``."""
-    x, n = _absorb_points("scatter_stats_window", grid, x, u, dict(y=y, wa=wa, wb=wb, noise=noise, mean_out=mean_out), u_is="a grid vector")
+    x, n = _absorb_points("scatter_stats_window", grid, x, u, [(("n",), dict(y=y, wa=wa, wb=wb, noise=noise, mean_out=mean_out), None)], u_is="a grid vector")
     if ring.d != grid.d or ring.x.dtype != x.dtype or ring.x.device != x.device:
         raise ValueError(f"scatter_stats_window: the ring holds {ring.d}-d {ring.x.dtype} points on {ring.x.device}")
     if n == 0:
         return
     r = ring.ref()
-    rc = _hip.fn("wiski_scatter_stats_window", x.dtype)(grid.ref, _hip.dptr(x), _hip.dptr(y.contiguous()), _hip.dptr(wa.contiguous()),
-                                                        _hip.dptr(wb.contiguous()), _hip.dptr(noise.contiguous()), ctypes.c_int64(n), ctypes.byref(r),
-                                                        _hip.dptr(b), _hip.dptr(A_half), _hip.dptr(cnt), _hip.dptr(u), _hip.dptr(res),
-                                                        _hip.dptr(mean_out), _hip.dptr(stats), _hip.dptr(err), _hip.dptr(ring.void_left),
-                                                        _hip.stream_ptr(x.device))
-    _hip.check(rc, "wiski_scatter_stats_window")
+    _absorb_call("wiski_absorb_window", grid, x.dtype, x.device, _absorb_record(x, (y, wa, wb, noise), (b, A_half, cnt, stats, err), (u, res, mean_out)),
+                 ctypes.byref(r), _hip.dptr(ring.void_left))
     ring.advance(n)
 
 
@@ -919,7 +899,7 @@ class SiteRing:
 
 
 def revisit_sites(grid, ring, form, pvar, sigma2, damping, b, A_half, cnt, stats, err, u, res=None, log_z=None, change=None):
-    """One expectation-propagation launch over the stored sites of one form (``wiski_revisit_sites``): every slot
+    """One expectation-propagation launch over the stored sites of one form (``wiski_absorb_revisit``): every slot
     of ``ring`` whose form is ``form`` ("interval", "poisson", "binomial") is re-matched against its cavity under the grid mean ``u``
     [m] and the posterior variance ``pvar`` [cap] of f at the slots' points, damped by ``damping`` in [0, 1], and enters
     (b, A_half, cnt, stats) -- and the carried residual ``res``, if given -- with the difference of its site; the ring's ytilde /
@@ -941,10 +921,9 @@ def revisit_sites(grid, ring, form, pvar, sigma2, damping, b, A_half, cnt, stats
     if change is None:
         change = torch.zeros(ring.cap, dtype=dtype, device=device)
     r = ring.ref()
-    rc = _hip.fn("wiski_revisit_sites", dtype)(grid.ref, ctypes.byref(r), SITE_FORMS[form], _hip.dptr(pvar.contiguous()), float(sigma2), float(damping),
-                                               _hip.dptr(b), _hip.dptr(A_half), _hip.dptr(cnt), _hip.dptr(u), _hip.dptr(res), _hip.dptr(stats),
-                                               _hip.dptr(err), _hip.dptr(log_z), _hip.dptr(change), _hip.stream_ptr(device))
-    _hip.check(rc, "wiski_revisit_sites")
+    # the points are the ring's slots: the record carries the targets and the carry alone
+    _absorb_call("wiski_absorb_revisit", grid, dtype, device, _absorb_record(None, (None,) * 4, (b, A_half, cnt, stats, err), (u, res, None)),
+                 ctypes.byref(r), SITE_FORMS[form], _hip.dptr(pvar.contiguous()), float(sigma2), float(damping), _hip.dptr(log_z), _hip.dptr(change))
     return log_z, change
 
 
@@ -1530,7 +1509,6 @@ def half_stencil_group_slices(grid, g_lo, g_hi):
 
 class _StreamArgs64(ctypes.Structure):
     _fields_ = [(n, ctypes.c_double if t is ctypes.c_float else t) for n, t in _StreamArgs32._fields_]
-
 
 
 class _PcgAsync(ctypes.Structure):

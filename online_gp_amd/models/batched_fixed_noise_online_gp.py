@@ -1744,7 +1744,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         return self._condition(absorb, inplace, self._gamma(_decay))
 
     def _absorb_grad(self, cache, X, Yc, Nc, present, half_delta=None):
-        """_absorb for [n, d + 1] channel tensors (values Yc, noises Nc, bool present), one launch (wiski_scatter_stats_grad).  The
+        """_absorb for [n, d + 1] channel tensors (values Yc, noises Nc, bool present), one launch (wiski_absorb with channels = d + 1).  The
         carried residual follows when the mean state is current.  What a derivative row cannot be followed through is given up
         rather than updated: the spectral factor is marked stale (it rebuilds from the stencil, exactly), the two-level block is
         lost, a carried root pair is dropped, and no rank update is prepared."""
@@ -1782,7 +1782,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         return u, scale2.rsqrt()
 
     def _absorb_robust(self, cache, X, Y, noise, src):
-        """_absorb of one value-only batch with Huber weights, one launch (wiski_scatter_stats_robust).  `src`: the model whose
+        """_absorb of one value-only batch with Huber weights, one launch (wiski_absorb_robust).  `src`: the model whose
         posterior the weights are taken against -- this one, or in the functional form without a decay the parent, whose statistics
         the clone still equals.  Everything that follows the stream point by point receives the effective weights wa omega and
         wb omega: a carried root pair, the spectral factor, the path probes, the noise-weight sum.  The two-level block is given up
@@ -1889,7 +1889,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         return sites, int(entered) + int(dropped)
 
     def _absorb_interval(self, cache, X, lo, hi, noise, src, half_delta=None):
-        """_absorb_matched with the interval launch (wiski_scatter_stats_interval)."""
+        """_absorb_matched with the interval launch (wiski_absorb_interval)."""
         self.last_interval_sites, grown = self._absorb_matched(
             cache, X, noise, src, "interval observations", half_delta=half_delta, store=("interval", lo, hi),
             launch=lambda X, *rest, **kw: grid_ops.scatter_stats_interval(self._grid, X, lo.contiguous(), hi.contiguous(), *rest, **kw))
@@ -1924,7 +1924,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         return new_gp
 
     def _absorb_count(self, cache, X, y, t, family, src, half_delta=None):
-        """_absorb_matched with the count launch (wiski_scatter_stats_count), at noise = wa = wb = 1 -- the effective noise
+        """_absorb_matched with the count launch (wiski_absorb_count), at noise = wa = wb = 1 -- the effective noise
         variance of a point is sigma2 / omega = 1 / tau."""
         self.last_count_sites, grown = self._absorb_matched(
             cache, X, None, src, "count observations", half_delta=half_delta, store=(family, y, t),
@@ -1945,7 +1945,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
     def refine_sites_(self, sweeps=1, damping=1.0, tol=None):
         """Expectation-propagation sweeps over the stored interval and count observations, in place.  Per sweep the
         grid mean is taken from the prediction cache and the posterior variance at the stored points from the path every posterior
-        call takes (one more solve); then ONE launch per form present in the ring (``wiski_revisit_sites``) re-matches every stored
+        call takes (one more solve); then ONE launch per form present in the ring (``wiski_absorb_revisit``) re-matches every stored
         site against its cavity, damped by ``damping`` in [0, 1], and scatters only the difference of the site -- all slots against
         the same mean and variance (parallel EP).  The carried residual follows in the launch; the noise-weight sum moves by the
         weight deltas on the device; what cannot follow a weight that shrinks is given up, as after a point has left a window: a
@@ -2082,7 +2082,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         return self._condition(lambda model, cache, src: model._absorb_hetero(cache, X, Y, noise, src), inplace, self._gamma(_decay), reads_posterior=True)
 
     def _absorb_hetero(self, cache, X, Y, noise, src):
-        """_absorb of one batch into BOTH models, one launch (wiski_scatter_stats_hetero).  `src`: the model whose posteriors -- its own
+        """_absorb of one batch into BOTH models, one launch (wiski_absorb_hetero).  `src`: the model whose posteriors -- its own
         and its noise model's -- everything is taken against: this one, or in the functional form without a decay the parent.  f is
         followed with (wa omega_f, y wb omega_f), omega_f = 1 / e; the noise model with its sites at unit weights.  Returns what
         num_data grows by: the points that entered f and those outside the grid (which _raise_out_of_bounds takes off again)."""
@@ -2189,7 +2189,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
                                reads_posterior=True)
 
     def _absorb_labels(self, cache, X, y, noise, src):
-        """_absorb of one batch of labels, one launch for all outputs (wiski_scatter_stats_label): _absorb_matched for the one form
+        """_absorb of one batch of labels, one launch for all outputs (wiski_absorb_label): _absorb_matched for the one form
         that couples the outputs, in its order -- the source posterior is read first (`src` as there: its C grid means from the
         prediction cache, which finishes whatever is pending and leaves a stencil shard, and its C posterior variances at X), then
         the launch is prepared (_before_launch, the carried residual) as _site_targets does, then everything that follows the stream
@@ -2302,7 +2302,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
                                reads_posterior=True)
 
     def _absorb_input_noise(self, cache, X, y, xvar, noise, src, half_delta=None):
-        """_absorb_matched with the noisy-input launch (wiski_scatter_stats_input_noise).  "posterior": the variances of f and of its
+        """_absorb_matched with the noisy-input launch (wiski_absorb_input_noise).  "posterior": the variances of f and of its
         partial derivatives at X are the diagonal of ONE posterior_jet covariance of `src`; "mean": the variance of f as for intervals,
         no slope variance.  The pseudo-target is y itself."""
         gvar = []
@@ -2467,7 +2467,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
 
     def _absorb_grad_interval(self, cache, X, lo, hi, noise, present, src):
         """_absorb for [n, d + 1] channel tensors of bounds (lo, hi, noises, bool present), one launch
-        (wiski_scatter_stats_grad_interval).  `src`: the model whose posterior the sites are matched against, as in _absorb_matched:
+        (wiski_absorb_grad_interval).  `src`: the model whose posterior the sites are matched against, as in _absorb_matched:
         its grid mean from the prediction cache, and the variances of f and of its partial derivatives at X from the diagonal of ONE
         posterior_jet covariance.  The followers are those of _absorb_grad: what a derivative row cannot be followed through is
         given up.  Returns what num_data grows by: the channels that entered, and the present channels of points outside the grid
@@ -2547,7 +2547,7 @@ class FixedNoiseOnlineSKIGP(torch.nn.Module):
         self._absorb_window(self._kernel_cache, X[lo:], Y[lo:], None if noise is None else noise.reshape(X.shape[0], -1)[lo:], init=True)
 
     def _absorb_window(self, cache, X, Y, noise, init=False):
-        """_absorb of one value-only batch through the ring, one launch per `window` points (wiski_scatter_stats_window): a batch larger
+        """_absorb of one value-only batch through the ring, one launch per `window` points (wiski_absorb_window): a batch larger
         than the window is split on the host so that the slots of a launch are distinct.  The carried residual follows when the mean
         state is current.  What cannot follow a point that leaves is given up rather than updated, as under a decay: a carried root
         pair is dropped, the spectral factor marked stale (it rebuilds from the stencil, exactly), the two-level block lost, no rank

@@ -246,7 +246,7 @@ def test_absorb_and_count_sites_run_the_same_site(fam, tdt):
 def test_absorb_refuses_the_count_group_with_what_the_kernel_does_not_do(tdt):
     """Through the full argument record plus the count group (wiski_absorb_count): every combination the contract refuses is
     WISKI_E_BADARG before any launch -- every buffer untouched -- while the record without the offending field runs and equals
-    wiski_scatter_stats_count; res and mean_out are optional, the record's d_y is ignored."""
+    grid_ops.scatter_stats_count; res and mean_out are optional, the record's d_y is ignored."""
     from online_gp_amd import _hip, grid_ops
 
     c = _kernel_case("d3", "poisson")
@@ -279,10 +279,6 @@ def test_absorb_refuses_the_count_group_with_what_the_kernel_does_not_do(tdt):
                ("sigma2 = inf", call(sigma2=float("inf"))), ("sigma2 = nan", call(sigma2=float("nan"))), ("no y", call(y_=None)), ("no t", call(t_=None)),
                ("family 2", call(family=2)), ("family -1", call(family=-1)), ("no pvar", call(pvar_=None)), ("no ytilde_out", call(yt_=None)),
                ("no omega_out", call(omega_=None)), ("no logz_out", call(logz_=None))]
-    rc = _hip.fn("wiski_scatter_stats_count", tdt)(grid.ref, p(X), None, p(t), ctypes.c_int(0), p(pvar), ctypes.c_double(KS2), p(wa), p(wa), p(noise),
-                                                   ctypes.c_int64(N), p(buf["b"]), p(buf["A"]), p(buf["cnt"]), p(u), p(buf["res"]), p(mean), p(buf["stats"]),
-                                                   p(err), p(yt), p(omega), p(logz), stream)
-    refused.append(("entry without y", rc))
     rc = _hip.fn("wiski_count_sites", tdt)(p(mean), p(pvar), p(y), p(t), ctypes.c_int(5), ctypes.c_int64(N), p(yt), p(omega), p(logz), stream)
     refused.append(("sites, family 5", rc))
     rc = _hip.fn("wiski_count_sites", tdt)(p(mean), None, p(y), p(t), ctypes.c_int(0), ctypes.c_int64(N), p(yt), p(omega), p(logz), stream)

@@ -212,7 +212,7 @@ def test_kernel_is_declared_and_listed_for_the_build():
     from online_gp_amd import _hip, grid_ops
 
     hdr = open(os.path.join(ROOT, "include", "wiski.h")).read()
-    for name in ("wiski_scatter_stats_count", "wiski_absorb_count", "wiski_count_sites"):
+    for name in ("wiski_absorb_count", "wiski_count_sites"):
         assert name + "_f32" in hdr and name + "_f64" in hdr
     assert "scatter_count.h" in _hip._HEADERS and os.path.exists(os.path.join(ROOT, "online_gp_amd", "csrc", "scatter_count.h"))
     assert '#include "scatter_count.h"' in open(os.path.join(ROOT, "online_gp_amd", "csrc", "scatter_stats.hip")).read()

@@ -129,7 +129,7 @@ def test_kernel_matches_the_dense_reference(name, tdt, tol):
 
 @pytest.mark.parametrize("tdt,tol", DTYPES)
 def test_all_channels_exact_is_the_derivative_absorb(tdt, tol):
-    """Equal bounds on every present channel: the launch equals wiski_scatter_stats_grad on the same values, omega = 1 and
+    """Equal bounds on every present channel: the launch equals grid_ops.scatter_stats_grad on the same values, omega = 1 and
     ytilde = the value exactly (d = 3)."""
     from online_gp_amd import grid_ops
 
@@ -152,7 +152,7 @@ def test_all_channels_exact_is_the_derivative_absorb(tdt, tol):
 
 @pytest.mark.parametrize("tdt,tol", DTYPES)
 def test_only_the_value_channel_is_the_interval_absorb(tdt, tol):
-    """Channel 0 alone present: the sites equal those of wiski_scatter_stats_interval bit for bit, the statistics to the bounds (d = 3)."""
+    """Channel 0 alone present: the sites equal those of grid_ops.scatter_stats_interval bit for bit, the statistics to the bounds (d = 3)."""
     from online_gp_amd import grid_ops
 
     c = _case("d3")
@@ -182,7 +182,7 @@ def test_only_the_value_channel_is_the_interval_absorb(tdt, tol):
 def test_absorb_refuses_the_group_with_what_the_kernel_does_not_do(tdt):
     """Through the full argument record plus the form's arguments (wiski_absorb_grad_interval): every combination the contract
     refuses is WISKI_E_BADARG before any launch -- every buffer untouched -- while the clean record runs and equals
-    wiski_scatter_stats_grad_interval; res and mean_out are optional, the record's d_y is ignored."""
+    grid_ops.scatter_stats_grad_interval; res and mean_out are optional, the record's d_y is ignored."""
     from online_gp_amd import _hip, grid_ops
 
     c = _case("d3")

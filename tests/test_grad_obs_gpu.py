@@ -140,7 +140,7 @@ def test_kernel_without_derivative_channels_is_the_value_absorb(name, tdt, tol):
 def test_absorb_refuses_channels_with_what_the_kernel_does_not_do(tdt):
     """Through the full argument record (wiski_absorb): channels with the full stencil, a guard, zero regions, a shard, nout > 1 or a
     channel count other than d + 1 is WISKI_E_BADARG before any launch -- every buffer untouched -- while the same record without
-    the offending field runs and equals wiski_scatter_stats_grad."""
+    the offending field runs and equals grid_ops.scatter_stats_grad."""
     from online_gp_amd import _hip, grid_ops
 
     c = _kernel_case("d3")

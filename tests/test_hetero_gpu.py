@@ -277,7 +277,7 @@ def test_a_multiplier_beyond_the_working_precision_skips_the_point(level, tdt):
 def test_absorb_refuses_the_hetero_group_with_what_the_kernel_does_not_do(tdt):
     """Through the full argument record plus the hetero group (wiski_absorb_hetero): every combination the contract refuses is
     WISKI_E_BADARG before any launch -- every buffer of both models untouched -- while the record without the offending field runs
-    and equals wiski_scatter_stats_hetero; res, res2 and mean_out are optional; n = 0 does nothing."""
+    and equals grid_ops.scatter_stats_hetero; res, res2 and mean_out are optional; n = 0 does nothing."""
     from online_gp_amd import _hip, grid_ops
 
     c = _kernel_case("d3")

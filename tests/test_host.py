@@ -52,6 +52,34 @@ def test_ctypes_structs_have_the_layout_of_the_header(tmp_path):
     assert got == want, (got, want)
 
 
+def test_absorb_argtypes_follow_the_prototypes_of_the_header():
+    """Every entry of _hip.ABSORB_SIGNATURES against its prototype in include/wiski.h: as many argtypes as parameters, and in order a
+    pointer as c_void_p or the POINTER of the struct the header names, double / int / int32_t / int64_t / float as c_double / c_int /
+    c_int32 / c_int64 / c_float -- so the one scalar in the working precision (huber_c) is c_float in _f32 and c_double in _f64.  The
+    table covers the record entry of every observation form, wiski_absorb itself and the site-only entries, in both precisions."""
+    from online_gp_amd import _hip
+
+    hdr = open(os.path.join(ROOT, "include", "wiski.h")).read()
+    forms = ["robust", "window", "interval", "grad_interval", "count", "revisit", "hetero", "label", "input_noise"]
+    names = ["wiski_absorb"] + ["wiski_absorb_" + f for f in forms] + ["wiski_count_sites", "wiski_hetero_sites", "wiski_label_sites", "wiski_label_proba"]
+    assert set(_hip.ABSORB_SIGNATURES) == {n + s for n in names for s in ("_f32", "_f64")}
+    scalars = {"double": ctypes.c_double, "float": ctypes.c_float, "int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64}
+    for name, sig in _hip.ABSORB_SIGNATURES.items():
+        m = re.search(r"^int " + name + r"\(([^;]*)\);", hdr, re.M)
+        assert m, name
+        params = [prm.strip() for prm in m.group(1).split(",")]
+        assert len(params) == len(sig), (name, len(params), len(sig))
+        for prm, at in zip(params, sig):
+            ty = prm[:prm.rindex(" ")].replace("const ", "").strip()
+            if not ty.endswith("*"):
+                assert at is scalars[ty], (name, prm, at)
+            elif ty.startswith("wiski_"):
+                assert issubclass(at, ctypes._Pointer) and at._type_ is getattr(_hip, ty[:-1]), (name, prm, at)
+            else:
+                assert at is ctypes.c_void_p or (issubclass(at, ctypes._Pointer) and at._type_ is scalars[ty[:-1]]), (name, prm, at)
+        assert ("float huber_c" in params) == name.endswith("robust_f32") and ("double huber_c" in params) == name.endswith("robust_f64")
+
+
 def test_workspace_query_runs_without_gpu(built_lib):
     from online_gp_amd import grid_ops
 

@@ -260,7 +260,7 @@ def test_absorb_and_label_sites_run_the_same_site(tdt):
 @pytest.mark.parametrize("tdt", [torch.float32, torch.float64])
 def test_absorb_refuses_what_the_label_kernel_does_not_do(tdt):
     """Through the full argument record plus the label group (wiski_absorb_label): every combination the contract refuses is
-    WISKI_E_BADARG before any launch -- every buffer untouched -- while the plain record runs and equals wiski_scatter_stats_label."""
+    WISKI_E_BADARG before any launch -- every buffer untouched -- while the plain record runs and equals grid_ops.scatter_stats_label."""
     from online_gp_amd import _hip, grid_ops
 
     c = _kernel_case("d3")

@@ -273,7 +273,7 @@ def test_damping_zero_changes_nothing_bit_for_bit(tdt):
 def test_absorb_refuses_the_revisit_group_with_what_the_kernel_does_not_do(tdt):
     """Through the full argument record plus the revisit group (wiski_absorb_revisit): every combination the contract refuses is
     WISKI_E_BADARG before any launch -- every buffer and the ring untouched -- while the record without the offending field runs and
-    equals wiski_revisit_sites; res is optional, the record's points are not looked at; an empty ring is WISKI_OK and does nothing."""
+    equals grid_ops.revisit_sites; res is optional, the record's points are not looked at; an empty ring is WISKI_OK and does nothing."""
     from online_gp_amd import _hip, grid_ops
 
     c = _kernel_case("d3", "interval")

@@ -171,11 +171,11 @@ def test_kernel_is_declared_and_listed_for_the_build():
     from online_gp_amd import _hip, grid_ops
 
     hdr = open(os.path.join(ROOT, "include", "wiski.h")).read()
-    for name in ("wiski_revisit_sites_f32", "wiski_revisit_sites_f64", "wiski_absorb_revisit_f32", "wiski_absorb_revisit_f64", "wiski_site_ring"):
+    for name in ("wiski_absorb_revisit_f32", "wiski_absorb_revisit_f64", "wiski_site_ring"):
         assert name in hdr
     assert "scatter_revisit.h" in _hip._HEADERS and os.path.exists(os.path.join(ROOT, "online_gp_amd", "csrc", "scatter_revisit.h"))
     assert '#include "scatter_revisit.h"' in open(os.path.join(ROOT, "online_gp_amd", "csrc", "scatter_stats.hip")).read()
-    assert callable(grid_ops.revisit_sites) and set(_hip.REVISIT_SIGNATURES) == {n + s for n in ("wiski_revisit_sites", "wiski_absorb_revisit") for s in ("_f32", "_f64")}
+    assert callable(grid_ops.revisit_sites) and {"wiski_absorb_revisit" + s for s in ("_f32", "_f64")} <= set(_hip.ABSORB_SIGNATURES)
     assert grid_ops.SITE_FORMS == {"interval": rv.INTERVAL, "poisson": rv.POISSON, "binomial": rv.BINOMIAL}
     assert ctypes.sizeof(_hip.wiski_site_ring) == 80
     # the public argument record has not grown: callers built against the previous header keep working

@@ -176,7 +176,7 @@ def test_kernel_matches_the_reference_over_several_passes_of_a_block(tdt, tol):
 def test_absorb_refuses_the_ring_with_what_the_kernel_does_not_do(tdt):
     """Through the full argument record plus the ring (wiski_absorb_window): every combination the contract refuses is WISKI_E_BADARG
     before any launch -- every buffer and the ring bit-identical -- n = 0 does nothing, and the record without the offending field
-    runs and equals wiski_scatter_stats_window; res and mean_out are optional."""
+    runs and equals grid_ops.scatter_stats_window; res and mean_out are optional."""
     from online_gp_amd import _hip, grid_ops
 
     c = _kernel_case("d3")

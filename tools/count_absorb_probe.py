@@ -2,9 +2,9 @@
 family against the interval absorb (unchanged code, same build), each timed with HIP events around single launches (median over
 --reps, after --warm warm-up launches, the forms interleaved so that they share whatever else the machine is doing):
 
-  poisson   wiski_scatter_stats_count, family Poisson: counts drawn at the points' own predictive means, exposures exp(U(-1, 2));
-  binomial  wiski_scatter_stats_count, family binomial: successes out of 1..40 trials drawn likewise;
-  interval  wiski_scatter_stats_interval with the same carry (u, res, mean_out) and outputs: a third of the points each one-sided,
+  poisson   wiski_absorb_count, family Poisson: counts drawn at the points' own predictive means, exposures exp(U(-1, 2));
+  binomial  wiski_absorb_count, family binomial: successes out of 1..40 trials drawn likewise;
+  interval  wiski_absorb_interval with the same carry (u, res, mean_out) and outputs: a third of the points each one-sided,
             two-sided and exact;
   sites     wiski_count_sites alone on the same q sites (Poisson): the quadrature without a scatter.
 

@@ -2,11 +2,11 @@
 q uniform points, three launches, each timed with HIP events around single launches (median over --reps, after --warm warm-up
 launches, the three interleaved so that they share whatever else the machine is doing):
 
-  grad_interval  wiski_scatter_stats_grad_interval with the carry (u, res, mean_out) and its three outputs: every point carries an
+  grad_interval  wiski_absorb_grad_interval with the carry (u, res, mean_out) and its three outputs: every point carries an
                  exact value and a full gradient bounded on one side (from 4 s violated to 3 s satisfied, either side), placed
                  around the channels' own predictive means;
-  grad           wiski_scatter_stats_grad with the same carry: the same points with values and full gradients as targets;
-  interval       wiski_scatter_stats_interval with the same carry and its three outputs: the value channel alone, bounded on one side.
+  grad           wiski_absorb at channels = d + 1, with the same carry: the same points with values and full gradients as targets;
+  interval       wiski_absorb_interval with the same carry and its three outputs: the value channel alone, bounded on one side.
 
 The targets are zeroed between launches outside the timed region (the sums otherwise grow without bound in fp32).  Prints one JSON
 line with the three medians and the fastest runs in microseconds, grad_interval / grad and grad_interval / interval, and the share

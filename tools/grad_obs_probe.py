@@ -2,7 +2,7 @@
 each timed with HIP events around single launches (median over --reps, after --warm warm-up launches, the three interleaved so that
 they share whatever else the machine is doing):
 
-  fused     wiski_scatter_stats_grad with all d + 1 channels present;
+  fused     wiski_absorb at channels = d + 1, all of them present;
   separate  d + 1 calls of the same entry, each with one channel present (what channel-by-channel absorbing would cost);
   value     today's value-only absorb (wiski_scatter_stats_cnt on the half stencil).
 

@@ -2,10 +2,10 @@
 three launches, each timed with HIP events around single launches (median over --reps, after --warm warm-up launches, the three
 interleaved so that they share whatever else the machine is doing):
 
-  input_noise  wiski_scatter_stats_input_noise with the carry (u, res, mean_out), gvar and its three outputs (omega, log Z, the
+  input_noise  wiski_absorb_input_noise with the carry (u, res, mean_out), gvar and its three outputs (omega, log Z, the
                slopes); the input variances are drawn so that s_in / dn is log-uniform in [1e-2, 1e2];
-  robust       wiski_scatter_stats_robust with the same carry and omega_out;
-  interval     wiski_scatter_stats_interval with the same carry and its three outputs, two-sided intervals of width 0.1 s .. 3 s
+  robust       wiski_absorb_robust with the same carry and omega_out;
+  interval     wiski_absorb_interval with the same carry and its three outputs, two-sided intervals of width 0.1 s .. 3 s
                around the points' own predictive means.
 
 The targets are zeroed between launches outside the timed region (the sums otherwise grow without bound in fp32).  Prints one JSON

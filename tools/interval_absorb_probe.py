@@ -2,9 +2,9 @@
 timed with HIP events around single launches (median over --reps, after --warm warm-up launches, the three interleaved so that they
 share whatever else the machine is doing):
 
-  interval  wiski_scatter_stats_interval with the carry (u, res, mean_out) and its three outputs; a third of the points each are
+  interval  wiski_absorb_interval with the carry (u, res, mean_out) and its three outputs; a third of the points each are
             one-sided bounds, two-sided intervals and exact values, placed around the points' own predictive means;
-  robust    wiski_scatter_stats_robust with the same carry and omega_out;
+  robust    wiski_absorb_robust with the same carry and omega_out;
   plain     the value-only absorb with the same carry (wiski_scatter_stats_step without zero regions, guard or owner workspace:
             k_scatter_stats_sym with u, res and mean_out).
 

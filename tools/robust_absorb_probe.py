@@ -2,7 +2,7 @@
 with HIP events around single launches (median over --reps, after --warm warm-up launches, the two interleaved so that they share
 whatever else the machine is doing):
 
-  robust  wiski_scatter_stats_robust with the carry (u, res, mean_out) and omega_out;
+  robust  wiski_absorb_robust with the carry (u, res, mean_out) and omega_out;
   plain   the value-only absorb with the same carry (wiski_scatter_stats_step without zero regions, guard or owner workspace:
           k_scatter_stats_sym with u, res and mean_out).
 

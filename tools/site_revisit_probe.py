@@ -2,9 +2,9 @@
 bounds, two launches, each timed with HIP events around single launches (median over --reps, after --warm warm-up launches, the two
 interleaved so that they share whatever else the machine is doing):
 
-  interval  wiski_scatter_stats_interval with the carry (u, res) and its three outputs: two thirds of the points are one-sided bounds
+  interval  wiski_absorb_interval with the carry (u, res) and its three outputs: two thirds of the points are one-sided bounds
             and two-sided intervals placed around the points' own predictive means, a third exact values;
-  revisit   wiski_revisit_sites over a ring of q slots that holds those points with the sites the interval launch gave them, against
+  revisit   wiski_absorb_revisit over a ring of q slots that holds those points with the sites the interval launch gave them, against
             the same u and a variance that leaves every cavity well above the threshold: every slot that is no exact value is
             re-matched and makes its delta sweep (the first sweep of a refine: every site moves).
 

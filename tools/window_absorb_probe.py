@@ -2,7 +2,7 @@
 timed with HIP events around its launches (median over --reps, after --warm warm-up rounds, the forms interleaved so that they share
 whatever else the machine is doing):
 
-  window    wiski_scatter_stats_window with the carry (u, res): q points enter, q leave, one launch;
+  window    wiski_absorb_window with the carry (u, res): q points enter, q leave, one launch;
   plain_q   the plain absorb (wiski_scatter_stats_cnt, half stencil, with the carry) of q points;
   plain_2q  the same of 2 q points: the atomics of `window` without the ring traffic;
   two_step  what a caller without the fused form would do: gather the q leaving points from the ring (five index_select launches and
