@@ -1093,7 +1093,10 @@ __global__ __launch_bounds__(256) void k_spectral_eval(int n, int r, const doubl
     sq = (double)s;
     nl = (double)((real)0.5 * (s / v + (real)log((double)v) + (real)1.8378770664093453));
     amax = fabs(mu);
+    // (the mean and |F_j|^2 slots are stored, not accumulated, but d_ws is promised "left zero": all of it, so that whoever shares it may rely on that)
     __hip_atomic_store(ws + j, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(ws + 64 + j, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(ws + 128 + j, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   if (threadIdx.x == 0) __hip_atomic_store(reinterpret_cast<int*>(ws + 192), 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   sq = block_reduce_sum(sq, s_red);

@@ -160,7 +160,7 @@ class OnlineSKIRegression(StreamingSKIWrapper):
 
     def _evaluate_from_factor(self, inputs, targets):
         """evaluate() of one chunk (<= 1024 points, one output) straight from the spectral factor: one projection launch and ONE launch
-        for means, variances and both metrics (wiski_spectral_evaluate; beyond 64 points or rank 512 the MFMA GEMM chol^-1 F^T + one
+        for means, variances and both metrics (wiski_spectral_evaluate; beyond 64 points or rank 1024 the MFMA GEMM chol^-1 F^T + one
         launch), one host read.  Same decisions as the posterior call
         (batched_fixed_noise_online_gp._eval_forward): only where the factor serves the mean as well -- the PCG state is not current and
         the factor's mean monitor is green; otherwise None and the general path runs."""
